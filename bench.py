@@ -14,11 +14,19 @@ repo).  Per-GPU batch is fixed (default 8 = train_darcy.py:66), so N GPUs proces
 weak scaling.  The optimizer step is excluded from `value` (BASELINE.json's metric is fwd+bwd)
 and reported separately as `train_step` (fwd+bwd+Adam).
 
-Prints ONE JSON line on rank 0 with the driver's contract fields plus
+Prints ONE JSON line on rank 0 with the driver's contract fields (metric, value, unit, ms_per_step,
+...).  A plain run does only what that line needs: set up, warm up, time exactly --steps steps in
+one block, write the outputs (--dump-outputs DIR), print.  Everything else is measured with --full:
   "roofline":     the dominant kernel's achieved FLOP/s (algorithmic FLOPs / mean launch time
                   measured here with HIP events on the launch stream) against the fp32 MFMA peak;
   "cpu_baseline": the CPU oracle (a port of the reference's torch-CPU path, validated bit-equal
-                  to it in the build container) timed on this host's cores on the same workload.
+                  to it in the build container) timed on this host's cores on the same workload;
+  "parity":       the timed step's results against that oracle; the device-route, Adam, batch-sweep
+                  and bf16 extras; the spread of repeated timed blocks ("timing_blocks").
+
+--dump-outputs DIR writes what the last timed step computed - the prediction (out), the loss and
+every parameter's gradient (grad.<name>) - as float32 DIR/<name>.npy, rank 0 only.  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -97,6 +105,11 @@ def parse():
     ap.add_argument("--no-parity", action="store_true", help="skip the parity block (oracle forward+backward on the host)")
     ap.add_argument("--math", choices=("fp32", "bf16"), default="fp32",
                     help="MFMA math mode of the contractions (pit_set_math_mode); fp32 = the reference's arithmetic")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: parity vs the oracle, extras, roofline probes, CPU baseline, "
+                         "derived rates and the spread of repeated timed blocks (the --no-* options select within it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's prediction, loss and gradients as float32 DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -223,6 +236,31 @@ def timed_blocks(run, steps, warmup, world, min_total=0.25, min_blocks=5, max_bl
     med = statistics.median(blocks)
     return med, {"blocks": len(blocks), "steps_per_block": steps, "min_ms_per_step": round(min(blocks) / steps * 1e3, 4),
                  "max_ms_per_step": round(max(blocks) / steps * 1e3, 4), "total_timed_s": round(sum(blocks), 3)}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, step, model):
+    """What the last timed step handed its caller - the prediction (None for a rollout step), the loss and every parameter's
+    gradient - as float32 ``dirname/<name>.npy``.  If the whole exceeds DUMP_LIMIT_BYTES, every array is cut to the same share
+    of its elements by a fixed-seed sample of flat indices (ascending), so two runs dump the same positions."""
+    import numpy as np
+    torch.cuda.synchronize()
+    arrays = {"out": step.out, "loss": step.loss}
+    arrays.update({f"grad.{k}": q.grad for k, q in model.named_parameters() if q.grad is not None})
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items() if v is not None}
+    total = sum(a.size for a in arrays.values()) * 4
+    budget = DUMP_LIMIT_BYTES - 256 * len(arrays)          # room for the .npy headers
+    share = min(1.0, budget / total)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        if share < 1.0:
+            n = max(1, int(a.size * share))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    log(f"outputs of the last timed step: {len(arrays)} arrays in {dirname}" + ("" if share == 1.0 else f" (sampled, {share:.3f})"))
 
 
 # ------------------------------------------------------------------------------------------
@@ -815,16 +853,21 @@ def main():
     else:
         run, mode = prepare(step, not args.no_graph)
     log(f"step prepared ({mode})")
-    dt, spread = timed_blocks(run, args.steps, args.warmup, world)
-    log(f"timed region done: {dt / args.steps * 1e3:.4f} ms/step (median of {spread['blocks']} blocks of {args.steps} steps, "
-        f"{spread['min_ms_per_step']}..{spread['max_ms_per_step']})")
+    dt = timed(run, args.steps, args.warmup, world)
+    log(f"timed region done: {dt / args.steps * 1e3:.4f} ms/step ({args.steps} steps)")
     ms = dt / args.steps * 1e3
     value = args.batch * world * args.steps / dt
     loss_val = float(step.loss)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step, model)
+    spread = None
+    if args.full:              # the same step repeated in further blocks of --steps steps: how far one block can be trusted
+        spread = timed_blocks(run, args.steps, 0, world)[1]
+        log(f"repeated blocks: {spread['min_ms_per_step']}..{spread['max_ms_per_step']} ms/step over {spread['blocks']} blocks")
 
     # N > 1 (and a 1-rank torch.distributed.run): SURVEY 8(e)'s parity row for the timed step - collective, every rank
     ddp_parity = None
-    if distributed and not args.no_parity and not args.rollout:
+    if args.full and distributed and not args.no_parity and not args.rollout:
         try:
             ddp_parity = parity_ddp(args, step, model, darcy_affine(device) if args.task == "darcy" else None, meta, world, rank)
         except Exception as exc:
@@ -833,7 +876,7 @@ def main():
             log("parity_ddp: " + json.dumps({k: v for k, v in (ddp_parity or {}).items() if k.startswith("rel_") or k == "error"}))
     # ... and a saturated-regime scaling point next to the latency-regime headline (collective too)
     ddp_sweep = None
-    if distributed and (not args.no_extras or args.ddp_sweep) and not args.rollout and args.sweep_batch != args.batch:
+    if args.full and distributed and (not args.no_extras or args.ddp_sweep) and not args.rollout and args.sweep_batch != args.batch:
         try:
             st6, _, _ = build_step(args, device, rank, world, args.sweep_batch, all_reduce=True)
             with Watchdog(args.watchdog, "capturing the saturated-batch step"):
@@ -881,9 +924,14 @@ def main():
                                      if distributed else None)},
             "loss": round(loss_val, 6),
             "peak_memory_GB": round(torch.cuda.max_memory_allocated() / 1e9, 3),
-            "timing": dict(spread, what="value = median over repeated blocks of exactly --steps steps, each bracketed by "
-                                        "barrier + synchronize (MAX over ranks)"),
+            "timing": {"blocks": 1, "steps_per_block": args.steps, "total_timed_s": round(dt, 4),
+                       "what": "value = ONE block of exactly --steps steps after --warmup steps, bracketed by barrier + "
+                               "synchronize (MAX over ranks)"},
         }
+        if spread is not None:
+            rec["timing_blocks"] = dict(spread, what="further blocks of --steps steps of the same step after the headline block "
+                                                     "(median, min, max): its run-to-run spread")
+    if rank == 0 and args.full:
         if args.task in MB_PER_SAMPLE_FWD:     # whole-step algorithmic activation traffic (fwd+bwd = 3x fwd)
             gbps = value * MB_PER_SAMPLE_FWD[args.task] * 3.0 / 1e3
             rec["step_hbm"] = {"algorithmic_GBps": round(gbps, 1), "frac_of_hbm_peak": round(gbps / HBM_PEAK_GBPS / world, 4),
@@ -918,7 +966,7 @@ def main():
                 rec["parity"] = {"error": f"{type(exc).__name__}: {exc}"}
                 log(f"parity block failed: {rec['parity']['error']}")
     extras = {}
-    if rank == 0 and world == 1 and not args.no_extras and not args.rollout and args.head_scale_route == "host":
+    if args.full and rank == 0 and world == 1 and not args.no_extras and not args.rollout and args.head_scale_route == "host":
         # ADVICE r3 / VERDICT r3 weak 1: the headline runs the EXACT head-scale route (host-evaluated c, legal while lmda is
         # frozen); a training step updates lmda and must take route 'device' (c evaluated in the kernels).  The same
         # fwd+loss+bwd step on that route - same seed, same inputs: its time and its parity against the oracle BEFORE any
@@ -943,7 +991,7 @@ def main():
             del st5, run5
         except Exception as exc:
             extras["device_route"] = {"error": f"{type(exc).__name__}: {exc}"}
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         # (a) the same step with Adam (capturable) inside the graph
         with ops.head_scale_route("device"):        # lmda changes inside the graph: the in-kernel head scale
             st2, _, _ = build_step(args, device, rank, world, args.batch, with_optimizer=True)
@@ -986,7 +1034,7 @@ def main():
         extras["roofline_saturated"] = roofline_probe(model, 256)
         extras["roofline_mlp_saturated"] = roofline_mlp_probe(model, 256)
         extras["roofline_dw_saturated"] = roofline_dw_probe(model, 256)
-    if rank == 0:
+    if rank == 0 and args.full:
         blk = roofline_block_probe(model, args.batch, step.mesh_out.reshape(-1, model.space_dim).shape[0]) \
             if (args.math == "fp32" and model.mesh_ltt is not None) else None
         bwd = roofline_attention_bwd_probe(model, args.batch)
@@ -1006,6 +1054,7 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(args.batch, args.cpu_iters)
             rec["speedup_vs_cpu_baseline"] = round(rec["value"] / rec["cpu_baseline"]["value"], 1)
+    if rank == 0:
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(rec) + "\n").encode())
     if distributed:

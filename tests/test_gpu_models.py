@@ -276,7 +276,7 @@ def test_bench_prints_exactly_one_json_line():
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "3",
-                        "--no-extras", "--cpu-iters", "3"], capture_output=True, text=True, timeout=600, cwd=root)
+                        "--full", "--no-extras", "--cpu-iters", "3"], capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[:2000]
@@ -290,6 +290,39 @@ def test_bench_prints_exactly_one_json_line():
     for key in ("value", "unit", "cores", "kind", "sample"):
         assert key in rec["cpu_baseline"], key
     assert "workload" in rec["config"] and rec["value"] > 0
+
+
+def test_plain_bench_times_exactly_its_steps_and_dumps_the_last_step(tmp_path):
+    """A plain bench.py run: the headline only (no --full records), exactly --steps timed steps, and --dump-outputs writes
+    the last timed step's prediction, loss and gradients as float32 arrays - the same for two runs with the same arguments."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    recs = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout[:2000]
+        recs.append(json.loads(lines[0]))
+    rec = recs[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in rec, key
+    for key in ("roofline", "cpu_baseline", "parity", "train_step", "timing_blocks"):
+        assert key not in rec, key
+    assert rec["steps"] == 7 and rec["timing"]["blocks"] == 1 and rec["timing"]["steps_per_block"] == 7
+    assert abs(rec["value"] - 8 * 1e3 / rec["ms_per_step"]) <= 1e-3 * rec["value"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert "out.npy" in names and "loss.npy" in names and any(n.startswith("grad.") for n in names)
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    out = np.load(tmp_path / "a" / "out.npy")
+    assert out.dtype == np.float32 and out.shape == (8, 43, 43, 1) and np.isfinite(out).all()
+    assert abs(float(np.load(tmp_path / "a" / "loss.npy")) - rec["loss"]) <= 1e-5 * abs(rec["loss"]) + 1e-6
+    for n in names:      # same seeded inputs and parameters: the same results up to the order of fp32 atomic sums
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and a.shape == b.shape and np.isfinite(a).all(), n
+        assert gio.rel_l2(a, b) <= 1e-5, n
 
 
 @pytest.mark.parametrize("kind", ["fixed", "batched", "periodic1d"])
