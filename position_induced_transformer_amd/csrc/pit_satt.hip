@@ -191,10 +191,11 @@ __device__ __forceinline__ void satt_body(const SattArgs& g, const int bid) {
     // MODE 0 leaves its rounded weights behind as A-fragment tiles [mesh sample][head][16-row tile][step][lane][8] (1 KB per wavefront
     // and step, contiguous): d(values) contracts the same (symmetric) matrix and reads them instead of forming every weight again
     // (twice, with its column halves).  Unconditional buffer stores: a NULL e_out is a resource of size 0 (every store dropped),
-    // the step beyond the last and the repeated samples of a batch-free mesh go to an out-of-range offset.
+    // the step beyond the last, the repeated samples of a batch-free mesh and - 128-row workgroups on an odd tile count - the
+    // waves whose 16-row tile lies beyond the sample's tiles * 4 go to an out-of-range offset (the region is sized by tiles alone).
     const long tile_base = (((long)(mb * H + hsel) * (g.tiles * 4) + t * 4 * RT + wave) * nsteps) * 64 + lane;     // in 16-byte units
     const __amdgpu_buffer_rsrc_t re = make_rsrc(g.e_out, (MODE == 0 && g.e_out) ? 0x7ffffff0u : 0u);
-    const bool e_mine = g.mesh_batch > 1 || b == 0;
+    const bool e_mine = (g.mesh_batch > 1 || b == 0) && t * 4 * RT + wave < g.tiles * 4;
 #define PIT_SATT_ESTORE(s_, frag_)                                                                                    \
     do { if (MODE == 0) {                                                                                             \
         const u32x4_t w_ = __builtin_bit_cast(u32x4_t, frag_);                                                       \

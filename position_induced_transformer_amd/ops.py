@@ -644,6 +644,24 @@ def _satt_pays(n_pts: int, n_head: int, d: int) -> bool:
     return SATT not in ("0", "", False)
 
 
+# The hand-offs are checked by address AND version counter: an in-place edit of the values between the producing chain and the
+# attention, or a gradient accumulated into / scaled in the consuming chain's d_x buffer by autograd or a hook, keeps the address but
+# leaves the bf16 copy stale - the prep launch then forms it again from what the tensor holds now.
+def _handoff_x16(values: torch.Tensor):
+    """bf16(values) written by the producing MLP chain (mlp_apply), or None if there is none or ``values`` changed since."""
+    x16 = getattr(values, "_pit_x16", None)
+    if x16 is None or getattr(values, "_pit_x16_version", None) != values._version:
+        return None
+    return x16
+
+
+def _handoff_g16_ready(link, d_out: torch.Tensor, shape) -> bool:
+    """True if the consuming chain's G16 (link["g16"]) was formed from exactly this d_out: its buffer, unchanged since."""
+    g16 = link.get("g16") if link is not None else None
+    return (g16 is not None and link.get("dx_ptr") == d_out.data_ptr() and link.get("dx_version") == d_out._version
+            and tuple(g16.shape) == tuple(shape))
+
+
 def _union_att_ok(plan: "MeshPlan", n_head: int, d: int, b: int, values: torch.Tensor) -> bool:
     if torch.are_deterministic_algorithms_enabled():       # (d(values) leaves these kernels as fp32 atomic adds)
         return False
@@ -736,7 +754,7 @@ class _PosAtt(torch.autograd.Function):
             ctx.satt_link = link
             if link is not None:
                 link.update(rowstat=rowstat, n_head=n_head, pts=int(j), mesh_batch=int(plan.mesh_batch), dim=int(d), batch=int(b), g16=None,
-                            dx_ptr=None)
+                            dx_ptr=None, dx_version=None)
             ctx.union = 0
             ctx.plan, ctx.n_head, ctx.concat, ctx.head_is_scale = plan, n_head, concat, head_is_scale
             ctx.head_param = head_param
@@ -826,7 +844,7 @@ class _PosAtt(torch.autograd.Function):
                 d_out = d_out.float().contiguous()
             lk = getattr(ctx, "satt_link", None)
             g16 = lk.get("g16") if lk is not None else None
-            g16_ready = g16 is not None and lk.get("dx_ptr") == d_out.data_ptr() and tuple(g16.shape) == (b, n_head, j, dv)
+            g16_ready = _handoff_g16_ready(lk, d_out, (b, n_head, j, dv))
             if lk is not None:
                 lk["g16"] = None                         # (consumed)
             if not g16_ready:
@@ -1046,7 +1064,7 @@ def posatt_apply(values: torch.Tensor, lmda: torch.Tensor, plan: MeshPlan, n_hea
     c = host_head_scale(lmda) if (not head_is_scale and get_head_scale_route() == "host") else None
     # the hand-offs between a dense self-attention layer on csrc/pit_satt.hip and the MLP chains either side of it (bf16 mode):
     # bf16(values) from the producing chain, and - on the way back - G16 from the consuming chain's backward
-    link = {"x16": getattr(values, "_pit_x16", None)} if concat else None
+    link = {"x16": _handoff_x16(values)} if concat else None
     out = _PosAtt.apply(values, lmda.reshape(-1), plan, n_head, concat, head_is_scale, param, slot, coord_dims, c,
                         out_bf16, link)
     if link is not None and link.get("rowstat") is not None:
@@ -1220,7 +1238,7 @@ class _Mlp(torch.autograd.Function):
             # the data path (dZ2, dZ1, d_x) in ONE launch on the forward's bf16 weight copies, then both weight-gradient reductions
             w1b, w2b = ctx.chain
             # x is a self-attention layer's concat buffer (csrc/pit_satt.hip): its backward's G16 = bf16(d_x_h / rowsum_h) is written here,
-            # beside d_x - that layer then needs no prep launch (it checks that the d_out it receives IS this d_x)
+            # beside d_x - that layer then needs no prep launch (it checks that the d_out it receives IS this d_x, unchanged: _handoff_g16_ready)
             lk, g16 = ctx.satt_link, None
             if (lk is not None and SATT_FUSE_PREP and d_x is not None and lk.get("rowstat") is not None and lk["dim"] == n1
                     and (1 + lk["n_head"]) * n1 == n0 and lk["batch"] * lk["pts"] == rows):
@@ -1231,7 +1249,7 @@ class _Mlp(torch.autograd.Function):
                                      lk["mesh_batch"] if g16 is not None else 0, _lib.stream_ptr())
             _lib.check(rc, "pit_mlp_chain_bwd")
             if g16 is not None:
-                lk["g16"], lk["dx_ptr"] = g16, d_x.data_ptr()
+                lk["g16"], lk["dx_ptr"], lk["dx_version"] = g16, d_x.data_ptr(), d_x._version
             if lk is not None and inplace and SATT_DW_RIDER and lk.get("rowstat") is not None:
                 # the weight-gradient reductions depend on this launch only: they ride in the attention layer's ONE backward launch
                 # (pit_satt_bwd's rider) instead of standing between the two
@@ -1301,7 +1319,7 @@ def mlp_apply(x, w1, b1, w2, b2, out_gelu: bool = False, concat_heads: int = 0) 
     y, buf = _Mlp.apply(x, w1, b1, w2, b2, out_gelu, int(concat_heads), link, y16_slot, dense)
     y._pit_concat = buf
     if y16_slot:
-        y._pit_x16 = y16_slot[0]
+        y._pit_x16, y._pit_x16_version = y16_slot[0], y._version
     return y
 
 

@@ -179,6 +179,67 @@ def test_inplace_gradient_slots_are_opt_in():
     assert ops._grad_slot(p) is None
 
 
+def test_satt_handoffs_are_refused_once_the_tensor_changed_in_place():
+    """The bf16 operands the MLP chains write for a dense self-attention layer (y16 beside y, G16 beside d_x) are taken only while
+    the tensor they were formed from is unchanged: an in-place edit of y, or a gradient accumulated into / scaled in d_x's buffer
+    (same address), sends the layer back to its prep launch."""
+    from position_induced_transformer_amd import ops
+    y = torch.zeros(2, 3, 4)
+    x16 = torch.zeros(6, 4, dtype=torch.bfloat16)
+    y._pit_x16, y._pit_x16_version = x16, y._version
+    assert ops._handoff_x16(y) is x16
+    y.mul_(2.0)
+    assert ops._handoff_x16(y) is None
+    assert ops._handoff_x16(torch.zeros(2, 3, 4)) is None
+    y2 = torch.zeros(2, 3, 4)
+    y2._pit_x16 = x16                                    # (no recorded version: not trusted)
+    assert ops._handoff_x16(y2) is None
+
+    d_x = torch.zeros(6, 12)
+    g16 = torch.zeros(2, 2, 3, 4, dtype=torch.bfloat16)
+    lk = {"g16": g16, "dx_ptr": d_x.data_ptr(), "dx_version": d_x._version}
+    d_out = d_x.reshape(2, 3, 12)                        # (what _Mlp.backward returns: a view, one version counter)
+    assert ops._handoff_g16_ready(lk, d_out, (2, 2, 3, 4))
+    assert not ops._handoff_g16_ready(lk, d_out, (2, 1, 3, 4))
+    assert not ops._handoff_g16_ready(lk, d_out.clone(), (2, 2, 3, 4))
+    assert not ops._handoff_g16_ready(None, d_out, (2, 2, 3, 4))
+    d_out.add_(1.0)                                      # another consumer's gradient accumulated in place, or a hook's mul_
+    assert d_out.data_ptr() == lk["dx_ptr"]
+    assert not ops._handoff_g16_ready(lk, d_out, (2, 2, 3, 4))
+
+
+def test_a_gradient_hook_that_edits_in_place_keeps_the_address_and_moves_the_version():
+    """What the G16 hand-off check relies on, with stock autograd: a Function whose backward returns a view of a fresh buffer, and a
+    hook on its input that scales the gradient in place - the next backward receives the same address with a newer version."""
+    seen = {}
+
+    class Producer(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, v):
+            return v * 1.0
+
+        @staticmethod
+        def backward(ctx, d):
+            seen["ptr"], seen["version"] = d.data_ptr(), d._version
+            return d
+
+    class Consumer(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, a):
+            return a.sum(-1)
+
+        @staticmethod
+        def backward(ctx, g):
+            d_x = torch.ones(6, 4)
+            seen["dx_ptr"], seen["dx_version"] = d_x.data_ptr(), d_x._version
+            return d_x.reshape(2, 3, 4)
+
+    a = Producer.apply(torch.zeros(2, 3, 4, requires_grad=True))
+    a.register_hook(lambda gr: gr.mul_(0.5))
+    Consumer.apply(a).sum().backward()
+    assert seen["ptr"] == seen["dx_ptr"] and seen["version"] != seen["dx_version"]
+
+
 # --------------------------------------------------------------------------- round 3
 def test_importing_ops_or_utils_does_not_fire_the_drop_in_side_effects():
     """the reference's import-time side effects (pit.py:1-11) belong to the drop-in module `pit` only."""
