@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PIT_ABI_VERSION 23
+#define PIT_ABI_VERSION 24
 #define PIT_DSCALE_SLOTS 1024 /* fp64 accumulators per head in pit_posatt_bwd's workspace */
 
 /* distance metric (dist2att variants) */
@@ -612,6 +612,22 @@ int pit_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq
 /* Layout probe used by the tests: D = A(32x8) * B(8x32) through the same
  * v_mfma_f32_32x32x2_f32 fragment maps the kernels use. */
 int pit_debug_mfma_tile(const float* a, const float* b, float* d, void* stream);
+
+/* Where the postponed weight-gradient jobs (pit_mlp_params_job, the `rider` arguments above) went: host-side counters of
+ * the CALLING THREAD, one per kind below, incremented when a launch accepts a job (PIT_RIDER_OWN: every
+ * pit_mlp_bwd_params call, which is also what a host that refuses a job makes).  Copies min(n, PIT_RIDER_KINDS) counters
+ * to out (host array) and zeroes them all when reset != 0; returns PIT_RIDER_KINDS.  No device work. */
+#define PIT_RIDER_OWN          0   /* pit_mlp_bwd_params: a launch of its own                                          */
+#define PIT_RIDER_PAIR_DW      1   /* pit_posatt_bwd, dense: posatt_bwd_pair_dw_kernel (narrow tiles, plan_dw_pair)    */
+#define PIT_RIDER_PAIR_WIDE    2   /* pit_posatt_bwd, dense: posatt_bwd_pair_wide_kernel (gemm_rr tiles, fp32 / bf16) */
+#define PIT_RIDER_SPARSE_PAIR  3   /* pit_posatt_bwd, candidate lists: posatt_sparse_bwd_dw_kernel                     */
+#define PIT_RIDER_SPARSE_ROWS  4   /* pit_posatt_bwd, candidate lists: posatt_sparse_rows_dw (d(scale) only)          */
+#define PIT_RIDER_DHEAD_FINISH 5   /* pit_posatt_dhead_finish: posatt_dhead_finish_dw                                 */
+#define PIT_RIDER_BLOCK        6   /* pit_block_bwd: `rider`                                                           */
+#define PIT_RIDER_BLOCK2       7   /* pit_block_bwd: `rider2`                                                          */
+#define PIT_RIDER_SATT         8   /* pit_satt_bwd: the merged d(values) + d(scale) launch                             */
+#define PIT_RIDER_KINDS        9
+int pit_debug_rider_counts(int* out, int n, int reset);
 
 #ifdef __cplusplus
 }

@@ -125,10 +125,11 @@ SIGNATURES = {
     "pit_instance_norm_bwd": [_P, _P, _P, _I, _I, _I, _P, _P],
     "pit_adam_step": [_P, _P, _P, _P, _L, _P, _F, _F, _I, _F, _F, _F, _F, _I, _P, _P],
     "pit_debug_mfma_tile": [_P, _P, _P, _P],
+    "pit_debug_rider_counts": [_P, _I, _I],
 }
 
 LONG_RETURN = {"pit_satt_tiles_elems"}
-ABI_VERSION = 23       # PIT_ABI_VERSION of include/pit_hip.h this binding was written against
+ABI_VERSION = 24       # PIT_ABI_VERSION of include/pit_hip.h this binding was written against
 
 _lib = None
 

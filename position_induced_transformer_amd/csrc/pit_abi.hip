@@ -19,6 +19,21 @@ thread_local int t_call_math = PIT_MATH_FP32;
 
 extern "C" int pit_version(void) { return PIT_ABI_VERSION; }
 
+namespace {
+thread_local int t_rider_counts[PIT_RIDER_KINDS];
+}  // namespace
+
+void pit_rider_note(int kind) {
+    if (kind >= 0 && kind < PIT_RIDER_KINDS) ++t_rider_counts[kind];
+}
+
+extern "C" int pit_debug_rider_counts(int* out, int n, int reset) {
+    for (int k = 0; out && k < n && k < PIT_RIDER_KINDS; ++k) out[k] = t_rider_counts[k];
+    if (reset)
+        for (int k = 0; k < PIT_RIDER_KINDS; ++k) t_rider_counts[k] = 0;
+    return PIT_RIDER_KINDS;
+}
+
 extern "C" const char* pit_error_string(int code) {
     switch (code) {
         case 0: return "ok";

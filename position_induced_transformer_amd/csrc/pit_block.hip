@@ -681,6 +681,8 @@ extern "C" int pit_block_bwd(const float* e, const float* inv, const float* qw, 
 #undef PIT_BLOCK_BWD
     PIT_CHECK_LAUNCH();
     for (int r = 0; r < 2; ++r)
+        if (carried[r]) pit_rider_note(r == 0 ? PIT_RIDER_BLOCK : PIT_RIDER_BLOCK2);
+    for (int r = 0; r < 2; ++r)
         if (jobs[r] && !carried[r]) {                   // too large to ride: the launches pit_mlp_bwd_params would have made
             const pit_mlp_params_job* j = jobs[r];
             const int rc = pit_mlp_bwd_params(j->x, j->ldx, j->rows, j->n0, j->n1, j->n2, j->h, j->out_gelu, j->d_y, j->ld_dy,

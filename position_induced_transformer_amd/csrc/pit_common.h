@@ -33,6 +33,8 @@ extern thread_local int t_call_math;
 #define PIT_ENTER_MATH(mode_) do { if (((mode_) & 0xff) != PIT_MATH_FP32 && ((mode_) & 0xff) != PIT_MATH_BF16) return PIT_ERR_UNSUPPORTED; \
                                    if (((mode_) & ~0xff & ~PIT_ATT_UNION) && ((mode_) & 0xff) != PIT_MATH_BF16) return PIT_ERR_UNSUPPORTED; \
                                    t_call_math = ((mode_) & 0xff); } while (0)
+// include/pit_hip.h, pit_debug_rider_counts: a host that accepts a postponed weight-gradient job notes it (kind = PIT_RIDER_*)
+void pit_rider_note(int kind);
 // bf16 storage (PIT_IO_*): a tensor kept as bf16 in memory is widened exactly (bits << 16), narrowed with RNE
 __device__ __forceinline__ float bf16_to_f(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
 __device__ __forceinline__ unsigned short f_to_bf16(float x) { return __builtin_bit_cast(unsigned short, (__bf16)x); }

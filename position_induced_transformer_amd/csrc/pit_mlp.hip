@@ -1928,6 +1928,7 @@ extern "C" int pit_mlp_bwd_params(const float* x, long ldx, int rows, int n0, in
     g1.a16 = save16; g1.b16 = x16;            // dZ1, x
     if (int rc = launch_gemm_pair_atomic(g2, g1, s)) return rc;
     PIT_CHECK_LAUNCH();
+    pit_rider_note(PIT_RIDER_OWN);
     return 0;
 }
 

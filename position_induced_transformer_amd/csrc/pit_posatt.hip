@@ -1807,6 +1807,7 @@ bool launch_bwd_pair(const AttArgs& a0, hipStream_t s, const pit_mlp_params_job*
         else { if (a0.bf16) PIT_PAIR_DW(false, true); else PIT_PAIR_DW(false, false); }
 #undef PIT_PAIR_DW
         *rider_done = true;
+        pit_rider_note(PIT_RIDER_PAIR_DW);
         return true;
     }
 #define PIT_PAIR_K(M_, BF_)                                                                                   \
@@ -1849,6 +1850,7 @@ bool launch_bwd_pair(const AttArgs& a0, hipStream_t s, const pit_mlp_params_job*
         wgrid = dim3((unsigned)(rows_wgs + cols_wgs + wdw.n1 + wdw.n2));
         wsm = std::max(sm, (size_t)65536);
         *rider_done = true;
+        pit_rider_note(PIT_RIDER_PAIR_WIDE);
     } else {
         wdw = pit_detail::DwPair();
     }
@@ -2932,6 +2934,7 @@ void launch_sparse_rows(const AttArgs& a, const SparseArgs& sp, hipStream_t s, c
 #undef PIT_SRW_CR
 #undef PIT_SRW
         *rider_done = true;
+        pit_rider_note(PIT_RIDER_SPARSE_ROWS);
         return;
     }
     const long xtotal = 8L * grid.x * ((grid.y + 7) / 8) * grid.z;
@@ -2980,6 +2983,7 @@ bool launch_sparse_bwd_pair(const AttArgs& a, const SparseArgs& sp, bool complet
 #undef PIT_SBW_C
 #undef PIT_SBW
         *rider_done = true;
+        pit_rider_note(PIT_RIDER_SPARSE_PAIR);
         if (!complete) hipLaunchKernelGGL(posatt_sparse_overflow_cols, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a, sp);
         return true;
     }
@@ -3417,6 +3421,7 @@ extern "C" int pit_posatt_dhead_finish(int n_layers, double* const* workspaces, 
         hipLaunchKernelGGL(posatt_dhead_finish_dw, dim3((unsigned)(total + dw.n1 + dw.n2)), dim3(256), DW_SMEM_4WAVES,
                            (hipStream_t)stream, fb, total, dw);
         PIT_CHECK_LAUNCH();
+        pit_rider_note(PIT_RIDER_DHEAD_FINISH);
         return 0;
     }
     hipLaunchKernelGGL(posatt_dhead_finish_batch, dim3(total), dim3(256), 0, (hipStream_t)stream, fb);

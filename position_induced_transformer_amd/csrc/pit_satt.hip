@@ -606,6 +606,7 @@ extern "C" int pit_satt_bwd(const float* mesh, int mesh_batch, int n_pts, int sp
             if (!riding) w = pit_detail::DwPair();
             dispatch_satt_bwd(g, g2, metric != PIT_METRIC_EUCLID, w, s);
             PIT_CHECK_LAUNCH();
+            if (riding) pit_rider_note(PIT_RIDER_SATT);
             return (rider && !riding) ? run_rider(rider, stream) : 0;
         }
         if (rider) { if (int rc = run_rider(rider, stream)) return rc; rider = nullptr; }

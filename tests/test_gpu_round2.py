@@ -722,11 +722,13 @@ def test_replays_leave_every_self_cleaning_buffer_clean(task, batch):
 
 # --------------------------------------------------------------------------- weight gradients riding with the attention backward
 @pytest.mark.parametrize("task,batch,math", [("darcy", 8, "fp32"), ("darcy", 8, "bf16"), ("burgers", 8, "fp32"),
-                                             ("elasticity", 2, "fp32"), ("vorticity", 2, "fp32")])
+                                             ("elasticity", 2, "fp32"), ("vorticity", 2, "fp32"), ("naca", 2, "fp32"),
+                                             ("vorticity", 4, "fp32")])
 def test_mlp_weight_gradients_carried_by_the_attention_backward_equal_their_own_launch(task, batch, math):
     """pit_hip.h `rider`: the postponed pit_mlp_bwd_params of a block's MLP performed by the following
     pit_posatt_bwd (inside its launch when both are small) against the same pass with the MLP backward issuing
-    its own reductions.  Everything but the atomics' summation order is identical."""
+    its own reductions (every Python switch of a carrying launch off: MLP_PARAMS_RIDER, WIDE_DW_RIDER, SATT_DW_RIDER).
+    Everything but the atomics' summation order is identical."""
     from position_induced_transformer_amd import ops, tasks, utils
     from position_induced_transformer_amd.ddp import FlatGradients
     model, sample, meta = tasks.make_task(task, seed=11)
@@ -735,15 +737,16 @@ def test_mlp_weight_gradients_carried_by_the_attention_backward_equal_their_own_
     flat = FlatGradients(model.parameters())
     got = {}
     ops._PENDING_DW.clear()                      # (entries of passes that earlier tests aborted on purpose: other models' slots)
+    saved = ops.MLP_PARAMS_RIDER, ops.WIDE_DW_RIDER, ops.SATT_DW_RIDER
     with ops.math_mode(math):
         for rider in (True, False, True):
-            ops.MLP_PARAMS_RIDER = rider
+            ops.MLP_PARAMS_RIDER = ops.WIDE_DW_RIDER = ops.SATT_DW_RIDER = rider
             try:
                 flat.zero_()
                 loss_fn(batch_t[-1], model(*batch_t[:-1])).backward()
                 torch.cuda.synchronize()
             finally:
-                ops.MLP_PARAMS_RIDER = True
+                ops.MLP_PARAMS_RIDER, ops.WIDE_DW_RIDER, ops.SATT_DW_RIDER = saved
             assert not ops._PENDING_DW
             got.setdefault(rider, []).append(flat.flat.clone())
     assert float(got[True][0].abs().max()) > 0
