@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PIT_ABI_VERSION 24
+#define PIT_ABI_VERSION 25
 #define PIT_DSCALE_SLOTS 1024 /* fp64 accumulators per head in pit_posatt_bwd's workspace */
 
 /* distance metric (dist2att variants) */
@@ -231,6 +231,34 @@ int pit_posatt_bwd(const float* mesh_out, const float* mesh_in, int mesh_batch, 
                    const int* nbr_idx, const int* nbr_cnt, int nbr_cap, int nbr_complete,
                    const int* rev_ptr, const int* rev_row, const pit_mlp_params_job* rider,
                    int coord_dims, int math_mode, void* stream);
+
+/* Gradients w.r.t. the mesh coordinates of one pit_posatt_fwd call (ABI 25).  The reference forms the distances with ordinary
+ * tensor ops, m = sum((mesh_out[:,None] - mesh_in[None])**2) (pit.py:47,134), so autograd differentiates through the meshes.
+ * Per head, with P the kept weights, g_i = d_out[i, out_col0 + h*dim : +dim], gv_ij = g_i . values_j, a_i = sum_j P_ij gv_ij and
+ * s_ij = P_ij (gv_ij - a_i):
+ *     d_mesh_out[i] = 2c sum_j s_ij (mesh_in[j] - mesh_out[i]),   d_mesh_in[j] = 2c sum_i s_ij (mesh_out[i] - mesh_in[j])
+ * summed over the heads and, for batch-free meshes (mesh_batch = 1), over the samples.  The quantile threshold only feeds a
+ * comparison and contributes nothing.
+ *   Arguments up to rev_row: those of the pit_posatt_bwd call of the same layer (rowstat / scale from the forward; the candidate
+ *            lists select the same kernels, rev_ptr / rev_row are needed for d_mesh_in; nbr_complete as there).
+ *   d_mesh_out (mesh_batch, n_out, space_dim), d_mesh_in (mesh_batch, n_in, space_dim): written, or added to with accumulate=1;
+ *            NULL = not needed.  Self attention may pass the same buffer for both: the key terms are then added to the row terms.
+ *   workspace: pit_posatt_dmesh_workspace(...) bytes, no initial contents needed.  Per-sample partials are summed in a fixed
+ *            order (no atomics): the same bits on every run.  No host synchronisation, no allocation.
+ * fp32 only (the d_out and values of the fp32 math mode); a periodic metric returns PIT_ERR_UNSUPPORTED (the reference also
+ * differentiates through the period and the minimum / abs tie rules, pit.py:190-191,248-250).  No coordinate channels
+ * (coord_dims = 0: the caller materialises the concat). */
+int pit_posatt_dmesh(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                     int space_dim, int metric, float period,
+                     const float* values, int batch, int dim, long ld_values, long values_bstride,
+                     const float* head, int n_head, int head_is_scale, const float* scale,
+                     const float* rowstat, int masked,
+                     const float* d_out, long ld_dout, long dout_bstride, int out_col0,
+                     const int* nbr_idx, const int* nbr_cnt, int nbr_cap, int nbr_complete,
+                     const int* rev_ptr, const int* rev_row,
+                     float* d_mesh_out, float* d_mesh_in, int accumulate, void* workspace, void* stream);
+/* Bytes of pit_posatt_dmesh's workspace (0 for invalid sizes). */
+long pit_posatt_dmesh_workspace(int mesh_batch, int n_out, int n_in, int space_dim, int batch, int n_head);
 
 /* Finishing step of n_layers (<= 32) pit_posatt_bwd calls issued with PIT_HEAD_DEFER, in ONE
  * launch: per layer l drains workspaces[l] (n_heads[l]*PIT_DSCALE_SLOTS doubles, left zero), applies

@@ -72,6 +72,14 @@ SIGNATURES = {
                        _P, _L, _L, _I,
                        _P, _L, _L, _I,
                        _P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _P],
+    "pit_posatt_dmesh": [_P, _P, _I, _I, _I, _I, _I, _F,
+                         _P, _I, _I, _L, _L,
+                         _P, _I, _I, _P,
+                         _P, _I,
+                         _P, _L, _L, _I,
+                         _P, _P, _I, _I, _P, _P,
+                         _P, _P, _I, _P, _P],
+    "pit_posatt_dmesh_workspace": [_I, _I, _I, _I, _I, _I],
     "pit_posatt_dhead_finish": [_I, _P, _P, _P, _P, _P, _P, _P, _P],
     "pit_block_supported": [_I, _I, _I, _I],
     "pit_block_weights": [_P, _I, _I, _I, _F, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P],
@@ -128,8 +136,8 @@ SIGNATURES = {
     "pit_debug_rider_counts": [_P, _I, _I],
 }
 
-LONG_RETURN = {"pit_satt_tiles_elems"}
-ABI_VERSION = 24       # PIT_ABI_VERSION of include/pit_hip.h this binding was written against
+LONG_RETURN = {"pit_satt_tiles_elems", "pit_posatt_dmesh_workspace"}
+ABI_VERSION = 25       # PIT_ABI_VERSION of include/pit_hip.h this binding was written against
 
 _lib = None
 

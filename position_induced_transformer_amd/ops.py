@@ -679,14 +679,83 @@ def _union_att_ok(plan: "MeshPlan", n_head: int, d: int, b: int, values: torch.T
 UNION_ATT_MIN_DIM = 128            # (width 64 models take the fused decoder launch; a layer that cannot keeps the candidate-list kernels)
 
 
+def mesh_grad_wanted(*meshes) -> bool:
+    """True when autograd records and one of the mesh tensors requires grad: the forward then takes the per-layer path whose
+    attention layers pass the meshes to _PosAtt (pit.py:47,134 differentiates through the coordinates)."""
+    return torch.is_grad_enabled() and any(torch.is_tensor(m) and m.requires_grad for m in meshes)
+
+
+def _check_mesh_grad(metric: str) -> None:
+    """Refusals of the mesh-gradient path, raised before anything is launched."""
+    if metric != "euclid":
+        raise NotImplementedError(
+            f"gradients w.r.t. the mesh coordinates are implemented for the Euclidean metric only, not {metric!r}: the reference "
+            "also differentiates through the period and the minimum / abs tie rules of the periodic distances (pit.py:190-191,248-250)")
+    if get_math_mode() != "fp32":
+        raise NotImplementedError(
+            "gradients w.r.t. the mesh coordinates are implemented for the fp32 math mode only (set_math_mode('fp32')): the bf16 "
+            "mode's rounded weights are not the ones the closed-form mesh gradient re-forms")
+
+
+def _mesh_grads(ctx, values, head, rowstat, scale, d_out):
+    """(d mesh_out, d mesh_in) of a _PosAtt layer: pit_posatt_dmesh after the layer's d(values) / d(head) launches."""
+    if not getattr(ctx, "mesh_grad", False):
+        return None, None
+    need_o, need_i = ctx.needs_input_grad[12], ctx.needs_input_grad[13]
+    if ctx.mesh_same:
+        need_o = need_i = need_o or need_i
+    if not (need_o or need_i):
+        return None, None
+    plan, n_head = ctx.plan, ctx.n_head
+    b, j, dv = values.shape
+    if d_out.dtype != torch.float32:
+        d_out = d_out.float()
+    d_out = _row_view(d_out)
+    dev = values.device
+    d_mo = torch.empty(plan.mesh_out.shape, device=dev, dtype=torch.float32) if need_o else None
+    d_mi = d_mo if ctx.mesh_same else (torch.empty(plan.mesh_in.shape, device=dev, dtype=torch.float32) if need_i else None)
+    if need_i and plan.nbr_idx is not None:
+        plan.ensure_reverse_lists()
+    L = _lib.lib()
+    ws = torch.empty(((L.pit_posatt_dmesh_workspace(plan.mesh_batch, plan.n_out, plan.n_in, plan.sdim, b, n_head) + 3) // 4,),
+                     device=dev, dtype=torch.float32)
+    rc = L.pit_posatt_dmesh(
+        plan.mesh_out.data_ptr(), plan.mesh_in.data_ptr(), plan.mesh_batch, plan.n_out, plan.n_in, plan.sdim,
+        plan.metric_id, plan.period,
+        values.data_ptr(), b, dv, values.stride(1), values.stride(0),
+        head.data_ptr(), n_head, 1 if ctx.head_is_scale else 0, scale.data_ptr(),
+        rowstat.data_ptr(), 1 if plan.masked else 0,
+        d_out.data_ptr(), d_out.stride(1), d_out.stride(0), dv if ctx.concat else 0,
+        _lib.ptr(plan.nbr_idx), _lib.ptr(plan.nbr_cnt), plan.nbr_cap, plan.lists_complete(),
+        _lib.ptr(plan.rev_ptr), _lib.ptr(plan.rev_row),
+        _lib.ptr(d_mo), _lib.ptr(d_mi), 0, ws.data_ptr(), _lib.stream_ptr())
+    _lib.check(rc, "pit_posatt_dmesh")
+    if ctx.mesh_same:
+        return d_mo.view(ctx.mesh_shapes[0]), None
+    return (d_mo.view(ctx.mesh_shapes[0]) if d_mo is not None else None,
+            d_mi.view(ctx.mesh_shapes[1]) if d_mi is not None else None)
+
+
 class _PosAtt(torch.autograd.Function):
     """dist2att + convolution (+ the self-attention concat) as one op."""
 
     @staticmethod
     def forward(ctx, values, head, plan: MeshPlan, n_head: int, concat: bool, head_is_scale: bool,
-                head_param=None, out_slot=None, coord_dims: int = 0, scale_in=None, out_bf16: bool = False, link=None):
+                head_param=None, out_slot=None, coord_dims: int = 0, scale_in=None, out_bf16: bool = False, link=None,
+                mesh_out=None, mesh_in=None):
         _need_gpu(values, head)
         ctx.math = _math_code()
+        # the caller's mesh tensors arrive only when one of them requires grad (posatt_apply): then the layer keeps the
+        # per-row / dense kernels, whose rowstat pit_posatt_dmesh reads in the backward
+        ctx.mesh_grad = mesh_out is not None or mesh_in is not None
+        ctx.mesh_same = mesh_out is mesh_in
+        ctx.mesh_shapes = (tuple(mesh_out.shape) if mesh_out is not None else None,
+                           tuple(mesh_in.shape) if mesh_in is not None else None)
+        if ctx.mesh_grad:
+            _check_mesh_grad(plan.metric)
+            if coord_dims:
+                raise RuntimeError("mesh gradients need the coordinate concat materialised (ops.materialize_coords)")
+            out_bf16 = False
         out_bf16 = bool(out_bf16 and not concat and plan.nbr_idx is not None and ctx.math == MATH_MODES["bf16"])
         ctx.coord_dims = int(coord_dims)
         # masked layer over a coherently ordered mesh: the union-tile kernels (decided per kind of plan, MeshPlan.union_tiles)
@@ -708,7 +777,7 @@ class _PosAtt(torch.autograd.Function):
         # round 5: masked cross attention on a batch-free mesh pair with a slab plan and a width that is a multiple of 64 - the
         # union-tile contraction of csrc/pit_edge.hip (weights once per call, d_out read once in the backward): Vorticity / Cylinder
         ctx.uatt = None
-        if UNION_ATT and not concat and not coord_dims and out_buf is None and _union_att_ok(plan, n_head, d, b, values):
+        if UNION_ATT and not ctx.mesh_grad and not concat and not coord_dims and out_buf is None and _union_att_ok(plan, n_head, d, b, values):
             w = _new_decoder_weights(plan, head, scale_in, n_head, head_is_scale, True)      # (Q too: 2 KB per slab)
             _launch_decoder_weights(w)
             out = torch.empty((b, plan.n_out, n_head * d), device=values.device, dtype=torch.bfloat16 if out_bf16 else torch.float32)
@@ -726,7 +795,7 @@ class _PosAtt(torch.autograd.Function):
         # round 6, bf16 mode: the processor's dense self-attention (locality 1.0) at hid 128 / 256 on bf16 MFMA with the values rounded
         # once per layer (csrc/pit_satt.hip)
         ctx.satt = None
-        if _satt_pays(int(plan.n_in), int(n_head), int(d)) and concat and not coord_dims and plan.self_attn and not plan.masked and ctx.math == MATH_MODES["bf16"] \
+        if not ctx.mesh_grad and _satt_pays(int(plan.n_in), int(n_head), int(d)) and concat and not coord_dims and plan.self_attn and not plan.masked and ctx.math == MATH_MODES["bf16"] \
                 and values.dtype == torch.float32 and values.stride(1) % 4 == 0 and values.stride(0) % 4 == 0 and values.data_ptr() % 16 == 0 \
                 and _lib.lib().pit_satt_supported(int(plan.n_in), int(n_head), int(d), int(b), int(plan.mesh_batch)):
             k_head, k_is_scale = (scale_in, True) if scale_in is not None else (head, head_is_scale)
@@ -863,7 +932,8 @@ class _PosAtt(torch.autograd.Function):
                     _defer_head_finish(work, d_head, head, scale, n_head, 1 | (4 if ctx.head_is_scale else 0))
                 else:
                     _finish_heads_now(work, d_head, head, scale, n_head, flags)
-            return d_values, (None if slot is not None else d_head), None, None, None, None, None, None, None, None, None, None
+            return (d_values, (None if slot is not None else d_head), None, None, None, None, None, None, None, None, None, None) \
+                + _mesh_grads(ctx, values, head, rowstat, scale, d_out)
         if ctx.uatt is not None:                         # the union-tile backward: d_out read once, d(values) added from the tiles
             if rider is not None:
                 _dw_run(rider)
@@ -883,7 +953,8 @@ class _PosAtt(torch.autograd.Function):
                     _defer_head_finish(work, d_head, head, w.scale, n_head, 1 | (4 if ctx.head_is_scale else 0))
                 else:
                     _finish_heads_now(work, d_head, head, w.scale, n_head, flags)
-            return d_values, (None if slot is not None else d_head), None, None, None, None, None, None, None, None, None, None
+            return (d_values, (None if slot is not None else d_head), None, None, None, None, None, None, None, None, None, None) \
+                + _mesh_grads(ctx, values, head, rowstat, scale, d_out)
 
         def launch(dv, dh, stream_ptr, job=None):
             rc = _lib.lib().pit_posatt_bwd(
@@ -905,7 +976,8 @@ class _PosAtt(torch.autograd.Function):
         launch(d_values, d_head, _lib.stream_ptr(), rider)
         if defer:
             _defer_head_finish(work, d_head, head, scale, n_head, 1 | (4 if ctx.head_is_scale else 0))
-        return d_values, (None if slot is not None else d_head), None, None, None, None, None, None, None, None, None, None
+        return (d_values, (None if slot is not None else d_head), None, None, None, None, None, None, None, None, None, None) \
+            + _mesh_grads(ctx, values, head, rowstat, scale, d_out)
 
 
 # Where the head scale c = tan(0.25*pi*(1-1e-7)*(1+sin(lmda))) (pit.py:48) is evaluated.
@@ -1051,13 +1123,21 @@ def materialize_coords(func: torch.Tensor) -> torch.Tensor:
 
 @torch.compiler.disable
 def posatt_apply(values: torch.Tensor, lmda: torch.Tensor, plan: MeshPlan, n_head: int, concat: bool,
-                 head_is_scale: bool = False, coord_dims: int = 0, out_bf16: bool = False) -> torch.Tensor:
+                 head_is_scale: bool = False, coord_dims: int = 0, out_bf16: bool = False,
+                 mesh_out: Optional[torch.Tensor] = None, mesh_in: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[b,n,h*D+d] = sum_j softmax_j(-c_h m[n,j] | quantile mask)[n,j] * values[b,j,d]
     (pit.py:46-57); with ``concat`` the inputs are prepended (pit.py:44).  ``lmda`` is the
     (H,1,1) parameter, or the scale c itself when ``head_is_scale`` (tests inject it).
     ``coord_dims`` > 0: the first coord_dims value channels are the key coordinates (plan.mesh_in), ``values`` holds
     the others (candidate-list layers only, see pit_hip.h).
+    ``mesh_out`` / ``mesh_in``: the caller's mesh tensors (those ``plan`` was built from).  When grad mode is on and one of
+    them requires grad they become inputs of the op and receive d(mesh) from pit_posatt_dmesh (Euclidean metric, fp32 mode;
+    NotImplementedError otherwise); otherwise they are ignored.
     Opaque to torch.compile (dynamo runs it eagerly: raw pointers cross a ctypes boundary)."""
+    meshes = ()
+    if mesh_grad_wanted(mesh_out, mesh_in):
+        _check_mesh_grad(plan.metric)
+        meshes = (mesh_out, mesh_in)
     out_buf = _concat_buffer_of(values, plan.n_out, n_head) if concat else None
     slot = [out_buf] if out_buf is not None else None
     param = lmda if isinstance(lmda, torch.nn.Parameter) else None
@@ -1066,7 +1146,7 @@ def posatt_apply(values: torch.Tensor, lmda: torch.Tensor, plan: MeshPlan, n_hea
     # bf16(values) from the producing chain, and - on the way back - G16 from the consuming chain's backward
     link = {"x16": _handoff_x16(values)} if concat else None
     out = _PosAtt.apply(values, lmda.reshape(-1), plan, n_head, concat, head_is_scale, param, slot, coord_dims, c,
-                        out_bf16, link)
+                        out_bf16, link, *meshes)
     if link is not None and link.get("rowstat") is not None:
         out._pit_satt = link
     elif concat and plan.self_attn and not plan.masked and plan.nbr_idx is None and not coord_dims:

@@ -142,12 +142,24 @@ class posatt(nn.Module):
         if self._overridden():
             inputs = ops.materialize_coords(inputs)
             return torch.cat((inputs, self._composed(mesh, mesh, inputs)), dim=-1)
+        if ops.mesh_grad_wanted(mesh):           # d(mesh) through the layer: refused up front for what it does not cover
+            ops._check_mesh_grad(self._metric)
+            plan = self._plan(mesh, mesh, True)
+            return ops.posatt_apply(ops.materialize_coords(inputs), self.lmda, plan, self.n_head, concat=True,
+                                    mesh_out=mesh, mesh_in=mesh)
         plan = self._plan(mesh, mesh, True)
         return ops.posatt_apply(inputs, self.lmda, plan, self.n_head, concat=True)
 
     def _cross(self, mesh_out, mesh_in, inputs, out_bf16: bool = False):
         if self._overridden():
             return self._composed(mesh_out, mesh_in, inputs)
+        if ops.mesh_grad_wanted(mesh_out, mesh_in):
+            # d(mesh) through the layer: no bf16 output, no fused coordinate read - the concat is materialised so that its
+            # coordinate channels pass their gradient to mesh_in as well
+            ops._check_mesh_grad(self._metric)
+            plan = self._plan(mesh_out, mesh_in, False)
+            return ops.posatt_apply(ops.materialize_coords(inputs), self.lmda, plan, self.n_head, concat=False,
+                                    mesh_out=mesh_out, mesh_in=mesh_in)
         plan = self._plan(mesh_out, mesh_in, False)
         if out_bf16:                             # (pit.decoder, bf16 mode: the result feeds a kaiming_mlp that reads bf16)
             return ops.posatt_apply(ops.materialize_coords(inputs), self.lmda, plan, self.n_head, concat=False, out_bf16=True)
@@ -167,9 +179,12 @@ class posatt(nn.Module):
         (``scale`` is the lmda parameter, as in the reference).  Built by running the fused HIP
         kernel on the identity as values, so it is exactly the matrix ``forward`` applies - there
         is no second, eager implementation of the mask/softmax; ``forward`` never builds it."""
+        if ops.mesh_grad_wanted(mesh_out, mesh_in):
+            ops._check_mesh_grad(self._metric)
         plan = ops.MeshPlan(self._metric, mesh_out, mesh_in, float(locality), False)
         eye = torch.eye(plan.n_in, device=mesh_in.device).unsqueeze(0).repeat(plan.mesh_batch, 1, 1)
-        att = ops.posatt_apply(eye, scale, plan, self.n_head, concat=False)          # (mb, L_out, H*L_in)
+        att = ops.posatt_apply(eye, scale, plan, self.n_head, concat=False, mesh_out=mesh_out,
+                               mesh_in=mesh_in)                                   # (mb, L_out, H*L_in)
         att = att.reshape(plan.mesh_batch, plan.n_out, self.n_head, plan.n_in).permute(0, 2, 1, 3)
         return att if self._batched else att[0]
 
@@ -257,6 +272,18 @@ class pit(nn.Module):
                                   for _ in range(self.n_blocks)])
         self.up = posatt_cross(self.n_head, self.hid_dim, self.de_local)
         self.de = kaiming_mlp(self.n_head * self.hid_dim, self.hid_dim, self.out_dim)
+
+    def _mesh_grad(self, *meshes) -> bool:
+        """The per-layer path for gradients w.r.t. the meshes: grad mode on and one of ``meshes`` (or ``self.mesh_ltt``) requires
+        grad.  Then every attention layer runs on its own (_PosAtt with the meshes as inputs), none of the fused launches does.
+        What that path does not cover (periodic metrics, the bf16 math mode) raises here, before anything is launched."""
+        if not ops.mesh_grad_wanted(self.mesh_ltt, *meshes):
+            return False
+        for m in (self.down, *self.conv, self.up):
+            if isinstance(m, posatt):
+                ops._check_mesh_grad(m._metric)
+        ops._check_mesh_grad("euclid")
+        return True
 
     @staticmethod
     def _mlp_gelu(layer, x, concat_heads: int = 0):
@@ -349,6 +376,8 @@ class pit(nn.Module):
         return plan if ops.edge_fusion_supported(plan, up.n_head, hid, batch, True) else None
 
     def encoder(self, mesh_in, func_in, mesh_ltt):
+        if self._mesh_grad(mesh_in, mesh_ltt):
+            return self._mlp_gelu(self.en_layer, self.down(mesh_ltt, mesh_in, func_in), self._heads_of_block(0, self.hid_dim))
         # the fused processor's weights depend on (mesh_ltt, lmda) only: they are formed by extra workgroups of the
         # encoder-side launch (ops.early_block_weights) instead of a launch of their own; processor() picks them up
         early = None
@@ -438,6 +467,10 @@ class pit(nn.Module):
         return ops.block_weights(plan, [a.lmda for a in self.conv], heads, need_q)
 
     def processor(self, func_ltt, mesh_ltt):
+        if self._mesh_grad(mesh_ltt):
+            for i, (a, w) in enumerate(zip(self.conv, self.mlp)):
+                func_ltt = self._mlp_gelu(w, a(mesh_ltt, func_ltt), self._heads_of_block(i + 1, self.hid_dim))
+            return func_ltt
         fused = self._fused_processor(func_ltt, mesh_ltt)
         if fused is not None:
             return fused
@@ -487,6 +520,8 @@ class pit(nn.Module):
         # and with it the decoder MLP's saved activations and their gradients are kept in memory as bf16 when the
         # decoder MLP's shape runs on the kernels that read them (ops.mlp_bf16_io_supported); fp32 accumulation throughout
         de, up = self.de, self.up
+        if self._mesh_grad(mesh_ltt, mesh_out):
+            return de(up(mesh_out, mesh_ltt, func_ltt))
         # small regime on batch-free meshes: up-projection + decoder MLP as ONE launch per direction (every math mode: the
         # launch is latency-bound and contracts in fp32, like the fused processor blocks)
         if torch.is_tensor(func_ltt) and func_ltt.is_cuda and func_ltt.dim() == 3 and func_ltt.dtype == torch.float32 \

@@ -39,6 +39,7 @@ class _FixedMeshForward:
     residual = False
 
     def forward(self, mesh_in, func_in, mesh_out):
+        self._mesh_grad(mesh_in, mesh_out)          # (refuses what the mesh-gradient path does not cover, before any launch)
         size = mesh_out.shape[:-1]
         batch = func_in.shape[0]
         mesh_in = mesh_in.reshape(-1, self.space_dim)
@@ -102,6 +103,7 @@ class pit_elasticity(P.pit):
         self.en_layer = P.kaiming_mlp(self.n_head * self.in_dim, self.hid_dim, self.hid_dim)
 
     def forward(self, mesh_in, func_in, mesh_out):
+        self._mesh_grad(mesh_in, mesh_out)
         size = mesh_out.shape[:-1]
         mesh_ltt = mesh_out
         ltt = self.encoder(mesh_in, func_in, mesh_ltt)
@@ -126,6 +128,7 @@ class pit_naca(P.pit):
         return ltt.reshape(b, -1, self.space_dim), mesh_out.reshape(b, -1, self.space_dim)
 
     def forward(self, mesh_in, func_in, mesh_out):
+        self._mesh_grad(mesh_in, mesh_out)
         size = mesh_out.shape[:-1]
         mesh_ltt, mesh_flat = self.ltt_mesh(mesh_out)
         ltt = self.encoder(mesh_in, func_in, mesh_ltt)
