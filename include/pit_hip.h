@@ -18,7 +18,13 @@
  * posatt_fixed / _periodic1d / _periodic2d (pit.py:129-144,186-200,243-258) where
  * the attention weights are shared by the whole batch, and = b for the per-sample
  * meshes of posatt (pit.py:46-52).  Meshes are (mesh_batch, n, space_dim) contiguous,
- * space_dim in {1,2,3}.
+ * 1 <= space_dim <= PIT_MAX_SPACE_DIM (ABI 26; 1..3 before) for pit_select_wide_fwd, pit_plan_fwd, pit_neighbors_fwd,
+ * pit_posatt_fwd / _fwd_job / _bwd, pit_posatt_dmesh and its workspace query: with 4..8 coordinates these run per-layer
+ * kernels (streaming selection passes, dense rows / cols, candidate-list rows / cols, wave-per-row / per-key mesh
+ * gradients).  pit_select_fwd keeps 1..3 (PIT_ERR_SIZE beyond).  The fused entries keep 1..3: pit_block_weights,
+ * pit_slab_plan_build, pit_encoder_fwd / _bwd return PIT_ERR_SIZE, pit_satt_fwd / _bwd PIT_ERR_UNSUPPORTED; their
+ * *_supported predicates do not see space_dim, so the caller routes around them (ops.py does).  Distances follow
+ * ATen-CPU's summation order for torch.sum.
  */
 #ifndef PIT_HIP_H
 #define PIT_HIP_H
@@ -27,7 +33,8 @@
 extern "C" {
 #endif
 
-#define PIT_ABI_VERSION 25
+#define PIT_ABI_VERSION 26
+#define PIT_MAX_SPACE_DIM 8   /* largest space_dim any entry accepts */
 #define PIT_DSCALE_SLOTS 1024 /* fp64 accumulators per head in pit_posatt_bwd's workspace */
 
 /* distance metric (dist2att variants) */
@@ -105,6 +112,10 @@ int pit_head_scale(const float* lmda, int n_head, float* scale_out, void* stream
 int pit_select_fwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
                    int space_dim, int metric, float period, int rank_k, int need_kth,
                    float* stats, void* stream);
+/* pit_select_fwd for 1 <= space_dim <= PIT_MAX_SPACE_DIM (ABI 26); pit_select_fwd itself keeps space_dim in {1,2,3}. */
+int pit_select_wide_fwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                        int space_dim, int metric, float period, int rank_k, int need_kth,
+                        float* stats, void* stream);
 
 /* The transposed lists (key -> listing rows) of candidate lists that were built WITHOUT them (rev_ptr = NULL in pit_plan_fwd /
  * pit_neighbors_fwd): round 4 - per-sample plans are rebuilt every step and only a backward that walks the lists by key

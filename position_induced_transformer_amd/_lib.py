@@ -50,6 +50,7 @@ SIGNATURES = {
     "pit_error_string": [_I],
     "pit_head_scale": [_P, _I, _P, _P],
     "pit_select_fwd": [_P, _P, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P],
+    "pit_select_wide_fwd": [_P, _P, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P],
     "pit_plan_fwd": [_P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P],
     "pit_lists_transpose": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
     "pit_neighbors_fwd": [_P, _P, _I, _I, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _P, _P],
@@ -137,7 +138,7 @@ SIGNATURES = {
 }
 
 LONG_RETURN = {"pit_satt_tiles_elems", "pit_posatt_dmesh_workspace"}
-ABI_VERSION = 25       # PIT_ABI_VERSION of include/pit_hip.h this binding was written against
+ABI_VERSION = 26       # PIT_ABI_VERSION of include/pit_hip.h this binding was written against
 
 _lib = None
 

@@ -77,6 +77,65 @@ __device__ __forceinline__ float sq_dist3t(float ox, float oy, float oz, float i
     return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
 }
 
+// Meshes with 4..8 coordinates (space_dim 4..8).  Kernels that take them are instantiated with a compile-time maximum
+// MAXD in {4, 8}: MAXD 4 is the (x, y, z, 0) float4 of every existing instance, MAXD 8 holds c0..c3 in lo and c4..c7 in hi,
+// zero-padded.  The squared distance follows ATen-CPU's order for torch.sum over the last axis:
+// left to right for d <= 4 and d = 8; for d = 5, 6, 7 the first four terms are partial sums of an unrolled loop, so
+// ((((q0 + q4) + q5) + q6) + q1) + q2) + q3 with the missing q5/q6 left out (adding +0 leaves the value unchanged).
+struct pt8 { float4 lo, hi; };
+template <int MAXD> struct mesh_pt { using type = float4; };
+template <> struct mesh_pt<8> { using type = pt8; };
+template <int MAXD> using mesh_pt_t = typename mesh_pt<MAXD>::type;
+
+template <bool PERIODIC>
+__device__ __forceinline__ float sq_term(float o, float i, float period) {
+    float d = __fsub_rn(o, i);
+    if (PERIODIC) { d = fabsf(d); d = fminf(d, __fsub_rn(period, d)); }
+    return __fmul_rn(d, d);
+}
+template <bool PERIODIC>
+__device__ __forceinline__ float sq_dist8t(const pt8& o, const pt8& i, int used, float period) {
+    const float q0 = sq_term<PERIODIC>(o.lo.x, i.lo.x, period), q1 = sq_term<PERIODIC>(o.lo.y, i.lo.y, period);
+    const float q2 = sq_term<PERIODIC>(o.lo.z, i.lo.z, period), q3 = sq_term<PERIODIC>(o.lo.w, i.lo.w, period);
+    const float q4 = sq_term<PERIODIC>(o.hi.x, i.hi.x, period), q5 = sq_term<PERIODIC>(o.hi.y, i.hi.y, period);
+    const float q6 = sq_term<PERIODIC>(o.hi.z, i.hi.z, period), q7 = sq_term<PERIODIC>(o.hi.w, i.hi.w, period);
+    if (used >= 5 && used <= 7)
+        return __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(q0, q4), q5), q6), q1), q2), q3);
+    return __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(q0, q1), q2), q3), q4), q5), q6), q7);
+}
+// one call for either point type: the float4 form is exactly sq_dist3t / sq_dist3 (`used` is not read)
+template <bool PERIODIC>
+__device__ __forceinline__ float sq_distp(const float4& o, const float4& i, int used, float period) {
+    (void)used;
+    return sq_dist3t<PERIODIC>(o.x, o.y, o.z, i.x, i.y, i.z, period);
+}
+template <bool PERIODIC>
+__device__ __forceinline__ float sq_distp(const pt8& o, const pt8& i, int used, float period) {
+    return sq_dist8t<PERIODIC>(o, i, used, period);
+}
+__device__ __forceinline__ float sq_distp(const float4& o, const float4& i, int used, bool periodic, float period) {
+    (void)used;
+    return sq_dist3(o.x, o.y, o.z, i.x, i.y, i.z, periodic, period);
+}
+__device__ __forceinline__ float sq_distp(const pt8& o, const pt8& i, int used, bool periodic, float period) {
+    return periodic ? sq_dist8t<true>(o, i, used, period) : sq_dist8t<false>(o, i, used, period);
+}
+// coordinate k (< 8) of a point
+__device__ __forceinline__ float pt_coord(const pt8& p, int k) {
+    const float4& v = k < 4 ? p.lo : p.hi;
+    switch (k & 3) { case 0: return v.x; case 1: return v.y; case 2: return v.z; default: return v.w; }
+}
+// point `idx` of a contiguous (n, sdim) mesh through plain loads, coordinates from `used` on as 0
+__device__ __forceinline__ pt8 load_pt8(const float* mesh, long idx, int sdim, int used) {
+    const float* p = mesh + idx * sdim;
+    pt8 v;
+    v.lo.x = p[0];
+    v.lo.y = used > 1 ? p[1] : 0.0f; v.lo.z = used > 2 ? p[2] : 0.0f; v.lo.w = used > 3 ? p[3] : 0.0f;
+    v.hi.x = used > 4 ? p[4] : 0.0f; v.hi.y = used > 5 ? p[5] : 0.0f;
+    v.hi.z = used > 6 ? p[6] : 0.0f; v.hi.w = used > 7 ? p[7] : 0.0f;
+    return v;
+}
+
 // ATen's lerp as torch.quantile applies it.
 __device__ __forceinline__ float quantile_lerp(float a, float b, float w) {
     float diff = __fsub_rn(b, a);

@@ -348,6 +348,124 @@ __global__ __launch_bounds__(256) void dmesh_cols_lists(DmArgs a) {
         for (int k = 0; k < a.sdim; ++k) a.cols_ws[((long)s * a.n_in + key) * a.sdim + k] = (float)dy[k];
 }
 
+// ---- meshes with 4..8 coordinates (space_dim 4..8) ------------------------------------------------------------------
+// The forward's distances (pit_common.h sq_dist8t: ATen-CPU's summation order) and the same closed form as above, with a
+// wave per row / per key for dense and candidate-list layers alike: a dense layer scans every key / row (as an overflowed
+// list does).  Not optimised.
+__device__ __forceinline__ float pt8_at(const pt8& p, int k) { return pt_coord(p, k); }
+__device__ __forceinline__ double pt8_sel(const double (&v)[8], int k) {
+    double r = v[0];
+#pragma unroll
+    for (int i = 1; i < 8; ++i) r = (k == i) ? v[i] : r;
+    return r;
+}
+
+// grid (ceil(n_out / 4), batch), four waves, a wave per row
+__global__ __launch_bounds__(256) void dmesh_rows_wide(DmArgs a) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int row = blockIdx.x * 4 + wave, s = blockIdx.y;
+    if (row >= a.n_out) return;                                    // (wave-uniform; no barriers below)
+    const int mb = a.mesh_batch == 1 ? 0 : s;
+    const long rid = (long)mb * a.n_out + row;
+    const pt8 x = load_pt8(a.mesh_out, rid, a.sdim, a.sdim);
+    const bool sparse = a.nbr_idx != nullptr;
+    const int cnt = sparse ? a.nbr_cnt[rid] : a.n_in;
+    const bool scan_all = !sparse || cnt > a.cap;
+    const int total = scan_all ? a.n_in : cnt;
+    const int* list = sparse ? a.nbr_idx + rid * a.cap : nullptr;
+    const int masked = sparse ? 1 : a.masked;
+    double dx[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int h = 0; h < a.n_head; ++h) {
+        const float c = head_c(a, h);
+        const float4 rs = row_stat(a, mb, h, row);
+        double A = 0.0, B[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, C[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int base = 0; base < total; base += 64) {
+            const int e = base + lane;
+            const bool valid = e < total;
+            const int j = valid ? (scan_all ? e : list[e]) : 0;
+            const pt8 y = load_pt8(a.mesh_in, (long)mb * a.n_in + j, a.sdim, a.sdim);
+            const float p = weight(sq_dist8t<false>(x, y, a.sdim, 0.0f), c, rs, valid, masked);
+            unsigned long long mask = __builtin_amdgcn_ballot_w64(p != 0.0f);
+            while (mask) {
+                const int src = __builtin_ctzll(mask);
+                mask &= mask - 1ull;
+                const int jj = __builtin_amdgcn_readlane(j, src);
+                const double pp = (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), src));
+                const double gv = (double)wave_dot(a, s, h, row, jj);
+                A += pp * gv;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const float yk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pt8_at(y, k)), src));
+                    const float d = __fsub_rn(yk, pt8_at(x, k));
+                    B[k] += pp * gv * d;
+                    C[k] += pp * d;
+                }
+            }
+        }
+        if (lane == 0) a.a_ws[((long)s * a.n_head + h) * a.n_out + row] = (float)A;
+        const double c2 = 2.0 * (double)c;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) dx[k] += c2 * (B[k] - A * C[k]);
+    }
+    if (lane == 0)
+        for (int k = 0; k < a.sdim; ++k) a.rows_ws[((long)s * a.n_out + row) * a.sdim + k] = (float)pt8_sel(dx, k);
+}
+
+// grid (ceil(n_in / 4), batch), four waves, a wave per key
+__global__ __launch_bounds__(256) void dmesh_cols_wide(DmArgs a) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int key = blockIdx.x * 4 + wave, s = blockIdx.y;
+    if (key >= a.n_in) return;
+    const int mb = a.mesh_batch == 1 ? 0 : s;
+    const pt8 y = load_pt8(a.mesh_in, (long)mb * a.n_in + key, a.sdim, a.sdim);
+    const bool sparse = a.nbr_idx != nullptr;
+    const int masked = sparse ? 1 : a.masked;
+    double dy[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int h = 0; h < a.n_head; ++h) {
+        const float c = head_c(a, h);
+        const float* arow = a.a_ws + ((long)s * a.n_head + h) * a.n_out;
+        double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        auto add = [&](int nrow, bool valid) {
+            const pt8 x = load_pt8(a.mesh_out, (long)mb * a.n_out + nrow, a.sdim, a.sdim);
+            const float p = weight(sq_dist8t<false>(x, y, a.sdim, 0.0f), c, row_stat(a, mb, h, nrow), valid, masked);
+            unsigned long long mask = __builtin_amdgcn_ballot_w64(p != 0.0f);
+            while (mask) {
+                const int src = __builtin_ctzll(mask);
+                mask &= mask - 1ull;
+                const int ii = __builtin_amdgcn_readlane(nrow, src);
+                const double pp = (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), src));
+                const double t = pp * ((double)wave_dot(a, s, h, ii, key) - (double)arow[ii]);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const float xk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pt8_at(x, k)), src));
+                    acc[k] += t * __fsub_rn(xk, pt8_at(y, k));
+                }
+            }
+        };
+        if (sparse) {
+            const int beg = a.rev_ptr[(long)mb * (a.n_in + 1) + key], end = a.rev_ptr[(long)mb * (a.n_in + 1) + key + 1];
+            const int* rrow = a.rev_row + (long)mb * a.n_out * a.cap;
+            for (int base = beg; base < end; base += 64) {
+                const int e = base + lane;
+                const int nrow = (e < end) ? rrow[e] : -1;     // -1: slot of a row that overflowed its list
+                add(nrow >= 0 ? nrow : 0, nrow >= 0);
+            }
+        }
+        if (!sparse || !a.complete) {                          // dense layers: every row; lists: the rows that overflowed
+            for (int base = 0; base < a.n_out; base += 64) {
+                const int nrow = base + lane;
+                const bool valid = nrow < a.n_out && (!sparse || a.nbr_cnt[(long)mb * a.n_out + nrow] > a.cap);
+                add(valid ? nrow : 0, valid);
+            }
+        }
+        const double c2 = 2.0 * (double)c;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) dy[k] += c2 * acc[k];
+    }
+    if (lane == 0)
+        for (int k = 0; k < a.sdim; ++k) a.cols_ws[((long)s * a.n_in + key) * a.sdim + k] = (float)pt8_sel(dy, k);
+}
+
 // ---- fixed-order reduction over the samples --------------------------------------------------------------------------
 // out (mesh_batch, n, sdim) = [out +] sum over the samples that share the mesh of ws (batch, n, sdim), in sample order
 __global__ __launch_bounds__(256) void dmesh_reduce(const float* __restrict__ ws, int batch, int mesh_batch, long per,
@@ -372,7 +490,7 @@ long ws_floats(int batch, int n_out, int n_in, int space_dim, int n_head) {
 
 extern "C" long pit_posatt_dmesh_workspace(int mesh_batch, int n_out, int n_in, int space_dim, int batch, int n_head) {
     (void)mesh_batch;
-    if (n_out <= 0 || n_in <= 0 || space_dim < 1 || space_dim > 3 || batch <= 0 || n_head <= 0) return 0;
+    if (n_out <= 0 || n_in <= 0 || space_dim < 1 || space_dim > PIT_MAX_SPACE_DIM || batch <= 0 || n_head <= 0) return 0;
     return ws_floats(batch, n_out, n_in, space_dim, n_head) * 4;
 }
 
@@ -392,7 +510,7 @@ extern "C" int pit_posatt_dmesh(const float* mesh_out, const float* mesh_in, int
     }
     if (!mesh_out || !mesh_in || !values || !head || !rowstat || !d_out || !workspace) return PIT_ERR_NULL;
     if (mesh_batch <= 0 || n_out <= 0 || n_in <= 0 || batch <= 0 || dim <= 0 || n_head <= 0) return PIT_ERR_SIZE;
-    if (space_dim < 1 || space_dim > 3 || (mesh_batch != 1 && mesh_batch != batch) || out_col0 < 0) return PIT_ERR_SIZE;
+    if (space_dim < 1 || space_dim > PIT_MAX_SPACE_DIM || (mesh_batch != 1 && mesh_batch != batch) || out_col0 < 0) return PIT_ERR_SIZE;
     if (batch > 65535 || n_head > 65535) return PIT_ERR_UNSUPPORTED;
     if (ld_values < dim || ld_dout < out_col0 + (long)n_head * dim || values_bstride < 0 || dout_bstride < 0) return PIT_ERR_SIZE;
     const bool sparse = masked && nbr_idx && nbr_cnt;
@@ -421,7 +539,9 @@ extern "C" int pit_posatt_dmesh(const float* mesh_out, const float* mesh_in, int
     a.cols_ws = a.rows_ws + (long)batch * n_out * space_dim;
     hipStream_t st = (hipStream_t)stream;
     // rows pass: d mesh_out and the a_i the cols pass needs
-    if (sparse) hipLaunchKernelGGL(dmesh_rows_lists, dim3((unsigned)((n_out + 3) / 4), (unsigned)batch), dim3(256), 0, st, a);
+    if (!sparse) { a.nbr_idx = nullptr; a.nbr_cnt = nullptr; }
+    if (space_dim > 3) hipLaunchKernelGGL(dmesh_rows_wide, dim3((unsigned)((n_out + 3) / 4), (unsigned)batch), dim3(256), 0, st, a);
+    else if (sparse) hipLaunchKernelGGL(dmesh_rows_lists, dim3((unsigned)((n_out + 3) / 4), (unsigned)batch), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(dmesh_rows_dense, dim3((unsigned)((n_out + 31) / 32), (unsigned)batch), dim3(64), 0, st, a);
     PIT_CHECK_LAUNCH();
     if (d_mesh_out) {
@@ -431,7 +551,8 @@ extern "C" int pit_posatt_dmesh(const float* mesh_out, const float* mesh_in, int
         PIT_CHECK_LAUNCH();
     }
     if (d_mesh_in) {
-        if (sparse) hipLaunchKernelGGL(dmesh_cols_lists, dim3((unsigned)((n_in + 3) / 4), (unsigned)batch), dim3(256), 0, st, a);
+        if (space_dim > 3) hipLaunchKernelGGL(dmesh_cols_wide, dim3((unsigned)((n_in + 3) / 4), (unsigned)batch), dim3(256), 0, st, a);
+        else if (sparse) hipLaunchKernelGGL(dmesh_cols_lists, dim3((unsigned)((n_in + 3) / 4), (unsigned)batch), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(dmesh_cols_dense, dim3((unsigned)((n_in + 31) / 32), (unsigned)batch), dim3(64), 0, st, a);
         PIT_CHECK_LAUNCH();
         // self attention (d_mesh_in == d_mesh_out): the key terms add onto the row terms just written

@@ -166,6 +166,33 @@ __device__ __forceinline__ float4 load_point4(__amdgpu_buffer_rsrc_t r, unsigned
     v.w = 0.0f;
     return v;
 }
+// the same for a compile-time maximum of coordinates (pit_common.h: mesh_pt_t): MAXD 4 is load_point4
+template <int MAXD>
+__device__ __forceinline__ mesh_pt_t<MAXD> load_pointp(__amdgpu_buffer_rsrc_t r, unsigned bytes, long idx, int sdim, int used) {
+    if constexpr (MAXD > 4) {
+        const unsigned base = (unsigned)(idx * sdim) * 4u;
+        pt8 v;
+        v.lo.x = buf_load(r, base);
+        v.lo.y = buf_load(r, used > 1 ? base + 4u : bytes);
+        v.lo.z = buf_load(r, used > 2 ? base + 8u : bytes);
+        v.lo.w = buf_load(r, used > 3 ? base + 12u : bytes);
+        v.hi.x = buf_load(r, used > 4 ? base + 16u : bytes);
+        v.hi.y = buf_load(r, used > 5 ? base + 20u : bytes);
+        v.hi.z = buf_load(r, used > 6 ? base + 24u : bytes);
+        v.hi.w = buf_load(r, used > 7 ? base + 28u : bytes);
+        return v;
+    } else {
+        return load_point4(r, bytes, idx, sdim, used);
+    }
+}
+// a row record of the cols kernel: the point and the row's threshold T ({xo.xyz, T} as one float4 for MAXD 4)
+struct rec8 { pt8 x; float t; };
+template <int MAXD> struct col_rec { using type = float4; };
+template <> struct col_rec<8> { using type = rec8; };
+__device__ __forceinline__ const float4& rec_pt(const float4& r) { return r; }
+__device__ __forceinline__ float rec_t(const float4& r) { return r.w; }
+__device__ __forceinline__ const pt8& rec_pt(const rec8& r) { return r.x; }
+__device__ __forceinline__ float rec_t(const rec8& r) { return r.t; }
 
 // Cross-wave reduction as a reduce-scatter through LDS: every wave parks its partial tile (and NX
 // per-lane scalars), one barrier, then wave w sums and owns accumulator registers
@@ -214,11 +241,12 @@ __device__ __forceinline__ float summed(const float* red, int nwaves, int q, int
 // key instead of four 4-B loads (bare-loop measurements, tools/micro/mfma_mix.hip: a dword load per fp32 MFMA caps
 // the matrix pipe at ~100 of 154 TF/s whatever the occupancy, a dwordx4 per four MFMAs at ~125) - and its four
 // results of a row are adjacent too (16-B stores).  Needs 16-B aligned rows and dim % 4 == 0 (launch_rows checks).
-template <int CT, int MODE, bool MASKED, bool BF, int NPX = 0, bool IL = false>
+template <int CT, int MODE, bool MASKED, bool BF, int NPX = 0, bool IL = false, int MAXD = 4>
 __device__ __forceinline__ void posatt_rows_body(const AttArgs& a, const int bx, const int by, const int bz) {
     static_assert(!IL || CT == 4, "interleaved tiles are the CT == 4 layout");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float4* s_xi = reinterpret_cast<float4*>(smem);
+    using PT = mesh_pt_t<MAXD>;
+    PT* s_xi = reinterpret_cast<PT*>(smem);
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
     const int half = lane >> 5, l31 = lane & 31;
@@ -240,7 +268,7 @@ __device__ __forceinline__ void posatt_rows_body(const AttArgs& a, const int bx,
     const unsigned mi_bytes = (unsigned)((long)a.mesh_batch * a.n_in * a.sdim * 4);
     const __amdgpu_buffer_rsrc_t rmo = make_rsrc(a.mesh_out, mo_bytes);
     const __amdgpu_buffer_rsrc_t rmi = make_rsrc(a.mesh_in, mi_bytes);
-    const float4 xo = load_point4(rmo, mo_bytes, rowid, a.sdim, a.coords_used);
+    const PT xo = load_pointp<MAXD>(rmo, mo_bytes, rowid, a.sdim, a.coords_used);
     float T = __builtin_inff(), s_min = 0.0f, inv_l = 0.0f, mbar = 0.0f;
     if (MODE == 0) {
         if (MASKED) {
@@ -387,14 +415,14 @@ __device__ __forceinline__ void posatt_rows_body(const AttArgs& a, const int bx,
             auto weights = [&](float (&pw)[NP], bool (&anyk)[NP / 4], int st, auto full_tag) {
                 constexpr bool FULL = decltype(full_tag)::value;
                 const int jj = jb + st * 2 * NP;
-                const float4* xk = s_xi + hk;                          // this half-wave's keys: s_xi[jj + koff + hk]
+                const PT* xk = s_xi + hk;                          // this half-wave's keys: s_xi[jj + koff + hk]
 #pragma unroll
                 for (int q = 0; q < NP / 4; ++q) anyk[q] = false;
 #pragma unroll
                 for (int u = 0; u < NP; ++u) {
                     const int koff = 8 * (u / 4) + (BF ? (u % 4) : 2 * (u % 4));
                     bool jv = true;
-                    float4 xi;
+                    PT xi;
                     if (FULL) {
                         xi = xk[jj + koff];
                     } else {
@@ -402,7 +430,9 @@ __device__ __forceinline__ void posatt_rows_body(const AttArgs& a, const int bx,
                         jv = jl < je;
                         xi = s_xi[jv ? jl : jb];
                     }
-                    const float m = sq_dist3t<PER>(xo.x, xo.y, xo.z, xi.x, xi.y, xi.z, a.period);
+                    float m;                                               // (MAXD 4: the code of the existing instances)
+                    if constexpr (MAXD > 4) m = sq_dist8t<PER>(xo, xi, a.coords_used, a.period);
+                    else m = sq_dist3t<PER>(xo.x, xo.y, xo.z, xi.x, xi.y, xi.z, a.period);
                     const float sv = __fmul_rn(m, c);
                     bool keep = jv;
                     if (MASKED) keep = keep && (sv <= T);
@@ -461,7 +491,7 @@ __device__ __forceinline__ void posatt_rows_body(const AttArgs& a, const int bx,
             __syncthreads();
 #pragma unroll 4
             for (int idx = threadIdx.x; idx < len; idx += blockDim.x)
-                s_xi[idx] = load_point4(rmi, mi_bytes, (long)mb * a.n_in + jc0 + idx, a.sdim, a.coords_used);
+                s_xi[idx] = load_pointp<MAXD>(rmi, mi_bytes, (long)mb * a.n_in + jc0 + idx, a.sdim, a.coords_used);
             __syncthreads();
             // Software pipeline: while the MFMAs of step st run, the vector ALU already forms the weights
             // of step st+1 (independent work in ONE basic block, so the scheduler interleaves them) and the
@@ -655,12 +685,14 @@ __global__ __launch_bounds__(512) void posatt_rows_kernel(AttArgs a) {
 // ------------------------------------------------------------------------------------
 // cols kernel: d values
 // ------------------------------------------------------------------------------------
-template <int CT, bool MASKED, bool BF, int NPX = 0, bool IL = false>
+template <int CT, bool MASKED, bool BF, int NPX = 0, bool IL = false, int MAXD = 4>
 __device__ __forceinline__ void posatt_cols_body(const AttArgs& a, const int bx, const int by, const int bz) {
     static_assert(!IL || CT == 4, "interleaved tiles are the CT == 4 layout (see posatt_rows_body)");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float4* s_rec = reinterpret_cast<float4*>(smem);                   // [ROW_CHUNK] {xo.xyz, T}
-    float2* s_nrm = reinterpret_cast<float2*>(smem + ROW_CHUNK * sizeof(float4));   // [ROW_CHUNK] {S_min, 1/L}
+    using PT = mesh_pt_t<MAXD>;
+    using RT = typename col_rec<MAXD>::type;
+    RT* s_rec = reinterpret_cast<RT*>(smem);                           // [ROW_CHUNK] {xo.xyz, T}
+    float2* s_nrm = reinterpret_cast<float2*>(smem + ROW_CHUNK * sizeof(RT));   // [ROW_CHUNK] {S_min, 1/L}
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
     const int half = lane >> 5, l31 = lane & 31;
@@ -674,7 +706,7 @@ __device__ __forceinline__ void posatt_cols_body(const AttArgs& a, const int bx,
     const unsigned mi_bytes = (unsigned)((long)a.mesh_batch * a.n_in * a.sdim * 4);
     const __amdgpu_buffer_rsrc_t rmo = make_rsrc(a.mesh_out, mo_bytes);
     const __amdgpu_buffer_rsrc_t rmi = make_rsrc(a.mesh_in, mi_bytes);
-    const float4 xi = load_point4(rmi, mi_bytes, (long)mb * a.n_in + (jvalid ? j : a.n_in - 1), a.sdim, a.coords_used);
+    const PT xi = load_pointp<MAXD>(rmi, mi_bytes, (long)mb * a.n_in + (jvalid ? j : a.n_in - 1), a.sdim, a.coords_used);
 
     const __amdgpu_buffer_rsrc_t rdout = make_rsrc(a.d_out, a.dout_bytes);
     const unsigned ldd4 = (unsigned)a.ld_dout * 4u;
@@ -765,7 +797,7 @@ __device__ __forceinline__ void posatt_cols_body(const AttArgs& a, const int bx,
                 auto weights = [&](float (&pw)[NP], bool (&anyk)[NP / 4], int st, auto full_tag) {
                     constexpr bool FULL = decltype(full_tag)::value;
                     const int nn = nb + st * 2 * NP;
-                    const float4* rk = s_rec + hk;
+                    const RT* rk = s_rec + hk;
                     const float2* nk = s_nrm + hk;
 #pragma unroll
                     for (int q = 0; q < NP / 4; ++q) anyk[q] = false;
@@ -773,7 +805,7 @@ __device__ __forceinline__ void posatt_cols_body(const AttArgs& a, const int bx,
                     for (int u = 0; u < NP; ++u) {
                         const int koff = 8 * (u / 4) + (BF ? (u % 4) : 2 * (u % 4));
                         bool nv = true;
-                        float4 r0;
+                        RT r0;
                         float2 r1;
                         if (FULL) {
                             r0 = rk[nn + koff];
@@ -784,10 +816,12 @@ __device__ __forceinline__ void posatt_cols_body(const AttArgs& a, const int bx,
                             r0 = s_rec[nv ? nl : nb];
                             r1 = s_nrm[nv ? nl : nb];
                         }
-                        const float m = sq_dist3t<PER>(r0.x, r0.y, r0.z, xi.x, xi.y, xi.z, a.period);
+                        float m;
+                        if constexpr (MAXD > 4) m = sq_dist8t<PER>(rec_pt(r0), xi, a.coords_used, a.period);
+                        else m = sq_dist3t<PER>(r0.x, r0.y, r0.z, xi.x, xi.y, xi.z, a.period);
                         const float sv = __fmul_rn(m, c);
                         bool keep = nv;
-                        if (MASKED) keep = keep && (sv <= r0.w);
+                        if (MASKED) keep = keep && (sv <= rec_t(r0));
                         float p = __expf(r1.x - sv) * r1.y;
                         if (MASKED || !FULL) p = keep ? p : 0.0f;
                         pw[u] = p;
@@ -837,10 +871,12 @@ __device__ __forceinline__ void posatt_cols_body(const AttArgs& a, const int bx,
 #pragma unroll 2
                 for (int idx = threadIdx.x; idx < len; idx += blockDim.x) {
                     const long rowid = (long)mb * a.n_out + nc0 + idx;
-                    const float4 xo = load_point4(rmo, mo_bytes, rowid, a.sdim, a.coords_used);
+                    const PT xo = load_pointp<MAXD>(rmo, mo_bytes, rowid, a.sdim, a.coords_used);
                     const float4 rs4 = *reinterpret_cast<const float4*>(
                         a.rowstat + (((long)mb * a.n_head + h) * a.n_out + nc0 + idx) * 4);
-                    float4 r0; r0.x = xo.x; r0.y = xo.y; r0.z = xo.z; r0.w = rs4.x;
+                    RT r0;
+                    if constexpr (MAXD > 4) { r0.x = xo; r0.t = rs4.x; }
+                    else { r0.x = xo.x; r0.y = xo.y; r0.z = xo.z; r0.w = rs4.x; }
                     s_rec[idx] = r0;
                     s_nrm[idx] = make_float2(rs4.y, rs4.z);
                 }
@@ -973,6 +1009,15 @@ __device__ __forceinline__ void posatt_cols_body(const AttArgs& a, const int bx,
 template <int CT, bool MASKED, bool BF, bool IL = false>
 __global__ __launch_bounds__(512) void posatt_cols_kernel(AttArgs a) {
     posatt_cols_body<CT, MASKED, BF, 0, IL>(a, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+// meshes with 4..8 coordinates (space_dim 4..8): one column tile per workgroup, MAXD 8 points (launch_rows8 / launch_cols8)
+template <int MODE, bool MASKED, bool BF>
+__global__ __launch_bounds__(512) void posatt_rows_kernel8(AttArgs a) {
+    posatt_rows_body<1, MODE, MASKED, BF, 0, false, 8>(a, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+template <bool MASKED, bool BF>
+__global__ __launch_bounds__(512) void posatt_cols_kernel8(AttArgs a) {
+    posatt_cols_body<1, MASKED, BF, 0, false, 8>(a, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 // d(scale) and d(values) of one layer in ONE launch: the two are independent (both read d_out,
@@ -1615,8 +1660,50 @@ bool interleave_ok(const AttArgs& a, int mode) {
     return dout && al(a.d_values) && a.ld_dvalues % 4 == 0 && a.dvalues_bstride % 4 == 0;
 }
 
+// meshes with 4..8 coordinates: one column tile per workgroup, the key chunk staged as 32-B points (64 KiB) / the row
+// records as 48 B ({point, T}: 48 KiB) - below the 96 KiB the kernels are allowed
+void launch_rows8(AttArgs a, int mode, hipStream_t s) {
+    const bool bf = (mode == 0) && a.bf16 != 0;
+    const int n_tiles = (a.n_out + 31) / 32;
+    a.colgroups = (a.ncols + 31) / 32;
+    const int nwaves = max(1, min(8, pow2_floor(a.n_in / 32)));
+    const dim3 grid(a.mesh_batch * a.colgroups, a.n_head, n_tiles), block(64 * nwaves);
+    const size_t stage = (size_t)min(KEY_CHUNK, a.n_in) * sizeof(pt8), red = (size_t)nwaves * (16 + 2) * 64 * sizeof(float);
+    const size_t sm = stage > red ? stage : red;
+#define PIT_R8(MODE_, MASKED_, BF_)                                                                                    \
+    do {                                                                                                               \
+        static bool once = ((void)hipFuncSetAttribute((const void*)posatt_rows_kernel8<MODE_, MASKED_, BF_>,           \
+                                                      hipFuncAttributeMaxDynamicSharedMemorySize, 98304), true);       \
+        (void)once;                                                                                                    \
+        hipLaunchKernelGGL((posatt_rows_kernel8<MODE_, MASKED_, BF_>), grid, block, sm, s, a);                         \
+    } while (0)
+    if (mode == 1) { if (a.masked) PIT_R8(1, true, false); else PIT_R8(1, false, false); }
+    else if (bf) { if (a.masked) PIT_R8(0, true, true); else PIT_R8(0, false, true); }
+    else { if (a.masked) PIT_R8(0, true, false); else PIT_R8(0, false, false); }
+#undef PIT_R8
+}
+void launch_cols8(AttArgs a, hipStream_t s) {
+    const int j_tiles = (a.n_in + 31) / 32;
+    a.colgroups = (a.ncols + 31) / 32;
+    const int nwaves = max(1, min(8, pow2_floor(a.n_out * a.n_head / 32)));
+    const dim3 grid(a.colgroups, j_tiles, a.mesh_batch), block(64 * nwaves);
+    const size_t stage = (size_t)ROW_CHUNK * (sizeof(rec8) + sizeof(float2)), red = (size_t)nwaves * 16 * 64 * sizeof(float);
+    const size_t sm = stage > red ? stage : red;
+#define PIT_C8(MASKED_, BF_)                                                                                           \
+    do {                                                                                                               \
+        static bool once = ((void)hipFuncSetAttribute((const void*)posatt_cols_kernel8<MASKED_, BF_>,                  \
+                                                      hipFuncAttributeMaxDynamicSharedMemorySize, 98304), true);       \
+        (void)once;                                                                                                    \
+        hipLaunchKernelGGL((posatt_cols_kernel8<MASKED_, BF_>), grid, block, sm, s, a);                                \
+    } while (0)
+    if (a.bf16) { if (a.masked) PIT_C8(true, true); else PIT_C8(false, true); }
+    else { if (a.masked) PIT_C8(true, false); else PIT_C8(false, false); }
+#undef PIT_C8
+}
+
 template <int MODE>
 void launch_rows(const AttArgs& a0, hipStream_t s) {
+    if (a0.sdim > 3) { launch_rows8(a0, MODE, s); return; }
     AttArgs a = a0;
     const bool bf = (MODE == 0) && a.bf16 != 0;
     const int n_tiles = (a.n_out + 31) / 32;
@@ -1684,6 +1771,7 @@ void launch_rows(const AttArgs& a0, hipStream_t s) {
 }
 
 void launch_cols(const AttArgs& a0, hipStream_t s) {
+    if (a0.sdim > 3) { launch_cols8(a0, s); return; }
     AttArgs a = a0;
     const bool bf = a.bf16 != 0;
     const int j_tiles = (a.n_in + 31) / 32;
@@ -1765,7 +1853,7 @@ __global__ __launch_bounds__(512, 4) void posatt_bwd_pair_dw_kernel(AttArgs ar, 
 
 // `rider` (may be null) is carried along when the narrow-tile kernel is the one chosen; *rider_done says so
 bool launch_bwd_pair(const AttArgs& a0, hipStream_t s, const pit_mlp_params_job* job = nullptr, bool* rider_done = nullptr) {
-    if (env_int("PIT_NO_BWD_PAIR") || env_int("PIT_FORCE_CT") || env_int("PIT_FORCE_WAVES")) return false;
+    if (env_int("PIT_NO_BWD_PAIR") || env_int("PIT_FORCE_CT") || env_int("PIT_FORCE_WAVES") || a0.sdim > 3) return false;
     const int n_tiles = (a0.n_out + 31) / 32, j_tiles = (a0.n_in + 31) / 32;
     {   // either part would take the large-regime kernels: keep them separate
         const long work_r = (long)n_tiles * a0.n_head * a0.mesh_batch * ((a0.ncols + 31) / 32) * ((a0.n_in + 1) / 2);
@@ -1879,7 +1967,7 @@ struct SparseArgs {
     const int* rev_ptr; const int* rev_row; long rev_stride;
 };
 
-template <int NH, int CR, int MODE>
+template <int NH, int CR, int MODE, int MAXD = 4>
 __device__ __forceinline__ void sparse_rows_body(const AttArgs& a, const SparseArgs& sp, const int bx, const int by, const int bz) {
     // keys gathered per batch: G x CR value registers in flight; at 8 columns per lane two keys keep the rows kernels
     // at 5 waves per SIMD (93 registers; four keys: 128) - these kernels hide gather latency with occupancy
@@ -1898,7 +1986,7 @@ __device__ __forceinline__ void sparse_rows_body(const AttArgs& a, const SparseA
     const __amdgpu_buffer_rsrc_t rmi = make_rsrc(a.mesh_in, mi_bytes);
     const __amdgpu_buffer_rsrc_t rvals = make_rsrc(a.values, a.values_bytes);
     const unsigned ld4 = (unsigned)a.ld_values * 4u;
-    const float4 xo = load_point4(rmo, mo_bytes, row, a.sdim, a.coords_used);
+    const mesh_pt_t<MAXD> xo = load_pointp<MAXD>(rmo, mo_bytes, row, a.sdim, a.coords_used);
 
     float c[NH], T[NH], smin[NH], invl[NH], mbar[NH];
 #pragma unroll
@@ -1953,8 +2041,10 @@ __device__ __forceinline__ void sparse_rows_body(const AttArgs& a, const SparseA
         const int i = base + lane;
         const bool valid = i < total;
         const int j = valid ? (scan_all ? i : (base == 0 ? j_first : list[i])) : 0;
-        const float4 xi = load_point4(rmi, mi_bytes, (long)mb * a.n_in + j, a.sdim, a.coords_used);
-        const float m = sq_dist3(xo.x, xo.y, xo.z, xi.x, xi.y, xi.z, per, a.period);
+        const mesh_pt_t<MAXD> xi = load_pointp<MAXD>(rmi, mi_bytes, (long)mb * a.n_in + j, a.sdim, a.coords_used);
+        float m;
+        if constexpr (MAXD > 4) m = sq_distp(xo, xi, a.coords_used, per, a.period);
+        else m = sq_dist3(xo.x, xo.y, xo.z, xi.x, xi.y, xi.z, per, a.period);
         float p[NH];
         bool any = false;
 #pragma unroll
@@ -2080,7 +2170,7 @@ __global__ __launch_bounds__(256, 4) void posatt_sparse_rows_x(AttArgs a, Sparse
 // D16 (PIT_IO_DOUT_BF16): d_out holds bf16 - a lane then owns CR/2 PAIRS of adjacent columns {128 q + 2 lane, +1} and one
 // 4-B load fetches both (2-B loads per lane made the launch 3x slower than the fp32 one: 615 vs 220 us on the Vorticity
 // decoder); needs CR, dim and out_col0 even (the launch helper checks), cross attention only (no residual).
-template <int CR, bool D16 = false>
+template <int CR, bool D16 = false, int MAXD = 4>
 __device__ __forceinline__ void sparse_cols_body(const AttArgs& a, const SparseArgs& sp, const int bx, const int by) {
     static_assert(!D16 || CR % 2 == 0, "bf16 d_out: column pairs");
     constexpr int G = (CR >= 8) ? 2 : ((CR >= 4) ? 4 : 8);      // (see sparse_rows_body)
@@ -2097,7 +2187,7 @@ __device__ __forceinline__ void sparse_cols_body(const AttArgs& a, const SparseA
     const __amdgpu_buffer_rsrc_t rdout = make_rsrc(a.d_out, a.dout_bytes);
     constexpr unsigned ES = D16 ? 2u : 4u;                   // bytes per d_out element
     const unsigned ldd4 = (unsigned)a.ld_dout * ES;
-    const float4 xi = load_point4(rmi, mi_bytes, kid, a.sdim, a.coords_used);
+    const mesh_pt_t<MAXD> xi = load_pointp<MAXD>(rmi, mi_bytes, kid, a.sdim, a.coords_used);
     unsigned doff[CR];
     bool cvalid[CR];
     int cb[CR], cd[CR];
@@ -2124,9 +2214,11 @@ __device__ __forceinline__ void sparse_cols_body(const AttArgs& a, const SparseA
             int nrow = (e < end) ? rrow[e] : -1;
             const bool valid = nrow >= 0;                   // -1: slot of a row that overflowed its list
             nrow = valid ? nrow : 0;
-            const float4 xo = load_point4(rmo, mo_bytes, (long)mb * a.n_out + nrow, a.sdim, a.coords_used);
+            const mesh_pt_t<MAXD> xo = load_pointp<MAXD>(rmo, mo_bytes, (long)mb * a.n_out + nrow, a.sdim, a.coords_used);
             const float4 rs4 = *reinterpret_cast<const float4*>(a.rowstat + (((long)mb * a.n_head + h) * a.n_out + nrow) * 4);
-            const float m = sq_dist3(xo.x, xo.y, xo.z, xi.x, xi.y, xi.z, per, a.period);
+            float m;
+            if constexpr (MAXD > 4) m = sq_distp(xo, xi, a.coords_used, per, a.period);
+            else m = sq_dist3(xo.x, xo.y, xo.z, xi.x, xi.y, xi.z, per, a.period);
             const float sv = __fmul_rn(m, c);
             const bool keep = valid && (sv <= rs4.x);
             const float p = keep ? __expf(rs4.y - sv) * rs4.z : 0.0f;
@@ -2193,6 +2285,7 @@ __global__ __launch_bounds__(256) void posatt_sparse_cols_x(AttArgs a, SparseArg
 
 // rows whose candidate list overflowed are not in the transposed lists: add their contribution
 // to d(values) with atomics (rare: duplicated points / massive ties).
+template <int MAXD = 4>
 __device__ __forceinline__ void sparse_overflow_body(const AttArgs& a, const SparseArgs& sp, const int bx) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long rows_total = (long)a.mesh_batch * a.n_out;
@@ -2204,7 +2297,7 @@ __device__ __forceinline__ void sparse_overflow_body(const AttArgs& a, const Spa
     const unsigned mi_bytes = (unsigned)((long)a.mesh_batch * a.n_in * a.sdim * 4);
     const __amdgpu_buffer_rsrc_t rmo = make_rsrc(a.mesh_out, mo_bytes);
     const __amdgpu_buffer_rsrc_t rmi = make_rsrc(a.mesh_in, mi_bytes);
-    const float4 xo = load_point4(rmo, mo_bytes, row, a.sdim, a.coords_used);
+    const mesh_pt_t<MAXD> xo = load_pointp<MAXD>(rmo, mo_bytes, row, a.sdim, a.coords_used);
     const bool per = a.periodic != 0;
     for (int h = 0; h < a.n_head; ++h) {
         const float c = a.head_is_scale ? a.head[h] : head_scale_from_lmda(a.head[h]);
@@ -2212,8 +2305,10 @@ __device__ __forceinline__ void sparse_overflow_body(const AttArgs& a, const Spa
         for (int base = 0; base < a.n_in; base += 64) {
             const int j = base + lane;
             const bool valid = j < a.n_in;
-            const float4 xi = load_point4(rmi, mi_bytes, (long)mb * a.n_in + (valid ? j : 0), a.sdim, a.coords_used);
-            const float m = sq_dist3(xo.x, xo.y, xo.z, xi.x, xi.y, xi.z, per, a.period);
+            const mesh_pt_t<MAXD> xi = load_pointp<MAXD>(rmi, mi_bytes, (long)mb * a.n_in + (valid ? j : 0), a.sdim, a.coords_used);
+            float m;
+            if constexpr (MAXD > 4) m = sq_distp(xo, xi, a.coords_used, per, a.period);
+            else m = sq_dist3(xo.x, xo.y, xo.z, xi.x, xi.y, xi.z, per, a.period);
             const float sv = __fmul_rn(m, c);
             const bool keep = valid && (sv <= rs4.x);
             const float p = keep ? __expf(rs4.y - sv) * rs4.z : 0.0f;
@@ -2238,6 +2333,22 @@ __device__ __forceinline__ void sparse_overflow_body(const AttArgs& a, const Spa
 
 __global__ __launch_bounds__(256) void posatt_sparse_overflow_cols(AttArgs a, SparseArgs sp) {
     sparse_overflow_body(a, sp, blockIdx.x);
+}
+
+// ------------------------------------------------------------------------------------
+// Meshes with 4..8 coordinates (space_dim 4..8): the candidate-list bodies with MAXD 8 points, one column (pair) per lane
+// (the dense instances follow posatt_cols_kernel).  The paired, tiled, union and fused launches are not taken for these
+// meshes (speed for them is not a goal yet).
+template <int NH, int MODE>
+__global__ __launch_bounds__(256, 4) void posatt_sparse_rows8(AttArgs a, SparseArgs sp) {
+    sparse_rows_body<NH, 1, MODE, 8>(a, sp, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+template <int CR, bool D16>
+__global__ __launch_bounds__(256) void posatt_sparse_cols8(AttArgs a, SparseArgs sp) {
+    sparse_cols_body<CR, D16, 8>(a, sp, blockIdx.x, blockIdx.y);
+}
+__global__ __launch_bounds__(256) void posatt_sparse_overflow_cols8(AttArgs a, SparseArgs sp) {
+    sparse_overflow_body<8>(a, sp, blockIdx.x);
 }
 
 // d(values) over the transposed lists and d(scale) over the rows of a sparse layer in ONE launch:
@@ -2826,7 +2937,7 @@ int union_wave_lds(int nh, int n_in) {
 // does the shape qualify?  (the caller made sure a.head holds the scales: head_is_scale)  Eight consecutive columns per lane:
 // 16-byte loads and stores of the value / output rows.
 bool union_ok(const AttArgs& a, const SparseArgs& sp) {
-    return a.masked && sp.nbr_idx && sp.nbr_cnt && a.n_in <= 4096 && a.n_head <= 2 && a.coord_dims == 0 && sp.cap <= 64 &&
+    return a.sdim <= 3 && a.masked && sp.nbr_idx && sp.nbr_cnt && a.n_in <= 4096 && a.n_head <= 2 && a.coord_dims == 0 && sp.cap <= 64 &&
            a.n_out >= 16 && a.dim % 8 == 0 && a.ld_values % 4 == 0 && a.values_bstride % 4 == 0 &&
            (reinterpret_cast<uintptr_t>(a.values) & 15) == 0 && !env_int("PIT_NO_UNION_TILES");
 }
@@ -2908,6 +3019,12 @@ void launch_sparse_rows(const AttArgs& a, const SparseArgs& sp, hipStream_t s, c
                         bool* rider_done = nullptr, const WeightsArgs* wjob = nullptr) {
     const int nh = (a.n_head % 2 == 0) ? 2 : 1;
     const long rows = (long)a.mesh_batch * a.n_out;
+    if (a.sdim > 3) {                                 // 4..8 coordinates: one column per lane, nothing carried along
+        const dim3 grid8((unsigned)((rows + 3) / 4), (a.ncols + 63) / 64, a.n_head / nh), block8(256);
+        if (nh == 2) hipLaunchKernelGGL((posatt_sparse_rows8<2, MODE>), grid8, block8, 0, s, a, sp);
+        else hipLaunchKernelGGL((posatt_sparse_rows8<1, MODE>), grid8, block8, 0, s, a, sp);
+        return;
+    }
     const int cr = cr_for(a.ncols, rows * (a.n_head / nh));
     dim3 grid((unsigned)((rows + 3) / 4), (a.ncols + 64 * cr - 1) / (64 * cr), a.n_head / nh), block(256);
     if (MODE == 0 && wjob && (long)grid.x * grid.y * grid.z <= 4096) {       // small launch: carry the processor's weights
@@ -2956,7 +3073,7 @@ void launch_sparse_rows(const AttArgs& a, const SparseArgs& sp, hipStream_t s, c
 // parts separately)
 bool launch_sparse_bwd_pair(const AttArgs& a, const SparseArgs& sp, bool complete, hipStream_t s,
                             const pit_mlp_params_job* job = nullptr, bool* rider_done = nullptr) {
-    if (env_int("PIT_NO_BWD_PAIR")) return false;
+    if (env_int("PIT_NO_BWD_PAIR") || a.sdim > 3) return false;
     const int nh = (a.n_head % 2 == 0) ? 2 : 1;
     const long rows = (long)a.mesh_batch * a.n_out, keys = (long)a.mesh_batch * a.n_in;
     const int crr = cr_for(a.ncols, rows * (a.n_head / nh));
@@ -3002,6 +3119,15 @@ bool launch_sparse_bwd_pair(const AttArgs& a, const SparseArgs& sp, bool complet
 
 void launch_sparse_cols(const AttArgs& a, const SparseArgs& sp, bool complete, hipStream_t s) {
     const long keys = (long)a.mesh_batch * a.n_in;
+    if (a.sdim > 3) {                                 // 4..8 coordinates: one column (bf16 d_out: one column pair) per lane
+        const int cr8 = a.dout16 ? 2 : 1;
+        const dim3 grid8((unsigned)((keys + 3) / 4), (a.ncols + 64 * cr8 - 1) / (64 * cr8)), block8(256);
+        if (a.dout16) hipLaunchKernelGGL((posatt_sparse_cols8<2, true>), grid8, block8, 0, s, a, sp);
+        else hipLaunchKernelGGL((posatt_sparse_cols8<1, false>), grid8, block8, 0, s, a, sp);
+        const long rows8 = (long)a.mesh_batch * a.n_out;
+        if (!complete) hipLaunchKernelGGL(posatt_sparse_overflow_cols8, dim3((unsigned)((rows8 + 3) / 4)), dim3(256), 0, s, a, sp);
+        return;
+    }
     const int cr = a.dout16 ? std::max(2, cr_for(a.ncols, keys)) : cr_for(a.ncols, keys);
     dim3 grid((unsigned)((keys + 3) / 4), (a.ncols + 64 * cr - 1) / (64 * cr)), block(256);
     const long xtotal = 8L * grid.x * ((grid.y + 7) / 8);
@@ -3033,7 +3159,7 @@ int fill_common(AttArgs& a, const float* mesh_out, const float* mesh_in, int mes
     if (!mesh_out || !mesh_in || !values || !head) return PIT_ERR_NULL;
     if (coord_dims < 0 || coord_dims >= dim || coord_dims > space_dim) return PIT_ERR_SIZE;
     if (mesh_batch <= 0 || n_out <= 0 || n_in <= 0 || batch <= 0 || dim <= 0 || n_head <= 0) return PIT_ERR_SIZE;
-    if (space_dim < 1 || space_dim > 3) return PIT_ERR_SIZE;
+    if (space_dim < 1 || space_dim > PIT_MAX_SPACE_DIM) return PIT_ERR_SIZE;
     if (metric < PIT_METRIC_EUCLID || metric > PIT_METRIC_PERIODIC2D) return PIT_ERR_METRIC;
     if (mesh_batch != 1 && mesh_batch != batch) return PIT_ERR_SIZE;
     if (n_head > 65535 || (long)batch * dim > 0x7fffffffL) return PIT_ERR_UNSUPPORTED;

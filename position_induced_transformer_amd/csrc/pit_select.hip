@@ -32,6 +32,18 @@ __device__ __forceinline__ void load_point(const float* p, int sdim, int used, f
     z = (used > 2) ? p[2] : 0.0f;
     (void)sdim;
 }
+// a point as the distance helpers take it (pit_common.h): MAXD 4 is (x, y, z, 0), MAXD 8 up to eight coordinates
+template <int MAXD>
+__device__ __forceinline__ mesh_pt_t<MAXD> load_sel(const float* p, int sdim, int used) {
+    if constexpr (MAXD > 4) {
+        return load_pt8(p, 0, sdim, used);
+    } else {
+        float4 v;
+        load_point(p, sdim, used, v.x, v.y, v.z);
+        v.w = 0.0f;
+        return v;
+    }
+}
 
 template <int ITEMS>
 __global__ __launch_bounds__(256) void select_rows_reg(SelectArgs a) {
@@ -465,7 +477,8 @@ __global__ __launch_bounds__(256) void plan_rows_lane(SelectArgs a, int cap, int
 }
 
 // one workgroup per row, distances recomputed per pass
-__global__ __launch_bounds__(256) void select_rows_stream(SelectArgs a) {
+template <int MAXD>
+__device__ __forceinline__ void select_rows_stream_body(const SelectArgs& a) {
     __shared__ int s_cnt[4];
     __shared__ uint32_t s_min[4];
     const int lane = threadIdx.x & 63;
@@ -475,13 +488,20 @@ __global__ __launch_bounds__(256) void select_rows_stream(SelectArgs a) {
     const int mb = (int)(row / a.n_out);
     const float* po = a.mesh_out + row * a.sdim;
     const float* pin = a.mesh_in + (long)mb * a.n_in * a.sdim;
-    float ox, oy, oz;
+    float ox, oy, oz;                                     // (MAXD 4: the code of the existing instance)
     load_point(po, a.sdim, a.coords_used, ox, oy, oz);
+    mesh_pt_t<MAXD> xo{};
+    if constexpr (MAXD > 4) xo = load_sel<MAXD>(po, a.sdim, a.coords_used);
 
     auto key_at = [&](int j) -> uint32_t {
-        float ix, iy, iz;
-        load_point(pin + (long)j * a.sdim, a.sdim, a.coords_used, ix, iy, iz);
-        return __float_as_uint(sq_dist3(ox, oy, oz, ix, iy, iz, a.periodic != 0, a.period));
+        if constexpr (MAXD > 4) {
+            const mesh_pt_t<MAXD> xi = load_sel<MAXD>(pin + (long)j * a.sdim, a.sdim, a.coords_used);
+            return __float_as_uint(sq_distp(xo, xi, a.coords_used, a.periodic != 0, a.period));
+        } else {
+            float ix, iy, iz;
+            load_point(pin + (long)j * a.sdim, a.sdim, a.coords_used, ix, iy, iz);
+            return __float_as_uint(sq_dist3(ox, oy, oz, ix, iy, iz, a.periodic != 0, a.period));
+        }
     };
     // block-wide count of keys < cand (strict) or <= cand, and min of keys > bound
     auto block_count = [&](uint32_t cand, bool inclusive) -> int {
@@ -531,6 +551,8 @@ __global__ __launch_bounds__(256) void select_rows_stream(SelectArgs a) {
         a.stats[2 * rows + row] = __uint_as_float(kmin);
     }
 }
+__global__ __launch_bounds__(256) void select_rows_stream(SelectArgs a) { select_rows_stream_body<4>(a); }
+__global__ __launch_bounds__(256) void select_rows_stream8(SelectArgs a) { select_rows_stream_body<8>(a); }
 
 template <int ITEMS>
 void launch_reg(const SelectArgs& a, hipStream_t s) {
@@ -549,6 +571,48 @@ void launch_reg(const SelectArgs& a, hipStream_t s) {
 // has k+2 entries plus ties.  The sparse attention kernels evaluate the exact mask on it.
 // A row whose count exceeds `cap` keeps its true count (list truncated): consumers treat
 // count > cap as "scan all keys".
+// (neighbors_kernel8's body; neighbors_kernel below keeps its own code)
+template <int MAXD>
+__device__ __forceinline__ void neighbors_body(const SelectArgs& a, int cap, int* __restrict__ nbr_idx,
+                                               int* __restrict__ nbr_cnt, int* __restrict__ counts) {
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const long rows = (long)a.mesh_batch * a.n_out;
+    const long row = (long)blockIdx.x * 4 + wave;
+    if (row >= rows) return;
+    const int mb = (int)(row / a.n_out);
+    const float* po = a.mesh_out + row * a.sdim;
+    const float* pin = a.mesh_in + (long)mb * a.n_in * a.sdim;
+    float ox, oy, oz;                                     // (MAXD 4: the code of the existing instance)
+    load_point(po, a.sdim, a.coords_used, ox, oy, oz);
+    mesh_pt_t<MAXD> xo{};
+    if constexpr (MAXD > 4) xo = load_sel<MAXD>(po, a.sdim, a.coords_used);
+    const float bound = a.stats[rows + row] * 1.00000047683715820312f;     // m_(k+1) * (1 + 2^-21)
+    int total = 0;
+    int* out = nbr_idx + row * cap;
+    for (int j0 = 0; j0 < a.n_in; j0 += 64) {
+        const int j = j0 + lane;
+        bool in = false;
+        if (j < a.n_in) {
+            if constexpr (MAXD > 4) {
+                const mesh_pt_t<MAXD> xi = load_sel<MAXD>(pin + (long)j * a.sdim, a.sdim, a.coords_used);
+                in = sq_distp(xo, xi, a.coords_used, a.periodic != 0, a.period) <= bound;
+            } else {
+                float ix, iy, iz;
+                load_point(pin + (long)j * a.sdim, a.sdim, a.coords_used, ix, iy, iz);
+                in = sq_dist3(ox, oy, oz, ix, iy, iz, a.periodic != 0, a.period) <= bound;
+            }
+        }
+        const unsigned long long mask = __builtin_amdgcn_ballot_w64(in);
+        const int pos = total + __popcll(mask & ((1ull << lane) - 1ull));
+        if (in && pos < cap) {
+            out[pos] = j;
+            if (counts) atomicAdd(counts + (long)mb * a.n_in + j, 1);     // per-key counts for the transpose
+        }
+        total += __popcll(mask);
+    }
+    if (lane == 0) nbr_cnt[row] = total;
+}
 __global__ __launch_bounds__(256) void neighbors_kernel(SelectArgs a, int cap, int* __restrict__ nbr_idx,
                                                         int* __restrict__ nbr_cnt, int* __restrict__ counts) {
     const int lane = threadIdx.x & 63;
@@ -581,6 +645,10 @@ __global__ __launch_bounds__(256) void neighbors_kernel(SelectArgs a, int cap, i
         total += __popcll(mask);
     }
     if (lane == 0) nbr_cnt[row] = total;
+}
+__global__ __launch_bounds__(256) void neighbors_kernel8(SelectArgs a, int cap, int* __restrict__ nbr_idx,
+                                                         int* __restrict__ nbr_cnt, int* __restrict__ counts) {
+    neighbors_body<8>(a, cap, nbr_idx, nbr_cnt, counts);
 }
 
 // reverse lists (key -> rows that list it), CSR per mesh sample: counts come from
@@ -660,11 +728,11 @@ extern "C" int pit_head_scale(const float* lmda, int n_head, float* scale_out, v
     return 0;
 }
 
-extern "C" int pit_select_fwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
-                              int space_dim, int metric, float period, int rank_k, int need_kth,
-                              float* stats, void* stream) {
+static int select_fwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                      int space_dim, int metric, float period, int rank_k, int need_kth,
+                      float* stats, void* stream) {
     if (!mesh_out || !mesh_in || !stats) return PIT_ERR_NULL;
-    if (mesh_batch <= 0 || n_out <= 0 || n_in <= 0 || space_dim < 1 || space_dim > 3) return PIT_ERR_SIZE;
+    if (mesh_batch <= 0 || n_out <= 0 || n_in <= 0 || space_dim < 1 || space_dim > PIT_MAX_SPACE_DIM) return PIT_ERR_SIZE;
     if (metric < PIT_METRIC_EUCLID || metric > PIT_METRIC_PERIODIC2D) return PIT_ERR_METRIC;
     if (need_kth && (rank_k < 0 || rank_k > n_in - 1)) return PIT_ERR_SIZE;
     SelectArgs a;
@@ -675,6 +743,11 @@ extern "C" int pit_select_fwd(const float* mesh_out, const float* mesh_in, int m
     a.period = period; a.rank_k = rank_k; a.need_kth = need_kth;
     hipStream_t s = (hipStream_t)stream;
     const int items = (n_in + 63) / 64;
+    if (space_dim > 3) {                                  // 4..8 coordinates: the streaming kernel for every row length
+        hipLaunchKernelGGL(select_rows_stream8, dim3((unsigned)((long)mesh_batch * n_out)), dim3(256), 0, s, a);
+        PIT_CHECK_LAUNCH();
+        return 0;
+    }
     if (items <= 1) launch_reg<1>(a, s);
     else if (items <= 2) launch_reg<2>(a, s);
     else if (items <= 4) launch_reg<4>(a, s);
@@ -688,6 +761,18 @@ extern "C" int pit_select_fwd(const float* mesh_out, const float* mesh_in, int m
     }
     PIT_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int pit_select_fwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                              int space_dim, int metric, float period, int rank_k, int need_kth,
+                              float* stats, void* stream) {
+    if (mesh_out && mesh_in && stats && (space_dim < 1 || space_dim > 3)) return PIT_ERR_SIZE;   // (1..3: pit_select_wide_fwd takes 1..8)
+    return select_fwd(mesh_out, mesh_in, mesh_batch, n_out, n_in, space_dim, metric, period, rank_k, need_kth, stats, stream);
+}
+extern "C" int pit_select_wide_fwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                                   int space_dim, int metric, float period, int rank_k, int need_kth,
+                                   float* stats, void* stream) {
+    return select_fwd(mesh_out, mesh_in, mesh_batch, n_out, n_in, space_dim, metric, period, rank_k, need_kth, stats, stream);
 }
 
 // plain fill kernel used instead of hipMemsetAsync: a memset NODE of a captured hipGraph is not reliably
@@ -804,13 +889,12 @@ extern "C" int pit_plan_fwd(const float* mesh_out, const float* mesh_in, int mes
                             int* nbr_idx, int* nbr_cnt, int* rev_ptr, int* rev_row, int* workspace, int flags, void* stream) {
     if (!mesh_out || !mesh_in || !stats || !nbr_idx || !nbr_cnt) return PIT_ERR_NULL;
     if (rev_ptr && (!rev_row || !workspace)) return PIT_ERR_NULL;
-    if (mesh_batch <= 0 || n_out <= 0 || n_in <= 0 || space_dim < 1 || space_dim > 3 || cap <= 0) return PIT_ERR_SIZE;
+    if (mesh_batch <= 0 || n_out <= 0 || n_in <= 0 || space_dim < 1 || space_dim > PIT_MAX_SPACE_DIM || cap <= 0) return PIT_ERR_SIZE;
     if (metric < PIT_METRIC_EUCLID || metric > PIT_METRIC_PERIODIC2D) return PIT_ERR_METRIC;
     if (rank_k < 0 || rank_k > n_in - 1) return PIT_ERR_SIZE;
     const int items = (n_in + 63) / 64;
-    if (items > 64 || (flags & PIT_PLAN_TWO_PASSES)) {        // long rows: the two streaming passes
-        int rc = pit_select_fwd(mesh_out, mesh_in, mesh_batch, n_out, n_in, space_dim, metric, period, rank_k, 1, stats,
-                                stream);
+    if (items > 64 || (flags & PIT_PLAN_TWO_PASSES) || space_dim > 3) {   // long rows, 4..8 coordinates: the two streaming passes
+        int rc = select_fwd(mesh_out, mesh_in, mesh_batch, n_out, n_in, space_dim, metric, period, rank_k, 1, stats, stream);
         if (rc) return rc;
         return pit_neighbors_fwd(mesh_out, mesh_in, mesh_batch, n_out, n_in, space_dim, metric, period, stats, cap,
                                  nbr_idx, nbr_cnt, rev_ptr, rev_row, workspace, stream);
@@ -891,7 +975,7 @@ extern "C" int pit_neighbors_fwd(const float* mesh_out, const float* mesh_in, in
                                  void* stream) {
     if (!mesh_out || !mesh_in || !stats || !nbr_idx || !nbr_cnt) return PIT_ERR_NULL;
     if (rev_ptr && (!rev_row || !workspace)) return PIT_ERR_NULL;
-    if (mesh_batch <= 0 || n_out <= 0 || n_in <= 0 || space_dim < 1 || space_dim > 3 || cap <= 0) return PIT_ERR_SIZE;
+    if (mesh_batch <= 0 || n_out <= 0 || n_in <= 0 || space_dim < 1 || space_dim > PIT_MAX_SPACE_DIM || cap <= 0) return PIT_ERR_SIZE;
     if (metric < PIT_METRIC_EUCLID || metric > PIT_METRIC_PERIODIC2D) return PIT_ERR_METRIC;
     hipStream_t s = (hipStream_t)stream;
     SelectArgs a;
@@ -908,8 +992,12 @@ extern "C" int pit_neighbors_fwd(const float* mesh_out, const float* mesh_in, in
         fill_int(rev_row, rows * cap, -1, s);
     }
     const bool agg = rev_ptr && n_in <= NBR_LDS_KEYS;
-    hipLaunchKernelGGL(neighbors_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a, cap, nbr_idx, nbr_cnt,
-                       agg ? nullptr : counts);
+    if (space_dim > 3)
+        hipLaunchKernelGGL(neighbors_kernel8, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a, cap, nbr_idx, nbr_cnt,
+                           agg ? nullptr : counts);
+    else
+        hipLaunchKernelGGL(neighbors_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a, cap, nbr_idx, nbr_cnt,
+                           agg ? nullptr : counts);
     PIT_CHECK_LAUNCH();
     if (rev_ptr) return launch_transpose(nbr_idx, nbr_cnt, mesh_batch, n_out, n_in, cap, rev_ptr, rev_row, counts, cursor, !agg, s);
     return 0;

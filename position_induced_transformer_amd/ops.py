@@ -20,6 +20,7 @@ import torch
 from . import _lib
 
 METRIC_ID = {"euclid": 0, "periodic1d": 1, "periodic2d": 2}
+MAX_SPACE_DIM = 8                  # PIT_MAX_SPACE_DIM of include/pit_hip.h: coordinates per mesh point
 
 # In-place gradient accumulation is OPT-IN per parameter: ddp.FlatGradients marks the parameters whose
 # ``.grad`` it owns (``mark_inplace_grad``), and only for those - while the ``.grad`` is still the
@@ -409,8 +410,8 @@ class MeshPlan:
         self.mesh_in = self.mesh_out if (self_attn and mesh_in is mesh_out) else mesh_in.detach().contiguous()
         self.mesh_batch = mesh_out.shape[0] if batched else 1
         self.n_out, self.n_in, self.sdim = mesh_out.shape[-2], mesh_in.shape[-2], mesh_out.shape[-1]
-        if not 1 <= self.sdim <= 3:
-            raise RuntimeError("space_dim must be 1, 2 or 3")
+        if not 1 <= self.sdim <= MAX_SPACE_DIM:
+            raise RuntimeError(f"space_dim must be between 1 and {MAX_SPACE_DIM}, got {self.sdim}")
         self.period = mesh_period(metric, self.mesh_in) if period is None else float(period)
         self.rank_k, self.rank_w = quantile_rank(locality, self.n_in)
         self.masked = bool(locality < 1.0)
@@ -433,11 +434,12 @@ class MeshPlan:
         if cap:
             self._build_lists(cap, self._wants_reverse_lists(cap))      # selection + lists in one pass
         elif self.stats is not None:
-            rc = _lib.lib().pit_select_fwd(self.mesh_out.data_ptr(), self.mesh_in.data_ptr(), self.mesh_batch,
+            name = "pit_select_fwd" if self.sdim <= 3 else "pit_select_wide_fwd"     # (the first keeps space_dim 1..3)
+            rc = getattr(_lib.lib(), name)(self.mesh_out.data_ptr(), self.mesh_in.data_ptr(), self.mesh_batch,
                                            self.n_out, self.n_in, self.sdim, self.metric_id, self.period,
                                            self.rank_k, 1 if self.masked else 0, self.stats.data_ptr(),
                                            _lib.stream_ptr())
-            _lib.check(rc, "pit_select_fwd")
+            _lib.check(rc, name)
 
     def _union_key(self, cap):
         return (self.metric, self.n_out, self.n_in, cap, self.mesh_batch > 1, self.sdim)
@@ -666,7 +668,7 @@ def _union_att_ok(plan: "MeshPlan", n_head: int, d: int, b: int, values: torch.T
     if torch.are_deterministic_algorithms_enabled():       # (d(values) leaves these kernels as fp32 atomic adds)
         return False
     if not (plan.mesh_batch == 1 and plan.masked and plan.nbr_idx is not None and not plan.self_attn and n_head in (1, 2)
-            and d % 64 == 0 and d >= UNION_ATT_MIN_DIM):
+            and d % 64 == 0 and d >= UNION_ATT_MIN_DIM and plan.sdim <= 3):
         return False
     if values.stride(1) % 4 or values.stride(0) % 4 or values.data_ptr() % 16:
         return False
@@ -797,7 +799,7 @@ class _PosAtt(torch.autograd.Function):
         ctx.satt = None
         if not ctx.mesh_grad and _satt_pays(int(plan.n_in), int(n_head), int(d)) and concat and not coord_dims and plan.self_attn and not plan.masked and ctx.math == MATH_MODES["bf16"] \
                 and values.dtype == torch.float32 and values.stride(1) % 4 == 0 and values.stride(0) % 4 == 0 and values.data_ptr() % 16 == 0 \
-                and _lib.lib().pit_satt_supported(int(plan.n_in), int(n_head), int(d), int(b), int(plan.mesh_batch)):
+                and plan.sdim <= 3 and _lib.lib().pit_satt_supported(int(plan.n_in), int(n_head), int(d), int(b), int(plan.mesh_batch)):
             k_head, k_is_scale = (scale_in, True) if scale_in is not None else (head, head_is_scale)
             out = out_buf if out_buf is not None else torch.empty((b, plan.n_out, (n_head + 1) * d), device=values.device, dtype=torch.float32)
             # (the producing MLP chain may already have written bf16(values): link["x16"] - then no prep launch)
@@ -1409,8 +1411,9 @@ BLOCK_FUSION = os.environ.get("PIT_BLOCK_FUSION", "1") != "0"
 BLOCK_MAX_LAYERS = 16              # MAX_LAYERS of csrc/pit_block_dev.h: blocks whose weights one pit_block_weights launch forms
 
 
-def block_fusion_supported(n_pts: int, n_head: int, dim: int, batch: int) -> bool:
-    return BLOCK_FUSION and bool(_lib.lib().pit_block_supported(int(n_pts), int(n_head), int(dim), int(batch)))
+def block_fusion_supported(n_pts: int, n_head: int, dim: int, batch: int, space_dim: int = 3) -> bool:
+    """space_dim > 3: the per-layer kernels (the fused launches take at most three coordinates)."""
+    return BLOCK_FUSION and space_dim <= 3 and bool(_lib.lib().pit_block_supported(int(n_pts), int(n_head), int(dim), int(batch)))
 
 
 # Round 4: large-regime self-attention of batch-free models on PRECOMPUTED weights (pit_posatt_pre_fwd / _bwd): the weights
@@ -1419,8 +1422,9 @@ def block_fusion_supported(n_pts: int, n_head: int, dim: int, batch: int) -> boo
 PRE_WEIGHTS = os.environ.get("PIT_PRE_WEIGHTS", "1") != "0"
 
 
-def pre_weights_supported(n_pts: int, n_head: int, dim: int, batch: int) -> bool:
-    return PRE_WEIGHTS and bool(_lib.lib().pit_posatt_pre_supported(int(n_pts), int(n_head), int(dim), int(batch)))
+def pre_weights_supported(n_pts: int, n_head: int, dim: int, batch: int, space_dim: int = 3) -> bool:
+    """space_dim > 3: the per-layer kernels (pit_block_weights takes at most three coordinates)."""
+    return PRE_WEIGHTS and space_dim <= 3 and bool(_lib.lib().pit_posatt_pre_supported(int(n_pts), int(n_head), int(dim), int(batch)))
 
 
 def block_weights(plan: "MeshPlan", lmdas, n_head: int, need_q: bool = True):
@@ -1790,7 +1794,7 @@ def edge_fusion_supported(plan: MeshPlan, n_head: int, dim: int, batch: int, nee
     """The fused encoder- / decoder-side launch covers this layer: a masked cross-attention on a batch-free mesh pair with
     complete candidate lists (and, for the decoder, unions of at most 64 keys per 16-row slab), 1-2 heads, hidden width 32 / 64,
     in the latency regime."""
-    if not EDGE_FUSION or plan.mesh_batch != 1 or plan.self_attn or not plan.masked or plan.nbr_idx is None:
+    if not EDGE_FUSION or plan.mesh_batch != 1 or plan.self_attn or not plan.masked or plan.nbr_idx is None or plan.sdim > 3:
         return False
     if needs_union and torch.are_deterministic_algorithms_enabled():     # (the decoder's d(values): fp32 atomic adds)
         return False
@@ -2140,7 +2144,7 @@ def _new_fold_weights(plan: MeshPlan, head, scale_in, n_head: int, head_is_scale
 def fold_att_supported(plan: MeshPlan, n_head: int, dim: int, batch: int) -> bool:
     """The fold attention launches cover this layer: a masked cross attention on a batch-free mesh pair with complete candidate
     lists whose unions fit a tile for slabs of at least 64 rows, 1-2 heads, a width that is a multiple of 64."""
-    if plan.mesh_batch != 1 or plan.self_attn or not plan.masked or plan.nbr_idx is None:
+    if plan.mesh_batch != 1 or plan.self_attn or not plan.masked or plan.nbr_idx is None or plan.sdim > 3:
         return False
     if torch.are_deterministic_algorithms_enabled() and FOLD_TILES in ("0", False):         # (d(values) as fp32 atomic adds)
         return False

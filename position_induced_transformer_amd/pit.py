@@ -443,7 +443,8 @@ class pit(nn.Module):
                 if any(not getattr(f, "_pit_internal", False) for f in m._forward_hooks.values()) \
                         or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks:
                     return None
-        if (n_pts is not None and mesh_ltt.shape[0] != n_pts) or not ops.block_fusion_supported(mesh_ltt.shape[0], heads, hid, batch):
+        if (n_pts is not None and mesh_ltt.shape[0] != n_pts) or not ops.block_fusion_supported(mesh_ltt.shape[0], heads, hid, batch,
+                                                                                                      mesh_ltt.shape[-1]):
             return None
         return self.conv[0]._plan(mesh_ltt, mesh_ltt, True)
 
@@ -460,7 +461,8 @@ class pit(nn.Module):
             if type(a) not in kinds or type(a) is not type(self.conv[0]) or a.locality != 1.0 or a.n_head != heads or a.in_dim != hid \
                     or "forward" in a.__dict__ or a._forward_hooks or a._forward_pre_hooks or a._backward_hooks or a._backward_pre_hooks:
                 return None
-        if mesh_ltt.shape[0] != func_ltt.shape[1] or not ops.pre_weights_supported(mesh_ltt.shape[0], heads, hid, func_ltt.shape[0]):
+        if mesh_ltt.shape[0] != func_ltt.shape[1] or not ops.pre_weights_supported(mesh_ltt.shape[0], heads, hid, func_ltt.shape[0],
+                                                                                                 mesh_ltt.shape[-1]):
             return None
         plan = self.conv[0]._plan(mesh_ltt, mesh_ltt, True)
         need_q = torch.is_grad_enabled() and any(a.lmda.requires_grad for a in self.conv)
