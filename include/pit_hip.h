@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define PIT_ABI_VERSION 26
+#define PIT_ABI_VERSION 27
 #define PIT_MAX_SPACE_DIM 8   /* largest space_dim any entry accepts */
 #define PIT_DSCALE_SLOTS 1024 /* fp64 accumulators per head in pit_posatt_bwd's workspace */
 
@@ -647,6 +647,79 @@ int pit_instance_norm_bwd(const float* d_y, const float* y, const float* rstd, i
 int pit_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long n,
                   long long* step, float lr0, float eta_min, int cosine_t_max, float beta1, float beta2,
                   float eps, float weight_decay, int zero_grads, float* scalars, void* stream);
+
+/* ---- Ragged batches of per-sample clouds (ABI 27; csrc/pit_ragged.hip) --------------------------------------------------------
+ * Padded tensors plus per-sample lengths ON THE DEVICE: sample s of a (mesh_batch, n, ...) tensor holds len[s] real points
+ * followed by padding, and comes out as pit.py:46-57 computes it for that cloud ALONE (a batch of one with len[s] points): its own
+ * quantile rank floor(fl32(q) * fl32(len_in[s] - 1)), its own kept sets, its own softmax.  len_out / len_in: mesh_batch int32 each
+ * in device memory, read by the kernels (no host synchronisation: one captured hipGraph serves every mix of sizes up to the padded
+ * n_out / n_in); self attention passes one buffer for both.  Precondition 1 <= len[s] <= padded width; the kernels clamp into that
+ * range, so a bad length cannot address outside the buffers.  Per-sample meshes only (batch = mesh_batch), Euclidean metric,
+ * 1 <= space_dim <= 3 (PIT_ERR_UNSUPPORTED beyond), PIT_MATH_FP32 only (PIT_ERR_UNSUPPORTED otherwise).  The rules:
+ *   - keys j >= len_in[s] are never read (coordinates, value rows): the padding may hold anything, NaN included;
+ *   - rows i >= len_out[s]: `out` is written as ZERO in every head column (with copy_inputs the copied columns are copied as they
+ *     are), their stats / rowstat are zeros, their d_out is never read;
+ *   - d_values of keys j >= len_in[s] is written as zero, residual included.
+ * Every sum has a fixed order except d(scale)'s fp64 slots (see pit_posatt_ragged_bwd).
+ *
+ * pit_plan_ragged_fwd: the selection statistics of pit_select_fwd over the first len_in[s] keys of every row: stats
+ *   (3*mesh_batch*n_out floats, the layout of pit_select_fwd), rank k_s and interpolation weight w_s formed in the kernel with
+ *   the fp32 operations of torch.quantile (fp32 product, floor, fp32 difference); rank_w (mesh_batch floats) receives w_s.
+ *   locality: the quantile q in [0, 1]; need_kth = 0: only the row minimum (nothing masked).
+ *   nbr_idx != NULL (need_kth = 1): also the candidate lists of pit_neighbors_fwd over the first len_in[s] keys - nbr_idx
+ *   (rows, cap), nbr_cnt (rows) the TRUE count; `cap` is the caller's, chosen from the padded width, so it does not depend on the
+ *   lengths; a row with count > cap is truncated and its consumers scan all keys of the sample (the existing convention); rows
+ *   i >= len_out[s] get count 0.  The transposed lists come from pit_lists_transpose on these lists: padded rows appear in no
+ *   range and padded keys have empty ranges. */
+int pit_plan_ragged_fwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                        int space_dim, const int* len_out, const int* len_in, float locality, int need_kth,
+                        float* stats, float* rank_w, int cap, int* nbr_idx, int* nbr_cnt, void* stream);
+/* pit_posatt_fwd on a ragged batch.  stats / rank_w from pit_plan_ragged_fwd (rank_w may be NULL when masked = 0); the other
+ * arguments as in pit_posatt_fwd (batch = mesh_batch; no coordinate channels).  nbr_idx / nbr_cnt / nbr_cap: the candidate lists
+ * of pit_plan_ragged_fwd (masked layers; NULL = the dense kernel): one wave per row walks its list, or all keys when it overflowed. */
+int pit_posatt_ragged_fwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                          int space_dim, const int* len_out, const int* len_in,
+                          const float* values, int dim, long ld_values, long values_bstride,
+                          const float* head, int n_head, int head_is_scale,
+                          const float* stats, const float* rank_w, int masked,
+                          float* out, long ld_out, long out_bstride, int out_col0, int copy_inputs,
+                          float* rowstat, float* scale_out,
+                          const int* nbr_idx, const int* nbr_cnt, int nbr_cap, int math_mode, void* stream);
+/* pit_posatt_bwd on a ragged batch: d_values (NULL = not needed), d_head (NULL = not needed), scale, rowstat, accumulate_head
+ * (PIT_HEAD_ACCUMULATE / PIT_HEAD_DEFER) and workspace (n_head*PIT_DSCALE_SLOTS doubles, zero on entry, left zero unless
+ * deferred) as in pit_posatt_bwd.  With lists, d(scale) walks them by row; d(values) walks rev_ptr / rev_row (pit_lists_transpose)
+ * by key, rows in ascending order, then the overflowed rows - no atomics; rev_ptr = NULL: the dense d(values) kernel.
+ * d(scale) partial sums meet in the workspace's fp64 slots through atomics, as in pit_posatt_bwd: the order inside a slot is
+ * not fixed, and the fp32 result is the same from run to run only in so far as fp64 rounding differences vanish in the final
+ * rounding.  Everything else has a fixed summation order. */
+int pit_posatt_ragged_bwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                          int space_dim, const int* len_out, const int* len_in,
+                          const float* values, int dim, long ld_values, long values_bstride,
+                          const float* head, int n_head, int head_is_scale, const float* scale,
+                          const float* rowstat, int masked,
+                          const float* d_out, long ld_dout, long dout_bstride, int out_col0,
+                          float* d_values, long ld_dvalues, long dvalues_bstride, int add_residual,
+                          float* d_head, int accumulate_head, double* workspace,
+                          const int* nbr_idx, const int* nbr_cnt, int nbr_cap, const int* rev_ptr, const int* rev_row,
+                          int math_mode, void* stream);
+/* RelLpNorm (utils.py:86-98) of every sample TRUNCATED to its first len[s] points: true / pred (batch, npts, nch) contiguous,
+ * norms (batch, nch, 2) = {||true - pred||_p, ||true||_p}, *loss = sum_s mean_c of their ratio.  Padded points are skipped (not
+ * multiplied by zero).  The backward writes d_pred (batch, npts, nch) = *gloss (NULL: 1) times the gradient, zero on padded points. */
+int pit_rel_lp_loss_ragged_fwd(const float* tru, const float* pred, const int* len, int batch, int npts, int nch, int p,
+                               float* norms, float* loss, void* stream);
+int pit_rel_lp_loss_ragged_bwd(const float* tru, const float* pred, const int* len, int batch, int npts, int nch, int p,
+                               const float* norms, const float* gloss, float* d_pred, void* stream);
+
+/* pit_mlp_bwd_params with a FIXED summation order (ABI 27): the rows are cut into at most 16 slabs, every slab is contracted into
+ * partial matrices of its own (no atomics) and a second launch adds them slab by slab - the same bits on every run, where
+ * pit_mlp_bwd_params adds its slabs with fp32 atomics.  fp32 tensors only; arguments as pit_mlp_bwd_params, plus workspace:
+ * pit_mlp_bwd_params_ordered_workspace(...) bytes, no initial contents needed.  The ragged path uses it so that "padding never
+ * enters the arithmetic" can be stated bit for bit; plain fp32 FMAs, about the cost of the data path it follows. */
+long pit_mlp_bwd_params_ordered_workspace(int rows, int n0, int n1, int n2);
+int pit_mlp_bwd_params_ordered(const float* x, long ldx, int rows, int n0, int n1, int n2, const float* h,
+                               int out_gelu, const float* d_y, long ld_dy,
+                               float* d_w1, float* d_b1, float* d_w2, float* d_b2,
+                               int accumulate, const float* scratch, float* workspace, void* stream);
 
 /* Layout probe used by the tests: D = A(32x8) * B(8x32) through the same
  * v_mfma_f32_32x32x2_f32 fragment maps the kernels use. */

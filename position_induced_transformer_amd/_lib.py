@@ -125,10 +125,28 @@ SIGNATURES = {
                     _P, _L, _P, _P, _P, _P, _I, _P, _I, _P],
     "pit_mlp_bwd_data": [_I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _L, _P, _L, _P, _I, _P],
     "pit_mlp_bwd_params": [_P, _L, _I, _I, _I, _I, _P, _I, _P, _L, _P, _P, _P, _P, _I, _P, _I, _P],
+    "pit_mlp_bwd_params_ordered": [_P, _L, _I, _I, _I, _I, _P, _I, _P, _L, _P, _P, _P, _P, _I, _P, _P, _P],
+    "pit_mlp_bwd_params_ordered_workspace": [_I, _I, _I, _I],
     "pit_mlp_bwd_params_deferrable": [_I, _I, _I, _I, _I, _L],
     "pit_rel_lp_loss_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
     "pit_rel_lp_loss_fwd_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P],
     "pit_rel_lp_loss_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "pit_plan_ragged_fwd": [_P, _P, _I, _I, _I, _I, _P, _P, _F, _I, _P, _P, _I, _P, _P, _P],
+    "pit_posatt_ragged_fwd": [_P, _P, _I, _I, _I, _I, _P, _P,
+                              _P, _I, _L, _L,
+                              _P, _I, _I,
+                              _P, _P, _I,
+                              _P, _L, _L, _I, _I,
+                              _P, _P, _P, _P, _I, _I, _P],
+    "pit_posatt_ragged_bwd": [_P, _P, _I, _I, _I, _I, _P, _P,
+                              _P, _I, _L, _L,
+                              _P, _I, _I, _P,
+                              _P, _I,
+                              _P, _L, _L, _I,
+                              _P, _L, _L, _I,
+                              _P, _I, _P, _P, _P, _I, _P, _P, _I, _P],
+    "pit_rel_lp_loss_ragged_fwd": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "pit_rel_lp_loss_ragged_bwd": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
     "pit_rel_max_norm": [_P, _P, _I, _I, _I, _P, _P, _P],
     "pit_instance_norm_fwd": [_P, _L, _L, _I, _I, _I, _F, _P, _P, _P],
     "pit_instance_norm_bwd": [_P, _P, _P, _I, _I, _I, _P, _P],
@@ -137,8 +155,8 @@ SIGNATURES = {
     "pit_debug_rider_counts": [_P, _I, _I],
 }
 
-LONG_RETURN = {"pit_satt_tiles_elems", "pit_posatt_dmesh_workspace"}
-ABI_VERSION = 26       # PIT_ABI_VERSION of include/pit_hip.h this binding was written against
+LONG_RETURN = {"pit_satt_tiles_elems", "pit_posatt_dmesh_workspace", "pit_mlp_bwd_params_ordered_workspace"}
+ABI_VERSION = 27       # PIT_ABI_VERSION of include/pit_hip.h this binding was written against
 
 _lib = None
 

@@ -381,6 +381,51 @@ _UNION_DECISIONS = {}
 ATT_UNION = 0x2000                                           # PIT_ATT_UNION
 
 
+def as_lengths(lengths, device, batch: int) -> torch.Tensor:
+    """Per-sample point counts of a ragged batch as the kernels read them: a contiguous int32 tensor of shape (batch,) on
+    ``device``.  A device tensor is used as it is when it already has that form (so a captured graph sees later in-place
+    updates); int64 tensors and Python sequences are converted once.  Precondition, not checked (a check would synchronise):
+    1 <= lengths[s] <= padded width - the kernels clamp into that range."""
+    if torch.is_tensor(lengths):
+        if lengths.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"lengths must be an int32 or int64 tensor, got {lengths.dtype}")
+        t = lengths.detach().reshape(-1)
+        if t.dtype != torch.int32 or t.device != device or not t.is_contiguous():
+            t = t.to(device=device, dtype=torch.int32).contiguous()
+    else:
+        t = torch.tensor([int(v) for v in lengths], dtype=torch.int32, device=device)
+    if t.numel() != batch:
+        raise ValueError(f"lengths must hold one entry per sample: {t.numel()} entries for a batch of {batch}")
+    return t
+
+
+RAGGED_LIST_CAP = None      # tests: force the list capacity of ragged plans (a small value makes rows overflow)
+
+
+def ragged_list_capacity(rank_k: int, n_in: int) -> int:
+    """Capacity of a ragged plan's candidate lists, from the PADDED width (so it does not depend on the lengths): k + 2 keys plus
+    room for ties, as for any masked layer; 0 = no lists (not much shorter than the row, or beyond pit_lists_transpose's 4096 keys)."""
+    if RAGGED_LIST_CAP is not None:
+        return int(RAGGED_LIST_CAP)
+    want = rank_k + 2
+    cap = ((want + max(16, want // 4) + 15) // 16) * 16
+    return 0 if (cap * 3 > n_in or n_in > 4096) else cap
+
+
+def check_ragged(metric: str, mesh_out, mesh_in) -> None:
+    """What a ragged batch (per-sample lengths) does not cover, refused before anything is launched."""
+    if metric != "euclid":
+        raise ValueError(f"lengths are defined for per-sample Euclidean meshes only, not for the {metric} metric")
+    if mesh_out.dim() != 3 or mesh_in.dim() != 3:
+        raise ValueError("lengths need per-sample (batch, n, space_dim) meshes: a batch-free mesh has no per-sample length")
+    if mesh_grad_wanted(mesh_out, mesh_in):
+        raise NotImplementedError("lengths with a mesh that requires grad: mesh gradients are not implemented for ragged batches")
+    if get_math_mode() != "fp32":
+        raise NotImplementedError("lengths in the bf16 math mode: ragged batches run in the fp32 math mode only")
+    if mesh_out.shape[-1] > 3:
+        raise NotImplementedError(f"lengths with space_dim > 3 (got {mesh_out.shape[-1]}): ragged batches take 1 to 3 coordinates")
+
+
 class MeshPlan:
     """Everything about a (mesh_out, mesh_in, metric, locality) pair that does not depend on
     lmda: contiguous 3-d meshes, period, quantile rank and the selection statistics
@@ -388,10 +433,20 @@ class MeshPlan:
 
     __slots__ = ("mesh_out", "mesh_in", "mesh_batch", "n_out", "n_in", "sdim", "metric", "metric_id", "period",
                  "rank_k", "rank_w", "masked", "self_attn", "stats", "nbr_idx", "nbr_cnt", "nbr_cap", "rev_ptr",
-                 "rev_row", "_complete", "_union", "_slab", "_fold")
+                 "rev_row", "_complete", "_union", "_slab", "_fold", "len_out", "len_in", "rank_w_dev")
 
     def __init__(self, metric: str, mesh_out: torch.Tensor, mesh_in: torch.Tensor, locality: float,
-                 self_attn: bool, period: Optional[float] = None):
+                 self_attn: bool, period: Optional[float] = None, len_out=None, len_in=None):
+        """``len_out`` / ``len_in`` (both or neither; self attention: the same object): per-sample point counts of a ragged
+        batch (``as_lengths``).  The plan then holds the statistics of pit_plan_ragged_fwd - rank and interpolation weight are
+        formed per sample on the device - and its layers run on the pit_posatt_ragged_* entries only."""
+        self.len_out = self.len_in = self.rank_w_dev = None
+        if len_out is not None or len_in is not None:
+            if len_out is None or len_in is None:
+                raise ValueError("a ragged plan needs both len_out and len_in")
+            if metric not in METRIC_ID:
+                raise ValueError(f"unknown metric {metric!r}")
+            check_ragged(metric, mesh_out, mesh_in)
         _need_gpu(mesh_out, mesh_in)
         if metric not in METRIC_ID:
             raise ValueError(f"unknown metric {metric!r}")
@@ -423,6 +478,36 @@ class MeshPlan:
         self._union = None
         self._slab = None
         self._fold = None
+        if len_out is not None:
+            # ragged batch: statistics over the first len_in[s] keys, rank and weight per sample on the device (rank_k / rank_w
+            # above are those of the padded width: they only size the lists).  Candidate lists as for any masked layer: the
+            # capacity comes from the PADDED width, so it does not depend on the lengths; overflowed rows scan all keys
+            self.len_out = as_lengths(len_out, mesh_out.device, self.mesh_batch)
+            self.len_in = self.len_out if len_in is len_out else as_lengths(len_in, mesh_out.device, self.mesh_batch)
+            dev, mb = mesh_out.device, self.mesh_batch
+            self.stats = torch.empty((3, mb, self.n_out), device=dev, dtype=torch.float32)
+            self.rank_w_dev = torch.empty((mb,), device=dev, dtype=torch.float32)
+            cap = ragged_list_capacity(self.rank_k, self.n_in) if (self.masked and SPARSE_MASKED) else 0
+            if cap:
+                self.nbr_cap = cap
+                self.nbr_idx = torch.empty((mb, self.n_out, cap), device=dev, dtype=torch.int32)
+                self.nbr_cnt = torch.empty((mb, self.n_out), device=dev, dtype=torch.int32)
+            rc = _lib.lib().pit_plan_ragged_fwd(self.mesh_out.data_ptr(), self.mesh_in.data_ptr(), mb, self.n_out,
+                                                self.n_in, self.sdim, self.len_out.data_ptr(), self.len_in.data_ptr(),
+                                                float(np.float32(locality)), 1 if self.masked else 0, self.stats.data_ptr(),
+                                                self.rank_w_dev.data_ptr(), cap, _lib.ptr(self.nbr_idx), _lib.ptr(self.nbr_cnt),
+                                                _lib.stream_ptr())
+            _lib.check(rc, "pit_plan_ragged_fwd")
+            if cap and torch.is_grad_enabled():          # the transposed lists: d(values) walks them by key
+                self.rev_ptr = torch.empty((mb, self.n_in + 1), device=dev, dtype=torch.int32)
+                self.rev_row = torch.empty((mb, self.n_out * cap), device=dev, dtype=torch.int32)
+                ws = torch.empty((2 * mb * self.n_in,), device=dev, dtype=torch.int32)
+                rc = _lib.lib().pit_lists_transpose(self.nbr_idx.data_ptr(), self.nbr_cnt.data_ptr(), mb, self.n_out, self.n_in, cap,
+                                                    self.rev_ptr.data_ptr(), self.rev_row.data_ptr(), ws.data_ptr(), _lib.stream_ptr())
+                _lib.check(rc, "pit_lists_transpose")
+            if _capturing():
+                _pin(self.len_out, self.len_in)
+            return
         cap = 0
         if self.masked and SPARSE_MASKED:
             want = self.rank_k + 2
@@ -736,6 +821,66 @@ def _mesh_grads(ctx, values, head, rowstat, scale, d_out):
         return d_mo.view(ctx.mesh_shapes[0]), None
     return (d_mo.view(ctx.mesh_shapes[0]) if d_mo is not None else None,
             d_mi.view(ctx.mesh_shapes[1]) if d_mi is not None else None)
+
+
+class _PosAttRagged(torch.autograd.Function):
+    """_PosAtt on a ragged plan (MeshPlan with lengths): pit_posatt_ragged_fwd / _bwd, one launch per layer and direction
+    (+ the d(lmda) finish); none of the fused / union / tiled / paired launches is taken."""
+
+    @staticmethod
+    def forward(ctx, values, head, plan: MeshPlan, n_head: int, concat: bool, head_is_scale: bool):
+        _need_gpu(values, head)
+        values = _row_view(values)
+        b, j, d = values.shape
+        if j != plan.n_in:
+            raise RuntimeError(f"inputs have {j} points but mesh_in has {plan.n_in}")
+        if plan.mesh_batch != b:
+            raise RuntimeError("mesh batch and input batch differ")
+        head = head.detach().reshape(-1).contiguous()
+        if head.numel() != n_head:
+            raise RuntimeError("lmda must hold one value per head")
+        width = (n_head + (1 if concat else 0)) * d
+        out = torch.empty((b, plan.n_out, width), device=values.device, dtype=torch.float32)
+        rowstat = torch.empty((b, n_head, plan.n_out, 4), device=values.device, dtype=torch.float32)
+        scale = torch.empty((n_head,), device=values.device, dtype=torch.float32)
+        rc = _lib.lib().pit_posatt_ragged_fwd(
+            plan.mesh_out.data_ptr(), plan.mesh_in.data_ptr(), b, plan.n_out, plan.n_in, plan.sdim,
+            plan.len_out.data_ptr(), plan.len_in.data_ptr(),
+            values.data_ptr(), d, values.stride(1), values.stride(0),
+            head.data_ptr(), n_head, 1 if head_is_scale else 0,
+            plan.stats.data_ptr(), plan.rank_w_dev.data_ptr(), 1 if plan.masked else 0,
+            out.data_ptr(), out.stride(1), out.stride(0), d if concat else 0, 1 if concat else 0,
+            rowstat.data_ptr(), scale.data_ptr(), _lib.ptr(plan.nbr_idx), _lib.ptr(plan.nbr_cnt), plan.nbr_cap,
+            MATH_MODES["fp32"], _lib.stream_ptr())
+        _lib.check(rc, "pit_posatt_ragged_fwd")
+        ctx.plan, ctx.n_head, ctx.concat, ctx.head_is_scale = plan, n_head, concat, head_is_scale
+        ctx.save_for_backward(values, head, rowstat, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        values, head, rowstat, scale = ctx.saved_tensors
+        plan, n_head = ctx.plan, ctx.n_head
+        b, j, d = values.shape
+        d_out = d_out.contiguous()
+        _need_gpu(d_out)
+        need_v, need_h = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        d_values = torch.empty((b, j, d), device=values.device, dtype=torch.float32) if need_v else None
+        d_head = torch.empty((n_head,), device=values.device, dtype=torch.float32) if need_h else None
+        work = _dscale_workspace(values.device, n_head) if need_h else None
+        if need_v or need_h:
+            rc = _lib.lib().pit_posatt_ragged_bwd(
+                plan.mesh_out.data_ptr(), plan.mesh_in.data_ptr(), b, plan.n_out, plan.n_in, plan.sdim,
+                plan.len_out.data_ptr(), plan.len_in.data_ptr(),
+                values.data_ptr(), d, values.stride(1), values.stride(0),
+                head.data_ptr(), n_head, 1 if ctx.head_is_scale else 0, scale.data_ptr(),
+                rowstat.data_ptr(), 1 if plan.masked else 0,
+                d_out.data_ptr(), d_out.stride(1), d_out.stride(0), d if ctx.concat else 0,
+                _lib.ptr(d_values), d, j * d, 1 if ctx.concat else 0,
+                _lib.ptr(d_head), 0, _lib.ptr(work), _lib.ptr(plan.nbr_idx), _lib.ptr(plan.nbr_cnt), plan.nbr_cap,
+                _lib.ptr(plan.rev_ptr), _lib.ptr(plan.rev_row), MATH_MODES["fp32"], _lib.stream_ptr())
+            _lib.check(rc, "pit_posatt_ragged_bwd")
+        return d_values, d_head, None, None, None, None
 
 
 class _PosAtt(torch.autograd.Function):
@@ -1136,6 +1281,14 @@ def posatt_apply(values: torch.Tensor, lmda: torch.Tensor, plan: MeshPlan, n_hea
     them requires grad they become inputs of the op and receive d(mesh) from pit_posatt_dmesh (Euclidean metric, fp32 mode;
     NotImplementedError otherwise); otherwise they are ignored.
     Opaque to torch.compile (dynamo runs it eagerly: raw pointers cross a ctypes boundary)."""
+    if plan.len_out is not None:                   # ragged batch: the pit_posatt_ragged_* entries, every layer on its own
+        if mesh_grad_wanted(mesh_out, mesh_in):
+            raise NotImplementedError("lengths with a mesh that requires grad: mesh gradients are not implemented for ragged batches")
+        if get_math_mode() != "fp32":
+            raise NotImplementedError("lengths in the bf16 math mode: ragged batches run in the fp32 math mode only")
+        if coord_dims:
+            raise RuntimeError("ragged batches need the coordinate concat materialised (ops.materialize_coords)")
+        return _PosAttRagged.apply(values, lmda.reshape(-1), plan, n_head, concat, head_is_scale)
     meshes = ()
     if mesh_grad_wanted(mesh_out, mesh_in):
         _check_mesh_grad(plan.metric)
@@ -1229,7 +1382,8 @@ class _Mlp(torch.autograd.Function):
     """kaiming_mlp forward/backward, optionally with the trailing gelu of pit.py:111,121."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, out_gelu: bool, concat_heads: int = 0, satt_link=None, y16_slot=None, after_dense_att: bool = False):
+    def forward(ctx, x, w1, b1, w2, b2, out_gelu: bool, concat_heads: int = 0, satt_link=None, y16_slot=None, after_dense_att: bool = False,
+                ordered: bool = False):
         _need_gpu(w1, b1, w2, b2)
         _need_gpu_bf16_ok(x)
         shape = x.shape
@@ -1259,7 +1413,9 @@ class _Mlp(torch.autograd.Function):
         ctx.math = _math_code() | ((IO_X_BF16 | IO_SAVE_BF16 | IO_DX_BF16) if x16 else 0)
         ctx.x16 = x16
         ctx.chain = None
-        if not x16 and chain_mlp_supported(rows, n0, n1, n2, out_gelu) and x2.stride(0) % 4 == 0 and x2.data_ptr() % 16 == 0 \
+        # ragged batches: the weight gradients are summed in a fixed order (pit_mlp_bwd_params_ordered) - fp32 tensors, the plain kernels
+        ctx.ordered = bool(ordered) and not x16
+        if not x16 and not ctx.ordered and chain_mlp_supported(rows, n0, n1, n2, out_gelu) and x2.stride(0) % 4 == 0 and x2.data_ptr() % 16 == 0 \
                 and _chain_weight_ok(w1) and _chain_weight_ok(w2):
             # bf16 mode, hid 128 / 256, a few thousand rows: GEMM1 + gelu + GEMM2 + gelu in ONE launch (csrc/pit_chain.hip)
             w1b, w2b = bf16_weights([w1, w2])
@@ -1316,7 +1472,18 @@ class _Mlp(torch.autograd.Function):
         L = _lib.lib()
         z2p = z2.data_ptr() if ctx.out_gelu else 0
         og = 1 if ctx.out_gelu else 0
-        if ctx.chain is not None and d_y2.stride(0) % 4 == 0 and d_y2.data_ptr() % 16 == 0:
+        if ctx.ordered:
+            # the data path, then both weight-gradient reductions slab by slab in a fixed order: the same bits on every run
+            rc = L.pit_mlp_bwd_data(rows, n0, n1, n2, w1.data_ptr(), w2.data_ptr(), z1.data_ptr(), z2p, og,
+                                    d_y2.data_ptr(), d_y2.stride(0), _lib.ptr(d_x), n0, scratch.data_ptr(),
+                                    MATH_MODES["fp32"], _lib.stream_ptr())
+            _lib.check(rc, "pit_mlp_bwd_data")
+            work = torch.empty((int(L.pit_mlp_bwd_params_ordered_workspace(rows, n0, n1, n2)) // 4,), device=dev, dtype=torch.float32)
+            rc = L.pit_mlp_bwd_params_ordered(x2.data_ptr(), x2.stride(0), rows, n0, n1, n2, h.data_ptr(), og, d_y2.data_ptr(),
+                                              d_y2.stride(0), d_w1.data_ptr(), d_b1.data_ptr(), d_w2.data_ptr(), d_b2.data_ptr(),
+                                              1 if inplace else 0, scratch.data_ptr(), work.data_ptr(), _lib.stream_ptr())
+            _lib.check(rc, "pit_mlp_bwd_params_ordered")
+        elif ctx.chain is not None and d_y2.stride(0) % 4 == 0 and d_y2.data_ptr() % 16 == 0:
             # the data path (dZ2, dZ1, d_x) in ONE launch on the forward's bf16 weight copies, then both weight-gradient reductions
             w1b, w2b = ctx.chain
             # x is a self-attention layer's concat buffer (csrc/pit_satt.hip): its backward's G16 = bf16(d_x_h / rowsum_h) is written here,
@@ -1383,16 +1550,21 @@ class _Mlp(torch.autograd.Function):
             _lib.check(rc, "pit_mlp_bwd")
         dx = d_x.reshape(ctx.in_shape) if need_x else None
         if inplace:
-            return dx, None, None, None, None, None, None, None, None, None
-        return dx, d_w1, d_b1, d_w2, d_b2, None, None, None, None, None
+            return dx, None, None, None, None, None, None, None, None, None, None
+        return dx, d_w1, d_b1, d_w2, d_b2, None, None, None, None, None, None
 
 
 @torch.compiler.disable
-def mlp_apply(x, w1, b1, w2, b2, out_gelu: bool = False, concat_heads: int = 0) -> torch.Tensor:
+def mlp_apply(x, w1, b1, w2, b2, out_gelu: bool = False, concat_heads: int = 0, ordered: bool = False) -> torch.Tensor:
     """kaiming_mlp forward (pit.py:21-26) (+ trailing gelu).  ``concat_heads=H`` (the result feeds a
     self-attention layer with H heads: pit.py:116-121) makes the kernels write the result directly into the
     first columns of that layer's (b, L, (1+H)*n2) concat buffer; the returned tensor is that strided view and
-    carries the buffer (``_pit_concat``), so the attention kernel skips copying its inputs (pit.py:44)."""
+    carries the buffer (``_pit_concat``), so the attention kernel skips copying its inputs (pit.py:44).
+    ``ordered`` (ragged batches, fp32 mode): the backward sums the weight gradients in a fixed order (pit_mlp_bwd_params_ordered)."""
+    if ordered:
+        if get_math_mode() != "fp32":
+            raise NotImplementedError("ordered weight gradients run in the fp32 math mode only")
+        return _Mlp.apply(x, w1, b1, w2, b2, out_gelu, 0, None, None, False, True)
     link = getattr(x, "_pit_satt", None)         # x is the output of a dense self-attention layer on csrc/pit_satt.hip
     dense = bool(getattr(x, "_pit_dense_att", False))      # ... or of one on the fp32-era kernels (posatt_apply)
     if concat_heads <= 0 or x.dim() != 3:
@@ -2570,6 +2742,54 @@ def rel_lp_loss(true, pred, out_dim: int, p: int, pred_scale=None, pred_shift=No
             clear.zero_()
         return _FusedLoss.apply(pred, spec)
     return _RelLpLoss.apply(pred, true, out_dim, p, pred_scale, pred_shift, unit_seed, clear)
+
+
+class _RelLpLossRagged(torch.autograd.Function):
+    """RelLpNorm of every sample truncated to its first lengths[s] points (pit_rel_lp_loss_ragged_*): padded points are
+    skipped and get a zero gradient; ``true`` gets none (data)."""
+
+    @staticmethod
+    def forward(ctx, pred, true, lengths, out_dim: int, p: int):
+        _need_gpu(pred, true)
+        b = true.size(0)
+        t = true.detach().reshape(b, -1, out_dim).contiguous()
+        q = pred.detach().reshape(b, -1, out_dim).contiguous()
+        if t.shape != q.shape:
+            raise RuntimeError(f"true {tuple(true.shape)} and pred {tuple(pred.shape)} do not match")
+        npts = t.shape[1]
+        norms = torch.empty((b, out_dim, 2), device=t.device, dtype=torch.float32)
+        loss = torch.empty((), device=t.device, dtype=torch.float32)
+        rc = _lib.lib().pit_rel_lp_loss_ragged_fwd(t.data_ptr(), q.data_ptr(), lengths.data_ptr(), b, npts, out_dim, int(p),
+                                                   norms.data_ptr(), loss.data_ptr(), _lib.stream_ptr())
+        _lib.check(rc, "pit_rel_lp_loss_ragged_fwd")
+        ctx.meta = (b, npts, out_dim, int(p), pred.shape)
+        ctx.save_for_backward(t, q, norms, lengths)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        t, q, norms, lengths = ctx.saved_tensors
+        b, npts, out_dim, p, shape = ctx.meta
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        g = g.contiguous()
+        d_pred = torch.empty_like(q)
+        rc = _lib.lib().pit_rel_lp_loss_ragged_bwd(t.data_ptr(), q.data_ptr(), lengths.data_ptr(), b, npts, out_dim, p,
+                                                   norms.data_ptr(), g.data_ptr(), d_pred.data_ptr(), _lib.stream_ptr())
+        _lib.check(rc, "pit_rel_lp_loss_ragged_bwd")
+        return d_pred.reshape(shape), None, None, None, None
+
+
+@torch.compiler.disable
+def rel_lp_loss_ragged(true, pred, lengths, out_dim: int, p: int) -> torch.Tensor:
+    """sum_s mean_c ||true_s - pred_s||_p / ||true_s||_p over the first lengths[s] points of every sample."""
+    if torch.is_grad_enabled() and true.requires_grad:
+        raise NotImplementedError("RelLpNorm with lengths gives `true` no gradient (it is data)")
+    _need_gpu(pred, true)
+    lengths = as_lengths(lengths, pred.device, true.size(0))
+    if _capturing():
+        _pin(lengths)
+    return _RelLpLossRagged.apply(pred, true, lengths, out_dim, p)
 
 
 _RELMAX_WS = {}

@@ -80,12 +80,12 @@ class kaiming_mlp(nn.Module):
         nn.init.kaiming_normal_(self.mlp1.weight)
         nn.init.kaiming_normal_(self.mlp2.weight)
 
-    def forward(self, x, out_gelu: bool = False, concat_heads: int = 0):
+    def forward(self, x, out_gelu: bool = False, concat_heads: int = 0, ordered: bool = False):
         """``out_gelu=True`` fuses the gelu that pit.encoder/processor apply to the result
         (pit.py:111,121) into the second GEMM's epilogue; ``concat_heads=H`` writes the result into the
         concat buffer of the H-head self-attention layer that consumes it (ops.mlp_apply)."""
         return ops.mlp_apply(x, self.mlp1.weight, self.mlp1.bias, self.mlp2.weight, self.mlp2.bias, out_gelu,
-                             concat_heads)
+                             concat_heads, ordered)
 
 
 class posatt(nn.Module):
@@ -105,7 +105,12 @@ class posatt(nn.Module):
         self._plans = OrderedDict()          # LRU of mesh plans (batch-free meshes)
 
     # -- selection statistics: cached for fixed meshes, rebuilt per call for per-sample meshes
-    def _plan(self, mesh_out, mesh_in, self_attn):
+    def _plan(self, mesh_out, mesh_in, self_attn, len_out=None, len_in=None):
+        if len_out is not None or len_in is not None:
+            # a ragged batch: refused here for batch-free / periodic operators, before any shape check
+            if not self._batched:
+                self._no_lengths()
+            return ops.MeshPlan(self._metric, mesh_out, mesh_in, self.locality, self_attn, len_out=len_out, len_in=len_in)
         if self._batched:
             if mesh_out.dim() != 3:
                 raise RuntimeError(f"{type(self).__name__} expects (batch, L, space_dim) meshes")
@@ -126,6 +131,22 @@ class posatt(nn.Module):
             ops._pin(plan)        # its buffers' addresses are now baked into a hipGraph: never release them
         return plan
 
+    def _no_lengths(self):
+        raise ValueError(f"{type(self).__name__}: lengths are defined for per-sample meshes (posatt / posatt_cross) only - "
+                         "a batch-free mesh has no per-sample length")
+
+    def _ragged(self, mesh_out, mesh_in, inputs, len_out, len_in, self_attn, plan=None):
+        """The layer on a ragged batch (ops.MeshPlan with lengths -> pit_posatt_ragged_*).  ``plan``: a plan built for exactly
+        these meshes, lengths and this locality (pit.processor builds one for all its blocks)."""
+        if self._overridden():
+            raise NotImplementedError("lengths with an overridden dist2att / convolution")
+        if len_out is None or len_in is None:
+            raise ValueError(f"{type(self).__name__}: cross attention on a ragged batch needs both len_out and len_in")
+        if plan is None:
+            plan = self._plan(mesh_out, mesh_in, self_attn, len_out, len_in)
+        return ops.posatt_apply(ops.materialize_coords(inputs), self.lmda, plan, self.n_head, concat=self_attn,
+                                mesh_out=mesh_out, mesh_in=mesh_in)
+
     def _overridden(self) -> bool:
         """True if a subclass replaced ``dist2att`` or ``convolution``: the reference's ``forward`` calls
         ``self.dist2att`` / ``self.convolution`` (pit.py:42-43,68-69), so such a subclass expects its methods to be
@@ -138,7 +159,12 @@ class posatt(nn.Module):
         att = self.dist2att(mesh_out, mesh_in, self.lmda, self.locality)
         return self.convolution(att, ops.materialize_coords(inputs))
 
-    def forward(self, mesh, inputs):
+    def forward(self, mesh, inputs, lengths=None):
+        """``lengths`` (per-sample meshes only): point counts of a ragged batch - sample s is computed from its first
+        lengths[s] points alone, rows beyond come out as zeros in the head columns (README, "Ragged batches")."""
+        if lengths is not None:
+            lengths = ops.as_lengths(lengths, mesh.device, mesh.shape[0]) if mesh.dim() == 3 else lengths
+            return self._ragged(mesh, mesh, inputs, lengths, lengths, True)
         if self._overridden():
             inputs = ops.materialize_coords(inputs)
             return torch.cat((inputs, self._composed(mesh, mesh, inputs)), dim=-1)
@@ -150,7 +176,9 @@ class posatt(nn.Module):
         plan = self._plan(mesh, mesh, True)
         return ops.posatt_apply(inputs, self.lmda, plan, self.n_head, concat=True)
 
-    def _cross(self, mesh_out, mesh_in, inputs, out_bf16: bool = False):
+    def _cross(self, mesh_out, mesh_in, inputs, out_bf16: bool = False, len_out=None, len_in=None):
+        if len_out is not None or len_in is not None:
+            return self._ragged(mesh_out, mesh_in, inputs, len_out, len_in, False)
         if self._overridden():
             return self._composed(mesh_out, mesh_in, inputs)
         if ops.mesh_grad_wanted(mesh_out, mesh_in):
@@ -174,11 +202,21 @@ class posatt(nn.Module):
         return ops.posatt_apply(inputs, self.lmda, plan, self.n_head, concat=False)
 
     # -- dense helpers kept for API compatibility with the reference (not used by forward)
-    def dist2att(self, mesh_out, mesh_in, scale, locality):
+    def dist2att(self, mesh_out, mesh_in, scale, locality, len_out=None, len_in=None):
         """Dense attention weights ((b,)H,L_out,L_in) of pit.py:46-52 for code that inspects them
         (``scale`` is the lmda parameter, as in the reference).  Built by running the fused HIP
         kernel on the identity as values, so it is exactly the matrix ``forward`` applies - there
-        is no second, eager implementation of the mask/softmax; ``forward`` never builds it."""
+        is no second, eager implementation of the mask/softmax; ``forward`` never builds it.
+        ``len_out`` / ``len_in`` (ragged batches): padded rows and padded keys of the matrix are zero."""
+        if len_out is not None or len_in is not None:
+            if not self._batched:
+                self._no_lengths()
+            if len_out is None or len_in is None:
+                raise ValueError("dist2att on a ragged batch needs both len_out and len_in")
+            plan = ops.MeshPlan(self._metric, mesh_out, mesh_in, float(locality), False, len_out=len_out, len_in=len_in)
+            eye = torch.eye(plan.n_in, device=mesh_in.device).unsqueeze(0).repeat(plan.mesh_batch, 1, 1)
+            att = ops.posatt_apply(eye, scale, plan, self.n_head, concat=False, mesh_out=mesh_out, mesh_in=mesh_in)
+            return att.reshape(plan.mesh_batch, plan.n_out, self.n_head, plan.n_in).permute(0, 2, 1, 3)
         if ops.mesh_grad_wanted(mesh_out, mesh_in):
             ops._check_mesh_grad(self._metric)
         plan = ops.MeshPlan(self._metric, mesh_out, mesh_in, float(locality), False)
@@ -204,8 +242,8 @@ class posatt(nn.Module):
 class posatt_cross(posatt):
     """Cross attention mesh_in -> mesh_out on per-sample meshes (pit.py:59-71)."""
 
-    def forward(self, mesh_out, mesh_in, inputs, out_bf16: bool = False):
-        return self._cross(mesh_out, mesh_in, inputs, out_bf16)
+    def forward(self, mesh_out, mesh_in, inputs, out_bf16: bool = False, len_out=None, len_in=None):
+        return self._cross(mesh_out, mesh_in, inputs, out_bf16, len_out, len_in)
 
 
 class posatt_fixed(posatt):
@@ -286,10 +324,11 @@ class pit(nn.Module):
         return True
 
     @staticmethod
-    def _mlp_gelu(layer, x, concat_heads: int = 0):
+    def _mlp_gelu(layer, x, concat_heads: int = 0, ordered: bool = False):
         # scripts may replace en_layer / mlp[i] by their own modules (train_elasticity.py:39)
+        # (ordered: ragged batches - the weight gradients of OUR MLPs are summed in a fixed order)
         if isinstance(layer, kaiming_mlp):
-            return layer(x, out_gelu=True, concat_heads=concat_heads)
+            return layer(x, out_gelu=True, concat_heads=concat_heads, ordered=ordered)
         return gelu(layer(x))
 
     def _heads_of_block(self, i: int, width: int) -> int:
@@ -375,7 +414,24 @@ class pit(nn.Module):
             return None
         return plan if ops.edge_fusion_supported(plan, up.n_head, hid, batch, True) else None
 
-    def encoder(self, mesh_in, func_in, mesh_ltt):
+    def _ragged_lengths(self, meshes, **lengths):
+        """Lengths of a ragged batch as device tensors; None when no length was given."""
+        if all(v is None for v in lengths.values()):
+            return None
+        mesh = meshes[0]
+        if not (torch.is_tensor(mesh) and mesh.dim() == 3):
+            raise ValueError("lengths need per-sample (batch, n, space_dim) meshes: a batch-free mesh has no per-sample length")
+        return tuple(None if v is None else ops.as_lengths(v, mesh.device, mesh.shape[0]) for v in lengths.values())
+
+    def encoder(self, mesh_in, func_in, mesh_ltt, len_in=None, len_ltt=None):
+        """``len_in`` / ``len_ltt`` (keywords; ragged batches of per-sample clouds): point counts of ``mesh_in`` and
+        ``mesh_ltt``.  With lengths every layer runs on its own on the ragged kernels."""
+        rag = self._ragged_lengths((mesh_in, mesh_ltt), len_in=len_in, len_ltt=len_ltt)
+        if rag is not None:
+            len_in, len_ltt = rag
+            if len_in is None or len_ltt is None:
+                raise ValueError("encoder: a ragged batch needs both len_in and len_ltt")
+            return self._mlp_gelu(self.en_layer, self.down(mesh_ltt, mesh_in, func_in, len_out=len_ltt, len_in=len_in), ordered=True)
         if self._mesh_grad(mesh_in, mesh_ltt):
             return self._mlp_gelu(self.en_layer, self.down(mesh_ltt, mesh_in, func_in), self._heads_of_block(0, self.hid_dim))
         # the fused processor's weights depend on (mesh_ltt, lmda) only: they are formed by extra workgroups of the
@@ -468,7 +524,19 @@ class pit(nn.Module):
         need_q = torch.is_grad_enabled() and any(a.lmda.requires_grad for a in self.conv)
         return ops.block_weights(plan, [a.lmda for a in self.conv], heads, need_q)
 
-    def processor(self, func_ltt, mesh_ltt):
+    def processor(self, func_ltt, mesh_ltt, len_ltt=None):
+        rag = self._ragged_lengths((mesh_ltt,), len_ltt=len_ltt)
+        if rag is not None:
+            # one plan (selection statistics of mesh_ltt under these lengths) for all blocks that are OUR layers of one locality
+            own = [a for a in self.conv if type(a) is posatt and "forward" not in a.__dict__ and not a._overridden()]
+            shared = own[0]._plan(mesh_ltt, mesh_ltt, True, rag[0], rag[0]) if len(own) > 1 else None
+            for a, w in zip(self.conv, self.mlp):
+                if shared is not None and a in own and a.locality == own[0].locality:
+                    func_ltt = a._ragged(mesh_ltt, mesh_ltt, func_ltt, rag[0], rag[0], True, plan=shared)
+                else:
+                    func_ltt = a(mesh_ltt, func_ltt, lengths=rag[0])
+                func_ltt = self._mlp_gelu(w, func_ltt, ordered=True)
+            return func_ltt
         if self._mesh_grad(mesh_ltt):
             for i, (a, w) in enumerate(zip(self.conv, self.mlp)):
                 func_ltt = self._mlp_gelu(w, a(mesh_ltt, func_ltt), self._heads_of_block(i + 1, self.hid_dim))
@@ -517,7 +585,14 @@ class pit(nn.Module):
         return ops.fold_decoder_apply(func_ltt, up.lmda, plan, heads, (de.mlp1.weight, de.mlp1.bias, de.mlp2.weight, de.mlp2.bias),
                                       fold_att)
 
-    def decoder(self, mesh_ltt, func_ltt, mesh_out):
+    def decoder(self, mesh_ltt, func_ltt, mesh_out, len_ltt=None, len_out=None):
+        rag = self._ragged_lengths((mesh_ltt, mesh_out), len_ltt=len_ltt, len_out=len_out)
+        if rag is not None:
+            len_ltt, len_out = rag
+            if len_ltt is None or len_out is None:
+                raise ValueError("decoder: a ragged batch needs both len_ltt and len_out")
+            f = self.up(mesh_out, mesh_ltt, func_ltt, len_out=len_out, len_in=len_ltt)
+            return self.de(f, ordered=True) if isinstance(self.de, kaiming_mlp) else self.de(f)
         # bf16 mode (BASELINE configs 3 and 5): the up-projection's output - the largest tensor of the model, rows x H*hid -
         # and with it the decoder MLP's saved activations and their gradients are kept in memory as bf16 when the
         # decoder MLP's shape runs on the kernels that read them (ops.mlp_bf16_io_supported); fp32 accumulation throughout

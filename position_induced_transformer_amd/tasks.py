@@ -102,7 +102,17 @@ class pit_elasticity(P.pit):
         super().__init__(*args, **kw)
         self.en_layer = P.kaiming_mlp(self.n_head * self.in_dim, self.hid_dim, self.hid_dim)
 
-    def forward(self, mesh_in, func_in, mesh_out):
+    def forward(self, mesh_in, func_in, mesh_out, len_in=None, len_out=None):
+        """``len_in`` / ``len_out``: point counts of a ragged batch (padded clouds); the latent mesh is ``mesh_out``, so
+        ``len_out`` is its length vector too, and ``len_in`` alone means both.  Padded rows of the result are finite
+        (the decoder MLP's bias path) and meaningless: mask them, e.g. with ``RelLpNorm(...)(true, pred, lengths)``."""
+        if len_in is not None or len_out is not None:
+            len_in = len_out if len_in is None else len_in
+            len_out = len_in if len_out is None else len_out
+            size = mesh_out.shape[:-1]
+            ltt = self.encoder(mesh_in, func_in, mesh_out, len_in=len_in, len_ltt=len_out)
+            ltt = self.processor(ltt, mesh_out, len_ltt=len_out)
+            return self.decoder(mesh_out, ltt, mesh_out, len_ltt=len_out, len_out=len_out).reshape(*size, self.out_dim)
         self._mesh_grad(mesh_in, mesh_out)
         size = mesh_out.shape[:-1]
         mesh_ltt = mesh_out
@@ -186,6 +196,25 @@ def rollout_loss(model, mesh, x, y, steps: int, loss_fn, recompute: bool = False
 
 
 # ----------------------------------------------------------------------------- configs
+def ragged_clouds(lengths, width: int, space_dim: int = 2, channels: int = 1, out_dim: int = 1, device="cpu", seed: int = 0,
+                  pad_value: float = 0.0):
+    """Synthetic ragged batch of point clouds for tests and examples: sample s has lengths[s] points uniform in the unit
+    cube, an input function and a target, each padded to ``width`` points with ``pad_value`` (NaN shows that padding
+    never enters the arithmetic).  Returns (mesh, func, target, lengths as an int32 tensor), all on ``device``."""
+    g = torch.Generator().manual_seed(seed)
+    b = len(lengths)
+    mesh = torch.full((b, width, space_dim), pad_value)
+    func = torch.full((b, width, channels), pad_value)
+    target = torch.full((b, width, out_dim), pad_value)
+    for s, n in enumerate(lengths):
+        if not 1 <= n <= width:
+            raise ValueError(f"length {n} outside [1, {width}]")
+        mesh[s, :n] = torch.rand((n, space_dim), generator=g)
+        func[s, :n] = torch.randn((n, channels), generator=g)
+        target[s, :n] = torch.randn((n, out_dim), generator=g)
+    return mesh.to(device), func.to(device), target.to(device), torch.tensor(list(lengths), dtype=torch.int32, device=device)
+
+
 def make_task(name: str, device="cuda", seed: int = 0):
     """Build (model, sample_fn) for a named configuration of the reference.
 

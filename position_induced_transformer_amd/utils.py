@@ -95,7 +95,14 @@ class RelLpNorm:
         self._out_dim = out_dim
         self._ord = p
 
-    def __call__(self, true, pred):
+    def __call__(self, true, pred, lengths=None):
+        """``lengths`` (ragged batches; int32 / int64 device tensor or a Python list, one entry per sample): the norms of
+        sample s run over its first lengths[s] points only - utils.py:86-98 on the truncated sample; padded points are
+        skipped and ``pred`` gets a zero gradient there.  Device tensors only."""
+        if lengths is not None:
+            if float(self._ord) != int(self._ord) or int(self._ord) < 1:
+                raise NotImplementedError(f"RelLpNorm with lengths: integer p >= 1, got p = {self._ord}")
+            return ops.rel_lp_loss_ragged(true, pred, lengths, self._out_dim, int(self._ord))
         if pred.is_cuda or true.is_cuda:
             # device tensors always go through the HIP kernels (no eager-PyTorch path on the GPU)
             if float(self._ord) != int(self._ord) or int(self._ord) < 1:
