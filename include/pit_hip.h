@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define PIT_ABI_VERSION 27
+#define PIT_ABI_VERSION 28
 #define PIT_MAX_SPACE_DIM 8   /* largest space_dim any entry accepts */
 #define PIT_DSCALE_SLOTS 1024 /* fp64 accumulators per head in pit_posatt_bwd's workspace */
 
@@ -702,6 +702,43 @@ int pit_posatt_ragged_bwd(const float* mesh_out, const float* mesh_in, int mesh_
                           float* d_head, int accumulate_head, double* workspace,
                           const int* nbr_idx, const int* nbr_cnt, int nbr_cap, const int* rev_ptr, const int* rev_row,
                           int math_mode, void* stream);
+/* ---- A mesh shared by the whole batch against per-sample clouds (ABI 28; csrc/pit_ragged.hip) -------------------------------
+ * The three entries above with, for each mesh, a sample stride in POINTS and a length pointer that may be NULL:
+ *   out_stride / in_stride: points between two samples' meshes; 0 = ONE (n, space_dim) mesh shared by every sample, read in
+ *     place (no expanded copy); otherwise >= n_out / n_in (PIT_ERR_SIZE for anything between);
+ *   len_out / len_in: NULL = every sample has the full width n_out / n_in.
+ * Sample s comes out as pit.py:46-57 computes it for (shared mesh, cloud_s) as a batch of one - the broadcast of a (n, s) mesh
+ * against a (b, n', s) mesh in pit.py:47-48 - and, with a length on the cloud side, for the cloud's first len[s] points alone:
+ * the rank floor(fl32(q) * fl32(len_in[s] - 1)) is per sample when the keys are the cloud and that of the full width when the
+ * keys are the shared mesh; row tiles end at len_out[s] only when the rows are the cloud.  Only coordinates are shared: stats
+ * (3*mesh_batch*n_out), rank_w, nbr_idx / nbr_cnt (choose cap from the full / padded n_in), the transposed lists of
+ * pit_lists_transpose (call it with mesh_batch samples as before), rowstat, values, out and d_values are all PER SAMPLE - the
+ * d(values) of a shared-key layer has mesh_batch * n_in rows.  The zero rules of ABI 27 hold on the side that has lengths.
+ * With strides n_out / n_in and both lengths given these are pit_plan_ragged_fwd / pit_posatt_ragged_fwd / _bwd bit for bit
+ * (one implementation); those three keep refusing NULL lengths. */
+int pit_plan_ragged_strided_fwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                                int space_dim, long out_stride, long in_stride, const int* len_out, const int* len_in,
+                                float locality, int need_kth, float* stats, float* rank_w, int cap, int* nbr_idx,
+                                int* nbr_cnt, void* stream);
+int pit_posatt_ragged_strided_fwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                                  int space_dim, long out_stride, long in_stride, const int* len_out, const int* len_in,
+                                  const float* values, int dim, long ld_values, long values_bstride,
+                                  const float* head, int n_head, int head_is_scale,
+                                  const float* stats, const float* rank_w, int masked,
+                                  float* out, long ld_out, long out_bstride, int out_col0, int copy_inputs,
+                                  float* rowstat, float* scale_out,
+                                  const int* nbr_idx, const int* nbr_cnt, int nbr_cap, int math_mode, void* stream);
+int pit_posatt_ragged_strided_bwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                                  int space_dim, long out_stride, long in_stride, const int* len_out, const int* len_in,
+                                  const float* values, int dim, long ld_values, long values_bstride,
+                                  const float* head, int n_head, int head_is_scale, const float* scale,
+                                  const float* rowstat, int masked,
+                                  const float* d_out, long ld_dout, long dout_bstride, int out_col0,
+                                  float* d_values, long ld_dvalues, long dvalues_bstride, int add_residual,
+                                  float* d_head, int accumulate_head, double* workspace,
+                                  const int* nbr_idx, const int* nbr_cnt, int nbr_cap, const int* rev_ptr, const int* rev_row,
+                                  int math_mode, void* stream);
+
 /* RelLpNorm (utils.py:86-98) of every sample TRUNCATED to its first len[s] points: true / pred (batch, npts, nch) contiguous,
  * norms (batch, nch, 2) = {||true - pred||_p, ||true||_p}, *loss = sum_s mean_c of their ratio.  Padded points are skipped (not
  * multiplied by zero).  The backward writes d_pred (batch, npts, nch) = *gloss (NULL: 1) times the gradient, zero on padded points. */

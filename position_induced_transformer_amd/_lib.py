@@ -145,6 +145,20 @@ SIGNATURES = {
                               _P, _L, _L, _I,
                               _P, _L, _L, _I,
                               _P, _I, _P, _P, _P, _I, _P, _P, _I, _P],
+    "pit_plan_ragged_strided_fwd": [_P, _P, _I, _I, _I, _I, _L, _L, _P, _P, _F, _I, _P, _P, _I, _P, _P, _P],
+    "pit_posatt_ragged_strided_fwd": [_P, _P, _I, _I, _I, _I, _L, _L, _P, _P,
+                                      _P, _I, _L, _L,
+                                      _P, _I, _I,
+                                      _P, _P, _I,
+                                      _P, _L, _L, _I, _I,
+                                      _P, _P, _P, _P, _I, _I, _P],
+    "pit_posatt_ragged_strided_bwd": [_P, _P, _I, _I, _I, _I, _L, _L, _P, _P,
+                                      _P, _I, _L, _L,
+                                      _P, _I, _I, _P,
+                                      _P, _I,
+                                      _P, _L, _L, _I,
+                                      _P, _L, _L, _I,
+                                      _P, _I, _P, _P, _P, _I, _P, _P, _I, _P],
     "pit_rel_lp_loss_ragged_fwd": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "pit_rel_lp_loss_ragged_bwd": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
     "pit_rel_max_norm": [_P, _P, _I, _I, _I, _P, _P, _P],
@@ -156,7 +170,7 @@ SIGNATURES = {
 }
 
 LONG_RETURN = {"pit_satt_tiles_elems", "pit_posatt_dmesh_workspace", "pit_mlp_bwd_params_ordered_workspace"}
-ABI_VERSION = 27       # PIT_ABI_VERSION of include/pit_hip.h this binding was written against
+ABI_VERSION = 28       # PIT_ABI_VERSION of include/pit_hip.h this binding was written against
 
 _lib = None
 

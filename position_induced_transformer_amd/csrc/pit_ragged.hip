@@ -16,6 +16,11 @@
 // columns with plain FMAs, 16 accumulators per lane.  A tile's partial sums are fp32, tiles are added in fp64 in a
 // fixed order: the same bits on every run (d(scale) meets in the fp64 slots of pit_posatt_bwd's workspace).
 // Tiles and workgroups beyond the sample's length exit early and the contracted loop ends at the length.
+//
+// A mesh SHARED by the whole batch against per-sample clouds (the *_strided entries, ABI 28): every kernel takes a sample stride
+// per mesh - 0 reads the one (n, space_dim) mesh in place for every sample, no expanded copy exists - and a length pointer that may
+// be NULL (every sample has the full width: the shared side has no padding).  Both are kernel arguments, so the branch is uniform
+// and the stride-0 address is the same for every sample; statistics, lists, rowstat, values and d(values) stay per sample.
 #include "pit_common.h"
 
 namespace {
@@ -23,7 +28,9 @@ namespace {
 constexpr int RT = 16;     // owner items per workgroup
 constexpr int KT = 64;     // contracted items per tile
 
-__device__ __forceinline__ int clamp_len(const int* len, int s, int n) { return max(1, min(len[s], n)); }
+// len == NULL: a side without lengths - every sample has the full width (the shared mesh of a mixed pair, or a cloud side given
+// without lengths); a wave-uniform branch on a kernel argument
+__device__ __forceinline__ int clamp_len(const int* len, int s, int n) { return len ? max(1, min(len[s], n)) : n; }
 
 __device__ __forceinline__ float4 load_pt3(const float* p, int sdim) {
     float4 v;
@@ -40,6 +47,7 @@ __device__ __forceinline__ float dist3(const float4& o, const float4& i) {
 // ---- selection: order statistics over the first len_in[s] keys of a row; one workgroup per row ----------------------
 struct RagSelectArgs {
     const float* mesh_out; const float* mesh_in;
+    long mo_stride, mi_stride;   // floats between two samples' meshes; 0 = one mesh shared by the batch (read in place)
     const int* len_out; const int* len_in;
     float* stats;        // [3][batch * n_out]
     float* rank_w;       // [batch]: fractional part of the sample's quantile rank
@@ -64,8 +72,8 @@ __global__ __launch_bounds__(256) void ragged_select_kernel(RagSelectArgs a) {
         if (threadIdx.x == 0) { a.stats[row] = 0.0f; a.stats[rows + row] = 0.0f; a.stats[2 * rows + row] = 0.0f; }
         return;
     }
-    const float4 xo = load_pt3(a.mesh_out + row * a.sdim, a.sdim);
-    const float* pin = a.mesh_in + (long)s * a.n_in * a.sdim;
+    const float4 xo = load_pt3(a.mesh_out + (long)s * a.mo_stride + (long)i * a.sdim, a.sdim);
+    const float* pin = a.mesh_in + (long)s * a.mi_stride;
     auto key_at = [&](int j) -> uint32_t { return __float_as_uint(dist3(xo, load_pt3(pin + (long)j * a.sdim, a.sdim))); };
     auto block_count = [&](uint32_t cand, bool inclusive) -> int {
         int c = 0;
@@ -116,6 +124,7 @@ __global__ __launch_bounds__(256) void ragged_select_kernel(RagSelectArgs a) {
 // ---- attention ------------------------------------------------------------------------------------------------------
 struct RagArgs {
     const float* mesh_out; const float* mesh_in;
+    long mo_stride, mi_stride;   // as in RagSelectArgs
     const int* len_out; const int* len_in;
     int batch, n_out, n_in, sdim;
     const float* values; int dim; long ld_values, values_bstride;
@@ -186,7 +195,7 @@ __global__ __launch_bounds__(256) void ragged_rows_kernel(RagArgs a) {
     if (tid < RT) {
         const int r = min(tid, live - 1);
         const long row = (long)s * a.n_out + r0 + r;
-        s_xo[tid] = load_pt3(a.mesh_out + row * a.sdim, a.sdim);
+        s_xo[tid] = load_pt3(a.mesh_out + (long)s * a.mo_stride + (long)(r0 + r) * a.sdim, a.sdim);
         float4 st;
         if (MODE == 0) {
             st.x = a.masked ? quantile_lerp(__fmul_rn(c, a.stats[row]), __fmul_rn(c, a.stats[rows_total + row]), a.rank_w[s])
@@ -203,7 +212,7 @@ __global__ __launch_bounds__(256) void ragged_rows_kernel(RagArgs a) {
     const float4 xo = s_xo[wr];
     const float4 rs = s_rs[wr];
     const bool rlive = wr < live;
-    const float* pin = a.mesh_in + (long)s * a.n_in * a.sdim;
+    const float* pin = a.mesh_in + (long)s * a.mi_stride;
     const float* vals = a.values + (long)s * a.values_bstride + col;
     float rsum = 0.0f, qsum = 0.0f;
     double tot[RT];
@@ -288,7 +297,7 @@ __global__ __launch_bounds__(256) void ragged_cols_kernel(RagArgs a) {
     if (cvalid)
         for (int r = live; r < keys_here; ++r) dv[(long)r * a.ld_dvalues] = 0.0f;       // padded keys: zero, residual included
     if (live == 0) return;
-    if (tid < RT) s_xi[tid] = load_pt3(a.mesh_in + ((long)s * a.n_in + k0 + min(tid, live - 1)) * a.sdim, a.sdim);
+    if (tid < RT) s_xi[tid] = load_pt3(a.mesh_in + (long)s * a.mi_stride + (long)(k0 + min(tid, live - 1)) * a.sdim, a.sdim);
     __syncthreads();
     const int wr = tid & 15, wk = tid >> 4;
     const float4 xi = s_xi[wr];
@@ -306,9 +315,8 @@ __global__ __launch_bounds__(256) void ragged_cols_kernel(RagArgs a) {
                 const int t = wk + 16 * u;
                 float p = 0.0f;
                 if (t < cnt && klive) {
-                    const long row = (long)s * a.n_out + n0 + t;
                     const float4 rs = *reinterpret_cast<const float4*>(a.rowstat + (((long)s * a.n_head + h) * a.n_out + n0 + t) * 4);
-                    const float m = dist3(load_pt3(a.mesh_out + row * a.sdim, a.sdim), xi);
+                    const float m = dist3(load_pt3(a.mesh_out + (long)s * a.mo_stride + (long)(n0 + t) * a.sdim, a.sdim), xi);
                     const float sv = __fmul_rn(m, c);
                     if (sv <= rs.x) p = __expf(rs.y - sv) * rs.z;
                 }
@@ -345,8 +353,8 @@ __global__ __launch_bounds__(256) void ragged_neighbors_kernel(RagSelectArgs a, 
     const int s = (int)(row / a.n_out), i = (int)(row - (long)s * a.n_out);
     const int lo = clamp_len(a.len_out, s, a.n_out), li = clamp_len(a.len_in, s, a.n_in);
     if (i >= lo) { if (lane == 0) nbr_cnt[row] = 0; return; }
-    const float4 xo = load_pt3(a.mesh_out + row * a.sdim, a.sdim);
-    const float* pin = a.mesh_in + (long)s * a.n_in * a.sdim;
+    const float4 xo = load_pt3(a.mesh_out + (long)s * a.mo_stride + (long)i * a.sdim, a.sdim);
+    const float* pin = a.mesh_in + (long)s * a.mi_stride;
     const float bound = a.stats[rows + row] * 1.00000047683715820312f;
     int total = 0;
     int* out = nbr_idx + row * cap;
@@ -404,8 +412,8 @@ __global__ __launch_bounds__(256) void ragged_list_rows_kernel(RagArgs a, RagLis
         const float4 rs = *reinterpret_cast<const float4*>(rsp);
         T = rs.x; smin = rs.y; inv = rs.z; mbar = rs.w;
     }
-    const float4 xo = load_pt3(a.mesh_out + row * a.sdim, a.sdim);
-    const float* pin = a.mesh_in + (long)s * a.n_in * a.sdim;
+    const float4 xo = load_pt3(a.mesh_out + (long)s * a.mo_stride + (long)n * a.sdim, a.sdim);
+    const float* pin = a.mesh_in + (long)s * a.mi_stride;
     const float* vals = a.values + (long)s * a.values_bstride;
     const int* list = L.idx + row * L.cap;
     const int cnt = L.cnt[row];
@@ -470,7 +478,7 @@ __global__ __launch_bounds__(256) void ragged_list_cols_kernel(RagArgs a, RagLis
         for (int q = 0; q < LQ; ++q) if (cv[q]) dv[col[q]] = 0.0f;
         return;
     }
-    const float4 xi = load_pt3(a.mesh_in + kid * a.sdim, a.sdim);
+    const float4 xi = load_pt3(a.mesh_in + (long)s * a.mi_stride + (long)j * a.sdim, a.sdim);
     const int beg = L.rev_ptr[(long)s * (a.n_in + 1) + j], end = L.rev_ptr[(long)s * (a.n_in + 1) + j + 1];
     const int* rrow = L.rev_row + (long)s * a.n_out * L.cap;
     const int* cnts = L.cnt + (long)s * a.n_out;
@@ -480,7 +488,7 @@ __global__ __launch_bounds__(256) void ragged_list_cols_kernel(RagArgs a, RagLis
         const float* go = a.d_out + (long)s * a.dout_bstride + a.out_col0 + (long)h * a.dim;
         auto add_row = [&](int n) {
             const float4 rs = *reinterpret_cast<const float4*>(a.rowstat + (((long)s * a.n_head + h) * a.n_out + n) * 4);
-            const float m = dist3(load_pt3(a.mesh_out + ((long)s * a.n_out + n) * a.sdim, a.sdim), xi);
+            const float m = dist3(load_pt3(a.mesh_out + (long)s * a.mo_stride + (long)n * a.sdim, a.sdim), xi);
             const float sv = __fmul_rn(m, c);
             if (sv <= rs.x) {
                 const float p = __expf(rs.y - sv) * rs.z;
@@ -696,14 +704,21 @@ static int rag_check_sizes(int batch, int n_out, int n_in, int space_dim) {
     return 0;
 }
 
-extern "C" int pit_plan_ragged_fwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
-                                   int space_dim, const int* len_out, const int* len_in, float locality, int need_kth,
-                                   float* stats, float* rank_w, int cap, int* nbr_idx, int* nbr_cnt, void* stream) {
-    if (!mesh_out || !mesh_in || !len_out || !len_in || !stats || !rank_w) return PIT_ERR_NULL;
+// a sample stride in points: 0 (one mesh for the whole batch) or at least the mesh's width
+static bool rag_stride_ok(long stride, int n) { return stride == 0 || stride >= n; }
+
+// The entry points below in one form: sample strides in POINTS per mesh (0 = shared by the batch) and lengths that may be NULL
+// (= full width).  The ABI 27 entries pass stride n and their (non-NULL) lengths: the arithmetic they always did.
+static int plan_ragged(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                       int space_dim, long out_stride, long in_stride, const int* len_out, const int* len_in, float locality, int need_kth,
+                       float* stats, float* rank_w, int cap, int* nbr_idx, int* nbr_cnt, void* stream) {
+    if (!mesh_out || !mesh_in || !stats || !rank_w) return PIT_ERR_NULL;
     if (int rc = rag_check_sizes(mesh_batch, n_out, n_in, space_dim)) return rc;
+    if (!rag_stride_ok(out_stride, n_out) || !rag_stride_ok(in_stride, n_in)) return PIT_ERR_SIZE;
     if (!(locality >= 0.0f && locality <= 1.0f)) return PIT_ERR_SIZE;
     RagSelectArgs a;
     a.mesh_out = mesh_out; a.mesh_in = mesh_in; a.len_out = len_out; a.len_in = len_in; a.stats = stats; a.rank_w = rank_w;
+    a.mo_stride = out_stride * space_dim; a.mi_stride = in_stride * space_dim;
     a.batch = mesh_batch; a.n_out = n_out; a.n_in = n_in; a.sdim = space_dim; a.q = locality; a.need_kth = need_kth;
     hipLaunchKernelGGL(ragged_select_kernel, dim3((unsigned)((long)mesh_batch * n_out)), dim3(256), 0, (hipStream_t)stream, a);
     PIT_CHECK_LAUNCH();
@@ -717,21 +732,23 @@ extern "C" int pit_plan_ragged_fwd(const float* mesh_out, const float* mesh_in, 
     return 0;
 }
 
-extern "C" int pit_posatt_ragged_fwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
-                                     int space_dim, const int* len_out, const int* len_in,
+static int posatt_ragged_fwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                                     int space_dim, long out_stride, long in_stride, const int* len_out, const int* len_in,
                                      const float* values, int dim, long ld_values, long values_bstride,
                                      const float* head, int n_head, int head_is_scale,
                                      const float* stats, const float* rank_w, int masked,
                                      float* out, long ld_out, long out_bstride, int out_col0, int copy_inputs,
                                      float* rowstat, float* scale_out,
                                      const int* nbr_idx, const int* nbr_cnt, int nbr_cap, int math_mode, void* stream) {
-    if (!mesh_out || !mesh_in || !len_out || !len_in || !values || !head || !stats || !out || !rowstat) return PIT_ERR_NULL;
+    if (!mesh_out || !mesh_in || !values || !head || !stats || !out || !rowstat) return PIT_ERR_NULL;
     if (masked && !rank_w) return PIT_ERR_NULL;
     if (int rc = rag_check_sizes(mesh_batch, n_out, n_in, space_dim)) return rc;
+    if (!rag_stride_ok(out_stride, n_out) || !rag_stride_ok(in_stride, n_in)) return PIT_ERR_SIZE;
     if (dim <= 0 || n_head <= 0 || (copy_inputs && n_out != n_in)) return PIT_ERR_SIZE;
     if (math_mode != PIT_MATH_FP32) return PIT_ERR_UNSUPPORTED;
     RagArgs a = RagArgs();
     a.mesh_out = mesh_out; a.mesh_in = mesh_in; a.len_out = len_out; a.len_in = len_in;
+    a.mo_stride = out_stride * space_dim; a.mi_stride = in_stride * space_dim;
     a.batch = mesh_batch; a.n_out = n_out; a.n_in = n_in; a.sdim = space_dim;
     a.values = values; a.dim = dim; a.ld_values = ld_values; a.values_bstride = values_bstride;
     a.head = head; a.n_head = n_head; a.head_is_scale = head_is_scale;
@@ -755,8 +772,8 @@ extern "C" int pit_posatt_ragged_fwd(const float* mesh_out, const float* mesh_in
     return 0;
 }
 
-extern "C" int pit_posatt_ragged_bwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
-                                     int space_dim, const int* len_out, const int* len_in,
+static int posatt_ragged_bwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                                     int space_dim, long out_stride, long in_stride, const int* len_out, const int* len_in,
                                      const float* values, int dim, long ld_values, long values_bstride,
                                      const float* head, int n_head, int head_is_scale, const float* scale,
                                      const float* rowstat, int masked,
@@ -765,13 +782,15 @@ extern "C" int pit_posatt_ragged_bwd(const float* mesh_out, const float* mesh_in
                                      float* d_head, int accumulate_head, double* workspace,
                                      const int* nbr_idx, const int* nbr_cnt, int nbr_cap, const int* rev_ptr, const int* rev_row,
                                      int math_mode, void* stream) {
-    if (!mesh_out || !mesh_in || !len_out || !len_in || !values || !head || !rowstat || !d_out) return PIT_ERR_NULL;
+    if (!mesh_out || !mesh_in || !values || !head || !rowstat || !d_out) return PIT_ERR_NULL;
     if (d_head && !workspace) return PIT_ERR_NULL;
     if (int rc = rag_check_sizes(mesh_batch, n_out, n_in, space_dim)) return rc;
+    if (!rag_stride_ok(out_stride, n_out) || !rag_stride_ok(in_stride, n_in)) return PIT_ERR_SIZE;
     if (dim <= 0 || n_head <= 0 || (add_residual && n_out != n_in)) return PIT_ERR_SIZE;
     if (math_mode != PIT_MATH_FP32) return PIT_ERR_UNSUPPORTED;
     RagArgs a = RagArgs();
     a.mesh_out = mesh_out; a.mesh_in = mesh_in; a.len_out = len_out; a.len_in = len_in;
+    a.mo_stride = out_stride * space_dim; a.mi_stride = in_stride * space_dim;
     a.batch = mesh_batch; a.n_out = n_out; a.n_in = n_in; a.sdim = space_dim;
     a.values = values; a.dim = dim; a.ld_values = ld_values; a.values_bstride = values_bstride;
     a.head = scale ? scale : head; a.n_head = n_head; a.head_is_scale = (scale || head_is_scale) ? 1 : 0;
@@ -815,6 +834,82 @@ extern "C" int pit_posatt_ragged_bwd(const float* mesh_out, const float* mesh_in
         }
     }
     return 0;
+}
+
+extern "C" int pit_plan_ragged_fwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                                   int space_dim, const int* len_out, const int* len_in, float locality, int need_kth,
+                                   float* stats, float* rank_w, int cap, int* nbr_idx, int* nbr_cnt, void* stream) {
+    if (!len_out || !len_in) return PIT_ERR_NULL;
+    return plan_ragged(mesh_out, mesh_in, mesh_batch, n_out, n_in, space_dim, n_out, n_in, len_out, len_in, locality, need_kth,
+                       stats, rank_w, cap, nbr_idx, nbr_cnt, stream);
+}
+
+extern "C" int pit_plan_ragged_strided_fwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                                           int space_dim, long out_stride, long in_stride, const int* len_out, const int* len_in,
+                                           float locality, int need_kth, float* stats, float* rank_w, int cap, int* nbr_idx,
+                                           int* nbr_cnt, void* stream) {
+    return plan_ragged(mesh_out, mesh_in, mesh_batch, n_out, n_in, space_dim, out_stride, in_stride, len_out, len_in, locality, need_kth,
+                       stats, rank_w, cap, nbr_idx, nbr_cnt, stream);
+}
+
+extern "C" int pit_posatt_ragged_fwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                                     int space_dim, const int* len_out, const int* len_in,
+                                     const float* values, int dim, long ld_values, long values_bstride,
+                                     const float* head, int n_head, int head_is_scale,
+                                     const float* stats, const float* rank_w, int masked,
+                                     float* out, long ld_out, long out_bstride, int out_col0, int copy_inputs,
+                                     float* rowstat, float* scale_out,
+                                     const int* nbr_idx, const int* nbr_cnt, int nbr_cap, int math_mode, void* stream) {
+    if (!len_out || !len_in) return PIT_ERR_NULL;
+    return posatt_ragged_fwd(mesh_out, mesh_in, mesh_batch, n_out, n_in, space_dim, n_out, n_in, len_out, len_in, values, dim, ld_values,
+                             values_bstride, head, n_head, head_is_scale, stats, rank_w, masked, out, ld_out, out_bstride, out_col0,
+                             copy_inputs, rowstat, scale_out, nbr_idx, nbr_cnt, nbr_cap, math_mode, stream);
+}
+
+extern "C" int pit_posatt_ragged_strided_fwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                                             int space_dim, long out_stride, long in_stride, const int* len_out, const int* len_in,
+                                             const float* values, int dim, long ld_values, long values_bstride,
+                                             const float* head, int n_head, int head_is_scale,
+                                             const float* stats, const float* rank_w, int masked,
+                                             float* out, long ld_out, long out_bstride, int out_col0, int copy_inputs,
+                                             float* rowstat, float* scale_out,
+                                             const int* nbr_idx, const int* nbr_cnt, int nbr_cap, int math_mode, void* stream) {
+    return posatt_ragged_fwd(mesh_out, mesh_in, mesh_batch, n_out, n_in, space_dim, out_stride, in_stride, len_out, len_in, values, dim,
+                             ld_values, values_bstride, head, n_head, head_is_scale, stats, rank_w, masked, out, ld_out, out_bstride,
+                             out_col0, copy_inputs, rowstat, scale_out, nbr_idx, nbr_cnt, nbr_cap, math_mode, stream);
+}
+
+extern "C" int pit_posatt_ragged_bwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                                     int space_dim, const int* len_out, const int* len_in,
+                                     const float* values, int dim, long ld_values, long values_bstride,
+                                     const float* head, int n_head, int head_is_scale, const float* scale,
+                                     const float* rowstat, int masked,
+                                     const float* d_out, long ld_dout, long dout_bstride, int out_col0,
+                                     float* d_values, long ld_dvalues, long dvalues_bstride, int add_residual,
+                                     float* d_head, int accumulate_head, double* workspace,
+                                     const int* nbr_idx, const int* nbr_cnt, int nbr_cap, const int* rev_ptr, const int* rev_row,
+                                     int math_mode, void* stream) {
+    if (!len_out || !len_in) return PIT_ERR_NULL;
+    return posatt_ragged_bwd(mesh_out, mesh_in, mesh_batch, n_out, n_in, space_dim, n_out, n_in, len_out, len_in, values, dim, ld_values,
+                             values_bstride, head, n_head, head_is_scale, scale, rowstat, masked, d_out, ld_dout, dout_bstride, out_col0,
+                             d_values, ld_dvalues, dvalues_bstride, add_residual, d_head, accumulate_head, workspace, nbr_idx, nbr_cnt,
+                             nbr_cap, rev_ptr, rev_row, math_mode, stream);
+}
+
+extern "C" int pit_posatt_ragged_strided_bwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                                             int space_dim, long out_stride, long in_stride, const int* len_out, const int* len_in,
+                                             const float* values, int dim, long ld_values, long values_bstride,
+                                             const float* head, int n_head, int head_is_scale, const float* scale,
+                                             const float* rowstat, int masked,
+                                             const float* d_out, long ld_dout, long dout_bstride, int out_col0,
+                                             float* d_values, long ld_dvalues, long dvalues_bstride, int add_residual,
+                                             float* d_head, int accumulate_head, double* workspace,
+                                             const int* nbr_idx, const int* nbr_cnt, int nbr_cap, const int* rev_ptr, const int* rev_row,
+                                             int math_mode, void* stream) {
+    return posatt_ragged_bwd(mesh_out, mesh_in, mesh_batch, n_out, n_in, space_dim, out_stride, in_stride, len_out, len_in, values, dim,
+                             ld_values, values_bstride, head, n_head, head_is_scale, scale, rowstat, masked, d_out, ld_dout, dout_bstride,
+                             out_col0, d_values, ld_dvalues, dvalues_bstride, add_residual, d_head, accumulate_head, workspace, nbr_idx,
+                             nbr_cnt, nbr_cap, rev_ptr, rev_row, math_mode, stream);
 }
 
 extern "C" int pit_rel_lp_loss_ragged_fwd(const float* tru, const float* pred, const int* len, int batch, int npts, int nch, int p,

@@ -426,6 +426,39 @@ def check_ragged(metric: str, mesh_out, mesh_in) -> None:
         raise NotImplementedError(f"lengths with space_dim > 3 (got {mesh_out.shape[-1]}): ragged batches take 1 to 3 coordinates")
 
 
+def mixed_pair(mesh_out, mesh_in):
+    """"out" / "in": which of the two meshes is the (n, space_dim) mesh SHARED by the whole batch when the other one is a
+    (batch, n', space_dim) stack of per-sample clouds (the broadcast of pit.py:47-48); None for two meshes of one rank."""
+    if not (torch.is_tensor(mesh_out) and torch.is_tensor(mesh_in)):
+        return None
+    if mesh_out.dim() == 2 and mesh_in.dim() == 3:
+        return "out"
+    if mesh_out.dim() == 3 and mesh_in.dim() == 2:
+        return "in"
+    return None
+
+
+def check_mixed(metric: str, mesh_out, mesh_in, len_out=None, len_in=None) -> str:
+    """What a shared mesh against per-sample clouds does not cover, refused before anything is launched; returns the shared side."""
+    shared = mixed_pair(mesh_out, mesh_in)
+    if (len_out if shared == "out" else len_in) is not None:
+        raise ValueError("a length for the mesh shared by the batch: every one of its points is real for every sample - lengths "
+                         "belong to the per-sample side only")
+    if metric != "euclid":
+        if len_out is not None or len_in is not None:
+            raise ValueError(f"lengths are defined for per-sample Euclidean meshes only, not for the {metric} metric")
+        raise RuntimeError("periodic metrics are defined for batch-free meshes only (pit.py:186-258)")
+    if mesh_grad_wanted(mesh_out, mesh_in):
+        raise NotImplementedError("a mesh that requires grad in a mixed pair: mesh gradients are not implemented for a shared mesh "
+                                  "against per-sample clouds")
+    if len_out is not None or len_in is not None:
+        if get_math_mode() != "fp32":
+            raise NotImplementedError("lengths in the bf16 math mode: ragged batches run in the fp32 math mode only")
+        if mesh_out.shape[-1] > 3:
+            raise NotImplementedError(f"lengths with space_dim > 3 (got {mesh_out.shape[-1]}): ragged batches take 1 to 3 coordinates")
+    return shared
+
+
 class MeshPlan:
     """Everything about a (mesh_out, mesh_in, metric, locality) pair that does not depend on
     lmda: contiguous 3-d meshes, period, quantile rank and the selection statistics
@@ -433,15 +466,34 @@ class MeshPlan:
 
     __slots__ = ("mesh_out", "mesh_in", "mesh_batch", "n_out", "n_in", "sdim", "metric", "metric_id", "period",
                  "rank_k", "rank_w", "masked", "self_attn", "stats", "nbr_idx", "nbr_cnt", "nbr_cap", "rev_ptr",
-                 "rev_row", "_complete", "_union", "_slab", "_fold", "len_out", "len_in", "rank_w_dev")
+                 "rev_row", "_complete", "_union", "_slab", "_fold", "len_out", "len_in", "rank_w_dev", "shared")
 
     def __init__(self, metric: str, mesh_out: torch.Tensor, mesh_in: torch.Tensor, locality: float,
                  self_attn: bool, period: Optional[float] = None, len_out=None, len_in=None):
         """``len_out`` / ``len_in`` (both or neither; self attention: the same object): per-sample point counts of a ragged
         batch (``as_lengths``).  The plan then holds the statistics of pit_plan_ragged_fwd - rank and interpolation weight are
-        formed per sample on the device - and its layers run on the pit_posatt_ragged_* entries only."""
+        formed per sample on the device - and its layers run on the pit_posatt_ragged_* entries only.
+        A MIXED pair - one (n, s) mesh shared by the batch, one (b, n', s) stack of clouds - means "the same n points for every
+        sample" (``shared`` = "out" / "in").  Only the cloud side can have a length; with one the plan keeps the shared mesh as it
+        is (a detached contiguous view, as for batch-free meshes: no copy) and its layers run on the pit_posatt_ragged_strided_*
+        entries, which read it in place; without one the plan holds an expanded (b, n, s) copy of the shared mesh, made once here,
+        and is from then on a per-sample plan like any other: the default kernels, untouched."""
         self.len_out = self.len_in = self.rank_w_dev = None
-        if len_out is not None or len_in is not None:
+        self.shared = mixed_pair(mesh_out, mesh_in)
+        if self.shared is not None:
+            if metric not in METRIC_ID:
+                raise ValueError(f"unknown metric {metric!r}")
+            check_mixed(metric, mesh_out, mesh_in, len_out, len_in)
+            _need_gpu(mesh_out, mesh_in)
+            if mesh_out.shape[-1] != mesh_in.shape[-1]:
+                raise RuntimeError("mesh_out and mesh_in must have the same number of coordinates")
+            if len_out is None and len_in is None:
+                b = (mesh_in if self.shared == "out" else mesh_out).shape[0]
+                if self.shared == "out":
+                    mesh_out = mesh_out.detach().unsqueeze(0).expand(b, -1, -1).contiguous()
+                else:
+                    mesh_in = mesh_in.detach().unsqueeze(0).expand(b, -1, -1).contiguous()
+        elif len_out is not None or len_in is not None:
             if len_out is None or len_in is None:
                 raise ValueError("a ragged plan needs both len_out and len_in")
             if metric not in METRIC_ID:
@@ -450,20 +502,21 @@ class MeshPlan:
         _need_gpu(mesh_out, mesh_in)
         if metric not in METRIC_ID:
             raise ValueError(f"unknown metric {metric!r}")
-        if mesh_out.dim() != mesh_in.dim() or mesh_out.dim() not in (2, 3):
+        ragged_mixed = self.shared is not None and (len_out is not None or len_in is not None)
+        if (mesh_out.dim() != mesh_in.dim() and not ragged_mixed) or mesh_out.dim() not in (2, 3) or mesh_in.dim() not in (2, 3):
             raise RuntimeError(f"mesh shapes {tuple(mesh_out.shape)} / {tuple(mesh_in.shape)} not supported")
         if mesh_out.shape[-1] != mesh_in.shape[-1]:
             raise RuntimeError("mesh_out and mesh_in must have the same number of coordinates")
-        batched = mesh_out.dim() == 3
+        batched = mesh_out.dim() == 3 or mesh_in.dim() == 3
         if batched and metric != "euclid":
             raise RuntimeError("periodic metrics are defined for batch-free meshes only (pit.py:186-258)")
-        if batched and mesh_out.shape[0] != mesh_in.shape[0]:
+        if batched and not ragged_mixed and mesh_out.shape[0] != mesh_in.shape[0]:
             raise RuntimeError("batched meshes must share the batch size")
         self.metric = metric
         self.metric_id = METRIC_ID[metric]
         self.mesh_out = mesh_out.detach().contiguous()
         self.mesh_in = self.mesh_out if (self_attn and mesh_in is mesh_out) else mesh_in.detach().contiguous()
-        self.mesh_batch = mesh_out.shape[0] if batched else 1
+        self.mesh_batch = (mesh_out if mesh_out.dim() == 3 else mesh_in).shape[0] if batched else 1
         self.n_out, self.n_in, self.sdim = mesh_out.shape[-2], mesh_in.shape[-2], mesh_out.shape[-1]
         if not 1 <= self.sdim <= MAX_SPACE_DIM:
             raise RuntimeError(f"space_dim must be between 1 and {MAX_SPACE_DIM}, got {self.sdim}")
@@ -478,6 +531,37 @@ class MeshPlan:
         self._union = None
         self._slab = None
         self._fold = None
+        if ragged_mixed:
+            # a shared mesh against ragged clouds: the plan of a ragged batch below, on the strided entries - stride 0 and no
+            # length on the shared side.  The list capacity comes from the full (shared keys) or padded (cloud keys) width, as
+            # ragged_list_capacity chooses it for the expanded pair; lists and their transpose are per sample either way
+            dev, mb = mesh_out.device, self.mesh_batch
+            self.len_out = None if len_out is None else as_lengths(len_out, dev, mb)
+            self.len_in = None if len_in is None else as_lengths(len_in, dev, mb)
+            self.stats = torch.empty((3, mb, self.n_out), device=dev, dtype=torch.float32)
+            self.rank_w_dev = torch.empty((mb,), device=dev, dtype=torch.float32)
+            cap = ragged_list_capacity(self.rank_k, self.n_in) if (self.masked and SPARSE_MASKED) else 0
+            if cap:
+                self.nbr_cap = cap
+                self.nbr_idx = torch.empty((mb, self.n_out, cap), device=dev, dtype=torch.int32)
+                self.nbr_cnt = torch.empty((mb, self.n_out), device=dev, dtype=torch.int32)
+            so, si = self.sample_strides()
+            rc = _lib.lib().pit_plan_ragged_strided_fwd(self.mesh_out.data_ptr(), self.mesh_in.data_ptr(), mb, self.n_out,
+                                                        self.n_in, self.sdim, so, si, _lib.ptr(self.len_out), _lib.ptr(self.len_in),
+                                                        float(np.float32(locality)), 1 if self.masked else 0, self.stats.data_ptr(),
+                                                        self.rank_w_dev.data_ptr(), cap, _lib.ptr(self.nbr_idx),
+                                                        _lib.ptr(self.nbr_cnt), _lib.stream_ptr())
+            _lib.check(rc, "pit_plan_ragged_strided_fwd")
+            if cap and torch.is_grad_enabled():          # the transposed lists, per sample: d(values) is per sample
+                self.rev_ptr = torch.empty((mb, self.n_in + 1), device=dev, dtype=torch.int32)
+                self.rev_row = torch.empty((mb, self.n_out * cap), device=dev, dtype=torch.int32)
+                ws = torch.empty((2 * mb * self.n_in,), device=dev, dtype=torch.int32)
+                rc = _lib.lib().pit_lists_transpose(self.nbr_idx.data_ptr(), self.nbr_cnt.data_ptr(), mb, self.n_out, self.n_in, cap,
+                                                    self.rev_ptr.data_ptr(), self.rev_row.data_ptr(), ws.data_ptr(), _lib.stream_ptr())
+                _lib.check(rc, "pit_lists_transpose")
+            if _capturing():
+                _pin(self.len_out, self.len_in, self.mesh_out, self.mesh_in)
+            return
         if len_out is not None:
             # ragged batch: statistics over the first len_in[s] keys, rank and weight per sample on the device (rank_k / rank_w
             # above are those of the padded width: they only size the lists).  Candidate lists as for any masked layer: the
@@ -525,6 +609,14 @@ class MeshPlan:
                                            self.rank_k, 1 if self.masked else 0, self.stats.data_ptr(),
                                            _lib.stream_ptr())
             _lib.check(rc, name)
+
+    def ragged(self) -> bool:
+        """The plan of a ragged batch: its layers run on the pit_posatt_ragged_* entries."""
+        return self.len_out is not None or self.len_in is not None
+
+    def sample_strides(self):
+        """(out, in) sample strides in points for the strided ragged entries: 0 for the mesh shared by the batch."""
+        return (0 if self.mesh_out.dim() == 2 else self.n_out, 0 if self.mesh_in.dim() == 2 else self.n_in)
 
     def _union_key(self, cap):
         return (self.metric, self.n_out, self.n_in, cap, self.mesh_batch > 1, self.sdim)
@@ -843,16 +935,18 @@ class _PosAttRagged(torch.autograd.Function):
         out = torch.empty((b, plan.n_out, width), device=values.device, dtype=torch.float32)
         rowstat = torch.empty((b, n_head, plan.n_out, 4), device=values.device, dtype=torch.float32)
         scale = torch.empty((n_head,), device=values.device, dtype=torch.float32)
-        rc = _lib.lib().pit_posatt_ragged_fwd(
-            plan.mesh_out.data_ptr(), plan.mesh_in.data_ptr(), b, plan.n_out, plan.n_in, plan.sdim,
-            plan.len_out.data_ptr(), plan.len_in.data_ptr(),
+        # (a shared mesh against ragged clouds: the strided entries - stride 0, no length on the shared side)
+        entry, extra = ("pit_posatt_ragged_fwd", ()) if plan.shared is None else ("pit_posatt_ragged_strided_fwd", plan.sample_strides())
+        rc = getattr(_lib.lib(), entry)(
+            plan.mesh_out.data_ptr(), plan.mesh_in.data_ptr(), b, plan.n_out, plan.n_in, plan.sdim, *extra,
+            _lib.ptr(plan.len_out), _lib.ptr(plan.len_in),
             values.data_ptr(), d, values.stride(1), values.stride(0),
             head.data_ptr(), n_head, 1 if head_is_scale else 0,
             plan.stats.data_ptr(), plan.rank_w_dev.data_ptr(), 1 if plan.masked else 0,
             out.data_ptr(), out.stride(1), out.stride(0), d if concat else 0, 1 if concat else 0,
             rowstat.data_ptr(), scale.data_ptr(), _lib.ptr(plan.nbr_idx), _lib.ptr(plan.nbr_cnt), plan.nbr_cap,
             MATH_MODES["fp32"], _lib.stream_ptr())
-        _lib.check(rc, "pit_posatt_ragged_fwd")
+        _lib.check(rc, entry)
         ctx.plan, ctx.n_head, ctx.concat, ctx.head_is_scale = plan, n_head, concat, head_is_scale
         ctx.save_for_backward(values, head, rowstat, scale)
         return out
@@ -869,9 +963,10 @@ class _PosAttRagged(torch.autograd.Function):
         d_head = torch.empty((n_head,), device=values.device, dtype=torch.float32) if need_h else None
         work = _dscale_workspace(values.device, n_head) if need_h else None
         if need_v or need_h:
-            rc = _lib.lib().pit_posatt_ragged_bwd(
-                plan.mesh_out.data_ptr(), plan.mesh_in.data_ptr(), b, plan.n_out, plan.n_in, plan.sdim,
-                plan.len_out.data_ptr(), plan.len_in.data_ptr(),
+            entry, extra = ("pit_posatt_ragged_bwd", ()) if plan.shared is None else ("pit_posatt_ragged_strided_bwd", plan.sample_strides())
+            rc = getattr(_lib.lib(), entry)(
+                plan.mesh_out.data_ptr(), plan.mesh_in.data_ptr(), b, plan.n_out, plan.n_in, plan.sdim, *extra,
+                _lib.ptr(plan.len_out), _lib.ptr(plan.len_in),
                 values.data_ptr(), d, values.stride(1), values.stride(0),
                 head.data_ptr(), n_head, 1 if ctx.head_is_scale else 0, scale.data_ptr(),
                 rowstat.data_ptr(), 1 if plan.masked else 0,
@@ -879,7 +974,7 @@ class _PosAttRagged(torch.autograd.Function):
                 _lib.ptr(d_values), d, j * d, 1 if ctx.concat else 0,
                 _lib.ptr(d_head), 0, _lib.ptr(work), _lib.ptr(plan.nbr_idx), _lib.ptr(plan.nbr_cnt), plan.nbr_cap,
                 _lib.ptr(plan.rev_ptr), _lib.ptr(plan.rev_row), MATH_MODES["fp32"], _lib.stream_ptr())
-            _lib.check(rc, "pit_posatt_ragged_bwd")
+            _lib.check(rc, entry)
         return d_values, d_head, None, None, None, None
 
 
@@ -1281,7 +1376,7 @@ def posatt_apply(values: torch.Tensor, lmda: torch.Tensor, plan: MeshPlan, n_hea
     them requires grad they become inputs of the op and receive d(mesh) from pit_posatt_dmesh (Euclidean metric, fp32 mode;
     NotImplementedError otherwise); otherwise they are ignored.
     Opaque to torch.compile (dynamo runs it eagerly: raw pointers cross a ctypes boundary)."""
-    if plan.len_out is not None:                   # ragged batch: the pit_posatt_ragged_* entries, every layer on its own
+    if plan.ragged():                              # ragged batch: the pit_posatt_ragged_* entries, every layer on its own
         if mesh_grad_wanted(mesh_out, mesh_in):
             raise NotImplementedError("lengths with a mesh that requires grad: mesh gradients are not implemented for ragged batches")
         if get_math_mode() != "fp32":

@@ -111,7 +111,11 @@ class posatt(nn.Module):
             if not self._batched:
                 self._no_lengths()
             return ops.MeshPlan(self._metric, mesh_out, mesh_in, self.locality, self_attn, len_out=len_out, len_in=len_in)
-        if self._batched:
+        if self._batched and ops.mixed_pair(mesh_out, mesh_in) is not None:
+            # one mesh shared by the batch against per-sample clouds: rebuilt per call, like every per-sample plan
+            return ops.MeshPlan(self._metric, mesh_out, mesh_in, self.locality, self_attn)
+        # (self attention on ONE (L, space_dim) mesh shared by the batch is the batch-free layer: the cached plan below)
+        if self._batched and not (self_attn and mesh_out is mesh_in and mesh_out.dim() == 2):
             if mesh_out.dim() != 3:
                 raise RuntimeError(f"{type(self).__name__} expects (batch, L, space_dim) meshes")
             return ops.MeshPlan(self._metric, mesh_out, mesh_in, self.locality, self_attn)
@@ -140,7 +144,9 @@ class posatt(nn.Module):
         these meshes, lengths and this locality (pit.processor builds one for all its blocks)."""
         if self._overridden():
             raise NotImplementedError("lengths with an overridden dist2att / convolution")
-        if len_out is None or len_in is None:
+        if ops.mixed_pair(mesh_out, mesh_in) is not None:
+            ops.check_mixed(self._metric, mesh_out, mesh_in, len_out, len_in)      # (a length for the shared side: ValueError)
+        elif len_out is None or len_in is None:
             raise ValueError(f"{type(self).__name__}: cross attention on a ragged batch needs both len_out and len_in")
         if plan is None:
             plan = self._plan(mesh_out, mesh_in, self_attn, len_out, len_in)
@@ -161,7 +167,9 @@ class posatt(nn.Module):
 
     def forward(self, mesh, inputs, lengths=None):
         """``lengths`` (per-sample meshes only): point counts of a ragged batch - sample s is computed from its first
-        lengths[s] points alone, rows beyond come out as zeros in the head columns (README, "Ragged batches")."""
+        lengths[s] points alone, rows beyond come out as zeros in the head columns (README, "Ragged batches").
+        A 2-d ``mesh`` (L, space_dim) is one mesh shared by the whole batch: what ``posatt_fixed.forward`` computes for it -
+        the batch-free plan from this module's LRU cache, the same launches; it has no per-sample length."""
         if lengths is not None:
             lengths = ops.as_lengths(lengths, mesh.device, mesh.shape[0]) if mesh.dim() == 3 else lengths
             return self._ragged(mesh, mesh, inputs, lengths, lengths, True)
@@ -211,12 +219,16 @@ class posatt(nn.Module):
         if len_out is not None or len_in is not None:
             if not self._batched:
                 self._no_lengths()
-            if len_out is None or len_in is None:
+            if ops.mixed_pair(mesh_out, mesh_in) is not None:
+                ops.check_mixed(self._metric, mesh_out, mesh_in, len_out, len_in)
+            elif len_out is None or len_in is None:
                 raise ValueError("dist2att on a ragged batch needs both len_out and len_in")
             plan = ops.MeshPlan(self._metric, mesh_out, mesh_in, float(locality), False, len_out=len_out, len_in=len_in)
             eye = torch.eye(plan.n_in, device=mesh_in.device).unsqueeze(0).repeat(plan.mesh_batch, 1, 1)
             att = ops.posatt_apply(eye, scale, plan, self.n_head, concat=False, mesh_out=mesh_out, mesh_in=mesh_in)
             return att.reshape(plan.mesh_batch, plan.n_out, self.n_head, plan.n_in).permute(0, 2, 1, 3)
+        if ops.mixed_pair(mesh_out, mesh_in) is not None:
+            ops.check_mixed(self._metric, mesh_out, mesh_in)
         if ops.mesh_grad_wanted(mesh_out, mesh_in):
             ops._check_mesh_grad(self._metric)
         plan = ops.MeshPlan(self._metric, mesh_out, mesh_in, float(locality), False)
@@ -240,7 +252,9 @@ class posatt(nn.Module):
 
 
 class posatt_cross(posatt):
-    """Cross attention mesh_in -> mesh_out on per-sample meshes (pit.py:59-71)."""
+    """Cross attention mesh_in -> mesh_out on per-sample meshes (pit.py:59-71).  Either mesh may be ONE (n, space_dim) mesh
+    shared by the whole batch against the other's (batch, n', space_dim) clouds - the broadcast of pit.py:47-48; only the cloud
+    side can have a length (README, "A latent mesh shared by the batch")."""
 
     def forward(self, mesh_out, mesh_in, inputs, out_bf16: bool = False, len_out=None, len_in=None):
         return self._cross(mesh_out, mesh_in, inputs, out_bf16, len_out, len_in)
@@ -418,18 +432,21 @@ class pit(nn.Module):
         """Lengths of a ragged batch as device tensors; None when no length was given."""
         if all(v is None for v in lengths.values()):
             return None
-        mesh = meshes[0]
-        if not (torch.is_tensor(mesh) and mesh.dim() == 3):
+        mesh = next((m for m in meshes if torch.is_tensor(m) and m.dim() == 3), None)      # (a mixed pair: the cloud side)
+        if mesh is None:
             raise ValueError("lengths need per-sample (batch, n, space_dim) meshes: a batch-free mesh has no per-sample length")
         return tuple(None if v is None else ops.as_lengths(v, mesh.device, mesh.shape[0]) for v in lengths.values())
 
     def encoder(self, mesh_in, func_in, mesh_ltt, len_in=None, len_ltt=None):
         """``len_in`` / ``len_ltt`` (keywords; ragged batches of per-sample clouds): point counts of ``mesh_in`` and
-        ``mesh_ltt``.  With lengths every layer runs on its own on the ragged kernels."""
+        ``mesh_ltt``.  With lengths every layer runs on its own on the ragged kernels.  A 2-d ``mesh_ltt`` is one latent mesh
+        shared by the whole batch: it has no length (``len_ltt`` must stay None) and the result has no padded rows."""
         rag = self._ragged_lengths((mesh_in, mesh_ltt), len_in=len_in, len_ltt=len_ltt)
         if rag is not None:
             len_in, len_ltt = rag
-            if len_in is None or len_ltt is None:
+            if ops.mixed_pair(mesh_ltt, mesh_in) is not None:
+                ops.check_mixed(getattr(self.down, "_metric", "euclid"), mesh_ltt, mesh_in, len_ltt, len_in)
+            elif len_in is None or len_ltt is None:
                 raise ValueError("encoder: a ragged batch needs both len_in and len_ltt")
             return self._mlp_gelu(self.en_layer, self.down(mesh_ltt, mesh_in, func_in, len_out=len_ltt, len_in=len_in), ordered=True)
         if self._mesh_grad(mesh_in, mesh_ltt):
@@ -485,7 +502,7 @@ class pit(nn.Module):
                 and device.type == "cuda" and mesh_ltt.device == device):
             return None
         heads = self.conv[0].n_head
-        kinds = (posatt_fixed, posatt_periodic1d, posatt_periodic2d)
+        kinds = (posatt, posatt_fixed, posatt_periodic1d, posatt_periodic2d)      # (posatt: on a 2-d mesh it is posatt_fixed)
         for a, w in zip(self.conv, self.mlp):
             if type(a) not in kinds or type(a) is not type(self.conv[0]) or a.locality != 1.0 or a.n_head != heads \
                     or a.in_dim != hid or type(w) is not kaiming_mlp:
@@ -512,7 +529,7 @@ class pit(nn.Module):
                 and func_ltt.is_cuda and func_ltt.dim() == 3 and func_ltt.dtype == torch.float32):
             return None
         hid, heads = func_ltt.shape[-1], self.conv[0].n_head
-        kinds = (posatt_fixed, posatt_periodic1d, posatt_periodic2d)
+        kinds = (posatt, posatt_fixed, posatt_periodic1d, posatt_periodic2d)      # (posatt: on a 2-d mesh it is posatt_fixed)
         for a in self.conv:
             if type(a) not in kinds or type(a) is not type(self.conv[0]) or a.locality != 1.0 or a.n_head != heads or a.in_dim != hid \
                     or "forward" in a.__dict__ or a._forward_hooks or a._forward_pre_hooks or a._backward_hooks or a._backward_pre_hooks:
@@ -589,7 +606,9 @@ class pit(nn.Module):
         rag = self._ragged_lengths((mesh_ltt, mesh_out), len_ltt=len_ltt, len_out=len_out)
         if rag is not None:
             len_ltt, len_out = rag
-            if len_ltt is None or len_out is None:
+            if ops.mixed_pair(mesh_out, mesh_ltt) is not None:
+                ops.check_mixed(getattr(self.up, "_metric", "euclid"), mesh_out, mesh_ltt, len_out, len_ltt)
+            elif len_ltt is None or len_out is None:
                 raise ValueError("decoder: a ragged batch needs both len_ltt and len_out")
             f = self.up(mesh_out, mesh_ltt, func_ltt, len_out=len_out, len_in=len_ltt)
             return self.de(f, ordered=True) if isinstance(self.de, kaiming_mlp) else self.de(f)

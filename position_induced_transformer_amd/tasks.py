@@ -121,6 +121,37 @@ class pit_elasticity(P.pit):
         return self.decoder(mesh_ltt, ltt, mesh_out).reshape(*size, self.out_dim)
 
 
+class pit_cloud_latent(P.pit):
+    """Per-sample clouds on ONE latent mesh shared by the whole batch: the encoder projects every cloud onto the fixed
+    ``mesh_ltt`` (L, space_dim) given to the constructor, the processor runs on it - the batch-free processor, no padding - and
+    the decoder projects back onto each sample's own query points.  ``func_in`` is fed to the encoder as it is (``in_dim``
+    channels, coordinates included if wanted, as in train_elasticity.py:39)."""
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if self.mesh_ltt is None:
+            raise ValueError("pit_cloud_latent needs the shared latent mesh (mesh_ltt)")
+        self.mesh_ltt = self.mesh_ltt.contiguous()
+        self.en_layer = P.kaiming_mlp(self.n_head * self.in_dim, self.hid_dim, self.hid_dim)
+
+    def forward(self, mesh_in, func_in, mesh_out, len_in=None, len_out=None):
+        """``mesh_in`` (b, n_in, space_dim) / ``mesh_out`` (b, n_out, space_dim): the clouds and the query points, padded;
+        ``len_in`` / ``len_out``: their point counts (None = full width; ``len_in`` alone serves both when ``mesh_out`` IS
+        ``mesh_in``).  The latent mesh has no length.  Padded rows of the result are finite (the decoder MLP's bias path)
+        and meaningless: mask them, e.g. with ``RelLpNorm(...)(true, pred, lengths)``."""
+        if ops.mesh_grad_wanted(self.mesh_ltt, mesh_in, mesh_out):         # (before anything is launched)
+            raise NotImplementedError("a mesh that requires grad in a mixed pair: mesh gradients are not implemented for a shared "
+                                      "mesh against per-sample clouds")
+        if len_out is None and len_in is not None and mesh_out is mesh_in:
+            len_out = len_in
+        size = mesh_out.shape[:-1]
+        mesh_ltt = self.mesh_ltt if self.mesh_ltt.device == mesh_in.device else self.mesh_ltt.to(mesh_in.device)
+        self.mesh_ltt = mesh_ltt
+        ltt = self.encoder(mesh_in, func_in, mesh_ltt, len_in=len_in)
+        ltt = self.processor(ltt, mesh_ltt)
+        return self.decoder(mesh_ltt, ltt, mesh_out, len_out=len_out).reshape(*size, self.out_dim)
+
+
 class pit_naca(P.pit):
     """train_naca.py:17-65: latent mesh = strided sub-grid of the body-fitted output grid."""
 
