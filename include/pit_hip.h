@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define PIT_ABI_VERSION 28
+#define PIT_ABI_VERSION 29
 #define PIT_MAX_SPACE_DIM 8   /* largest space_dim any entry accepts */
 #define PIT_DSCALE_SLOTS 1024 /* fp64 accumulators per head in pit_posatt_bwd's workspace */
 
@@ -619,6 +619,15 @@ int pit_rel_lp_loss_fwd_grad(const float* tru, const float* pred, const float* p
                              float* norms, float* loss, float* workspace, float* d_pred_unit,
                              float* d_true_unit, float* clear_buf, long clear_n, void* stream);
 
+/* ABI 29, reproducible mode: pit_rel_lp_loss_fwd_grad (same arguments, same workspace, d_pred_unit / d_true_unit / clear_buf
+ * may be NULL) with every sum in an order that depends on the sizes only: a series is never split over workgroups (one
+ * 1024-thread workgroup where the series fits it, else one 256-thread workgroup), and the terms of the (sample, channel)
+ * pairs are added in index order by the workgroup that arrives last.  Same call, same bits; no environment switch is read. */
+int pit_rel_lp_loss_fwd_grad_ordered(const float* tru, const float* pred, const float* pred_scale,
+                                     const float* pred_shift, int batch, int npts, int nch, int p,
+                                     float* norms, float* loss, float* workspace, float* d_pred_unit,
+                                     float* d_true_unit, float* clear_buf, long clear_n, void* stream);
+
 /* RelMaxNorm (utils.py:59-77), the evaluation metric of train_burgers.py:80 / train_sod.py:84 /
  * train_elasticity.py:118 / train_naca.py:132:  out = sum_b mean_c max_l|true - pred| / max_l|true|
  * over (batch, npts, nch) contiguous tensors.  Forward only (the scripts never differentiate it).
@@ -757,6 +766,41 @@ int pit_mlp_bwd_params_ordered(const float* x, long ldx, int rows, int n0, int n
                                int out_gelu, const float* d_y, long ld_dy,
                                float* d_w1, float* d_b1, float* d_w2, float* d_b2,
                                int accumulate, const float* scratch, float* workspace, void* stream);
+
+/* pit_mlp_bwd_params_ordered on fp32 MFMA (ABI 29; csrc/pit_dw_ordered.hip): the weight-gradient reductions of the reproducible
+ * mode (ops.set_reproducible).  Arguments as pit_mlp_bwd_params_ordered.  ONE contraction launch for both reductions - a
+ * workgroup contracts one row slab into one 64 x 64 tile of that slab's own partial matrices (v_mfma_f32_32x32x2_f32, plain
+ * stores, bias gradients as fixed-order column sums in the same launch) - and one finishing launch that adds the partials in slab
+ * order and writes (accumulate: adds to) d_w1 (n1, n0), d_b1 (n1), d_w2 (n2, n1), d_b2 (n2).  The slabs are a pure function of
+ * (rows, n0, n1, n2): at most 64 equal slabs of a multiple of 32 rows, enough for about 512 workgroups; never of the device, the
+ * environment or an address.  Same inputs, same bits - but not the bits of pit_mlp_bwd_params_ordered, whose partition differs.
+ * fp32 tensors; ldx >= n0, ld_dy >= n2 (PIT_ERR_SIZE otherwise, and for a slab beyond a 32-bit byte offset); any alignment.
+ * workspace: pit_mlp_bwd_params_ordered_mfma_workspace(...) bytes (0 for invalid sizes), no initial contents needed. */
+long pit_mlp_bwd_params_ordered_mfma_workspace(int rows, int n0, int n1, int n2);
+int pit_mlp_bwd_params_ordered_mfma(const float* x, long ldx, int rows, int n0, int n1, int n2, const float* h,
+                                    int out_gelu, const float* d_y, long ld_dy,
+                                    float* d_w1, float* d_b1, float* d_w2, float* d_b2,
+                                    int accumulate, const float* scratch, float* workspace, void* stream);
+
+/* Reproducible mode, candidate-list layers (ABI 29).
+ * pit_lists_sort_ranges: `sorted` (mesh_batch, rev_stride) <- rev_row with every key's range [rev_ptr[j], rev_ptr[j+1]) in
+ * ascending row order, the -1 slots of overflowed rows last; slots outside every range are not written (hand in a copy of
+ * rev_row).  Out of place (sorted != rev_row), rev_stride = n_out * cap as in pit_lists_transpose; mesh_batch <= 65535.
+ * d(values) of the list kernels is summed in list order, and pit_lists_transpose / pit_plan_fwd fill a range in whatever order
+ * their atomics land: with the sorted copy as pit_posatt_bwd's rev_row the sum has ONE order.
+ * pit_posatt_overflow_dv_ordered: d_values += the terms of the rows with nbr_cnt > nbr_cap, one wave per key, rows ascending, no
+ * atomics; call it after pit_posatt_bwd(..., nbr_complete = 1, ...) on the same stream (that call's own overflow pass adds with
+ * fp32 atomics and is skipped by the flag).  Nothing overflowed: every wave leaves after reading the counts.  Arguments as the
+ * same-named ones of pit_posatt_bwd (dim includes coord_dims, d_values holds the dim - coord_dims others); fp32 d_out only;
+ * 1 <= space_dim <= PIT_MAX_SPACE_DIM, every metric. */
+int pit_lists_sort_ranges(const int* rev_ptr, const int* rev_row, int mesh_batch, int n_in, long rev_stride,
+                          int* sorted, void* stream);
+int pit_posatt_overflow_dv_ordered(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                                   int space_dim, int metric, float period, int batch, int dim,
+                                   const float* head, int n_head, int head_is_scale, const float* scale,
+                                   const float* rowstat, const float* d_out, long ld_dout, long dout_bstride, int out_col0,
+                                   float* d_values, long ld_dvalues, long dvalues_bstride,
+                                   const int* nbr_cnt, int nbr_cap, int coord_dims, void* stream);
 
 /* Layout probe used by the tests: D = A(32x8) * B(8x32) through the same
  * v_mfma_f32_32x32x2_f32 fragment maps the kernels use. */

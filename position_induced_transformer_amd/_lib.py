@@ -127,9 +127,15 @@ SIGNATURES = {
     "pit_mlp_bwd_params": [_P, _L, _I, _I, _I, _I, _P, _I, _P, _L, _P, _P, _P, _P, _I, _P, _I, _P],
     "pit_mlp_bwd_params_ordered": [_P, _L, _I, _I, _I, _I, _P, _I, _P, _L, _P, _P, _P, _P, _I, _P, _P, _P],
     "pit_mlp_bwd_params_ordered_workspace": [_I, _I, _I, _I],
+    "pit_mlp_bwd_params_ordered_mfma": [_P, _L, _I, _I, _I, _I, _P, _I, _P, _L, _P, _P, _P, _P, _I, _P, _P, _P],
+    "pit_mlp_bwd_params_ordered_mfma_workspace": [_I, _I, _I, _I],
+    "pit_lists_sort_ranges": [_P, _P, _I, _I, _L, _P, _P],
+    "pit_posatt_overflow_dv_ordered": [_P, _P, _I, _I, _I, _I, _I, _F, _I, _I, _P, _I, _I, _P, _P,
+                                       _P, _L, _L, _I, _P, _L, _L, _P, _I, _I, _P],
     "pit_mlp_bwd_params_deferrable": [_I, _I, _I, _I, _I, _L],
     "pit_rel_lp_loss_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
     "pit_rel_lp_loss_fwd_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P],
+    "pit_rel_lp_loss_fwd_grad_ordered": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P],
     "pit_rel_lp_loss_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "pit_plan_ragged_fwd": [_P, _P, _I, _I, _I, _I, _P, _P, _F, _I, _P, _P, _I, _P, _P, _P],
     "pit_posatt_ragged_fwd": [_P, _P, _I, _I, _I, _I, _P, _P,
@@ -169,8 +175,9 @@ SIGNATURES = {
     "pit_debug_rider_counts": [_P, _I, _I],
 }
 
-LONG_RETURN = {"pit_satt_tiles_elems", "pit_posatt_dmesh_workspace", "pit_mlp_bwd_params_ordered_workspace"}
-ABI_VERSION = 28       # PIT_ABI_VERSION of include/pit_hip.h this binding was written against
+LONG_RETURN = {"pit_satt_tiles_elems", "pit_posatt_dmesh_workspace", "pit_mlp_bwd_params_ordered_workspace",
+               "pit_mlp_bwd_params_ordered_mfma_workspace"}
+ABI_VERSION = 29       # PIT_ABI_VERSION of include/pit_hip.h this binding was written against
 
 _lib = None
 

@@ -29,6 +29,33 @@ __device__ __forceinline__ unsigned* rel_ws_count(float* ws, int pairs, int pair
     return reinterpret_cast<unsigned*>(ws + 4 + 4 * pairs) + pair;
 }
 
+// Reproducible mode (ORD instances): the sum over the (sample, channel) pairs in INDEX order.  A pair's term
+// is parked in the pair's first fp64 slot (free here: an ORD series is never split, see pit_rel_lp_loss_fwd_grad_ordered) with
+// a returning exchange, then the pair takes its ticket; the workgroup of the last ticket calls rel_ordered_finish: thread t takes
+// the slots t, t + T, ... in ascending order (leaving zeros), the per-thread sums meet in wave_sum_d's fixed pattern and the
+// per-wave sums are added in wave order - an order that depends on (pairs, T) only.
+__device__ __forceinline__ bool rel_ordered_arrive(float* ws, int pairs, int pair, float term) {
+    unsigned long long* slot = reinterpret_cast<unsigned long long*>(rel_ws_sums(ws, pair));
+    const unsigned long long old = atomicExch(slot, (unsigned long long)__double_as_longlong((double)term));
+    asm volatile("" ::"v"(old));                       // returning atomic: performed before the ticket below
+    return atomicAdd(reinterpret_cast<unsigned*>(ws + 1), 1u) == (unsigned)pairs - 1u;
+}
+__device__ __forceinline__ void rel_ordered_finish(float* ws, int pairs, float* loss, double* s_fin) {
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < pairs; i += blockDim.x)
+        acc += __longlong_as_double((long long)atomicExch(reinterpret_cast<unsigned long long*>(rel_ws_sums(ws, i)), 0ull));
+    acc = wave_sum_d(acc);
+    if ((threadIdx.x & 63) == 0) s_fin[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double total = 0.0;
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) total += s_fin[w];
+        *loss = (float)total;
+        atomicExch(reinterpret_cast<unsigned*>(ws + 1), 0u);
+    }
+}
+
+template <bool ORD>
 __global__ __launch_bounds__(256) void rel_lp_fwd_kernel(const float* __restrict__ tru, const float* __restrict__ pred,
                                                           const float* __restrict__ scale, const float* __restrict__ shift,
                                                           int npts, int nch, int p, float* __restrict__ norms,
@@ -101,7 +128,13 @@ __global__ __launch_bounds__(256) void rel_lp_fwd_kernel(const float* __restrict
     __syncthreads();
     if (!s_last) return;
     const float nn = s_norm[0], dn = s_norm[1];
-    if (threadIdx.x == 0) {
+    if constexpr (ORD) {                              // (gridDim.z == 1: every workgroup is here, the barriers are uniform)
+        __shared__ double s_fin[4];
+        __shared__ int s_fin_last;
+        if (threadIdx.x == 0) s_fin_last = rel_ordered_arrive(ws, pairs, pair, s_norm[2]) ? 1 : 0;
+        __syncthreads();
+        if (s_fin_last) rel_ordered_finish(ws, pairs, loss, s_fin);
+    } else if (threadIdx.x == 0) {
         // sum over (sample, channel) in a persistent accumulator; the last pair publishes the loss and
         // leaves accumulator and arrival counter zero for the next call (no memset launch).  After the barrier:
         // these two dependent L2 round trips run beside the gradient pass of the other 255 threads
@@ -240,7 +273,7 @@ __global__ __launch_bounds__(256) void rel_max_fwd_kernel(const float* __restric
 // their own (round 5; non-finite terms propagate to *loss and the workspace is always left zero).
 // PK: the exponent at compile time (1, 2; 0 = the run-time p): with a run-time p the generic powf path is inlined for every value of the
 // series in both passes - 12.7 k instructions at PTS = 12, more than the instruction cache holds: the NACA loss took 26.7 us
-template <int PTS, int PK>
+template <int PTS, int PK, bool ORD>
 __global__ __launch_bounds__(1024) void rel_lp_fwd1_kernel(const float* __restrict__ tru, const float* __restrict__ pred,
                                                            const float* __restrict__ scale, const float* __restrict__ shift,
                                                            int npts, int nch, int p_arg, float* __restrict__ norms,
@@ -296,14 +329,23 @@ __global__ __launch_bounds__(1024) void rel_lp_fwd1_kernel(const float* __restri
         // never disturb the count - a packed count|fixed-point word (round 4) turned inf into a finite wrong loss and, once the
         // borrow hit the count, left the accumulator armed for every later call
         const float term = (float)(nnd / dnd / nch);
-        double* acc = reinterpret_cast<double*>(ws + 2);
-        const double old = atomicAdd(acc, (double)term);
-        asm volatile("" ::"v"(old));                   // returning atomic: performed before the ticket below
-        unsigned* counter = reinterpret_cast<unsigned*>(ws + 1);
-        if (atomicAdd(counter, 1u) == (unsigned)pairs - 1u) {
-            *loss = (float)__longlong_as_double(atomicExch(reinterpret_cast<unsigned long long*>(acc), 0ull));
-            atomicExch(counter, 0u);
+        if constexpr (!ORD) {
+            double* acc = reinterpret_cast<double*>(ws + 2);
+            const double old = atomicAdd(acc, (double)term);
+            asm volatile("" ::"v"(old));               // returning atomic: performed before the ticket below
+            unsigned* counter = reinterpret_cast<unsigned*>(ws + 1);
+            if (atomicAdd(counter, 1u) == (unsigned)pairs - 1u) {
+                *loss = (float)__longlong_as_double(atomicExch(reinterpret_cast<unsigned long long*>(acc), 0ull));
+                atomicExch(counter, 0u);
+            }
         }
+    }
+    if constexpr (ORD) {                              // the terms in pair order, by the workgroup of the last ticket
+        __shared__ double s_fin[16];
+        __shared__ int s_fin_last;
+        if (tid == 0) s_fin_last = rel_ordered_arrive(ws, pairs, pair, (float)(nnd / dnd / nch)) ? 1 : 0;
+        __syncthreads();
+        if (s_fin_last) rel_ordered_finish(ws, pairs, loss, s_fin);
     }
     if (!d_pred_unit && !d_true_unit) return;
 #pragma unroll
@@ -331,18 +373,20 @@ __global__ __launch_bounds__(1024) void rel_lp_fwd1_kernel(const float* __restri
 // the single-workgroup form when the series fits (and the grid is not huge); false = the split form
 bool launch_rel_lp_fwd1(const float* tru, const float* pred, const float* scale, const float* shift, int batch, int npts, int nch,
                         int p, float* norms, float* loss, float* ws, float* d_pred_unit, float* d_true_unit, float* clear_buf,
-                        long clear_n, hipStream_t s) {
+                        long clear_n, hipStream_t s, bool ordered = false) {
     static const bool off = getenv("PIT_NO_LOSS1") != nullptr;
-    if (off || npts > 16384 || (long)batch * nch > 4096) return false;          // (series of up to 16 values per thread: 64 registers)
+    if ((off && !ordered) || npts > 16384 || (long)batch * nch > 4096) return false;          // (series of up to 16 values per thread: 64 registers)
     const dim3 grid(nch, batch), block(1024);
     const int pts = (npts + 1023) / 1024;
-#define PIT_L1K(P_, K_) hipLaunchKernelGGL((rel_lp_fwd1_kernel<P_, K_>), grid, block, 0, s, tru, pred, scale, shift, npts, nch, p, norms, loss, ws, \
-                                           d_pred_unit, d_true_unit, clear_buf, clear_n)
+#define PIT_L1KO(P_, K_, O_) hipLaunchKernelGGL((rel_lp_fwd1_kernel<P_, K_, O_>), grid, block, 0, s, tru, pred, scale, shift, npts, nch, p, norms, \
+                                                loss, ws, d_pred_unit, d_true_unit, clear_buf, clear_n)
+#define PIT_L1K(P_, K_) do { if (ordered) PIT_L1KO(P_, K_, true); else PIT_L1KO(P_, K_, false); } while (0)
 #define PIT_L1(P_) do { if (p == 2) PIT_L1K(P_, 2); else if (p == 1) PIT_L1K(P_, 1); else PIT_L1K(P_, 0); } while (0)
     if (pts <= 1) PIT_L1(1); else if (pts <= 2) PIT_L1(2); else if (pts <= 4) PIT_L1(4); else if (pts <= 8) PIT_L1(8);
     else if (pts <= 12) PIT_L1(12); else PIT_L1(16);
 #undef PIT_L1
 #undef PIT_L1K
+#undef PIT_L1KO
     return true;
 }
 
@@ -376,7 +420,7 @@ extern "C" int pit_rel_lp_loss_fwd(const float* tru, const float* pred, const fl
         PIT_CHECK_LAUNCH();
         return 0;
     }
-    hipLaunchKernelGGL(rel_lp_fwd_kernel, dim3(nch, batch, rel_parts(batch, npts, nch)), dim3(256), 0, s, tru, pred,
+    hipLaunchKernelGGL(rel_lp_fwd_kernel<false>, dim3(nch, batch, rel_parts(batch, npts, nch)), dim3(256), 0, s, tru, pred,
                        pred_scale, pred_shift, npts, nch, p, norms, loss, workspace, (float*)nullptr, (float*)nullptr,
                        (float*)nullptr, 0L);
     PIT_CHECK_LAUNCH();
@@ -396,7 +440,31 @@ extern "C" int pit_rel_lp_loss_fwd_grad(const float* tru, const float* pred, con
         PIT_CHECK_LAUNCH();
         return 0;
     }
-    hipLaunchKernelGGL(rel_lp_fwd_kernel, dim3(nch, batch, rel_parts(batch, npts, nch)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(rel_lp_fwd_kernel<false>, dim3(nch, batch, rel_parts(batch, npts, nch)), dim3(256), 0, (hipStream_t)stream,
+                       tru, pred, pred_scale, pred_shift, npts, nch, p, norms, loss, workspace, d_pred_unit, d_true_unit,
+                       clear_n > 0 ? clear_buf : nullptr, clear_n);
+    PIT_CHECK_LAUNCH();
+    return 0;
+}
+
+// Reproducible mode: the same contract, every sum in an order that depends on the sizes only.  The one-workgroup-per-series
+// kernel where the series fits it (its norms are a fixed-order block reduction), else the 256-thread kernel with the series
+// NOT split (gridDim.z = 1: no partial sums meet in slots); the sum over the pairs in index order (rel_ordered_finish).  The
+// environment (PIT_NO_LOSS1) is not consulted.  d_pred_unit / d_true_unit / clear_buf may be null.
+extern "C" int pit_rel_lp_loss_fwd_grad_ordered(const float* tru, const float* pred, const float* pred_scale,
+                                                const float* pred_shift, int batch, int npts, int nch, int p,
+                                                float* norms, float* loss, float* workspace, float* d_pred_unit,
+                                                float* d_true_unit, float* clear_buf, long clear_n, void* stream) {
+    if (!tru || !pred || !norms || !loss || !workspace) return PIT_ERR_NULL;
+    if ((pred_scale == nullptr) != (pred_shift == nullptr)) return PIT_ERR_NULL;
+    if (batch <= 0 || npts <= 0 || nch <= 0 || p < 1 || batch > 65535 || clear_n < 0) return PIT_ERR_SIZE;
+    if (clear_n > 0 && !clear_buf) return PIT_ERR_NULL;
+    if (launch_rel_lp_fwd1(tru, pred, pred_scale, pred_shift, batch, npts, nch, p, norms, loss, workspace, d_pred_unit, d_true_unit,
+                           clear_n > 0 ? clear_buf : nullptr, clear_n, (hipStream_t)stream, true)) {
+        PIT_CHECK_LAUNCH();
+        return 0;
+    }
+    hipLaunchKernelGGL(rel_lp_fwd_kernel<true>, dim3(nch, batch, 1), dim3(256), 0, (hipStream_t)stream,
                        tru, pred, pred_scale, pred_shift, npts, nch, p, norms, loss, workspace, d_pred_unit, d_true_unit,
                        clear_n > 0 ? clear_buf : nullptr, clear_n);
     PIT_CHECK_LAUNCH();

@@ -2335,6 +2335,65 @@ __global__ __launch_bounds__(256) void posatt_sparse_overflow_cols(AttArgs a, Sp
     sparse_overflow_body(a, sp, blockIdx.x);
 }
 
+// Reproducible mode: d(values) of the rows whose candidate list overflowed, WITHOUT atomics.  One wave per
+// key scans the rows with nbr_cnt > cap in ascending order, re-forms P from rowstat exactly as sparse_overflow_body does, and
+// adds the sum of their terms to the d_values row of its key, which the list kernel has already written (same stream).  A key
+// belongs to one wave, the rows come in one order: the same bits on every run.  No overflowed row: the wave leaves after reading
+// the counts (no host synchronisation decides that).  Meshes of 4..8 coordinates take the MAXD 8 instance, as in every list
+// kernel (a.sdim > 3): the MAXD 4 point holds three coordinates.
+template <int MAXD>
+__global__ __launch_bounds__(256) void posatt_overflow_dv_ordered_kernel(AttArgs a, SparseArgs sp) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long keys = (long)a.mesh_batch * a.n_in;
+    const long kid = (long)blockIdx.x * 4 + wave;
+    // Did any row of the (at most two) samples this workgroup's four keys belong to overflow?  The counts are read ONCE per
+    // workgroup, 256 at a time, not once per wave.
+    const long klast = min((long)blockIdx.x * 4 + 3, keys - 1);
+    const int mb_lo = (int)(((long)blockIdx.x * 4) / a.n_in), mb_hi = (int)(klast / a.n_in);
+    int over = 0;
+    for (long n = (long)mb_lo * a.n_out + threadIdx.x; n < (long)(mb_hi + 1) * a.n_out; n += 256) over |= sp.nbr_cnt[n] > sp.cap;
+    if (!__syncthreads_or(over)) return;
+    if (kid >= keys) return;
+    const int mb = (int)(kid / a.n_in), j = (int)(kid - (long)mb * a.n_in);
+    const int* cnt = sp.nbr_cnt + (long)mb * a.n_out;
+    const unsigned mo_bytes = (unsigned)((long)a.mesh_batch * a.n_out * a.sdim * 4);
+    const unsigned mi_bytes = (unsigned)((long)a.mesh_batch * a.n_in * a.sdim * 4);
+    const __amdgpu_buffer_rsrc_t rmo = make_rsrc(a.mesh_out, mo_bytes);
+    const __amdgpu_buffer_rsrc_t rmi = make_rsrc(a.mesh_in, mi_bytes);
+    const __amdgpu_buffer_rsrc_t rdout = make_rsrc(a.d_out, a.dout_bytes);
+    const mesh_pt_t<MAXD> xi = load_pointp<MAXD>(rmi, mi_bytes, kid, a.sdim, a.coords_used);
+    const bool per = a.periodic != 0;
+    for (int c0 = 0; c0 < a.ncols; c0 += 64) {
+        const int col = c0 + lane;
+        int bb, dd;
+        col_split(a, col < a.ncols ? col : 0, mb, bb, dd);
+        const bool cvalid = col < a.ncols && dd >= a.coord_dims;       // (coordinate channels carry no gradient)
+        float acc = 0.0f;
+        for (int base = 0; base < a.n_out; base += 64) {
+            const int nl = base + lane;
+            unsigned long long mask = __builtin_amdgcn_ballot_w64(nl < a.n_out && cnt[min(nl, a.n_out - 1)] > sp.cap);
+            while (mask) {
+                const int n = base + __builtin_ctzll(mask);             // ascending rows
+                mask &= mask - 1ull;
+                const mesh_pt_t<MAXD> xo = load_pointp<MAXD>(rmo, mo_bytes, (long)mb * a.n_out + n, a.sdim, a.coords_used);
+                float m;
+                if constexpr (MAXD > 4) m = sq_distp(xo, xi, a.coords_used, per, a.period);
+                else m = sq_dist3(xo.x, xo.y, xo.z, xi.x, xi.y, xi.z, per, a.period);
+                for (int h = 0; h < a.n_head; ++h) {
+                    const float c = a.head_is_scale ? a.head[h] : head_scale_from_lmda(a.head[h]);
+                    const float4 rs4 = *reinterpret_cast<const float4*>(a.rowstat + (((long)mb * a.n_head + h) * a.n_out + n) * 4);
+                    const float sv = __fmul_rn(m, c);
+                    if (!(sv <= rs4.x)) continue;                       // (wave-uniform: one key, one row)
+                    const float p = __expf(rs4.y - sv) * rs4.z;
+                    const long go = (long)bb * a.dout_bstride + (long)n * a.ld_dout + a.out_col0 + (long)h * a.dim + dd;
+                    acc += p * buf_load(rdout, cvalid ? (unsigned)go * 4u : a.dout_bytes);
+                }
+            }
+        }
+        if (cvalid) a.d_values[(long)bb * a.dvalues_bstride + (long)j * a.ld_dvalues + (dd - a.coord_dims)] += acc;
+    }
+}
+
 // ------------------------------------------------------------------------------------
 // Meshes with 4..8 coordinates (space_dim 4..8): the candidate-list bodies with MAXD 8 points, one column (pair) per lane
 // (the dense instances follow posatt_cols_kernel).  The paired, tiled, union and fused launches are not taken for these
@@ -3510,6 +3569,37 @@ extern "C" int pit_posatt_bwd(const float* mesh_out, const float* mesh_in, int m
         PIT_CHECK_LAUNCH();
     }
     return rd.finish();
+}
+
+extern "C" int pit_posatt_overflow_dv_ordered(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
+                                              int space_dim, int metric, float period, int batch, int dim,
+                                              const float* head, int n_head, int head_is_scale, const float* scale,
+                                              const float* rowstat, const float* d_out, long ld_dout, long dout_bstride, int out_col0,
+                                              float* d_values, long ld_dvalues, long dvalues_bstride,
+                                              const int* nbr_cnt, int nbr_cap, int coord_dims, void* stream) {
+    if (!rowstat || !d_out || !d_values || !nbr_cnt) return PIT_ERR_NULL;
+    if (nbr_cap <= 0) return PIT_ERR_SIZE;
+    AttArgs a;
+    // (no values here: d_values stands in for the pointer and extent checks of fill_common)
+    int rc = fill_common(a, mesh_out, mesh_in, mesh_batch, n_out, n_in, space_dim, metric, period, d_values, batch, dim,
+                         ld_dvalues, dvalues_bstride, head, n_head, head_is_scale, coord_dims);
+    if (rc) return rc;
+    if (scale) { a.head = scale; a.head_is_scale = 1; }
+    a.masked = 1; a.rowstat = const_cast<float*>(rowstat);
+    a.d_out = d_out; a.ld_dout = ld_dout; a.dout_bstride = dout_bstride; a.out_col0 = out_col0;
+    a.d_values = d_values; a.ld_dvalues = ld_dvalues; a.dvalues_bstride = dvalues_bstride;
+    const unsigned long long de = (unsigned long long)(batch - 1) * dout_bstride + (unsigned long long)(n_out - 1) * ld_dout +
+                                  (unsigned long long)(out_col0 + n_head * dim);
+    if (de * 4ull > PIT_MAX_BUFFER_BYTES) return PIT_ERR_UNSUPPORTED;
+    a.dout_bytes = (unsigned)(de * 4ull);
+    a.dout_elems = (unsigned)de;
+    SparseArgs sp{nullptr, nbr_cnt, nbr_cap, nullptr, nullptr, 0};
+    const long keys = (long)mesh_batch * n_in;
+    const dim3 grid((unsigned)((keys + 3) / 4));
+    if (space_dim > 3) hipLaunchKernelGGL(posatt_overflow_dv_ordered_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, a, sp);
+    else hipLaunchKernelGGL(posatt_overflow_dv_ordered_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, a, sp);
+    PIT_CHECK_LAUNCH();
+    return 0;
 }
 
 #ifdef PIT_STAMPS

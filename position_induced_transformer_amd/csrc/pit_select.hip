@@ -1002,3 +1002,59 @@ extern "C" int pit_neighbors_fwd(const float* mesh_out, const float* mesh_in, in
     if (rev_ptr) return launch_transpose(nbr_idx, nbr_cnt, mesh_batch, n_out, n_in, cap, rev_ptr, rev_row, counts, cursor, !agg, s);
     return 0;
 }
+
+// Reproducible mode: every key's range of the transposed lists in ascending row order, the -1 slots of
+// overflowed rows last (as unsigned they are the largest value).  nbr_fill_* place a range's entries in whatever order their
+// atomics land; d(values) is summed in list order.  Out of place, one workgroup per key: a bitonic sort in LDS for ranges of at
+// most 4096 entries, a rank sort (ties between -1 slots broken by position) beyond.
+namespace {
+constexpr int SORT_LDS = 4096;
+__global__ __launch_bounds__(256) void lists_sort_ranges_kernel(const int* __restrict__ rev_ptr, const int* __restrict__ src, int n_in,
+                                                                long rev_stride, int* __restrict__ dst) {
+    __shared__ unsigned buf[SORT_LDS];
+    const int mb = blockIdx.y, j = blockIdx.x, tid = threadIdx.x;
+    const int beg = rev_ptr[(long)mb * (n_in + 1) + j], end = rev_ptr[(long)mb * (n_in + 1) + j + 1];
+    if (beg < 0 || end <= beg || (long)end > rev_stride) return;
+    const int len = end - beg;
+    const int* in = src + (long)mb * rev_stride + beg;
+    int* out = dst + (long)mb * rev_stride + beg;
+    if (len <= SORT_LDS) {
+        int p2 = 64;
+        while (p2 < len) p2 <<= 1;
+        for (int i = tid; i < p2; i += 256) buf[i] = i < len ? (unsigned)in[i] : 0xffffffffu;
+        __syncthreads();
+        for (int k = 2; k <= p2; k <<= 1)
+            for (int q = k >> 1; q > 0; q >>= 1) {
+                for (int i = tid; i < p2; i += 256) {
+                    const int x = i ^ q;
+                    if (x > i) {
+                        const unsigned u = buf[i], v = buf[x];
+                        if ((u > v) == ((i & k) == 0)) { buf[i] = v; buf[x] = u; }
+                    }
+                }
+                __syncthreads();
+            }
+        for (int i = tid; i < len; i += 256) out[i] = (int)buf[i];
+    } else {
+        for (int i = tid; i < len; i += 256) {
+            const unsigned v = (unsigned)in[i];
+            int rank = 0;
+            for (int t = 0; t < len; ++t) {
+                const unsigned u = (unsigned)in[t];
+                rank += (u < v || (u == v && t < i)) ? 1 : 0;
+            }
+            out[rank] = (int)v;
+        }
+    }
+}
+}  // namespace
+
+extern "C" int pit_lists_sort_ranges(const int* rev_ptr, const int* rev_row, int mesh_batch, int n_in, long rev_stride,
+                                     int* sorted, void* stream) {
+    if (!rev_ptr || !rev_row || !sorted) return PIT_ERR_NULL;
+    if (mesh_batch <= 0 || mesh_batch > 65535 || n_in <= 0 || rev_stride <= 0 || rev_row == sorted) return PIT_ERR_SIZE;
+    hipLaunchKernelGGL(lists_sort_ranges_kernel, dim3((unsigned)n_in, (unsigned)mesh_batch), dim3(256), 0, (hipStream_t)stream,
+                       rev_ptr, rev_row, n_in, rev_stride, sorted);
+    PIT_CHECK_LAUNCH();
+    return 0;
+}

@@ -156,8 +156,9 @@ class TrainStep:
         # the loss launch (unless FlatAdam(zero_grads=True) already did): no memset launch
         clear = None if getattr(self.optimizer, "zero_grads", False) else self.flat.flat
         # the loss the step applies to the prediction: a fused decoder accumulates its partial sums in the forward launch and
-        # forms d(pred) in the backward launch - no loss launch (ops.LossSpec; any other model runs the loss kernel below)
-        spec = ops.LossSpec(self.target, sc, sh, self.out_dim, self.p) if self.p in (1, 2) and ops.EDGE_FUSION else None
+        # forms d(pred) in the backward launch - no loss launch (ops.LossSpec; any other model, and the reproducible mode, run the
+        # loss kernel below)
+        spec = ops.LossSpec(self.target, sc, sh, self.out_dim, self.p) if self.p in (1, 2) and ops.EDGE_FUSION and not ops.reproducible_wanted() else None
         # per-thread state, read by the autograd nodes in their forward (ops._STEP)
         with ops.step_state(processor_hook=(self._on_processor_block, self._early_block) if early else None, loss=spec, clear=clear):
             self._step_body(sc, sh)

@@ -466,7 +466,7 @@ class MeshPlan:
 
     __slots__ = ("mesh_out", "mesh_in", "mesh_batch", "n_out", "n_in", "sdim", "metric", "metric_id", "period",
                  "rank_k", "rank_w", "masked", "self_attn", "stats", "nbr_idx", "nbr_cnt", "nbr_cap", "rev_ptr",
-                 "rev_row", "_complete", "_union", "_slab", "_fold", "len_out", "len_in", "rank_w_dev", "shared")
+                 "rev_row", "_complete", "_union", "_slab", "_fold", "len_out", "len_in", "rank_w_dev", "shared", "_rev_sorted")
 
     def __init__(self, metric: str, mesh_out: torch.Tensor, mesh_in: torch.Tensor, locality: float,
                  self_attn: bool, period: Optional[float] = None, len_out=None, len_in=None):
@@ -528,6 +528,7 @@ class MeshPlan:
         self.nbr_idx = self.nbr_cnt = self.rev_ptr = self.rev_row = None
         self.nbr_cap = 0
         self._complete = None
+        self._rev_sorted = None
         self._union = None
         self._slab = None
         self._fold = None
@@ -644,6 +645,19 @@ class MeshPlan:
             return
         _lib.check(rc, "pit_lists_transpose")
         self.rev_ptr, self.rev_row = rev_ptr, rev_row
+
+    def sorted_reverse_lists(self) -> torch.Tensor:
+        """The transposed lists with every key's range in ascending row order, -1 slots (overflowed rows) last
+        (pit_lists_sort_ranges): pit_lists_transpose fills a range in whatever order its atomics land, and d(values) is summed
+        in list order.  The reproducible mode reads this copy; ``rev_row`` itself stays as it was built, so a plan that was
+        cached with the mode off serves both (``_rev_sorted`` is the flag: built on first use in the mode)."""
+        if self._rev_sorted is None or self._rev_sorted[0] is not self.rev_row:
+            out = self.rev_row.clone()                  # (slots outside every range keep their contents)
+            rc = _lib.lib().pit_lists_sort_ranges(self.rev_ptr.data_ptr(), self.rev_row.data_ptr(), self.mesh_batch, self.n_in,
+                                                  self.n_out * self.nbr_cap, out.data_ptr(), _lib.stream_ptr())
+            _lib.check(rc, "pit_lists_sort_ranges")
+            self._rev_sorted = (self.rev_row, out)
+        return self._rev_sorted[1]
 
     def union_tiles(self) -> bool:
         """Round 4: do the masked-layer kernels take the UNION-TILE form (PIT_ATT_UNION) for this plan?  They contract 16
@@ -987,6 +1001,7 @@ class _PosAtt(torch.autograd.Function):
                 mesh_out=None, mesh_in=None):
         _need_gpu(values, head)
         ctx.math = _math_code()
+        ctx.repro = reproducible_wanted()          # (d(values) from sorted lists, overflowed rows in row order, no rider)
         # the caller's mesh tensors arrive only when one of them requires grad (posatt_apply): then the layer keeps the
         # per-row / dense kernels, whose rowstat pit_posatt_dmesh reads in the backward
         ctx.mesh_grad = mesh_out is not None or mesh_in is not None
@@ -1019,7 +1034,7 @@ class _PosAtt(torch.autograd.Function):
         # round 5: masked cross attention on a batch-free mesh pair with a slab plan and a width that is a multiple of 64 - the
         # union-tile contraction of csrc/pit_edge.hip (weights once per call, d_out read once in the backward): Vorticity / Cylinder
         ctx.uatt = None
-        if UNION_ATT and not ctx.mesh_grad and not concat and not coord_dims and out_buf is None and _union_att_ok(plan, n_head, d, b, values):
+        if UNION_ATT and not ctx.mesh_grad and not ctx.repro and not concat and not coord_dims and out_buf is None and _union_att_ok(plan, n_head, d, b, values):
             w = _new_decoder_weights(plan, head, scale_in, n_head, head_is_scale, True)      # (Q too: 2 KB per slab)
             _launch_decoder_weights(w)
             out = torch.empty((b, plan.n_out, n_head * d), device=values.device, dtype=torch.bfloat16 if out_bf16 else torch.float32)
@@ -1123,8 +1138,14 @@ class _PosAtt(torch.autograd.Function):
                 union = 0
         # d(values): from the union tiles (fp32 atomic adds: sums that differ in the last bits from run to run - not under
         # torch.use_deterministic_algorithms, nor with PIT_UNION_DV=lists), else from the transposed lists, built on demand
-        if need_v and not (union and UNION_DV != "lists" and not torch.are_deterministic_algorithms_enabled()):
+        repro = getattr(ctx, "repro", False)
+        if need_v and not (union and UNION_DV != "lists" and not torch.are_deterministic_algorithms_enabled() and not repro):
             plan.ensure_reverse_lists()
+        # reproducible mode: every key's range of the transposed lists in ascending row order (the order d(values) is summed in)
+        rev_row = plan.sorted_reverse_lists() if (repro and need_v and plan.rev_ptr is not None) else plan.rev_row
+        if repro and io:                            # (pit_posatt_overflow_dv_ordered reads an fp32 d_out)
+            raise NotImplementedError("the reproducible mode takes an fp32 d_out only")
+        ordered_lists = repro and need_v and plan.nbr_idx is not None and plan.masked and plan.rev_ptr is not None and not io
         d_values = torch.empty((b, j, dv), device=values.device, dtype=torch.float32) if need_v else None
         slot = _grad_slot(ctx.head_param) if need_h else None
         if slot is not None:
@@ -1142,7 +1163,7 @@ class _PosAtt(torch.autograd.Function):
         # LARGE (the decoder MLP's: inside that launch it costs more than a launch of its own, measured 34.7 vs 16.1 +
         # 15.7 us at Darcy b=8); left pending, the fused processor spreads it over its block launches (_Processor.backward)
         # or the next MLP backward / the end of the pass runs it
-        rider = None if (plan.nbr_idx is not None and _dw_pending_rows(values.device) >= BIG_RIDER_ROWS) \
+        rider = None if (repro or (plan.nbr_idx is not None and _dw_pending_rows(values.device) >= BIG_RIDER_ROWS)) \
             else _dw_take(values.device)
         if getattr(ctx, "satt", None) is not None:       # dense self-attention on bf16 MFMA (csrc/pit_satt.hip)
             job = None
@@ -1209,11 +1230,19 @@ class _PosAtt(torch.autograd.Function):
                 _lib.ptr(dv), dv.stride(1) if dv is not None else 0, dv.stride(0) if dv is not None else 0,
                 1 if concat else 0,
                 _lib.ptr(dh), acc_head, work.data_ptr(),
-                _lib.ptr(plan.nbr_idx), _lib.ptr(plan.nbr_cnt), plan.nbr_cap, plan.lists_complete(),
-                _lib.ptr(plan.rev_ptr), _lib.ptr(plan.rev_row),
+                _lib.ptr(plan.nbr_idx), _lib.ptr(plan.nbr_cnt), plan.nbr_cap, 1 if ordered_lists else plan.lists_complete(),
+                _lib.ptr(plan.rev_ptr), _lib.ptr(rev_row),
                 ctypes.cast(ctypes.pointer(job[0]), ctypes.c_void_p) if job is not None else None,
                 ctx.coord_dims, ctx.math | io | union, stream_ptr)
             _lib.check(rc, "pit_posatt_bwd")
+            if ordered_lists:
+                # the rows whose list overflowed (pit_posatt_bwd was told there are none: its pass adds with atomics), in row order
+                rc = _lib.lib().pit_posatt_overflow_dv_ordered(
+                    plan.mesh_out.data_ptr(), plan.mesh_in.data_ptr(), plan.mesh_batch, plan.n_out, plan.n_in,
+                    plan.sdim, plan.metric_id, plan.period, b, d, head.data_ptr(), n_head, 1 if ctx.head_is_scale else 0,
+                    scale.data_ptr(), rowstat.data_ptr(), d_out.data_ptr(), d_out.stride(1), d_out.stride(0), d if concat else 0,
+                    dv.data_ptr(), dv.stride(1), dv.stride(0), plan.nbr_cnt.data_ptr(), plan.nbr_cap, ctx.coord_dims, stream_ptr)
+                _lib.check(rc, "pit_posatt_overflow_dv_ordered")
 
         launch(d_values, d_head, _lib.stream_ptr(), rider)
         if defer:
@@ -1385,6 +1414,7 @@ def posatt_apply(values: torch.Tensor, lmda: torch.Tensor, plan: MeshPlan, n_hea
             raise RuntimeError("ragged batches need the coordinate concat materialised (ops.materialize_coords)")
         return _PosAttRagged.apply(values, lmda.reshape(-1), plan, n_head, concat, head_is_scale)
     meshes = ()
+    reproducible_wanted()                          # (bf16 mode: refused here, before anything is launched)
     if mesh_grad_wanted(mesh_out, mesh_in):
         _check_mesh_grad(plan.metric)
         meshes = (mesh_out, mesh_in)
@@ -1509,7 +1539,8 @@ class _Mlp(torch.autograd.Function):
         ctx.x16 = x16
         ctx.chain = None
         # ragged batches: the weight gradients are summed in a fixed order (pit_mlp_bwd_params_ordered) - fp32 tensors, the plain kernels
-        ctx.ordered = bool(ordered) and not x16
+        # (2: the reproducible mode's pit_mlp_bwd_params_ordered_mfma)
+        ctx.ordered = (2 if ordered == 2 else int(bool(ordered))) if not x16 else 0
         if not x16 and not ctx.ordered and chain_mlp_supported(rows, n0, n1, n2, out_gelu) and x2.stride(0) % 4 == 0 and x2.data_ptr() % 16 == 0 \
                 and _chain_weight_ok(w1) and _chain_weight_ok(w2):
             # bf16 mode, hid 128 / 256, a few thousand rows: GEMM1 + gelu + GEMM2 + gelu in ONE launch (csrc/pit_chain.hip)
@@ -1573,11 +1604,12 @@ class _Mlp(torch.autograd.Function):
                                     d_y2.data_ptr(), d_y2.stride(0), _lib.ptr(d_x), n0, scratch.data_ptr(),
                                     MATH_MODES["fp32"], _lib.stream_ptr())
             _lib.check(rc, "pit_mlp_bwd_data")
-            work = torch.empty((int(L.pit_mlp_bwd_params_ordered_workspace(rows, n0, n1, n2)) // 4,), device=dev, dtype=torch.float32)
-            rc = L.pit_mlp_bwd_params_ordered(x2.data_ptr(), x2.stride(0), rows, n0, n1, n2, h.data_ptr(), og, d_y2.data_ptr(),
-                                              d_y2.stride(0), d_w1.data_ptr(), d_b1.data_ptr(), d_w2.data_ptr(), d_b2.data_ptr(),
-                                              1 if inplace else 0, scratch.data_ptr(), work.data_ptr(), _lib.stream_ptr())
-            _lib.check(rc, "pit_mlp_bwd_params_ordered")
+            entry = "pit_mlp_bwd_params_ordered_mfma" if ctx.ordered == 2 else "pit_mlp_bwd_params_ordered"
+            work = torch.empty((int(getattr(L, entry + "_workspace")(rows, n0, n1, n2)) // 4,), device=dev, dtype=torch.float32)
+            rc = getattr(L, entry)(x2.data_ptr(), x2.stride(0), rows, n0, n1, n2, h.data_ptr(), og, d_y2.data_ptr(),
+                                   d_y2.stride(0), d_w1.data_ptr(), d_b1.data_ptr(), d_w2.data_ptr(), d_b2.data_ptr(),
+                                   1 if inplace else 0, scratch.data_ptr(), work.data_ptr(), _lib.stream_ptr())
+            _lib.check(rc, entry)
         elif ctx.chain is not None and d_y2.stride(0) % 4 == 0 and d_y2.data_ptr() % 16 == 0:
             # the data path (dZ2, dZ1, d_x) in ONE launch on the forward's bf16 weight copies, then both weight-gradient reductions
             w1b, w2b = ctx.chain
@@ -1656,6 +1688,13 @@ def mlp_apply(x, w1, b1, w2, b2, out_gelu: bool = False, concat_heads: int = 0, 
     first columns of that layer's (b, L, (1+H)*n2) concat buffer; the returned tensor is that strided view and
     carries the buffer (``_pit_concat``), so the attention kernel skips copying its inputs (pit.py:44).
     ``ordered`` (ragged batches, fp32 mode): the backward sums the weight gradients in a fixed order (pit_mlp_bwd_params_ordered)."""
+    if not ordered and reproducible_wanted():        # (ordered: the ragged path keeps its own kernel, whose bits its tests pin)
+        # reproducible mode: the data path, then pit_mlp_bwd_params_ordered_mfma; no rider, no hand-off (ordered = 2)
+        if concat_heads <= 0 or x.dim() != 3:
+            return _Mlp.apply(x, w1, b1, w2, b2, out_gelu, 0, None, None, False, 2)
+        y, buf = _Mlp.apply(x, w1, b1, w2, b2, out_gelu, int(concat_heads), None, None, False, 2)
+        y._pit_concat = buf
+        return y
     if ordered:
         if get_math_mode() != "fp32":
             raise NotImplementedError("ordered weight gradients run in the fp32 math mode only")
@@ -2738,17 +2777,19 @@ class _RelLpLoss(torch.autograd.Function):
         if _capturing():
             _pin(ws)
         unit_p = unit_t = None
-        if unit_seed is not None or clear is not None:
+        # reproducible mode: the entry whose sums all run in a fixed order (a series is never split, the pairs in index order)
+        fwd_grad = "pit_rel_lp_loss_fwd_grad_ordered" if reproducible_wanted() else "pit_rel_lp_loss_fwd_grad"
+        if unit_seed is not None or clear is not None or fwd_grad.endswith("_ordered"):
             if unit_seed is not None:
                 unit_p = torch.empty_like(q) if pred.requires_grad else None
                 unit_t = torch.empty_like(t) if true.requires_grad else None
             if clear is not None and (not clear.is_contiguous() or clear.dtype != torch.float32):
                 raise RuntimeError("clear must be a contiguous fp32 tensor")
-            rc = _lib.lib().pit_rel_lp_loss_fwd_grad(t.data_ptr(), q.data_ptr(), _lib.ptr(sc), _lib.ptr(sh), b, npts,
-                                                     out_dim, int(p), norms.data_ptr(), loss.data_ptr(), ws.data_ptr(),
-                                                     _lib.ptr(unit_p), _lib.ptr(unit_t), _lib.ptr(clear),
-                                                     clear.numel() if clear is not None else 0, _lib.stream_ptr())
-            _lib.check(rc, "pit_rel_lp_loss_fwd_grad")
+            rc = getattr(_lib.lib(), fwd_grad)(t.data_ptr(), q.data_ptr(), _lib.ptr(sc), _lib.ptr(sh), b, npts,
+                                               out_dim, int(p), norms.data_ptr(), loss.data_ptr(), ws.data_ptr(),
+                                               _lib.ptr(unit_p), _lib.ptr(unit_t), _lib.ptr(clear),
+                                               clear.numel() if clear is not None else 0, _lib.stream_ptr())
+            _lib.check(rc, fwd_grad)
         else:
             rc = _lib.lib().pit_rel_lp_loss_fwd(t.data_ptr(), q.data_ptr(), _lib.ptr(sc), _lib.ptr(sh), b, npts,
                                                 out_dim, int(p), norms.data_ptr(), loss.data_ptr(), ws.data_ptr(),
@@ -2988,6 +3029,49 @@ class math_mode:
     def __exit__(self, *exc):
         set_math_mode(self.prev)
         return False
+
+
+# Reproducible mode: every gradient summed in a fixed order - the per-layer path (no fused launch, no
+# rider), weight gradients through pit_mlp_bwd_params_ordered_mfma, d(values) of candidate-list layers from transposed lists
+# whose ranges are sorted, overflowed rows added by pit_posatt_overflow_dv_ordered.  fp32 math mode only.  Per thread, like the
+# math mode; PIT_REPRODUCIBLE=1 in the environment is the initial value (unmodified scripts).  Read in an operator's forward
+# and remembered on its autograd context.  NOT tied to torch.use_deterministic_algorithms.
+_REPRO = threading.local()
+_DEFAULT_REPRO = os.environ.get("PIT_REPRODUCIBLE", "0").strip().lower() not in ("", "0", "false", "off", "no")
+
+
+def set_reproducible(on: bool) -> None:
+    _REPRO.on = bool(on)
+
+
+def get_reproducible() -> bool:
+    return bool(getattr(_REPRO, "on", _DEFAULT_REPRO))
+
+
+class reproducible:
+    """`with ops.reproducible(): ...` - scoped set_reproducible (restored on exit, also after an exception)."""
+
+    def __init__(self, on: bool = True):
+        self.on, self.prev = bool(on), None
+
+    def __enter__(self):
+        self.prev = get_reproducible()
+        set_reproducible(self.on)
+        return self
+
+    def __exit__(self, *exc):
+        set_reproducible(self.prev)
+        return False
+
+
+def reproducible_wanted() -> bool:
+    """get_reproducible(), refusing what the mode does not cover before anything is launched."""
+    if not get_reproducible():
+        return False
+    if get_math_mode() != "fp32":
+        raise NotImplementedError("the reproducible mode (ops.set_reproducible) runs in the fp32 math mode only: the bf16 mode's "
+                                  "kernels add their partial sums in no fixed order")
+    return True
 
 
 def head_scale(lmda: torch.Tensor) -> torch.Tensor:

@@ -330,7 +330,8 @@ class pit(nn.Module):
         grad.  Then every attention layer runs on its own (_PosAtt with the meshes as inputs), none of the fused launches does.
         What that path does not cover (periodic metrics, the bf16 math mode) raises here, before anything is launched."""
         if not ops.mesh_grad_wanted(self.mesh_ltt, *meshes):
-            return False
+            # the reproducible mode takes the same per-layer path at the same decision points (bf16 mode: refused here)
+            return ops.reproducible_wanted()
         for m in (self.down, *self.conv, self.up):
             if isinstance(m, posatt):
                 ops._check_mesh_grad(m._metric)
