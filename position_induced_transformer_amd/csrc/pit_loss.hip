@@ -17,7 +17,7 @@ __device__ __forceinline__ float pow_abs(float x, int p) {
 }
 
 // Workspace layout (floats; ZERO before the first call, left zero by every call):
-//   [0] loss accumulator, [1] arrival counter over the (sample, channel) pairs,
+//   [0] unused, [1] arrival counter over the (sample, channel) pairs, [2..3] the loss accumulator (one fp64),
 //   then per pair 4 floats: {num, den} as one fp64 each is too wide for the float view - so per pair
 //   2 doubles (num, den) at double index 1 + 2*pair... see REL_WS_* below - and one arrival counter.
 // One (sample, channel) series is split over gridDim.z workgroups (one dependent-latency round trip each
@@ -138,12 +138,14 @@ __global__ __launch_bounds__(256) void rel_lp_fwd_kernel(const float* __restrict
         // sum over (sample, channel) in a persistent accumulator; the last pair publishes the loss and
         // leaves accumulator and arrival counter zero for the next call (no memset launch).  After the barrier:
         // these two dependent L2 round trips run beside the gradient pass of the other 255 threads
-        const float old = atomicAdd(ws, s_norm[2]);
+        // (the fp64 word of rel_lp_fwd1_kernel, ws[2..3]: fp32 atomics in arrival order strayed up to 3e-6 of the loss at 4100 pairs)
+        double* acc = reinterpret_cast<double*>(ws + 2);
+        const double old = atomicAdd(acc, (double)s_norm[2]);
         asm volatile("" ::"v"(old));
         unsigned* counter = reinterpret_cast<unsigned*>(ws + 1);
         const unsigned ticket = atomicAdd(counter, 1u);
         if (ticket == (unsigned)pairs - 1u) {
-            *loss = atomicExch(ws, 0.0f);
+            *loss = (float)__longlong_as_double(atomicExch(reinterpret_cast<unsigned long long*>(acc), 0ull));
             atomicExch(counter, 0u);
         }
     }
