@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define PIT_ABI_VERSION 29
+#define PIT_ABI_VERSION 30
 #define PIT_MAX_SPACE_DIM 8   /* largest space_dim any entry accepts */
 #define PIT_DSCALE_SLOTS 1024 /* fp64 accumulators per head in pit_posatt_bwd's workspace */
 
@@ -821,6 +821,44 @@ int pit_debug_mfma_tile(const float* a, const float* b, float* d, void* stream);
 #define PIT_RIDER_SATT         8   /* pit_satt_bwd: the merged d(values) + d(scale) launch                             */
 #define PIT_RIDER_KINDS        9
 int pit_debug_rider_counts(int* out, int n, int reset);
+
+/* Which kernels the GEMM core (csrc/pit_mlp.hip, csrc/pit_mlp_slab.hip: pit_mlp_*, pit_linear_*) launched: host-side
+ * counters of the CALLING THREAD, one per kind below, incremented by the host code at every launch site; one kind per kernel
+ * and per template instance that differs in tile geometry.  The PIT_GEMM_LAST_* slots are not counters: they hold the template
+ * arguments of the most recent fused launch.  Copies min(n, PIT_GEMM_KINDS) slots to out (host array) and zeroes them all when
+ * reset != 0; returns PIT_GEMM_KINDS.  No device work, nothing read by a kernel. */
+#define PIT_GEMM_RD_TN1            0   /* gemm_rd_kernel<1, *>: register-direct, one 32-column tile per wave               */
+#define PIT_GEMM_RD_TN2            1   /* gemm_rd_kernel<2, *>: two column tiles per wave                                  */
+#define PIT_GEMM_RD_PAIR           2   /* gemm_rd_pair_kernel<1, ATOMIC>: both weight-gradient reductions                  */
+#define PIT_GEMM_RD_TRIPLE_TN1     3   /* gemm_rd_triple_kernel<1>: dX + both reductions                                   */
+#define PIT_GEMM_RD_TRIPLE_TN2     4   /* gemm_rd_triple_kernel<2>                                                         */
+#define PIT_GEMM_LDS_32            5   /* gemm_lds_kernel<32, ...>: fp32 math, LDS-staged (with or without AGZ)            */
+#define PIT_GEMM_LDS_64            6   /* gemm_lds_kernel<64, ...>                                                         */
+#define PIT_GEMM_LDS_128           7   /* gemm_lds_kernel<128, ...>                                                        */
+#define PIT_GEMM_LDS_AGZ           8   /* ... of those, the launches with the trailing-gelu prologue (AGZ)                 */
+#define PIT_GEMM_BFL_32            9   /* gemm_bfl_kernel<32, ..., IO16 = false>: bf16 math, fp32 storage                  */
+#define PIT_GEMM_BFL_64           10   /* gemm_bfl_kernel<64, ..., false>                                                  */
+#define PIT_GEMM_BFL_128          11   /* gemm_bfl_kernel<128, ..., false>                                                 */
+#define PIT_GEMM_BFL_IO16         12   /* gemm_bfl_kernel<*, ..., IO16 = true>: bf16 storage (PIT_IO_*), any tile height   */
+#define PIT_GEMM_RR               13   /* gemm_rr_kernel, one reduction                                                    */
+#define PIT_GEMM_RR_PAIR          14   /* gemm_rr_kernel, the two reductions of one MLP                                    */
+#define PIT_GEMM_MUL_GELU_GRAD    15   /* mul_gelu_grad_kernel: the trailing-gelu prologue as a pass of its own            */
+#define PIT_GEMM_THIN_DZ1         16   /* thin_dz1_kernel                                                                  */
+#define PIT_GEMM_THIN_FWD         17   /* thin_fwd_kernel, streamed = 0                                                    */
+#define PIT_GEMM_THIN_FWD_STREAM  18   /* thin_fwd_kernel, streamed = 1                                                    */
+#define PIT_GEMM_THIN_DW          19   /* thin_dw_kernel                                                                   */
+#define PIT_GEMM_MLP_FWD16        20   /* mlp_fwd16_kernel<N1, KS>                                                         */
+#define PIT_GEMM_MLP_BWD16        21   /* mlp_bwd16_kernel<N1, TPW>                                                        */
+#define PIT_GEMM_MLP_FWD64        22   /* mlp_fwd64_kernel<KS, THIN = false>                                               */
+#define PIT_GEMM_MLP_FWD64_THIN   23   /* mlp_fwd64_kernel<KS, true>                                                       */
+#define PIT_GEMM_MLP_BWD64        24   /* mlp_bwd64_kernel<T, false>                                                       */
+#define PIT_GEMM_MLP_BWD64_THIN   25   /* mlp_bwd64_kernel<T, true>                                                        */
+#define PIT_GEMM_LAST_FWD16       26   /* last mlp_fwd16 instance: N1 * 100 + KS                                           */
+#define PIT_GEMM_LAST_BWD16       27   /* last mlp_bwd16 instance: N1 * 100 + TPW                                          */
+#define PIT_GEMM_LAST_FWD64       28   /* last mlp_fwd64 instance: KS                                                      */
+#define PIT_GEMM_LAST_BWD64       29   /* last mlp_bwd64 instance: T                                                       */
+#define PIT_GEMM_KINDS            30
+int pit_debug_gemm_counts(int* out, int n, int reset);
 
 #ifdef __cplusplus
 }

@@ -173,11 +173,12 @@ SIGNATURES = {
     "pit_adam_step": [_P, _P, _P, _P, _L, _P, _F, _F, _I, _F, _F, _F, _F, _I, _P, _P],
     "pit_debug_mfma_tile": [_P, _P, _P, _P],
     "pit_debug_rider_counts": [_P, _I, _I],
+    "pit_debug_gemm_counts": [_P, _I, _I],
 }
 
 LONG_RETURN = {"pit_satt_tiles_elems", "pit_posatt_dmesh_workspace", "pit_mlp_bwd_params_ordered_workspace",
                "pit_mlp_bwd_params_ordered_mfma_workspace"}
-ABI_VERSION = 29       # PIT_ABI_VERSION of include/pit_hip.h this binding was written against
+ABI_VERSION = 30       # PIT_ABI_VERSION of include/pit_hip.h this binding was written against
 
 _lib = None
 

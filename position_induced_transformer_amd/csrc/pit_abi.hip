@@ -21,6 +21,7 @@ extern "C" int pit_version(void) { return PIT_ABI_VERSION; }
 
 namespace {
 thread_local int t_rider_counts[PIT_RIDER_KINDS];
+thread_local int t_gemm_counts[PIT_GEMM_KINDS];
 }  // namespace
 
 void pit_rider_note(int kind) {
@@ -32,6 +33,20 @@ extern "C" int pit_debug_rider_counts(int* out, int n, int reset) {
     if (reset)
         for (int k = 0; k < PIT_RIDER_KINDS; ++k) t_rider_counts[k] = 0;
     return PIT_RIDER_KINDS;
+}
+
+void pit_gemm_note(int kind) {
+    if (kind >= 0 && kind < PIT_GEMM_LAST_FWD16) ++t_gemm_counts[kind];
+}
+void pit_gemm_note_last(int slot, int value) {
+    if (slot >= PIT_GEMM_LAST_FWD16 && slot < PIT_GEMM_KINDS) t_gemm_counts[slot] = value;
+}
+
+extern "C" int pit_debug_gemm_counts(int* out, int n, int reset) {
+    for (int k = 0; out && k < n && k < PIT_GEMM_KINDS; ++k) out[k] = t_gemm_counts[k];
+    if (reset)
+        for (int k = 0; k < PIT_GEMM_KINDS; ++k) t_gemm_counts[k] = 0;
+    return PIT_GEMM_KINDS;
 }
 
 extern "C" const char* pit_error_string(int code) {

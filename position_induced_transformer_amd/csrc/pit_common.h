@@ -35,6 +35,10 @@ extern thread_local int t_call_math;
                                    t_call_math = ((mode_) & 0xff); } while (0)
 // include/pit_hip.h, pit_debug_rider_counts: a host that accepts a postponed weight-gradient job notes it (kind = PIT_RIDER_*)
 void pit_rider_note(int kind);
+// include/pit_hip.h, pit_debug_gemm_counts: every launch site of pit_mlp.hip / pit_mlp_slab.hip notes its kernel (kind = a
+// PIT_GEMM_* counter); pit_gemm_note_last stores a value in a PIT_GEMM_LAST_* slot
+void pit_gemm_note(int kind);
+void pit_gemm_note_last(int slot, int value);
 // bf16 storage (PIT_IO_*): a tensor kept as bf16 in memory is widened exactly (bits << 16), narrowed with RNE
 __device__ __forceinline__ float bf16_to_f(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
 __device__ __forceinline__ unsigned short f_to_bf16(float x) { return __builtin_bit_cast(unsigned short, (__bf16)x); }

@@ -251,6 +251,8 @@ bool try_launch_mlp_fwd16(const float* x, long ldx, int rows, int n0, int n1, in
     } while (0)
     if (n1 == 32) PIT_F16(32); else if (n1 == 64) PIT_F16(64); else PIT_F16(128);
 #undef PIT_F16
+    pit_gemm_note(PIT_GEMM_MLP_FWD16);
+    pit_gemm_note_last(PIT_GEMM_LAST_FWD16, n1 * 100 + std::min(ks, 16));
     return true;
 }
 
@@ -428,6 +430,8 @@ bool try_launch_mlp_bwd16(int rows, int n0, int n1, int n2, const float* w1, con
     } while (0)
     if (n1 == 32) PIT_B16(32); else if (n1 == 64) PIT_B16(64); else PIT_B16(128);
 #undef PIT_B16
+    pit_gemm_note(PIT_GEMM_MLP_BWD16);
+    pit_gemm_note_last(PIT_GEMM_LAST_BWD16, n1 * 100 + std::max(1, std::min(tpw, 4)));
     return true;
 }
 
@@ -1264,6 +1268,7 @@ bool try_launch_thin(const GemmArgs& g, hipStream_t s) {
         (!(g.g16 || g.c16) || !g.a_gz) && (long)g.M * g.N >= min_out) {
         const long quads = (long)g.M * (g.N / 4);
         hipLaunchKernelGGL(thin_dz1_kernel, dim3((unsigned)std::min<long>((quads + 255) / 256, 8192)), dim3(256), 0, s, g);
+        pit_gemm_note(PIT_GEMM_THIN_DZ1);
         return true;
     }
     if ((g.epi == EPI_BIAS || g.epi == EPI_BIAS_GELU) && g.N <= THIN_MAX && g.a_cs == 1 && g.b_rs == 1 && g.K % 4 == 0 &&
@@ -1278,6 +1283,7 @@ bool try_launch_thin(const GemmArgs& g, hipStream_t s) {
         const int streamed = (g.K <= tpr * 4 && !g.a16 && a_bytes < PIT_MAX_BUFFER_BYTES && g.M >= 65536 && !no_stream) ? 1 : 0;
         hipLaunchKernelGGL(thin_fwd_kernel, dim3((unsigned)std::min<long>((g.M + rows_per_wg - 1) / rows_per_wg, streamed ? 2048 : 16384)),
                            dim3(256), 0, s, g, tpr, streamed);
+        pit_gemm_note(streamed ? PIT_GEMM_THIN_FWD_STREAM : PIT_GEMM_THIN_FWD);
         return true;
     }
     if (g.epi == EPI_ATOMIC && g.M <= THIN_MAX && g.ones_col == g.N - 1 && g.a_rs == 1 && g.b_cs == 1 && (g.N - 1) % 4 == 0 &&
@@ -1286,6 +1292,7 @@ bool try_launch_thin(const GemmArgs& g, hipStream_t s) {
         // one address serialise in L2 (~40 ns each) - 256 of them cost less than the pass over the rows
         const int slab = std::max(256, ((g.K + 255) / 256 + 15) / 16 * 16);
         hipLaunchKernelGGL(thin_dw_kernel, dim3((unsigned)((g.K + slab - 1) / slab)), dim3(256), 0, s, g, slab);
+        pit_gemm_note(PIT_GEMM_THIN_DW);
         return true;
     }
     return false;
@@ -1342,6 +1349,7 @@ void launch_gemm_rr(const GemmArgs& g1, const GemmArgs* g2, hipStream_t s) {
     else if (rm == 1 && rn == 2) PIT_RR(1, 2, 32, false);          // (experiments only: 64 x 128 tiles)
     else PIT_RR(1, 1, 64, false);
 #undef PIT_RR
+    pit_gemm_note(g2 ? PIT_GEMM_RR_PAIR : PIT_GEMM_RR);
 }
 
 bool try_launch_gemm_lds(GemmArgs g, hipStream_t s) {
@@ -1380,6 +1388,7 @@ bool try_launch_gemm_lds(GemmArgs g, hipStream_t s) {
             const long quads = (long)g.M * (g.K / 4);
             hipLaunchKernelGGL(mul_gelu_grad_kernel, dim3((unsigned)std::min<long>((quads + 255) / 256, 4096)), dim3(256), 0, s,
                                g.A, g.a_rs, g.a_gz, g.a_out, g.a_out_rs, g.M, g.K);
+            pit_gemm_note(PIT_GEMM_MUL_GELU_GRAD);
             g.A = g.a_out; g.a_rs = g.a_out_rs;
             g.a_bytes = (unsigned)((((unsigned long long)(g.M - 1) * g.a_rs) + g.K) * 4ull);
             g.a_gz = nullptr; g.a_out = nullptr;
@@ -1441,6 +1450,17 @@ bool try_launch_gemm_lds(GemmArgs g, hipStream_t s) {
 #else
 #define PIT_LDS(A_, B_, EPI_) do { (void)legacy_bf; if (g.bf16) PIT_BFL(A_, B_, EPI_); else PIT_LDS_BF(A_, B_, EPI_, false); } while (0)
 #endif
+#ifdef PIT_EXPERIMENTS
+    const bool use_bfl = g.bf16 && !legacy_bf;
+#else
+    const bool use_bfl = g.bf16;
+#endif
+    // pit_debug_gemm_counts: the tile kind of the launches below (kind 4 notes its own)
+    const int tile_kind = (use_bfl && io16) ? PIT_GEMM_BFL_IO16
+                        : use_bfl ? (bm == 128 ? PIT_GEMM_BFL_128 : bm == 64 ? PIT_GEMM_BFL_64 : PIT_GEMM_BFL_32)
+                                  : (bm == 128 ? PIT_GEMM_LDS_128 : bm == 64 ? PIT_GEMM_LDS_64 : PIT_GEMM_LDS_32);
+    if (kind != 4) pit_gemm_note(tile_kind);                 // (agz: fp32 math only, so an LDS kind)
+    if (agz) pit_gemm_note(PIT_GEMM_LDS_AGZ);
     switch (kind) {
         case 0: PIT_LDS(true, true, EPI_BIAS); break;
         case 1: PIT_LDS(true, true, EPI_BIAS_GELU); break;
@@ -1453,13 +1473,22 @@ bool try_launch_gemm_lds(GemmArgs g, hipStream_t s) {
             break;
         case 3: PIT_LDS(true, false, EPI_STORE); break;
         default:
-            if (g.bf16 && !legacy_bf && io16) hipLaunchKernelGGL((gemm_bfl_kernel<128, false, false, EPI_ATOMIC, true, BK128>), grid, block, 0, s, g);
+            if (g.bf16 && !legacy_bf && io16) {
+                hipLaunchKernelGGL((gemm_bfl_kernel<128, false, false, EPI_ATOMIC, true, BK128>), grid, block, 0, s, g);
+                pit_gemm_note(PIT_GEMM_BFL_IO16);
+            }
             else if (!no_rr && gemm_rr_ok(g)) launch_gemm_rr(g, nullptr, s);
-            else if (g.bf16 && !legacy_bf) hipLaunchKernelGGL((gemm_bfl_kernel<128, false, false, EPI_ATOMIC, false, BKF128>), grid, block, 0, s, g);
+            else if (g.bf16 && !legacy_bf) {
+                hipLaunchKernelGGL((gemm_bfl_kernel<128, false, false, EPI_ATOMIC, false, BKF128>), grid, block, 0, s, g);
+                pit_gemm_note(PIT_GEMM_BFL_128);
+            }
 #ifdef PIT_EXPERIMENTS
-            else if (g.bf16) hipLaunchKernelGGL((gemm_lds_kernel<128, false, false, EPI_ATOMIC, true>), grid, block, 0, s, g);
+            else if (g.bf16) { hipLaunchKernelGGL((gemm_lds_kernel<128, false, false, EPI_ATOMIC, true>), grid, block, 0, s, g); pit_gemm_note(PIT_GEMM_LDS_128); }
 #endif
-            else hipLaunchKernelGGL((gemm_lds_kernel<128, false, false, EPI_ATOMIC, false>), grid, block, 0, s, g);
+            else {
+                hipLaunchKernelGGL((gemm_lds_kernel<128, false, false, EPI_ATOMIC, false>), grid, block, 0, s, g);
+                pit_gemm_note(PIT_GEMM_LDS_128);
+            }
             break;
     }
 #undef PIT_LDS
@@ -1535,6 +1564,7 @@ int launch_gemm(GemmArgs g, hipStream_t s) {
     }
 #undef PIT_GEMM_TN
 #undef PIT_GEMM
+    pit_gemm_note(tn == 2 ? PIT_GEMM_RD_TN2 : PIT_GEMM_RD_TN1);
     return 0;
 }
 
@@ -1563,6 +1593,7 @@ int launch_gemm_pair_atomic(GemmArgs g1, GemmArgs g2, hipStream_t s) {
     const size_t sm = (size_t)8 * 16 * 64 * sizeof(float);
     hipLaunchKernelGGL((gemm_rd_pair_kernel<1, EPI_ATOMIC>), dim3(n1 + n2), dim3(512), sm, s, g1, g2, n1,
                        (int)L1.grid.x, (int)L1.grid.y, (int)L2.grid.x, (int)L2.grid.y);
+    pit_gemm_note(PIT_GEMM_RD_PAIR);
     return 0;
 }
 
@@ -1590,6 +1621,7 @@ int launch_gemm_bwd_tail(GemmArgs gx, GemmArgs g1, GemmArgs g2, hipStream_t s) {
     else
         hipLaunchKernelGGL((gemm_rd_triple_kernel<1>), dim3(nx + n1 + n2), dim3(512), sm, s, gx, g1, g2, nx, (int)Lx.grid.x,
                            n1, (int)L1.grid.x, (int)L1.grid.y, (int)L2.grid.x, (int)L2.grid.y);
+    pit_gemm_note(Lx.tn == 2 ? PIT_GEMM_RD_TRIPLE_TN2 : PIT_GEMM_RD_TRIPLE_TN1);
     return 0;
 }
 

@@ -370,6 +370,8 @@ bool try_launch_mlp_fwd64(const float* x, long ldx, int rows, int n0, int n1, in
         default: return false;
     }
 #undef PIT_SLAB_F
+    pit_gemm_note(thin ? PIT_GEMM_MLP_FWD64_THIN : PIT_GEMM_MLP_FWD64);
+    pit_gemm_note_last(PIT_GEMM_LAST_FWD64, ks);
     return true;
 }
 
@@ -390,5 +392,7 @@ bool try_launch_mlp_bwd64(int rows, int n0, int n1, int n2, const float* w1, con
                            else hipLaunchKernelGGL((mlp_bwd64_kernel<T_, false>), grid, block, 0, s, g); } while (0)
     if (tpw == 1) PIT_SLAB_B(1); else if (tpw == 2) PIT_SLAB_B(2); else if (tpw == 3) PIT_SLAB_B(3); else PIT_SLAB_B(4);
 #undef PIT_SLAB_B
+    pit_gemm_note(thin ? PIT_GEMM_MLP_BWD64_THIN : PIT_GEMM_MLP_BWD64);
+    pit_gemm_note_last(PIT_GEMM_LAST_BWD64, std::min(tpw, 4));
     return true;
 }

@@ -3093,4 +3093,14 @@ def debug_mfma_tile(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return d
 
 
+def gemm_launch_counts(reset: bool = False) -> list:
+    """The calling thread's launch record of the GEMM core (pit_debug_gemm_counts): one slot per PIT_GEMM_* kind of
+    include/pit_hip.h, in order (the library says how many).  Host-side integers; no device work."""
+    fn = _lib.lib().pit_debug_gemm_counts
+    n = fn(None, 0, 0)
+    buf = (ctypes.c_int * n)()
+    fn(buf, n, 1 if reset else 0)
+    return list(buf)
+
+
 _ = ctypes  # keep the import explicit: pointers cross the ABI as plain integers
