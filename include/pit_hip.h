@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define PIT_ABI_VERSION 30
+#define PIT_ABI_VERSION 31
 #define PIT_MAX_SPACE_DIM 8   /* largest space_dim any entry accepts */
 #define PIT_DSCALE_SLOTS 1024 /* fp64 accumulators per head in pit_posatt_bwd's workspace */
 
@@ -801,6 +801,53 @@ int pit_posatt_overflow_dv_ordered(const float* mesh_out, const float* mesh_in, 
                                    const float* rowstat, const float* d_out, long ld_dout, long dout_bstride, int out_col0,
                                    float* d_values, long ld_dvalues, long dvalues_bstride,
                                    const int* nbr_cnt, int nbr_cap, int coord_dims, void* stream);
+
+/* ---- Position attention on caller-supplied squared distances (ABI 31; csrc/pit_distmat.hip) ---------------------------
+ * The reference's extension point for another metric is overriding posatt.dist2att (pit.py:42-43,68-69); the layer itself is
+ * pit.py:48-57 applied to whatever matrix the metric produced.  These entries take that matrix instead of two meshes:
+ *   m        fp32 squared distances, (n_out, n_in) shared by the whole batch (m_bstride = 0) or one matrix per sample, samples
+ *            m_bstride floats apart (>= (n_out-1)*ld_m + n_in); rows ld_m floats apart (>= n_in).
+ * Precondition: m finite and >= 0 - not checked (a check would synchronise); the kernels form no index from the values of m, so
+ * nothing is addressed out of bounds whatever it holds.  PIT_MATH_FP32 only (PIT_ERR_UNSUPPORTED otherwise); a sample's rows of m,
+ * values and d_out must each fit a 32-bit byte offset (PIT_ERR_UNSUPPORTED beyond).  No host synchronisation, no allocation.
+ * Every sum except d(scale)'s fp64 slots has a fixed order and there are no other atomics: same input, same bits.
+ *
+ * pit_distmat_select_fwd - the sort inside torch.quantile (pit.py:49) for rows that are GIVEN: for each of the mesh_batch*n_out rows
+ *   stats[0][row] = m_(k), stats[1][row] = m_(k+1) (k+1 clipped to n_in-1), stats[2][row] = min_j m, the layout of pit_select_fwd;
+ *   rank_k as there; need_kth = 0: only the minimum.  Exact: MSB-first bitwise search over the row's bit patterns; a row of up to
+ *   2048 keys is staged in LDS once and searched there, a longer row is streamed.  mesh_batch = number of matrices (1: m_bstride unused).
+ * pit_distmat_fwd - pit.py:48-57 on m (posatt.forward :37-44 with copy_inputs, posatt_cross.forward :63-71): out, rowstat
+ *   ((m_bstride ? batch : 1), n_head, n_out, 4) = {T, S_min, 1/rowsum, mbar = sum_j P m} and scale_out; the other arguments as the
+ *   same-named ones of pit_posatt_fwd.  The kept set is pit_posatt_fwd's: fl(c m_ij) <= T_i = quantile_lerp(fl(c m_(k)), fl(c m_(k+1)), rank_w).
+ * pit_distmat_bwd - the backward of pit_distmat_fwd, for what the reference leaves to autograd through pit.py:48-57.  With
+ *   g_i = d_out[i, out_col0 + h*dim : +dim], gv_ij = g_i . values_j, a_i = sum_j P_ij gv_ij and s_ij = P_ij (gv_ij - a_i):
+ *     d_values[j] = sum_h sum_i P_ij g_i (+ d_out[j, 0:dim] with add_residual)          NULL = not needed
+ *     d c_h       = -sum_ij s_ij m_ij -> d_head through `workspace`, accumulate_head and  NULL = not needed
+ *                   the finishing step exactly as in pit_posatt_bwd (PIT_HEAD_ACCUMULATE / PIT_HEAD_DEFER)
+ *     d_m[i][j]   = -sum_h c_h s_ij, contiguous ((m_bstride ? batch : 1), n_out, n_in); for a   NULL = not needed
+ *                   shared matrix summed over the samples in ascending order inside the workgroup that owns the tile
+ *   out / ld_out / out_bstride: the forward's result (a_i = g_i . out_i) and a_workspace: pit_distmat_bwd_workspace(batch, n_out,
+ *   n_head) bytes (the a_i, (batch, n_head, n_out), no initial contents) - both needed with d_m only.
+ *   scale = the c written to scale_out by the forward (NULL = recompute from head).
+ * The contractions (P V, P^T g and the gv tiles) run on v_mfma_f32_32x32x2_f32. */
+int pit_distmat_select_fwd(const float* m, long ld_m, long m_bstride, int mesh_batch, int n_out, int n_in,
+                           int rank_k, int need_kth, float* stats, void* stream);
+int pit_distmat_fwd(const float* m, long ld_m, long m_bstride, int n_out, int n_in,
+                    const float* values, int batch, int dim, long ld_values, long values_bstride,
+                    const float* head, int n_head, int head_is_scale,
+                    const float* stats, float rank_w, int masked,
+                    float* out, long ld_out, long out_bstride, int out_col0, int copy_inputs,
+                    float* rowstat, float* scale_out, int math_mode, void* stream);
+long pit_distmat_bwd_workspace(int batch, int n_out, int n_head);
+int pit_distmat_bwd(const float* m, long ld_m, long m_bstride, int n_out, int n_in,
+                    const float* values, int batch, int dim, long ld_values, long values_bstride,
+                    const float* head, int n_head, int head_is_scale, const float* scale,
+                    const float* rowstat, int masked,
+                    const float* d_out, long ld_dout, long dout_bstride, int out_col0,
+                    float* d_values, long ld_dvalues, long dvalues_bstride, int add_residual,
+                    float* d_head, int accumulate_head, double* workspace,
+                    float* d_m, const float* out, long ld_out, long out_bstride, float* a_workspace,
+                    int math_mode, void* stream);
 
 /* Layout probe used by the tests: D = A(32x8) * B(8x32) through the same
  * v_mfma_f32_32x32x2_f32 fragment maps the kernels use. */

@@ -167,6 +167,22 @@ SIGNATURES = {
                                       _P, _I, _P, _P, _P, _I, _P, _P, _I, _P],
     "pit_rel_lp_loss_ragged_fwd": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "pit_rel_lp_loss_ragged_bwd": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
+    "pit_distmat_select_fwd": [_P, _L, _L, _I, _I, _I, _I, _I, _P, _P],
+    "pit_distmat_fwd": [_P, _L, _L, _I, _I,
+                        _P, _I, _I, _L, _L,
+                        _P, _I, _I,
+                        _P, _F, _I,
+                        _P, _L, _L, _I, _I,
+                        _P, _P, _I, _P],
+    "pit_distmat_bwd_workspace": [_I, _I, _I],
+    "pit_distmat_bwd": [_P, _L, _L, _I, _I,
+                        _P, _I, _I, _L, _L,
+                        _P, _I, _I, _P,
+                        _P, _I,
+                        _P, _L, _L, _I,
+                        _P, _L, _L, _I,
+                        _P, _I, _P,
+                        _P, _P, _L, _L, _P, _I, _P],
     "pit_rel_max_norm": [_P, _P, _I, _I, _I, _P, _P, _P],
     "pit_instance_norm_fwd": [_P, _L, _L, _I, _I, _I, _F, _P, _P, _P],
     "pit_instance_norm_bwd": [_P, _P, _P, _I, _I, _I, _P, _P],
@@ -177,8 +193,8 @@ SIGNATURES = {
 }
 
 LONG_RETURN = {"pit_satt_tiles_elems", "pit_posatt_dmesh_workspace", "pit_mlp_bwd_params_ordered_workspace",
-               "pit_mlp_bwd_params_ordered_mfma_workspace"}
-ABI_VERSION = 30       # PIT_ABI_VERSION of include/pit_hip.h this binding was written against
+               "pit_mlp_bwd_params_ordered_mfma_workspace", "pit_distmat_bwd_workspace"}
+ABI_VERSION = 31       # PIT_ABI_VERSION of include/pit_hip.h this binding was written against
 
 _lib = None
 

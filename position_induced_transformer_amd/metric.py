@@ -1,0 +1,166 @@
+"""Position attention under a metric of the caller's own: the layers take squared distances, not a hard-wired metric.
+
+The reference's extension point for another metric is overriding ``posatt.dist2att`` (pit.py:42-43,68-69); in this package such
+a subclass runs on the composed torch path.  The layers here keep the fused HIP kernels instead: ``sqdist(mesh_out, mesh_in)``
+is ordinary, differentiable torch code of the user's that returns the squared distances - (N, J), shared by the batch, or
+(b, N, J) - and pit.py:48-57 is applied to that matrix by csrc/pit_distmat.hip (``ops.posatt_dist_apply``).  The layer returns
+d loss / d m, so autograd differentiates through the metric, tie rules included: a mesh may require grad under ANY metric.
+
+    # channel flow: periodic in x (period 2 pi), walls in y; a learnable latent mesh
+    sq = sqdist_periodic_box((2 * math.pi, None))
+    ltt = torch.rand(256, 2) * torch.tensor([2 * math.pi, 1.0])
+    model = pit_metric(2, 1, 1, 64, 2, 2, ltt, 0.05, 0.05, sqdist=sq, learn_latent=True).cuda()
+    out = model(mesh_in, func_in, mesh_out)            # (J, 2) / (b, J, 1) / (N, 2) -> (b, N, 1)
+    out.square().sum().backward()                      # model.mesh_ltt.grad: through min(|dx|, l - |dx|) by autograd
+
+Precomputed matrices (geodesic distances on a surface or a graph) go to ``forward_dist(m_dist, inputs)``.  The entries of a
+matrix must be finite and >= 0; that is not checked (a check would synchronise).  fp32 math mode only; no ragged batches.
+
+Not part of ``pit.py``, whose star-exports are the reference's.
+"""
+from __future__ import annotations
+
+from collections import OrderedDict
+
+import torch
+import torch.nn as nn
+
+from . import ops
+from . import pit as _pit
+
+__all__ = ["sqdist_euclid", "sqdist_periodic_box", "posatt_metric", "posatt_cross_metric", "pit_metric"]
+
+
+def sqdist_euclid(mesh_out: torch.Tensor, mesh_in: torch.Tensor) -> torch.Tensor:
+    """sum((mesh_out[:, None] - mesh_in[None]) ** 2, -1), the op sequence of pit.py:47 / :134; batched or batch-free meshes."""
+    diff = mesh_out.unsqueeze(-2) - mesh_in.unsqueeze(-3)
+    return torch.sum(diff ** 2, dim=-1)
+
+
+def sqdist_periodic_box(periods):
+    """Squared distance on a box that is periodic in some axes: ``periods[k]`` is the period of coordinate k (a float or a
+    0-d tensor) or None for an axis that does not wrap; any number of coordinates.  The wrapped axes follow the op sequence of
+    pit.py:248-253 - d = |x - y|, d = minimum(d, l - d), sum of squares - so with every axis wrapped by the reference's own
+    period the result is the reference's bit for bit."""
+    periods = tuple(periods)
+
+    def sqdist(mesh_out: torch.Tensor, mesh_in: torch.Tensor) -> torch.Tensor:
+        if mesh_out.shape[-1] != len(periods) or mesh_in.shape[-1] != len(periods):
+            raise ValueError(f"sqdist_periodic_box of {len(periods)} axes got meshes with {mesh_out.shape[-1]} / {mesh_in.shape[-1]} coordinates")
+        d = abs(mesh_out.unsqueeze(-2) - mesh_in.unsqueeze(-3))
+        if all(p is not None for p in periods) and all(p is periods[0] or p == periods[0] for p in periods):
+            l = periods[0]                                  # one period for every axis: pit.py:251-253 literally
+            d = torch.minimum(d, l - d)
+        elif any(p is not None for p in periods):
+            cols = []
+            for k, p in enumerate(periods):
+                dk = d[..., k]
+                cols.append(dk if p is None else torch.minimum(dk, p - dk))
+            d = torch.stack(cols, dim=-1)
+        return torch.sum(d ** 2, dim=-1)
+    return sqdist
+
+
+class posatt_metric(nn.Module):
+    """Self attention under ``sqdist``: ``forward(mesh, inputs)`` returns ``cat((inputs, conv), -1)`` as posatt.forward does
+    (pit.py:37-44).  A plain module with an ``lmda`` parameter initialised as posatt's is (pit.py:35)."""
+
+    _PLAN_CACHE = 8
+    _self_attn = True
+
+    def __init__(self, n_head, in_dim, locality, sqdist=sqdist_euclid):
+        super().__init__()
+        self.locality = locality
+        self.n_head = n_head
+        self.in_dim = in_dim
+        self.sqdist = sqdist
+        self.lmda = nn.Parameter(torch.rand(n_head, 1, 1))
+        self._plans = OrderedDict()          # LRU of plans of shared (N, J) matrices
+
+    @staticmethod
+    def _refuse_lengths(lengths):
+        if lengths is not None:
+            raise NotImplementedError("lengths (ragged batches) with a caller-supplied distance matrix are not implemented")
+
+    def _plan(self, m_dist: torch.Tensor) -> ops.DistPlan:
+        """A shared (N, J) matrix keeps its plan: keyed on address, shape, version and locality, least recently used first out
+        (the plan holds the tensor, so its address cannot be handed to another tensor while the entry lives)."""
+        if m_dist.dim() != 2:
+            return ops.DistPlan(m_dist, self.locality)
+        key = (m_dist.data_ptr(), tuple(m_dist.shape), tuple(m_dist.stride()), m_dist._version, float(self.locality), m_dist.device.index)
+        plan = self._plans.get(key)
+        if plan is None:
+            plan = ops.DistPlan(m_dist, self.locality)
+            while len(self._plans) >= self._PLAN_CACHE:
+                self._plans.popitem(last=False)
+            self._plans[key] = plan
+        else:
+            self._plans.move_to_end(key)
+        if ops._capturing():
+            ops._pin(plan)
+        return plan
+
+    def forward_dist(self, m_dist, inputs, lengths=None):
+        """The layer on a precomputed matrix of squared distances, (N, J) or (b, N, J)."""
+        self._refuse_lengths(lengths)
+        ops._check_dist_mode()
+        ops.check_dist_shapes(m_dist, inputs, self._self_attn)
+        plan = self._plan(m_dist)
+        return ops.posatt_dist_apply(inputs, self.lmda, plan, self.n_head, concat=self._self_attn, m_dist=m_dist)
+
+    def forward(self, mesh, inputs, lengths=None):
+        self._refuse_lengths(lengths)
+        ops._check_dist_mode()
+        return self._on_fresh(self.sqdist(mesh, mesh), inputs)
+
+    def _on_fresh(self, m_dist, inputs):
+        # a matrix formed for this call: its plan is built for this call too, like every per-sample mesh plan (the cache of
+        # forward_dist is for matrices the caller keeps)
+        ops.check_dist_shapes(m_dist, inputs, self._self_attn)
+        plan = ops.DistPlan(m_dist, self.locality)
+        return ops.posatt_dist_apply(inputs, self.lmda, plan, self.n_head, concat=self._self_attn, m_dist=m_dist)
+
+    def dist2att(self, m_dist, scale, locality):
+        """Dense attention weights ((b,) H, N, J) of pit.py:48-52 on ``m_dist``: the fused kernel run on the identity as values,
+        as posatt.dist2att builds them (``scale`` is the lmda parameter)."""
+        ops._check_dist_mode()
+        plan = ops.DistPlan(m_dist, float(locality))
+        eye = torch.eye(plan.n_in, device=m_dist.device).unsqueeze(0).repeat(plan.mesh_batch, 1, 1)
+        att = ops.posatt_dist_apply(eye, scale, plan, self.n_head, concat=False, m_dist=m_dist)
+        att = att.reshape(plan.mesh_batch, plan.n_out, self.n_head, plan.n_in).permute(0, 2, 1, 3)
+        return att if m_dist.dim() == 3 else att[0]
+
+
+class posatt_cross_metric(posatt_metric):
+    """Cross attention mesh_in -> mesh_out under ``sqdist`` (posatt_cross.forward, pit.py:63-71)."""
+
+    _self_attn = False
+
+    def forward(self, mesh_out, mesh_in, inputs, out_bf16: bool = False, len_out=None, len_in=None):
+        self._refuse_lengths(len_out if len_out is not None else len_in)
+        ops._check_dist_mode()
+        return self._on_fresh(self.sqdist(mesh_out, mesh_in), inputs)
+
+
+class pit_metric(_pit.pit):
+    """``pit.pit`` whose down / conv[i] / up are the metric layers above.  ``pit.encoder / processor / decoder`` call replaced
+    modules as they are; none of the fused launches takes these layers.  ``forward(mesh_in, func_in, mesh_out)`` is the
+    fixed-mesh task forward: the coordinates of ``mesh_in`` are prepended to ``func_in`` (train_darcy.py:51-55).
+    ``learn_latent``: the latent mesh becomes a parameter."""
+
+    def __init__(self, space_dim, in_dim, out_dim, hid_dim, n_head, n_blocks, mesh_ltt, en_loc, de_loc, sqdist=sqdist_euclid,
+                 learn_latent: bool = False):
+        super().__init__(space_dim, in_dim, out_dim, hid_dim, n_head, n_blocks, mesh_ltt, en_loc, de_loc)
+        self.down = posatt_cross_metric(self.n_head, self.in_dim, self.en_local, sqdist)
+        self.conv = nn.ModuleList([posatt_metric(self.n_head, self.hid_dim, 1.0, sqdist) for _ in range(self.n_blocks)])
+        self.up = posatt_cross_metric(self.n_head, self.hid_dim, self.de_local, sqdist)
+        if learn_latent:
+            self.mesh_ltt = nn.Parameter(self.mesh_ltt.detach().clone())
+
+    def forward(self, mesh_in, func_in, mesh_out):
+        mesh_ltt = self.mesh_ltt.to(func_in.device) if self.mesh_ltt.device != func_in.device else self.mesh_ltt
+        coords = mesh_in if mesh_in.dim() == 3 else mesh_in.unsqueeze(0).expand(func_in.shape[0], -1, -1)
+        func = torch.cat((coords, func_in), dim=-1)
+        func = self.encoder(mesh_in, func, mesh_ltt)
+        func = self.processor(func, mesh_ltt)
+        return self.decoder(mesh_ltt, func, mesh_out)

@@ -1434,6 +1434,156 @@ def posatt_apply(values: torch.Tensor, lmda: torch.Tensor, plan: MeshPlan, n_hea
     return out
 
 
+# ---- position attention on caller-supplied squared distances (csrc/pit_distmat.hip; metric.py) ----------------------------------
+def _check_dist_mode() -> None:
+    if get_math_mode() != "fp32":
+        raise NotImplementedError("attention on a caller-supplied distance matrix runs in the fp32 math mode only (set_math_mode('fp32'))")
+
+
+def check_dist_shapes(m_dist, values, concat: bool) -> None:
+    """Shape refusals of a layer on a distance matrix, raised before the device check and before anything is launched."""
+    if not torch.is_tensor(m_dist) or m_dist.dim() not in (2, 3):
+        raise ValueError("m_dist must be an (N, J) or (b, N, J) tensor of squared distances")
+    if not torch.is_tensor(values) or values.dim() != 3:
+        raise ValueError("inputs must be a (batch, J, channels) tensor")
+    if values.shape[1] != m_dist.shape[-1]:
+        raise ValueError(f"inputs have {values.shape[1]} points but the distance matrix has {m_dist.shape[-1]} columns")
+    if m_dist.dim() == 3 and m_dist.shape[0] != values.shape[0]:
+        raise ValueError(f"the distance matrix holds {m_dist.shape[0]} samples, the inputs {values.shape[0]}")
+    if concat and m_dist.shape[-2] != m_dist.shape[-1]:
+        raise ValueError("the self-attention form needs a square distance matrix")
+
+
+class DistPlan:
+    """Selection statistics of a caller-supplied matrix of squared distances ``m_dist`` - (N, J), shared by the whole batch, or
+    (b, N, J), one per sample - under ``locality`` (pit_distmat_select_fwd: what the sort inside torch.quantile would find,
+    pit.py:49).  Keeps a detached view of the caller's tensor (a copy only where its rows are not contiguous); precondition:
+    finite and >= 0, not checked."""
+
+    def __init__(self, m_dist: torch.Tensor, locality: float):
+        _check_dist_mode()
+        if not torch.is_tensor(m_dist) or m_dist.dim() not in (2, 3):
+            raise ValueError("m_dist must be an (N, J) or (b, N, J) tensor of squared distances")
+        if m_dist.dtype != torch.float32:
+            raise ValueError(f"m_dist must be fp32, got {m_dist.dtype}")
+        if 0 in m_dist.shape:
+            raise ValueError(f"m_dist has an empty axis: {tuple(m_dist.shape)}")
+        if not (0.0 <= float(locality) <= 1.0):
+            raise ValueError(f"locality must lie in [0, 1], got {locality}")
+        _need_gpu(m_dist)
+        self.source = m_dist.detach()                      # (keeps the caller's storage - and with it its address - alive)
+        m = self.source if m_dist.dim() == 3 else self.source.unsqueeze(0)
+        mb, n, j = m.shape
+        if m.stride(2) != 1 or (n > 1 and m.stride(1) < j) or (mb > 1 and m.stride(0) < (n - 1) * m.stride(1) + j):
+            m = m.contiguous()
+        self.m = m
+        self.mesh_batch, self.n_out, self.n_in = int(mb), int(n), int(j)
+        self.ld_m = int(m.stride(1)) if n > 1 else int(j)
+        self.m_bstride = int(m.stride(0)) if mb > 1 else 0
+        self.locality = float(locality)
+        self.masked = self.locality < 1.0
+        self.rank_k, self.rank_w = quantile_rank(self.locality, self.n_in)
+        self.stats = torch.empty((3, mb * n), device=m.device, dtype=torch.float32)
+        rc = _lib.lib().pit_distmat_select_fwd(m.data_ptr(), self.ld_m, self.m_bstride, self.mesh_batch, self.n_out, self.n_in,
+                                               self.rank_k, 1, self.stats.data_ptr(), _lib.stream_ptr())
+        _lib.check(rc, "pit_distmat_select_fwd")
+        if _capturing():
+            _pin(self)
+
+
+class _PosAttDist(torch.autograd.Function):
+    """pit.py:48-57 (+ the concat of :44) on a DistPlan: pit_distmat_fwd / _bwd, one autograd node.  ``m_dist`` arrives only
+    when it requires grad and then receives d loss / d m."""
+
+    @staticmethod
+    def forward(ctx, values, head, plan: DistPlan, n_head: int, concat: bool, head_is_scale: bool, scale_in=None, m_dist=None):
+        _need_gpu(values, head)
+        values = _row_view(values)
+        b, j, d = values.shape
+        if j != plan.n_in:
+            raise RuntimeError(f"inputs have {j} points but the distance matrix has {plan.n_in} columns")
+        if plan.mesh_batch not in (1, b):
+            raise RuntimeError("distance-matrix batch and input batch differ")
+        if concat and plan.n_out != plan.n_in:
+            raise RuntimeError("the self-attention form needs a square distance matrix")
+        head = head.detach().reshape(-1).contiguous()
+        if head.numel() != n_head:
+            raise RuntimeError("lmda must hold one value per head")
+        width = (n_head + (1 if concat else 0)) * d
+        out = torch.empty((b, plan.n_out, width), device=values.device, dtype=torch.float32)
+        rowstat = torch.empty((plan.mesh_batch, n_head, plan.n_out, 4), device=values.device, dtype=torch.float32)
+        scale = torch.empty((n_head,), device=values.device, dtype=torch.float32)
+        # route 'host': the kernels are handed the scale the host evaluated for lmda (scale_in), as in _PosAtt
+        k_head, k_is_scale = (scale_in, True) if scale_in is not None else (head, head_is_scale)
+        rc = _lib.lib().pit_distmat_fwd(
+            plan.m.data_ptr(), plan.ld_m, plan.m_bstride, plan.n_out, plan.n_in,
+            values.data_ptr(), b, d, values.stride(1), values.stride(0),
+            k_head.data_ptr(), n_head, 1 if k_is_scale else 0,
+            plan.stats.data_ptr(), plan.rank_w, 1 if plan.masked else 0,
+            out.data_ptr(), out.stride(1), out.stride(0), d if concat else 0, 1 if concat else 0,
+            rowstat.data_ptr(), scale.data_ptr(), MATH_MODES["fp32"], _lib.stream_ptr())
+        _lib.check(rc, "pit_distmat_fwd")
+        ctx.plan, ctx.n_head, ctx.concat, ctx.head_is_scale = plan, n_head, concat, head_is_scale
+        ctx.m_shape = tuple(m_dist.shape) if m_dist is not None else None
+        # (d(m) needs a_i = g_i . out_i: the result itself is kept then)
+        ctx.save_for_backward(values, head, rowstat, scale, *((out,) if m_dist is not None else ()))
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        values, head, rowstat, scale = ctx.saved_tensors[:4]
+        out = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
+        plan, n_head = ctx.plan, ctx.n_head
+        b, j, d = values.shape
+        if d_out.dtype != torch.float32:
+            d_out = d_out.float()
+        d_out = _row_view(d_out)
+        _need_gpu(d_out)
+        need_v, need_h = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_m = ctx.m_shape is not None and ctx.needs_input_grad[7]
+        dev = values.device
+        d_values = torch.empty((b, j, d), device=dev, dtype=torch.float32) if need_v else None
+        d_head = torch.empty((n_head,), device=dev, dtype=torch.float32) if need_h else None
+        work = _dscale_workspace(dev, n_head) if need_h else None
+        d_m = torch.empty((plan.mesh_batch, plan.n_out, plan.n_in), device=dev, dtype=torch.float32) if need_m else None
+        L = _lib.lib()
+        a_ws = torch.empty(((L.pit_distmat_bwd_workspace(b, plan.n_out, n_head) + 3) // 4,), device=dev, dtype=torch.float32) if need_m else None
+        if need_v or need_h or need_m:
+            rc = L.pit_distmat_bwd(
+                plan.m.data_ptr(), plan.ld_m, plan.m_bstride, plan.n_out, plan.n_in,
+                values.data_ptr(), b, d, values.stride(1), values.stride(0),
+                head.data_ptr(), n_head, 1 if ctx.head_is_scale else 0, scale.data_ptr(),
+                rowstat.data_ptr(), 1 if plan.masked else 0,
+                d_out.data_ptr(), d_out.stride(1), d_out.stride(0), d if ctx.concat else 0,
+                _lib.ptr(d_values), d, j * d, 1 if ctx.concat else 0,
+                _lib.ptr(d_head), 0, _lib.ptr(work),
+                _lib.ptr(d_m), _lib.ptr(out) if need_m else None, out.stride(1) if need_m else 0, out.stride(0) if need_m else 0,
+                _lib.ptr(a_ws), MATH_MODES["fp32"], _lib.stream_ptr())
+            _lib.check(rc, "pit_distmat_bwd")
+        return d_values, d_head, None, None, None, None, None, (d_m.view(ctx.m_shape) if d_m is not None else None)
+
+
+@torch.compiler.disable
+def posatt_dist_apply(values: torch.Tensor, lmda: torch.Tensor, plan: DistPlan, n_head: int, concat: bool = False,
+                      head_is_scale: bool = False, m_dist: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``posatt_apply`` for squared distances the caller supplies: out[b,n,h*D+d] = sum_j softmax_j(-c_h m[n,j] | quantile
+    mask)[n,j] * values[b,j,d] (pit.py:48-57) with ``m`` = the matrix ``plan`` was built from; ``concat`` prepends the inputs
+    (pit.py:44).  ``m_dist``: the caller's own tensor (the one ``plan`` was built from); when grad mode is on and it requires
+    grad it becomes an input of the node and receives d loss / d m - autograd then carries the gradient on through whatever torch
+    code formed the distances, for any metric.  fp32 math mode only; head-scale routes as in ``posatt_apply``."""
+    _check_dist_mode()
+    if _capturing():
+        _pin(plan)                                 # its buffers' addresses are now baked into a hipGraph: never release them
+    values = materialize_coords(values)
+    c = host_head_scale(lmda) if (not head_is_scale and get_head_scale_route() == "host") else None
+    extra = ()
+    if m_dist is not None and torch.is_grad_enabled() and m_dist.requires_grad:
+        if tuple(m_dist.shape)[-2:] != (plan.n_out, plan.n_in) or m_dist.numel() != plan.mesh_batch * plan.n_out * plan.n_in:
+            raise ValueError("m_dist is not the matrix the plan was built from")
+        extra = (m_dist,)
+    return _PosAttDist.apply(values, lmda.reshape(-1), plan, n_head, concat, head_is_scale, c, *extra)
+
+
 # ---- one-launch MLP chains of the bf16 math mode (csrc/pit_chain.hip): hid 128 / 256 on a few thousand rows ----------------------
 # The chains read their weights as bf16: copies are kept per weight tensor and re-formed when the weight changed (version counter /
 # parameters_changed() epoch) - all requested copies in ONE launch.  Inside a stream capture nothing can be known about the
