@@ -347,6 +347,14 @@ int pit_block_bwd(const float* e, const float* inv, const float* qw, int n_pts, 
  *   m     (n_slabs*16, cap) squared distance of every candidate (rows beyond n_out: unused), the fp32 expression of pit.py:47 /
  *         :192-194 / :251-253; slot (n_slabs*16, cap) the candidate's position in the sorted union of its slab's keys;
  *   keys  (n_slabs, PIT_SLAB_UNION_MAX) that union, nkeys (n_slabs) its size.  stats / rank_w / idx / cnt / cap as pit_posatt_fwd.
+ * Which mesh rows a slab holds (patch geometry): patch_w == 0 - `rows` CONSECUTIVE rows, slab s = rows [s*rows, (s+1)*rows), n_slabs =
+ * ceil(n_out / rows).  patch_w > 0 (pit_decoder_weights / _fwd / _bwd only; rows == 16) - mesh_out is a row-major grid_w x grid_h
+ * tensor-product grid (n_out == grid_w*grid_h, mesh row of grid point (i, j) = i*grid_w + j) and a slab is a patch_w x patch_h PATCH
+ * of it (patch_w*patch_h == rows, patch_w a power of two): with ppr = ceil(grid_w / patch_w), slab s is patch (s / ppr, s % ppr) and
+ * its row r the grid point (pi*patch_h + r / patch_w, pj*patch_w + r % patch_w) - valid when inside the grid; n_slabs =
+ * ceil(grid_h / patch_h) * ppr.  The rows of a patch list neighbouring keys, so the union is about half a strip's (Darcy 43x43 ->
+ * 16x16: 12.9 keys on average, at most 19 - the 32-slot tile - against 24.5 / 32 of the consecutive plan).  m / slot stay slab-relative ((s*rows + r)*cap + i, zero for invalid
+ * rows); every tensor of the launches keeps its mesh-row layout.
  * All pointers are device memory owned by the caller; the struct is passed by pointer and read during the call. */
 #define PIT_SLAB_UNION_MAX 64
 typedef struct pit_slab_plan {
@@ -355,19 +363,32 @@ typedef struct pit_slab_plan {
     const int* idx; const int* cnt;
     const float* m; const unsigned short* slot; const int* keys; const int* nkeys;
     int rows;       /* rows per slab (ABI 19): 16 for the fused launches and pit_union_att_*, 64 / 128 / 256 for pit_fold_* */
+    int grid_w, grid_h, patch_w, patch_h;       /* slab geometry; all 0: consecutive rows */
 } pit_slab_plan;
 /* report: 3 ints, ZERO on entry (largest union, 1 if a list overflowed, longest list).  n_in <= 16384.  rows_per_slab: 16, 64, 128
  * or 256; m / slot hold n_slabs*rows_per_slab rows, n_slabs = ceil(n_out / rows_per_slab). */
 int pit_slab_plan_build(const float* mesh_out, const float* mesh_in, int n_out, int n_in, int space_dim, int metric, float period,
                         const int* nbr_idx, const int* nbr_cnt, int cap, int rows_per_slab, float* m, unsigned short* slot,
                         int* keys, int* nkeys, int* report, void* stream);
+/* The same for slabs that are patch_w x patch_h patches of a row-major grid_w x grid_h output grid (see pit_slab_plan):
+ * n_out == grid_w*grid_h, patch_w*patch_h == 16, patch_w a power of two; n_slabs = ceil(grid_h / patch_h) * ceil(grid_w / patch_w).
+ * stats / rank_w: the plan's (pit_plan_fwd).  The union holds only the candidates SOME head scale can keep - m <= lerp(m_(k),
+ * m_(k+1), rank_w) + 2^-20 m_(k+1), which covers every fp32 rounding of the mask decision - not the whole lists (every key up to
+ * m_(k+1)): a candidate beyond it has slot 65535 and belongs to no tile.  report[0] is the largest such union. */
+int pit_slab_plan_build_patch(const float* mesh_out, const float* mesh_in, int n_out, int n_in, int space_dim, int metric,
+                              float period, const int* nbr_idx, const int* nbr_cnt, int cap, int grid_w, int grid_h, int patch_w,
+                              int patch_h, const float* stats, float rank_w, float* m, unsigned short* slot, int* keys, int* nkeys,
+                              int* report, void* stream);
 /* 1 when the fused launches cover this shape: n_head 1 or 2, dim (= the MLP's hidden width) 32 or 64, 256 <= batch*rows <= 2^20 */
 int pit_edge_supported(int n_head, int dim, int batch, int rows_per_sample);
 /* The up-projection's softmax weights for one step: they depend on (mesh pair, lmda) only, so they are formed ONCE (one workgroup
  * per slab) and every (sample, slab) workgroup of pit_decoder_fwd / _bwd reads its tile as an MFMA operand:
  *   pw (n_slabs, n_head, 16, um) = P (normalised), qw (same shape; NULL: forward only) = P (m - mbar), zeros where a row does not
- *   list a slot; um = 32, 48 or 64 >= max_union (report[0] of pit_slab_plan_build), max_count = report[2]; scale_out (n_head) = c.
+ *   list a slot; um = 16 (patch plans), 32, 48 or 64 >= max_union (report[0] of pit_slab_plan_build), max_count = report[2];
+ *   scale_out (n_head) = c.
  * As a launch of its own, or - the job struct - as extra workgroups of pit_encoder_fwd's launch. */
+/* um of pit_decoder_weights / _fwd / _bwd for this plan and largest union (what sizes pw / qw); negative: an argument error */
+int pit_decoder_union_slots(const pit_slab_plan* plan, int max_union);
 int pit_decoder_weights(const pit_slab_plan* plan, const float* head, int head_is_scale, int n_head, int max_union, int max_count,
                         float* pw, float* qw, float* scale_out, const float* w1, float* w1f, int dim, void* stream);
 /* w1 / w1f (both or neither; ABI 18): the decoder MLP's first weight w1 (dim, n_head*dim), copied to w1f in the order the lanes of

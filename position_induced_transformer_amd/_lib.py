@@ -35,7 +35,8 @@ class BlockWeightsJob(ctypes.Structure):
 class SlabPlan(ctypes.Structure):
     """pit_slab_plan of include/pit_hip.h (the static per-slab plan of a masked cross-attention layer on a fixed mesh pair)."""
     _fields_ = [("n_out", _I), ("n_in", _I), ("cap", _I), ("n_slabs", _I), ("umax", _I), ("stats", _P), ("rank_w", _F),
-                ("idx", _P), ("cnt", _P), ("m", _P), ("slot", _P), ("keys", _P), ("nkeys", _P), ("rows", _I)]
+                ("idx", _P), ("cnt", _P), ("m", _P), ("slot", _P), ("keys", _P), ("nkeys", _P), ("rows", _I),
+                ("grid_w", _I), ("grid_h", _I), ("patch_w", _I), ("patch_h", _I)]       # (all 0: consecutive rows)
 
 
 class DecoderWeightsJob(ctypes.Structure):
@@ -86,6 +87,8 @@ SIGNATURES = {
     "pit_block_weights": [_P, _I, _I, _I, _F, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P],
     "pit_block_fwd": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _L, _I, _P],
     "pit_slab_plan_build": [_P, _P, _I, _I, _I, _I, _F, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
+    "pit_decoder_union_slots": [_P, _I],
+    "pit_slab_plan_build_patch": [_P, _P, _I, _I, _I, _I, _F, _P, _P, _I, _I, _I, _I, _I, _P, _F, _P, _P, _P, _P, _P, _P],
     "pit_fold_supported": [_I, _I, _I, _I, _I],
     "pit_fold_weights": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "pit_fold_att_fwd": [_P, _P, _L, _L, _I, _I, _I, _P, _P, _L, _L, _I, _I, _P],

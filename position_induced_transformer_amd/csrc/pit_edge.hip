@@ -74,6 +74,26 @@ __device__ __forceinline__ float pow_abs_p(float x, int p) {
     return p == 1 ? ax : ax * ax;
 }
 
+// ------------------------------------------------------------------------------------------------ slab geometry
+// Which mesh rows a slab holds (pit_hip.h: pit_slab_plan): a patch_w x patch_h patch of a row-major grid_w x grid_h output
+// grid.  Consecutive rows are the same thing on a grid of ONE line: the host side (slab_geometry) turns patch_w == 0 into
+// grid_w = n_out, grid_h = 1, patch_w = rows, patch_h = 1, so the kernels know one mapping and have no branch on the kind of plan.
+// The slab part is wave-uniform scalar arithmetic, the row part a shift, a mask and a multiply-add: no table, no load.
+struct SlabGeo { int i0, j0, sh, gw, gh; };
+__device__ __forceinline__ SlabGeo slab_geo(const pit_slab_plan& p, int slab) {
+    SlabGeo g;
+    g.sh = 31 - __clz(p.patch_w);                       // (patch_w is a power of two)
+    const int ppr = (p.grid_w + p.patch_w - 1) >> g.sh, pi = slab / ppr;
+    g.i0 = pi * p.patch_h; g.j0 = (slab - pi * ppr) << g.sh; g.gw = p.grid_w; g.gh = p.grid_h;
+    return g;
+}
+// mesh row of the slab's row r; ok: the row exists (beyond the grid's edge a patch is partly empty)
+__device__ __forceinline__ int slab_row(const SlabGeo& g, int r, bool& ok) {
+    const int i = g.i0 + (r >> g.sh), j = g.j0 + (r & ((1 << g.sh) - 1));
+    ok = i < g.gh && j < g.gw;
+    return i * g.gw + j;
+}
+
 // ------------------------------------------------------------------------------------------------ static slab plan
 struct SlabBuildArgs {
     const float *mesh_out, *mesh_in;
@@ -81,6 +101,19 @@ struct SlabBuildArgs {
     const int *idx, *cnt; int cap, umax;
     float* m; unsigned short* slot; int* keys; int* nkeys; int* report;      // report[0] = max union, [1] = 1 if a list overflowed, [2] = max count
     int er;                                                                  // rows per slab: 16 (the fused launches), 64 / 128 / 256 (pit_fold.hip)
+    pit_slab_plan geo;                                                       // grid_w / grid_h / patch_w / patch_h only (slab_geometry)
+    // patch plans: the rows' selection statistics (m_(k), m_(k+1): pit_plan_fwd) - a candidate joins the union only if SOME head
+    // scale can keep it.  The lists hold every key up to m_(k+1) (k + 2 keys and their ties), the mask keeps m <= lerp(m_(k),
+    // m_(k+1), w): on Darcy's 4 x 4 patches the lists' unions hold 13.8 keys on average and 21 at most, the keys that can be kept
+    // 12.9 and 19 (16 when counted at head scale 1 only: the other three are near-ties, kept at one c and not at another).
+    // Kept means fl(c m) <= lerp(fl(c m_k), fl(c m_k1), w) in fp32: with every rounding of both sides (the three products, the
+    // difference and the fma of the lerp, the lerp formed here) below 9 x 2^-24 m_(k+1) in all, a candidate beyond
+    // lerp + 2^-20 m_(k+1) is kept for no c for which the three products c m, c m_(k), c m_(k+1) are normal fp32 numbers: head
+    // scales that take them to 0 or to infinity (the mask then keeps every listed key) are outside what a patch plan serves - c =
+    // tan(K (1 + sin lmda)) of a trained model is of order 1 to 1e4 and the squared distances of a mesh in the unit square 1e-6 to 2.
+    // Such a candidate gets slot 65535 (dec_weights_body skips slots beyond the tile).
+    // NULL: every candidate joins (consecutive plans: what they always held).
+    const float* stats; float rank_w;
 };
 
 __global__ __launch_bounds__(256) void slab_plan_kernel(SlabBuildArgs a) {
@@ -92,11 +125,13 @@ __global__ __launch_bounds__(256) void slab_plan_kernel(SlabBuildArgs a) {
     __syncthreads();
     const int er = a.er;
     const int total = er * a.cap;
+    const SlabGeo sg = slab_geo(a.geo, slab);
     for (int e = tid; e < total; e += 256) {
         const int r = e / a.cap, i = e - r * a.cap;
-        const int row = slab * er + r;
+        bool rok;
+        const int row = slab_row(sg, r, rok);
         float mv = 0.0f;
-        if (row < a.n_out) {
+        if (rok) {
             const int c = a.cnt[row];
             if (c > a.cap && i == 0) atomicMax(a.report + 1, 1);
             if (i == 0) atomicMax(a.report + 2, min(c, a.cap));
@@ -106,7 +141,12 @@ __global__ __launch_bounds__(256) void slab_plan_kernel(SlabBuildArgs a) {
                 const float* xi = a.mesh_in + (long)j * a.sdim;
                 mv = sq_dist3(xo[0], a.used > 1 ? xo[1] : 0.0f, a.used > 2 ? xo[2] : 0.0f,
                               xi[0], a.used > 1 ? xi[1] : 0.0f, a.used > 2 ? xi[2] : 0.0f, a.periodic != 0, a.period);
-                atomicOr(&bm[j >> 5], 1u << (j & 31));
+                bool joins = true;
+                if (a.stats) {
+                    const float mk = a.stats[row], mk1 = a.stats[a.n_out + row];
+                    joins = mv <= quantile_lerp(mk, mk1, a.rank_w) + mk1 * 0x1p-20f;
+                }
+                if (joins) atomicOr(&bm[j >> 5], 1u << (j & 31));
             }
         }
         a.m[(long)(slab * er + r) * a.cap + i] = mv;
@@ -134,11 +174,12 @@ __global__ __launch_bounds__(256) void slab_plan_kernel(SlabBuildArgs a) {
     for (int s = nk + tid; s < a.umax; s += 256) a.keys[(long)slab * a.umax + s] = 0;      // padding: a valid key, weight 0
     for (int e = tid; e < total; e += 256) {
         const int r = e / a.cap, i = e - r * a.cap;
-        const int row = slab * er + r;
+        bool rok;
+        const int row = slab_row(sg, r, rok);
         int s = 0;
-        if (row < a.n_out && i < min(a.cnt[row], a.cap)) {
+        if (rok && i < min(a.cnt[row], a.cap)) {
             const int j = a.idx[(long)row * a.cap + i];
-            s = pref[j >> 5] + __popc(bm[j >> 5] & ((1u << (j & 31)) - 1u));
+            s = (bm[j >> 5] >> (j & 31) & 1u) ? pref[j >> 5] + __popc(bm[j >> 5] & ((1u << (j & 31)) - 1u)) : 65535;
         }
         a.slot[(long)(slab * er + r) * a.cap + i] = (unsigned short)min(s, 65535);
     }
@@ -190,14 +231,17 @@ __device__ __forceinline__ void dec_weights_body(const DecWArgs& g, int slab, fl
     }
     __syncthreads();
     const int rpw = 64 / lpr;
+    const SlabGeo sg = slab_geo(p, slab);
     for (int r0 = 0; r0 < ER; r0 += 4 * rpw) {
-        const int row_l = r0 + wave * rpw + lane / lpr, i = lane % lpr, n = slab * ER + row_l;
-        const int craw = ldi_if(p.cnt, n, n < p.n_out);
+        const int row_l = r0 + wave * rpw + lane / lpr, i = lane % lpr;
+        bool rok;
+        const int n = slab_row(sg, row_l, rok);
+        const int craw = ldi_if(p.cnt, n, rok);
         const long off = (long)(slab * ER + row_l) * p.cap + (i < p.cap ? i : 0);
         const float m = p.m[off];
         const int slot = p.slot[off];
         const bool valid = i < min(craw, p.cap);
-        const int nn = n < p.n_out ? n : p.n_out - 1;
+        const int nn = rok ? n : p.n_out - 1;
         const float mk = p.stats[nn], mk1 = p.stats[p.n_out + nn], mmin = p.stats[2 * (long)p.n_out + nn];
         for (int h = 0; h < H; ++h) {
             const float T = quantile_lerp(__fmul_rn(c[h], mk), __fmul_rn(c[h], mk1), p.rank_w);
@@ -255,7 +299,7 @@ struct DecFwdArgs {
     float *x, *z1, *h, *y;
     float* zero_buf; long zero_n;
     const float *tru, *lscale, *lshift; int loss_p; double* lpart;
-    int um;                                   // slots of the union tiles in LDS: 32, 48 or 64 >= the plan's largest union
+    int um;                                   // slots of the union tiles in LDS: 16 (patch plans), 32, 48 or 64 >= the plan's largest union
 };
 
 // The slab's union value rows: thread (r0 = tid / (D/4), q = tid % (D/4)) owns the 16-byte piece q of slots r0, r0 + 16, ... .
@@ -341,7 +385,10 @@ __global__ __launch_bounds__(4 * D) void decoder_fwd_kernel(DecFwdArgs g) {
     int b, slab;
     if (!slab_of_xcd(blockIdx.x, g.batch, p.n_slabs, b, slab)) return;
     const int nk = min(p.nkeys[slab], EU), nkup = (nk + 15) & ~15;
-    const long row0 = (long)b * p.n_out + slab * ER;             // first row of the slab in the (batch * n_out) row space
+    const long rowb = (long)b * p.n_out;                         // the sample's first row in the (batch * n_out) row space
+    const SlabGeo sg = slab_geo(p, slab);
+    bool rv;
+    const int n = slab_row(sg, l15, rv);                         // this lane's row of the slab (loss operands, thin output layer)
     const int c1 = wave * 16 + l15;
     ESTAMP(0, 0);
     // ---- ONE block of loads, nothing consumed inside it: the union keys first (the gather waits for them alone), then the
@@ -363,9 +410,7 @@ __global__ __launch_bounds__(4 * D) void decoder_fwd_kernel(DecFwdArgs g) {
     // the loss's operands of this lane's row, output channel 0 (wave 0 finishes the slab; every wave requests them: no branch)
     float l_t0 = 0.0f, l_sc0 = 1.0f, l_sh0 = 0.0f;
     if (LOSS) {
-        const int n = slab * ER + l15;
-        const bool rv = n < p.n_out;
-        l_t0 = ldg_if(g.tru, (row0 + l15) * g.n2, rv);
+        l_t0 = ldg_if(g.tru, (rowb + n) * g.n2, rv);
         const bool aff = rv && g.lscale != nullptr;              // (no affine map: out-of-range loads, the values are not used)
         l_sc0 = ldg_if(g.lscale, (long)n * g.n2, aff);
         l_sh0 = ldg_if(g.lshift, (long)n * g.n2, aff);
@@ -398,8 +443,10 @@ __global__ __launch_bounds__(4 * D) void decoder_fwd_kernel(DecFwdArgs g) {
 #pragma unroll
         for (int u = 0; u < (ER * K0 / 4 + NT - 1) / NT; ++u) {
             const int e = tid + u * NT, r = e / (K0 / 4), q = e % (K0 / 4);
-            if (e < ER * K0 / 4 && slab * ER + r < p.n_out)
-                *reinterpret_cast<float4*>(g.x + (row0 + r) * K0 + 4 * q) = *reinterpret_cast<const float4*>(xs + r * XP + 4 * q);
+            bool ok;
+            const int nr = slab_row(sg, r, ok);
+            if (e < ER * K0 / 4 && ok)
+                *reinterpret_cast<float4*>(g.x + (rowb + nr) * K0 + 4 * q) = *reinterpret_cast<const float4*>(xs + r * XP + 4 * q);
         }
     }
     // ---- decoder MLP, first layer: Z1 = X W1^T + b1, H = gelu(Z1)
@@ -418,7 +465,9 @@ __global__ __launch_bounds__(4 * D) void decoder_fwd_kernel(DecFwdArgs g) {
             const int r = 4 * kq + i;
             const float z = a0[i] + a1[i] + bias1;
             hs[r * HP + c1] = gelu_erf(z);
-            if (g.z1 && slab * ER + r < p.n_out && !(PIT_EDGE_DBG & 4)) g.z1[(row0 + r) * D + c1] = z;
+            bool ok;
+            const int nr = slab_row(sg, r, ok);
+            if (g.z1 && ok && !(PIT_EDGE_DBG & 4)) g.z1[(rowb + nr) * D + c1] = z;
         }
     }
     ESTAMP(0, 7);
@@ -426,8 +475,10 @@ __global__ __launch_bounds__(4 * D) void decoder_fwd_kernel(DecFwdArgs g) {
     ESTAMP(0, 8);
     if (g.h && !(PIT_EDGE_DBG & (4 | 1024))) {
         const int r = tid / (D / 4), q = tid % (D / 4);             // NT = 16 * D / 4: one 16-byte piece per thread
-        if (slab * ER + r < p.n_out)
-            *reinterpret_cast<float4*>(g.h + (row0 + r) * D + 4 * q) = *reinterpret_cast<const float4*>(hs + r * HP + 4 * q);
+        bool ok;
+        const int nr = slab_row(sg, r, ok);
+        if (ok)
+            *reinterpret_cast<float4*>(g.h + (rowb + nr) * D + 4 * q) = *reinterpret_cast<const float4*>(hs + r * HP + 4 * q);
     }
     if (wave != 0) {
         // the other waves clear this workgroup's share of the buffer the backward adds to (fire and forget, off wave 0's path)
@@ -443,8 +494,6 @@ __global__ __launch_bounds__(4 * D) void decoder_fwd_kernel(DecFwdArgs g) {
         return;
     }
     // ---- thin output layer (out_dim <= 4, pit.py:106): a row dot per output; the slab's share of the loss
-    const int n = slab * ER + l15;
-    const bool rv = n < p.n_out;
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
         if (o >= g.n2) break;
@@ -458,12 +507,12 @@ __global__ __launch_bounds__(4 * D) void decoder_fwd_kernel(DecFwdArgs g) {
         part += __shfl_xor(part, 16, 64);
         part += __shfl_xor(part, 32, 64);
         const float pred = part + w2s[4 * D + o];
-        if (kq == 0 && rv) g.y[(row0 + l15) * g.n2 + o] = pred;
+        if (kq == 0 && rv) g.y[(rowb + n) * g.n2 + o] = pred;
         if (LOSS) {
             double num = 0.0, den = 0.0;
             float t = l_t0, sc = l_sc0, sh = l_sh0;
             if (o > 0) {                                          // (further channels: their operands now - a round trip each)
-                t = ldg_if(g.tru, (row0 + l15) * g.n2 + o, rv);
+                t = ldg_if(g.tru, (rowb + n) * g.n2 + o, rv);
                 sc = ldg_if(g.lscale, (long)n * g.n2 + o, rv && g.lscale != nullptr);
                 sh = ldg_if(g.lshift, (long)n * g.n2 + o, rv && g.lscale != nullptr);
             }
@@ -528,7 +577,8 @@ __global__ __launch_bounds__(4 * D) void decoder_bwd_kernel(DecBwdArgs g) {
     int b, slab;
     if (!slab_of_xcd(blockIdx.x, g.batch, p.n_slabs, b, slab)) return;
     const int nk = min(p.nkeys[slab], EU), nkup = (nk + 15) & ~15;
-    const long row0 = (long)b * p.n_out + slab * ER;
+    const long rowb = (long)b * p.n_out;
+    const SlabGeo sg = slab_geo(p, slab);
     const int c1 = wave * 16 + l15;
 
     ESTAMP(1, 0);
@@ -549,17 +599,17 @@ __global__ __launch_bounds__(4 * D) void decoder_bwd_kernel(DecBwdArgs g) {
     const float w2c0 = g.w2[ec];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-        const int r = (tid + u * NT) / D;
-        const bool ok = slab * ER + r < p.n_out;
-        z1v[u] = ldg_if(g.z1, (row0 + r) * D + ec, ok);
+        bool ok;
+        const int n = slab_row(sg, (tid + u * NT) / D, ok);
+        z1v[u] = ldg_if(g.z1, (rowb + n) * D + ec, ok);
         dyv[u] = 0.0f; prv[u] = 0.0f; trv[u] = 0.0f; lsc[u] = 1.0f; lsh[u] = 0.0f;
         if (!LOSS) {
-            dyv[u] = ldg_if(g.d_y, (row0 + r) * g.ld_dy, ok);
+            dyv[u] = ldg_if(g.d_y, (rowb + n) * g.ld_dy, ok);
         } else {
-            prv[u] = ldg_if(g.pred, (row0 + r) * g.n2, ok);
-            trv[u] = ldg_if(g.tru, (row0 + r) * g.n2, ok);
+            prv[u] = ldg_if(g.pred, (rowb + n) * g.n2, ok);
+            trv[u] = ldg_if(g.tru, (rowb + n) * g.n2, ok);
             const bool aff = ok && g.lscale != nullptr;           // (no affine map: out-of-range loads give 0; scale 1 below)
-            const float a = ldg_if(g.lscale, (long)(slab * ER + r) * g.n2, aff), bq = ldg_if(g.lshift, (long)(slab * ER + r) * g.n2, aff);
+            const float a = ldg_if(g.lscale, (long)n * g.n2, aff), bq = ldg_if(g.lshift, (long)n * g.n2, aff);
             lsc[u] = g.lscale ? a : 1.0f;
             lsh[u] = bq;
         }
@@ -626,12 +676,12 @@ __global__ __launch_bounds__(4 * D) void decoder_bwd_kernel(DecBwdArgs g) {
     float acc[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-        const int r = (tid + u * NT) / D;
-        const bool ok = slab * ER + r < p.n_out;
+        bool ok;
+        const int n = slab_row(sg, (tid + u * NT) / D, ok);
         float v = dyv[u];
         if (LOSS) {
             v = dpred(prv[u], trv[u], lsc[u], lsh[u], nrm0, nrm1);
-            if (ec == 0 && ok) g.d_pred[(row0 + r) * g.n2] = v;
+            if (ec == 0 && ok) g.d_pred[(rowb + n) * g.n2] = v;
         }
         acc[u] = v * w2c0;
     }
@@ -645,18 +695,18 @@ __global__ __launch_bounds__(4 * D) void decoder_bwd_kernel(DecBwdArgs g) {
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const int r = (tid + u * NT) / D;
-            const bool ok = slab * ER + r < p.n_out;
+            bool ok;
+            const int n = slab_row(sg, (tid + u * NT) / D, ok);
             float v;
             if (!LOSS) {
-                v = ldg_if(g.d_y, (row0 + r) * g.ld_dy + o, ok);
+                v = ldg_if(g.d_y, (rowb + n) * g.ld_dy + o, ok);
             } else {
-                const long e = (long)(slab * ER + r) * g.n2 + o;
+                const long e = (long)n * g.n2 + o;
                 const bool aff = ok && g.lscale != nullptr;
                 const float a = ldg_if(g.lscale, e, aff), bq = ldg_if(g.lshift, e, aff);
-                v = dpred(ldg_if(g.pred, (row0 + r) * g.n2 + o, ok), ldg_if(g.tru, (row0 + r) * g.n2 + o, ok),
+                v = dpred(ldg_if(g.pred, (rowb + n) * g.n2 + o, ok), ldg_if(g.tru, (rowb + n) * g.n2 + o, ok),
                           g.lscale ? a : 1.0f, bq, nn, dn);
-                if (ec == o && ok) g.d_pred[(row0 + r) * g.n2 + o] = v;
+                if (ec == o && ok) g.d_pred[(rowb + n) * g.n2 + o] = v;
             }
             acc[u] += v * w2o;
         }
@@ -664,10 +714,11 @@ __global__ __launch_bounds__(4 * D) void decoder_bwd_kernel(DecBwdArgs g) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int r = (tid + u * NT) / D;
-        const bool ok = slab * ER + r < p.n_out;
+        bool ok;
+        const int n = slab_row(sg, r, ok);
         const float v = ok ? acc[u] * ((PIT_EDGE_DBG & 32) ? 1.0f : gelu_erf_grad(z1v[u])) : 0.0f;
         ds1[r * P1 + ec] = v;
-        if (ok && !(PIT_EDGE_DBG & 512)) g.dz1[(row0 + r) * D + ec] = v;
+        if (ok && !(PIT_EDGE_DBG & 512)) g.dz1[(rowb + n) * D + ec] = v;
     }
     ESTAMP(1, 4);
     park_union<D>(ut, nkup, tid, uv);
@@ -1210,18 +1261,39 @@ __global__ __launch_bounds__(256) void union_att_bwd_kernel(UAttArgs g) {
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-bool plan_ok(const pit_slab_plan* p, bool needs_union) {
+// a patch geometry (pit_hip.h: pit_slab_plan) that tiles a row-major gw x gh grid of n_out rows with pw x ph patches of `rows` rows
+bool patch_ok(int n_out, int rows, int gw, int gh, int pw, int ph) {
+    return gw > 0 && gh > 0 && pw > 0 && ph > 0 && (pw & (pw - 1)) == 0 && (long)gw * gh == n_out && pw * ph == rows;
+}
+int patch_slabs(int gw, int gh, int pw, int ph) { return ((gh + ph - 1) / ph) * ((gw + pw - 1) / pw); }
+// `patches`: the launch knows patch plans (the decoder's three); every other launch takes consecutive slabs only
+bool plan_ok(const pit_slab_plan* p, bool needs_union, bool patches = false) {
     if (!p || !p->stats || !p->idx || !p->cnt || !p->m) return false;
     if (p->rows != ER) return false;                 // (plans of taller slabs belong to pit_fold.hip)
-    if (p->n_out <= 0 || p->n_in <= 0 || p->cap <= 0 || p->cap > 64 || p->n_slabs != (p->n_out + ER - 1) / ER) return false;
+    if (p->n_out <= 0 || p->n_in <= 0 || p->cap <= 0 || p->cap > 64) return false;
+    if (p->patch_w != 0) {
+        if (!patches || !patch_ok(p->n_out, ER, p->grid_w, p->grid_h, p->patch_w, p->patch_h) ||
+            p->n_slabs != patch_slabs(p->grid_w, p->grid_h, p->patch_w, p->patch_h)) return false;
+    } else if (p->n_slabs != (p->n_out + ER - 1) / ER) return false;
     if (needs_union && (!p->slot || !p->keys || !p->nkeys || p->umax != EU)) return false;
     return true;
+}
+// The plan as the kernels read it: consecutive slabs of `rows` rows written as rows x 1 patches of a grid of one line (slab_geo)
+pit_slab_plan slab_geometry(const pit_slab_plan& plan, int rows) {
+    pit_slab_plan p = plan;
+    if (p.patch_w == 0) { p.grid_w = p.n_out; p.grid_h = 1; p.patch_w = rows; p.patch_h = 1; }
+    return p;
 }
 bool hid_ok(int n_head, int dim) { return (n_head == 1 || n_head == 2) && (dim == 32 || dim == 64); }
 
 // slots of the union tiles a launch reserves in LDS (what decides how many workgroups a CU holds: Darcy's decoder backward takes
 // 30 KB at 32 slots, 39 KB at 48 - four or more workgroups per CU, all 928 resident at once - and 47 KB at 64: three, a second round)
-int union_slots(int max_union) { return max_union <= 32 ? 32 : (max_union <= 48 ? 48 : 64); }
+// 16 slots: patch plans only, when no patch holds more than 16 keys (22 KB in the backward; every loop over the union's 16-slot
+// groups then runs once).  Darcy's patches hold up to 19 keys: it stays on the 32-slot tile, 31 KB.  Consecutive plans keep the
+// tiles they always had.
+int union_slots(int max_union, bool patches = false) {
+    return (patches && max_union <= 16) ? 16 : (max_union <= 32 ? 32 : (max_union <= 48 ? 48 : 64));
+}
 template <int H, int D>
 size_t dec_fwd_smem(int um) { return (size_t)(H * ER * (um + 4) + um * (D + 4) + ER * (H * D + 4) + ER * (D + 4) + 4 * D + 4) * 4; }
 template <int H, int D>
@@ -1237,12 +1309,13 @@ extern "C" int pit_edge_supported(int n_head, int dim, int batch, int rows_per_s
     return rows >= 256 && rows <= PIT_EDGE_MAX_ROWS;
 }
 
-extern "C" int pit_slab_plan_build(const float* mesh_out, const float* mesh_in, int n_out, int n_in, int space_dim, int metric,
-                                   float period, const int* nbr_idx, const int* nbr_cnt, int cap, int rows_per_slab, float* m,
-                                   unsigned short* slot, int* keys, int* nkeys, int* report, void* stream) {
-    if (!mesh_out || !mesh_in || !nbr_idx || !nbr_cnt || !m || !slot || !keys || !nkeys || !report) return PIT_ERR_NULL;
+namespace {
+// one launch for both kinds of slab: consecutive rows are rows_per_slab x 1 patches of a grid of one line (slab_geo)
+int slab_plan_launch(const float* mesh_out, const float* mesh_in, int n_out, int n_in, int space_dim, int metric, float period,
+                     const int* nbr_idx, const int* nbr_cnt, int cap, int rows_per_slab, int grid_w, int grid_h, int patch_w,
+                     int patch_h, const float* stats, float rank_w, float* m, unsigned short* slot, int* keys, int* nkeys,
+                     int* report, void* stream) {
     if (n_out <= 0 || n_in <= 0 || n_in > 16384 || space_dim < 1 || space_dim > 3 || cap <= 0) return PIT_ERR_SIZE;
-    if (rows_per_slab != 16 && rows_per_slab != 64 && rows_per_slab != 128 && rows_per_slab != 256) return PIT_ERR_SIZE;
     if (metric < PIT_METRIC_EUCLID || metric > PIT_METRIC_PERIODIC2D) return PIT_ERR_METRIC;
     SlabBuildArgs a;
     a.mesh_out = mesh_out; a.mesh_in = mesh_in; a.n_out = n_out; a.n_in = n_in; a.sdim = space_dim;
@@ -1250,9 +1323,32 @@ extern "C" int pit_slab_plan_build(const float* mesh_out, const float* mesh_in, 
     a.periodic = metric != PIT_METRIC_EUCLID; a.period = period;
     a.idx = nbr_idx; a.cnt = nbr_cnt; a.cap = cap; a.umax = EU;
     a.m = m; a.slot = slot; a.keys = keys; a.nkeys = nkeys; a.report = report; a.er = rows_per_slab;
-    hipLaunchKernelGGL(slab_plan_kernel, dim3((unsigned)((n_out + rows_per_slab - 1) / rows_per_slab)), dim3(256), 0, (hipStream_t)stream, a);
+    a.geo = pit_slab_plan();
+    a.geo.grid_w = grid_w; a.geo.grid_h = grid_h; a.geo.patch_w = patch_w; a.geo.patch_h = patch_h;
+    a.stats = stats; a.rank_w = rank_w;
+    hipLaunchKernelGGL(slab_plan_kernel, dim3((unsigned)patch_slabs(grid_w, grid_h, patch_w, patch_h)), dim3(256), 0, (hipStream_t)stream, a);
     PIT_CHECK_LAUNCH();
     return 0;
+}
+}  // namespace
+
+extern "C" int pit_slab_plan_build(const float* mesh_out, const float* mesh_in, int n_out, int n_in, int space_dim, int metric,
+                                   float period, const int* nbr_idx, const int* nbr_cnt, int cap, int rows_per_slab, float* m,
+                                   unsigned short* slot, int* keys, int* nkeys, int* report, void* stream) {
+    if (!mesh_out || !mesh_in || !nbr_idx || !nbr_cnt || !m || !slot || !keys || !nkeys || !report) return PIT_ERR_NULL;
+    if (rows_per_slab != 16 && rows_per_slab != 64 && rows_per_slab != 128 && rows_per_slab != 256) return PIT_ERR_SIZE;
+    return slab_plan_launch(mesh_out, mesh_in, n_out, n_in, space_dim, metric, period, nbr_idx, nbr_cnt, cap, rows_per_slab,
+                            n_out, 1, rows_per_slab, 1, nullptr, 0.0f, m, slot, keys, nkeys, report, stream);
+}
+
+extern "C" int pit_slab_plan_build_patch(const float* mesh_out, const float* mesh_in, int n_out, int n_in, int space_dim, int metric,
+                                         float period, const int* nbr_idx, const int* nbr_cnt, int cap, int grid_w, int grid_h,
+                                         int patch_w, int patch_h, const float* stats, float rank_w, float* m,
+                                         unsigned short* slot, int* keys, int* nkeys, int* report, void* stream) {
+    if (!mesh_out || !mesh_in || !nbr_idx || !nbr_cnt || !stats || !m || !slot || !keys || !nkeys || !report) return PIT_ERR_NULL;
+    if (n_out <= 0 || !patch_ok(n_out, ER, grid_w, grid_h, patch_w, patch_h)) return PIT_ERR_SIZE;
+    return slab_plan_launch(mesh_out, mesh_in, n_out, n_in, space_dim, metric, period, nbr_idx, nbr_cnt, cap, ER,
+                            grid_w, grid_h, patch_w, patch_h, stats, rank_w, m, slot, keys, nkeys, report, stream);
 }
 
 #define PIT_EDGE_DISPATCH(H_, D_, CALL_)                                         \
@@ -1267,18 +1363,24 @@ namespace {
 // pit_decoder_weights' argument checks -> kernel arguments
 int fill_dec_weights(DecWArgs& g, const pit_slab_plan* plan, const float* head, int head_is_scale, int n_head, int max_union,
                      int max_count, float* pw, float* qw, float* scale_out, const float* w1, float* w1f, int dim) {
-    if (!plan_ok(plan, true) || !head || !pw) return PIT_ERR_NULL;
+    if (!plan_ok(plan, true, true) || !head || !pw) return PIT_ERR_NULL;
     if ((w1 == nullptr) != (w1f == nullptr)) return PIT_ERR_NULL;
     if (w1f && (dim < 16 || dim % 16 != 0 || !aligned16(w1) || !aligned16(w1f))) return PIT_ERR_SIZE;
     g.w1 = w1; g.w1f = w1f; g.dim = dim; g.rb = ER;
     if ((n_head != 1 && n_head != 2) || max_union < 1 || max_union > EU || max_count < 1 || max_count > 64) return PIT_ERR_UNSUPPORTED;
     if (!aligned16(pw) || (qw && !aligned16(qw))) return PIT_ERR_SIZE;
-    g.p = *plan; g.head = head; g.head_is_scale = head_is_scale; g.n_head = n_head; g.um = union_slots(max_union);
+    g.p = slab_geometry(*plan, ER); g.head = head; g.head_is_scale = head_is_scale; g.n_head = n_head;
+    g.um = union_slots(max_union, plan->patch_w != 0);
     g.lpr = max_count <= 16 ? 16 : (max_count <= 32 ? 32 : 64);
     g.pw = pw; g.qw = qw; g.scale_out = scale_out;
     return 0;
 }
 }  // namespace
+
+extern "C" int pit_decoder_union_slots(const pit_slab_plan* plan, int max_union) {
+    if (!plan || max_union < 1 || max_union > EU) return PIT_ERR_UNSUPPORTED;
+    return union_slots(max_union, plan->patch_w != 0);
+}
 
 extern "C" int pit_decoder_weights(const pit_slab_plan* plan, const float* head, int head_is_scale, int n_head, int max_union,
                                    int max_count, float* pw, float* qw, float* scale_out, const float* w1, float* w1f, int dim,
@@ -1298,11 +1400,12 @@ extern "C" int pit_fold_weights(const pit_slab_plan* plan, const float* head, in
     if (!plan || !plan->stats || !plan->idx || !plan->cnt || !plan->m || !plan->slot || !plan->keys || !plan->nkeys || !head || !pw)
         return PIT_ERR_NULL;
     if ((plan->rows != 64 && plan->rows != 128 && plan->rows != 256) || plan->umax != EU || plan->cap <= 0 || plan->cap > 64 ||
-        plan->n_slabs != (plan->n_out + plan->rows - 1) / plan->rows) return PIT_ERR_SIZE;
+        plan->n_slabs != (plan->n_out + plan->rows - 1) / plan->rows || plan->patch_w != 0) return PIT_ERR_SIZE;
     if ((n_head != 1 && n_head != 2) || max_union < 1 || max_union > EU || max_count < 1 || max_count > 64) return PIT_ERR_UNSUPPORTED;
     if (!aligned16(pw) || (qw && !aligned16(qw))) return PIT_ERR_SIZE;
     DecWArgs g = DecWArgs();
-    g.p = *plan; g.head = head; g.head_is_scale = head_is_scale; g.n_head = n_head; g.um = union_slots(max_union);
+    g.p = slab_geometry(*plan, ER);                  // (a workgroup forms 16 consecutive rows of the tall slab)
+    g.head = head; g.head_is_scale = head_is_scale; g.n_head = n_head; g.um = union_slots(max_union);
     g.lpr = max_count <= 16 ? 16 : (max_count <= 32 ? 32 : 64);
     g.pw = pw; g.qw = qw; g.scale_out = scale_out; g.rb = plan->rows; g.pw16 = pw16; g.qw16 = qw16;
     hipLaunchKernelGGL(decoder_weights_kernel, dim3((unsigned)(plan->n_slabs * (plan->rows / ER))), dim3(256), 0, (hipStream_t)stream, g);
@@ -1318,18 +1421,18 @@ extern "C" int pit_decoder_fwd(const pit_slab_plan* plan, const float* values, l
                                int max_union, void* stream) {
     if (max_union < 1 || max_union > EU) return PIT_ERR_UNSUPPORTED;
     if (w1f && !aligned16(w1f)) return PIT_ERR_SIZE;
-    if (!plan_ok(plan, true) || !values || !pw || !w1 || !b1 || !w2 || !b2 || !y) return PIT_ERR_NULL;
+    if (!plan_ok(plan, true, true) || !values || !pw || !w1 || !b1 || !w2 || !b2 || !y) return PIT_ERR_NULL;
     if (!hid_ok(n_head, dim) || n2 < 1 || n2 > 4 || batch <= 0) return PIT_ERR_UNSUPPORTED;
     if ((z1 == nullptr) != (h == nullptr)) return PIT_ERR_NULL;
     if (ld_values % 4 || values_bstride % 4 || !aligned16(values) || !aligned16(w1) || !aligned16(pw) || (zero_buf && !aligned16(zero_buf)))
         return PIT_ERR_SIZE;
     if (loss_part && (!loss_true || (loss_p != 1 && loss_p != 2) || (loss_scale == nullptr) != (loss_shift == nullptr))) return PIT_ERR_UNSUPPORTED;
     DecFwdArgs g;
-    g.p = *plan; g.values = values; g.ld_values = ld_values; g.values_bstride = values_bstride; g.batch = batch;
+    g.p = slab_geometry(*plan, ER); g.values = values; g.ld_values = ld_values; g.values_bstride = values_bstride; g.batch = batch;
     g.pw = pw; g.w1 = w1; g.w1f = w1f; g.b1 = b1; g.w2 = w2; g.b2 = b2; g.n2 = n2;
     g.x = x; g.z1 = z1; g.h = h; g.y = y; g.zero_buf = zero_buf; g.zero_n = zero_buf ? zero_n : 0;
     g.tru = loss_true; g.lscale = loss_scale; g.lshift = loss_shift; g.loss_p = loss_p; g.lpart = loss_part;
-    g.um = union_slots(max_union);
+    g.um = union_slots(max_union, plan->patch_w != 0);
     const dim3 grid((unsigned)slab_grid(batch, plan->n_slabs));
     hipStream_t s = (hipStream_t)stream;
 #define PIT_DF(H_, D_)                                                                                                                \
@@ -1351,19 +1454,19 @@ extern "C" int pit_decoder_bwd(const pit_slab_plan* plan, const float* values, l
                                const float* loss_seed, int loss_p, const double* loss_part, float* d_pred, float* loss_out,
                                float* norms_out, int max_union, void* stream) {
     if (max_union < 1 || max_union > EU) return PIT_ERR_UNSUPPORTED;
-    if (!plan_ok(plan, true) || !values || !pw || !qw || !w1 || !w2 || !z1 || !dz1 || !d_values) return PIT_ERR_NULL;
+    if (!plan_ok(plan, true, true) || !values || !pw || !qw || !w1 || !w2 || !z1 || !dz1 || !d_values) return PIT_ERR_NULL;
     if (!hid_ok(n_head, dim) || n2 < 1 || n2 > 4 || batch <= 0) return PIT_ERR_UNSUPPORTED;
     if (!d_y && (!loss_pred || !loss_true || !loss_part || !d_pred || !loss_out || (loss_p != 1 && loss_p != 2) ||
                  (loss_scale == nullptr) != (loss_shift == nullptr))) return PIT_ERR_NULL;
     if (d_y && ld_dy < n2) return PIT_ERR_SIZE;
     if (ld_values % 4 || values_bstride % 4 || !aligned16(values) || !aligned16(pw) || !aligned16(qw)) return PIT_ERR_SIZE;
     DecBwdArgs g;
-    g.p = *plan; g.values = values; g.ld_values = ld_values; g.values_bstride = values_bstride; g.batch = batch;
+    g.p = slab_geometry(*plan, ER); g.values = values; g.ld_values = ld_values; g.values_bstride = values_bstride; g.batch = batch;
     g.pw = pw; g.qw = qw; g.w1 = w1; g.w2 = w2; g.n2 = n2; g.z1 = z1; g.d_y = d_y; g.ld_dy = ld_dy;
     g.dz1 = dz1; g.d_values = d_values; g.dvalues_bstride = dvalues_bstride; g.dscale = dscale;
     g.pred = loss_pred; g.tru = loss_true; g.lscale = loss_scale; g.lshift = loss_shift; g.gseed = loss_seed; g.loss_p = loss_p;
     g.lpart = loss_part; g.d_pred = d_pred; g.loss_out = loss_out; g.norms_out = norms_out;
-    g.um = union_slots(max_union);
+    g.um = union_slots(max_union, plan->patch_w != 0);
     const dim3 grid((unsigned)slab_grid(batch, plan->n_slabs));
     hipStream_t s = (hipStream_t)stream;
 #define PIT_DB(H_, D_)                                                                                                            \

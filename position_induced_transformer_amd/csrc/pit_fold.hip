@@ -510,7 +510,8 @@ size_t fold_smem(int H, bool bf, int um, bool bwd) {
 bool fold_plan_ok(const pit_slab_plan* p) {
     if (!p || !p->stats || !p->idx || !p->cnt || !p->m || !p->slot || !p->keys || !p->nkeys) return false;
     if (p->rows != 64 && p->rows != 128 && p->rows != 256) return false;
-    return p->n_out > 0 && p->n_in > 0 && p->cap > 0 && p->cap <= 64 && p->umax == EU && p->n_slabs == (p->n_out + p->rows - 1) / p->rows;
+    return p->n_out > 0 && p->n_in > 0 && p->cap > 0 && p->cap <= 64 && p->umax == EU && p->patch_w == 0 &&      // (consecutive slabs only)
+           p->n_slabs == (p->n_out + p->rows - 1) / p->rows;
 }
 int union_slots(int max_union) { return max_union <= 32 ? 32 : (max_union <= 48 ? 48 : 64); }
 

@@ -374,6 +374,36 @@ def mesh_period(metric: str, mesh_in: torch.Tensor) -> float:
 
 SLAB_UNION_MAX = 64                                          # PIT_SLAB_UNION_MAX
 FOLD_SLAB_ROWS = (256, 128, 64)                              # slab heights MeshPlan.fold_plan tries, tallest first
+# The fused decoder's slabs as 4 x 4 patches of a row-major output grid instead of 16 consecutive rows (pit_hip.h: pit_slab_plan,
+# patch geometry): the rows of a patch list neighbouring keys, so a slab's key union - what its gather, tile copies and atomic adds scale
+# with - is about half a strip's.  PIT_PATCH_SLABS=0: consecutive slabs everywhere (the A/B switch).
+PATCH_SLABS = os.environ.get("PIT_PATCH_SLABS", "1") != "0"
+PATCH_W = PATCH_H = 4
+
+
+def row_major_grid(mesh: torch.Tensor):
+    """(grid_w, grid_h) when ``mesh`` (n, 2) is EXACTLY a row-major tensor-product grid in the point order of
+    np.meshgrid(xs, ys) flattened (tasks.grid_mesh_2d; coordinate 0 runs fastest): mesh[i*grid_w + j] == (xs[j], ys[i]) bit for bit,
+    xs and ys strictly monotonic, both at least 4 long - index patches are then patches in space.  None for anything else: a
+    column-major (transposed) grid, a perturbed or unstructured mesh, a 1-D mesh.  One small device-to-host copy: call it where a
+    plan is built, never under stream capture."""
+    if not torch.is_tensor(mesh) or mesh.dim() != 2 or mesh.shape[1] != 2 or mesh.shape[0] < 16 or not mesh.dtype.is_floating_point:
+        return None
+    m = mesh.detach().cpu()
+    n = m.shape[0]
+    moved = (m[:, 1] != m[0, 1]).nonzero()
+    if moved.numel() == 0:
+        return None
+    gw = int(moved[0])
+    if gw < 4 or n % gw or n // gw < 4:
+        return None
+    gh = n // gw
+    g = m.view(gh, gw, 2)
+    xs, ys = g[0, :, 0], g[:, 0, 1]
+    if not (bool((g[:, :, 0] == xs[None, :]).all()) and bool((g[:, :, 1] == ys[:, None]).all())):
+        return None
+    mono = lambda v: bool((v[1:] > v[:-1]).all()) or bool((v[1:] < v[:-1]).all())
+    return (gw, gh) if mono(xs) and mono(ys) else None
 PLAN_FLAGS = 0                                               # pit_plan_fwd's `flags` (tests: 1 = PIT_PLAN_WAVE_PER_ROW, 2 = PIT_PLAN_TWO_PASSES)
 UNION_TILES = os.environ.get("PIT_UNION_TILES", "auto")      # "auto" (probe per kind of plan), "0", "1"
 UNION_DV = os.environ.get("PIT_UNION_DV", "auto")            # d(values) of union-tile layers: "auto", "lists" (transposed lists)
@@ -466,7 +496,7 @@ class MeshPlan:
 
     __slots__ = ("mesh_out", "mesh_in", "mesh_batch", "n_out", "n_in", "sdim", "metric", "metric_id", "period",
                  "rank_k", "rank_w", "masked", "self_attn", "stats", "nbr_idx", "nbr_cnt", "nbr_cap", "rev_ptr",
-                 "rev_row", "_complete", "_union", "_slab", "_fold", "len_out", "len_in", "rank_w_dev", "shared", "_rev_sorted")
+                 "rev_row", "_complete", "_union", "_slab", "_patch", "_fold", "len_out", "len_in", "rank_w_dev", "shared", "_rev_sorted")
 
     def __init__(self, metric: str, mesh_out: torch.Tensor, mesh_in: torch.Tensor, locality: float,
                  self_attn: bool, period: Optional[float] = None, len_out=None, len_in=None):
@@ -531,6 +561,7 @@ class MeshPlan:
         self._rev_sorted = None
         self._union = None
         self._slab = None
+        self._patch = None
         self._fold = None
         if ragged_mixed:
             # a shared mesh against ragged clouds: the plan of a ragged batch below, on the strided entries - stride 0 and no
@@ -697,12 +728,26 @@ class MeshPlan:
         self._union = hit
         return hit
 
-    def slab_plan(self):
+    def slab_plan(self, patch: bool = False):
         """Round 5: the static per-slab plan of this (fixed) mesh pair for the fused encoder- / decoder-side launches
         (csrc/pit_edge.hip; include/pit_hip.h: pit_slab_plan) as (struct, largest union of a 16-row slab's candidate keys), or
         None: per-sample meshes, no candidate lists, a list that overflowed its capacity.  Built once per plan - the meshes are
         batch-free and cached - with one host read of two ints; never under stream capture (a plan first seen there keeps the
-        per-layer kernels)."""
+        per-layer kernels).  ``patch`` (the fused decoder only): the plan whose slabs are 4 x 4 patches of the output grid when
+        mesh_out is a row-major grid (row_major_grid), cached next to the consecutive one; the consecutive plan otherwise."""
+        # (a plan first asked for a patch plan under stream capture - building one reads the mesh on the host - runs on its
+        # consecutive plan, if that one is cached, like any plan that has no patch plan)
+        if patch and PATCH_SLABS and self._patch is not False and not (self._patch is None and torch.cuda.is_current_stream_capturing()):
+            if self._patch is None:
+                self._patch = False
+                eligible = not (self.nbr_idx is None or self.mesh_batch != 1 or not self.masked or self.n_in > 16384 or self.nbr_cap > 64)
+                grid = row_major_grid(self.mesh_out) if eligible else None
+                if grid is not None:
+                    built = self._build_slab_plan(16, grid + (PATCH_W, PATCH_H))
+                    if built is not None and built[1] <= SLAB_UNION_MAX:
+                        self._patch = built
+            if self._patch:
+                return self._patch
         if self._slab is not None:
             return self._slab or None
         if self.nbr_idx is None or self.mesh_batch != 1 or not self.masked or self.n_in > 16384 or self.nbr_cap > 64:
@@ -718,27 +763,39 @@ class MeshPlan:
         self._slab = built
         return self._slab
 
-    def _build_slab_plan(self, rows: int):
+    def _build_slab_plan(self, rows: int, geo=None):
         """pit_slab_plan_build for slabs of `rows` rows: (struct, largest union, keep-alive tensors, longest list) or None when a
-        candidate list overflowed its capacity (one host read of three ints)."""
+        candidate list overflowed its capacity (one host read of three ints).  ``geo`` = (grid_w, grid_h, patch_w, patch_h):
+        pit_slab_plan_build_patch, the slabs are patches of the row-major output grid."""
         dev = self.mesh_out.device
-        n_slabs = (self.n_out + rows - 1) // rows
+        if geo is not None:
+            gw, gh, pw, ph = geo
+            n_slabs = -(-gh // ph) * -(-gw // pw)
+        else:
+            n_slabs = (self.n_out + rows - 1) // rows
         m = torch.empty((n_slabs * rows, self.nbr_cap), device=dev, dtype=torch.float32)
         slot = torch.empty((n_slabs * rows, self.nbr_cap), device=dev, dtype=torch.int16)
         keys = torch.empty((n_slabs, SLAB_UNION_MAX), device=dev, dtype=torch.int32)
         nkeys = torch.empty((n_slabs,), device=dev, dtype=torch.int32)
         report = torch.zeros((3,), device=dev, dtype=torch.int32)
-        rc = _lib.lib().pit_slab_plan_build(self.mesh_out.data_ptr(), self.mesh_in.data_ptr(), self.n_out, self.n_in, self.sdim,
-                                            self.metric_id, self.period, self.nbr_idx.data_ptr(), self.nbr_cnt.data_ptr(),
-                                            self.nbr_cap, rows, m.data_ptr(), slot.data_ptr(), keys.data_ptr(), nkeys.data_ptr(),
-                                            report.data_ptr(), _lib.stream_ptr())
+        if geo is not None:
+            rc = _lib.lib().pit_slab_plan_build_patch(self.mesh_out.data_ptr(), self.mesh_in.data_ptr(), self.n_out, self.n_in,
+                                                      self.sdim, self.metric_id, self.period, self.nbr_idx.data_ptr(),
+                                                      self.nbr_cnt.data_ptr(), self.nbr_cap, gw, gh, pw, ph, self.stats.data_ptr(),
+                                                      self.rank_w, m.data_ptr(), slot.data_ptr(), keys.data_ptr(),
+                                                      nkeys.data_ptr(), report.data_ptr(), _lib.stream_ptr())
+        else:
+            rc = _lib.lib().pit_slab_plan_build(self.mesh_out.data_ptr(), self.mesh_in.data_ptr(), self.n_out, self.n_in, self.sdim,
+                                                self.metric_id, self.period, self.nbr_idx.data_ptr(), self.nbr_cnt.data_ptr(),
+                                                self.nbr_cap, rows, m.data_ptr(), slot.data_ptr(), keys.data_ptr(), nkeys.data_ptr(),
+                                                report.data_ptr(), _lib.stream_ptr())
         _lib.check(rc, "pit_slab_plan_build")
         max_union, overflowed, max_count = report.tolist()
         if overflowed:
             return None
         sp = _lib.SlabPlan(self.n_out, self.n_in, self.nbr_cap, n_slabs, SLAB_UNION_MAX, self.stats.data_ptr(), self.rank_w,
                            self.nbr_idx.data_ptr(), self.nbr_cnt.data_ptr(), m.data_ptr(), slot.data_ptr(), keys.data_ptr(),
-                           nkeys.data_ptr(), rows)
+                           nkeys.data_ptr(), rows, *(geo or (0, 0, 0, 0)))
         return (sp, int(max_union), (m, slot, keys, nkeys), max(1, int(max_count)))
 
     def fold_plan(self):
@@ -1035,7 +1092,7 @@ class _PosAtt(torch.autograd.Function):
         # union-tile contraction of csrc/pit_edge.hip (weights once per call, d_out read once in the backward): Vorticity / Cylinder
         ctx.uatt = None
         if UNION_ATT and not ctx.mesh_grad and not ctx.repro and not concat and not coord_dims and out_buf is None and _union_att_ok(plan, n_head, d, b, values):
-            w = _new_decoder_weights(plan, head, scale_in, n_head, head_is_scale, True)      # (Q too: 2 KB per slab)
+            w = _new_decoder_weights(plan, head, scale_in, n_head, head_is_scale, True, patch=False)      # (Q too: 2 KB per slab)
             _launch_decoder_weights(w)
             out = torch.empty((b, plan.n_out, n_head * d), device=values.device, dtype=torch.bfloat16 if out_bf16 else torch.float32)
             sp, max_union = plan.slab_plan()[0], plan.slab_plan()[1]
@@ -2256,7 +2313,7 @@ def edge_fusion_supported(plan: MeshPlan, n_head: int, dim: int, batch: int, nee
         return False
     if not _lib.lib().pit_edge_supported(int(n_head), int(dim), int(batch), int(plan.n_out)):
         return False
-    sp = plan.slab_plan()
+    sp = plan.slab_plan(patch=needs_union)          # (needs_union: the fused decoder, the one consumer of patch plans)
     return sp is not None and (not needs_union or sp[1] <= SLAB_UNION_MAX)
 
 
@@ -2300,7 +2357,7 @@ class DecoderWeights:
     """The up-projection's softmax weights of one step (pit_decoder_weights): P / Q tiles per 16-row slab and the head scales c.
     They depend on (mesh pair, lmda) only: formed once per step - by extra workgroups of the encoder-side launch when pit.encoder
     could request them (early_decoder_weights), else by a launch of their own in front of the decoder launch."""
-    __slots__ = ("key", "pw", "qw", "scale", "job", "keep", "w1f")
+    __slots__ = ("key", "pw", "qw", "scale", "job", "keep", "w1f", "slab", "max_union")
 
 
 def _dec_weights_key(plan: MeshPlan, lmda, scale_in, n_head: int, head_is_scale: bool, w1=None):
@@ -2309,12 +2366,17 @@ def _dec_weights_key(plan: MeshPlan, lmda, scale_in, n_head: int, head_is_scale:
             (w1.data_ptr(), w1._version, tuple(w1.shape)) if w1 is not None else None)
 
 
-def _new_decoder_weights(plan: MeshPlan, lmda, scale_in, n_head: int, head_is_scale: bool, need_q: bool, w1=None) -> DecoderWeights:
-    sp, max_union, _t, max_count = plan.slab_plan()
-    um = 32 if max_union <= 32 else (48 if max_union <= 48 else 64)
+def _new_decoder_weights(plan: MeshPlan, lmda, scale_in, n_head: int, head_is_scale: bool, need_q: bool, w1=None,
+                         patch: bool = True) -> DecoderWeights:
+    """``patch``: on MeshPlan.slab_plan(patch=True) - the fused decoder's plan (tiles of 16 slots when no patch holds more keys);
+    False: on the consecutive plan (pit_union_att_*).  The launches that consume the tiles run on the plan they were formed
+    on (``slab`` / ``max_union`` of the result)."""
+    sp, max_union, _t, max_count = plan.slab_plan(patch)
+    um = _lib.lib().pit_decoder_union_slots(ctypes.byref(sp), max_union)      # (16 | 32 | 48 | 64: the launches' own choice)
     dev = plan.mesh_out.device
     w = DecoderWeights()
     w.key = _dec_weights_key(plan, lmda, scale_in, n_head, head_is_scale, w1)
+    w.slab, w.max_union = sp, max_union
     # the decoder MLP's W1 in MFMA-fragment order (pit_hip.h: w1f): formed with the tiles, once per step
     w1c = w1.detach() if (w1 is not None and w1.is_contiguous() and w1.dtype == torch.float32 and w1.dim() == 2
                           and w1.shape[0] % 16 == 0 and w1.shape[1] == n_head * w1.shape[0] and w1.data_ptr() % 16 == 0) else None
@@ -2359,7 +2421,7 @@ class _Decoder(torch.autograd.Function):
         b, j, d = values.shape
         n2 = w2.shape[0]
         dev = values.device
-        sp = plan.slab_plan()[0]
+        sp = weights.slab                      # (the plan the step's tiles were formed on)
         head = head.detach().reshape(-1).contiguous()
         w1c, b1c, w2c, b2c = (t.detach().contiguous() for t in (w1, b1, w2, b2))
         rows = b * plan.n_out
@@ -2383,7 +2445,7 @@ class _Decoder(torch.autograd.Function):
                                         weights.pw.data_ptr(), w1c.data_ptr(), _lib.ptr(w1f), b1c.data_ptr(), w2c.data_ptr(),
                                         b2c.data_ptr(), n2, _lib.ptr(x), _lib.ptr(z1), _lib.ptr(h), y.data_ptr(),
                                         _lib.ptr(dvals), dvals.numel() if dvals is not None else 0,
-                                        _lib.ptr(lt), _lib.ptr(ls), _lib.ptr(lh), lp, _lib.ptr(lpart), plan.slab_plan()[1],
+                                        _lib.ptr(lt), _lib.ptr(ls), _lib.ptr(lh), lp, _lib.ptr(lpart), weights.max_union,
                                         _lib.stream_ptr())
         _lib.check(rc, "pit_decoder_fwd")
         ctx.plan, ctx.n_head, ctx.head_is_scale, ctx.head_param, ctx.params = plan, n_head, head_is_scale, head_param, params
@@ -2402,7 +2464,7 @@ class _Decoder(torch.autograd.Function):
         b, j, d = values.shape
         n2, rows = w2.shape[0], b * plan.n_out
         dev = values.device
-        sp = plan.slab_plan()[0]
+        sp = weights.slab
         loss = ctx.loss
         inside = loss is not None and loss.token is not None and d_y.data_ptr() == loss.token.data_ptr()
         if loss is not None and loss.token is not None and not inside:
@@ -2436,7 +2498,7 @@ class _Decoder(torch.autograd.Function):
                                _lib.ptr(loss.scale) if inside else None, _lib.ptr(loss.shift) if inside else None,
                                _lib.ptr(loss.seed) if inside else None, loss.p if inside else 0,
                                _lib.ptr(loss.partials) if inside else None, d_pred.data_ptr() if inside else None,
-                               loss.value.data_ptr() if inside else None, None, plan.slab_plan()[1], _lib.stream_ptr())
+                               loss.value.data_ptr() if inside else None, None, weights.max_union, _lib.stream_ptr())
         _lib.check(rc, "pit_decoder_bwd")
         d_head = None
         if need_h:
