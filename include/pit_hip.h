@@ -870,6 +870,70 @@ int pit_distmat_bwd(const float* m, long ld_m, long m_bstride, int n_out, int n_
                     float* d_m, const float* out, long ld_out, long out_bstride, float* a_workspace,
                     int math_mode, void* stream);
 
+/* ---- The same layer on CANDIDATE LISTS of caller-supplied squared distances (additions to ABI 31; csrc/pit_distlist.hip) --------
+ * For problems whose (n_out, n_in) matrix cannot be formed: per row a list of `cap` slots (key, squared distance), O(n_out * cap)
+ * memory, any n_in.  A library built from this header defines PIT_HAS_DISTLIST; PIT_ABI_VERSION is unchanged (nothing that
+ * existed changed).
+ *   idx / sqd  int32 keys and fp32 squared distances of the same layout: (n_out, cap) shared by the whole batch (bstride = 0) or
+ *              one pair of lists per sample, samples bstride elements apart (>= (n_out-1)*ld + cap); rows ld elements apart
+ *              (>= cap).  n_out * cap < 2^31.
+ * A slot whose key lies outside [0, n_in) is PADDING: its sqd is never used (it may hold NaN), its key is never dereferenced and
+ * its d_sqd is 0 - so no key can address out of bounds, without a check that would synchronise.  Preconditions, not checked:
+ * valid sqd finite and >= 0; no key twice in a row (the result is wrong then, every access stays in bounds); for a masked layer
+ * at least rank_k + 2 valid slots per row.  The result is pit.py:48-57 on the dense matrix that holds the listed values and, at
+ * every unlisted pair, a value large enough to be masked and to weigh 0: rank_k / rank_w come from n_in (ops.quantile_rank), the
+ * order statistics from the valid listed values; slot t is kept iff valid and fl(c sqd) <= T (ties all kept); masked = 0: every
+ * valid slot is kept.  A row without a valid slot gives zero output, zero rowstat and zero gradients.
+ * PIT_MATH_FP32 only (PIT_ERR_UNSUPPORTED otherwise); a sample's rows of values, out and d_out must each fit a 32-bit byte offset.
+ * No host synchronisation, no allocation, capturable.  Every sum except d(scale)'s fp64 slots has a fixed order and there are no
+ * other atomics: same input, same bits.  Value, d_out and out rows move in 16-byte pieces where dim, the leading dimensions, the
+ * sample strides, out_col0 and the base addresses are all multiples of 4 floats, in 4-byte pieces otherwise.
+ *
+ * pit_distlist_select_fwd - stats[0..2][row] = {m_(k), m_(k+1) (k+1 clipped to the row's last valid rank), min} over the VALID
+ *   slots of each of the mesh_batch*n_out rows, the layout of pit_select_fwd.  Exact: MSB-first bitwise search on the bit patterns,
+ *   one wave per row with the row in registers; cap <= 2048 (PIT_ERR_UNSUPPORTED beyond).  need_kth = 0: only the minimum (the
+ *   other two rows of stats receive it too).  A row without a valid slot: 0, 0, 0.
+ * pit_distlist_fwd - out, rowstat ((bstride ? batch : 1), n_head, n_out, 4) = {T, S_min, 1/rowsum, mbar} and scale_out as
+ *   pit_distmat_fwd writes them.  One wave per (sample, row), slots in list order.
+ * pit_distlist_bwd - with g_i, gv, a_i = g_i . out_i and s = P (gv - a_i) as in pit_distmat_bwd:
+ *     d_values[j]  = sum over the slots that list j, ascending in (row, slot), of sum_h P g_i (+ d_out[j, 0:dim] with
+ *                    add_residual); a key nobody lists gets zeros (+ the residual).                        NULL = not needed
+ *     d c_h        = -sum s sqd -> d_head through `workspace`, accumulate_head, scale and the finishing step as in pit_distmat_bwd
+ *     d_sqd[i][t]  = -sum_h c_h s, contiguous ((bstride ? batch : 1), n_out, cap), 0 at padding and at slots not kept; for shared
+ *                    lists summed over the samples in ascending order inside the wave that owns the row; needs `out`.  NULL = not needed
+ *   The transposed index (needed with d_values) is the caller's, per list set mb:
+ *     rev_ptr    (mesh_batch, n_in + 1): key j is listed by the entries rev_ptr[mb][j] .. rev_ptr[mb][j+1] - 1 of rev_pos[mb]
+ *     rev_pos    (mesh_batch, n_out * cap): flat positions row * cap + slot, ascending inside every key's range
+ *     chunk_ptr  (mesh_batch, n_in + 1): a key whose range is longer than PIT_DISTLIST_CHUNK entries owns the chunk slots
+ *                chunk_ptr[mb][j] .. chunk_ptr[mb][j+1] - 1, ceil(length / PIT_DISTLIST_CHUNK) of them; any other key owns none
+ *     chunk_key  (mesh_batch, PIT_DISTLIST_CHUNK_SLOTS(n_out, cap)): the key that owns each chunk slot, n_in for a free slot
+ *   Such a key is summed chunk by chunk by separate waves into dv_workspace (pit_distlist_bwd_workspace(batch, n_out, cap, dim)
+ *   bytes, no initial contents) and its partial rows are added in chunk order.  Entries of these tables are clamped to their
+ *   ranges before use. */
+#define PIT_HAS_DISTLIST 1
+#define PIT_DISTLIST_MAX_CAP 2048
+#define PIT_DISTLIST_CHUNK 512
+#define PIT_DISTLIST_CHUNK_SLOTS(n_out, cap) ((long)(n_out) * (long)(cap) / (PIT_DISTLIST_CHUNK / 2) + 1)
+int pit_distlist_select_fwd(const int* idx, const float* sqd, long ld, long bstride, int cap, int mesh_batch, int n_out, int n_in,
+                            int rank_k, int need_kth, float* stats, void* stream);
+int pit_distlist_fwd(const int* idx, const float* sqd, long ld, long bstride, int cap, int n_out, int n_in,
+                     const float* values, int batch, int dim, long ld_values, long values_bstride,
+                     const float* head, int n_head, int head_is_scale,
+                     const float* stats, float rank_w, int masked,
+                     float* out, long ld_out, long out_bstride, int out_col0, int copy_inputs,
+                     float* rowstat, float* scale_out, int math_mode, void* stream);
+long pit_distlist_bwd_workspace(int batch, int n_out, int cap, int dim);
+int pit_distlist_bwd(const int* idx, const float* sqd, long ld, long bstride, int cap, int n_out, int n_in,
+                     const float* values, int batch, int dim, long ld_values, long values_bstride,
+                     const float* head, int n_head, int head_is_scale, const float* scale,
+                     const float* rowstat, int masked,
+                     const float* d_out, long ld_dout, long dout_bstride, int out_col0,
+                     float* d_values, long ld_dvalues, long dvalues_bstride, int add_residual,
+                     float* d_head, int accumulate_head, double* workspace,
+                     float* d_sqd, const float* out, long ld_out, long out_bstride,
+                     const int* rev_ptr, const int* rev_pos, const int* chunk_ptr, const int* chunk_key, float* dv_workspace,
+                     int math_mode, void* stream);
+
 /* Layout probe used by the tests: D = A(32x8) * B(8x32) through the same
  * v_mfma_f32_32x32x2_f32 fragment maps the kernels use. */
 int pit_debug_mfma_tile(const float* a, const float* b, float* d, void* stream);

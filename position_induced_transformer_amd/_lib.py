@@ -186,6 +186,23 @@ SIGNATURES = {
                         _P, _L, _L, _I,
                         _P, _I, _P,
                         _P, _P, _L, _L, _P, _I, _P],
+    "pit_distlist_select_fwd": [_P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _P, _P],
+    "pit_distlist_fwd": [_P, _P, _L, _L, _I, _I, _I,
+                         _P, _I, _I, _L, _L,
+                         _P, _I, _I,
+                         _P, _F, _I,
+                         _P, _L, _L, _I, _I,
+                         _P, _P, _I, _P],
+    "pit_distlist_bwd_workspace": [_I, _I, _I, _I],
+    "pit_distlist_bwd": [_P, _P, _L, _L, _I, _I, _I,
+                         _P, _I, _I, _L, _L,
+                         _P, _I, _I, _P,
+                         _P, _I,
+                         _P, _L, _L, _I,
+                         _P, _L, _L, _I,
+                         _P, _I, _P,
+                         _P, _P, _L, _L,
+                         _P, _P, _P, _P, _P, _I, _P],
     "pit_rel_max_norm": [_P, _P, _I, _I, _I, _P, _P, _P],
     "pit_instance_norm_fwd": [_P, _L, _L, _I, _I, _I, _F, _P, _P, _P],
     "pit_instance_norm_bwd": [_P, _P, _P, _I, _I, _I, _P, _P],
@@ -196,7 +213,16 @@ SIGNATURES = {
 }
 
 LONG_RETURN = {"pit_satt_tiles_elems", "pit_posatt_dmesh_workspace", "pit_mlp_bwd_params_ordered_workspace",
-               "pit_mlp_bwd_params_ordered_mfma_workspace", "pit_distmat_bwd_workspace"}
+               "pit_mlp_bwd_params_ordered_mfma_workspace", "pit_distmat_bwd_workspace", "pit_distlist_bwd_workspace"}
+# entries added to an ABI version after its first release (PIT_HAS_* in the header): a library of the same version built before
+# them lacks the symbols
+ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_workspace", "pit_distlist_bwd"}
+DISTLIST_CHUNK = 512   # PIT_DISTLIST_CHUNK
+
+
+def distlist_chunk_slots(n_out: int, cap: int) -> int:
+    """PIT_DISTLIST_CHUNK_SLOTS of include/pit_hip.h."""
+    return int(n_out) * int(cap) // (DISTLIST_CHUNK // 2) + 1
 ABI_VERSION = 31       # PIT_ABI_VERSION of include/pit_hip.h this binding was written against
 
 _lib = None
@@ -211,7 +237,13 @@ def lib() -> ctypes.CDLL:
                 "(hipcc --offload-arch=gfx950). There is no CPU or PyTorch fallback for the PiT hot path.")
         handle = ctypes.CDLL(LIB_PATH)
         for name, argtypes in SIGNATURES.items():
-            fn = getattr(handle, name)       # AttributeError if the ABI lost a symbol
+            try:
+                fn = getattr(handle, name)   # AttributeError if the ABI lost a symbol
+            except AttributeError:
+                if name not in ADDED_LATER:
+                    raise
+                raise RuntimeError(f"{LIB_PATH} was built before {name} joined PIT_ABI_VERSION {ABI_VERSION}: "
+                                   "rebuild it (python -m position_induced_transformer_amd.build)") from None
             fn.argtypes = argtypes
             fn.restype = ctypes.c_char_p if name == "pit_error_string" else (_L if name in LONG_RETURN else _I)
         got = handle.pit_version()           # the default library and a PIT_LIB_PATH override alike

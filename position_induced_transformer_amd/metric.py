@@ -16,11 +16,22 @@ d loss / d m, so autograd differentiates through the metric, tie rules included:
 Precomputed matrices (geodesic distances on a surface or a graph) go to ``forward_dist(m_dist, inputs)``.  The entries of a
 matrix must be finite and >= 0; that is not checked (a check would synchronise).  fp32 math mode only; no ragged batches.
 
+Where the (N, J) matrix cannot be formed - a decoder of 11 271 x 728 points per sample, geodesics on 50 000 vertices - the layers
+run on CANDIDATE LISTS instead: ``forward_list(idx, sqd, inputs)`` takes, per row, K slots (key, squared distance), (N, K) shared
+by the batch or (b, N, K); a slot whose key is outside [0, J) is padding.  Memory is O(N K), J is unlimited, the kept set is the
+dense layer's whenever the lists hold every key the dense layer keeps (``list_capacity(q, J)`` = k + 2 slots at least, more where
+ties are expected), and the layer returns d loss / d sqd in the shape of ``sqd``.  ``knn_lists(sqdist, mesh_out, mesh_in, k)``
+builds such lists from meshes under any metric with chunk x J peak memory and recomputes the listed distances differentiably,
+so a mesh may require grad; ``pit_metric(..., neighbors="auto")`` runs its down and up layers that way.
+
+    lists = knn_lists(sq, mesh_out, mesh_in, k=None, locality=0.02)     # NeighborLists(idx, sqd, cut_rows)
+    out = layer.forward_list(lists.idx, lists.sqd, inputs)
+
 Not part of ``pit.py``, whose star-exports are the reference's.
 """
 from __future__ import annotations
 
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import torch
 import torch.nn as nn
@@ -28,7 +39,8 @@ import torch.nn as nn
 from . import ops
 from . import pit as _pit
 
-__all__ = ["sqdist_euclid", "sqdist_periodic_box", "posatt_metric", "posatt_cross_metric", "pit_metric"]
+__all__ = ["sqdist_euclid", "sqdist_periodic_box", "posatt_metric", "posatt_cross_metric", "pit_metric", "list_capacity",
+           "NeighborLists", "knn_lists"]
 
 
 def sqdist_euclid(mesh_out: torch.Tensor, mesh_in: torch.Tensor) -> torch.Tensor:
@@ -61,6 +73,69 @@ def sqdist_periodic_box(periods):
     return sqdist
 
 
+def list_capacity(locality: float, n_in: int) -> int:
+    """Least list width ``forward_list`` accepts for a layer of ``locality`` over ``n_in`` keys: k + 2 with (k, w) =
+    ops.quantile_rank(locality, n_in); 1 for locality 1.0 (no selection)."""
+    return ops.list_capacity(locality, n_in)
+
+
+def default_neighbors(locality: float, n_in: int) -> int:
+    """List width ``knn_lists`` takes when none is given: list_capacity plus room for ties, in multiples of 16 (the rule of
+    ops.ragged_list_capacity), at most ``n_in``."""
+    want = list_capacity(locality, n_in)
+    return min(int(n_in), ((want + max(16, want // 4) + 15) // 16) * 16)
+
+
+NeighborLists = namedtuple("NeighborLists", ["idx", "sqd", "cut_rows"])
+
+
+def knn_lists(sqdist, mesh_out, mesh_in, k=None, chunk: int = 4096, locality: float = 1.0) -> NeighborLists:
+    """The ``k`` nearest keys of every row under ``sqdist``: ``idx`` (int64) and ``sqd`` of shape (N, k), or (b, N, k) when a
+    mesh is batched.  The keys come from dense distances of ``chunk`` rows at a time under no_grad (peak memory chunk x J) and
+    ``torch.topk``; ``sqd`` is then recomputed for the chosen pairs only, by calling ``sqdist`` with the rows as its batch axis -
+    sqdist((R, 1, s), (R, k, s)) -> (R, 1, k) - so autograd holds O(N k) and a mesh may require grad.  ``k`` None: list_capacity
+    of ``locality`` plus room for ties (default_neighbors).  ``cut_rows``: a 0-d tensor on the meshes' device, computed without
+    a synchronisation: the number of rows whose list may hold other keys than the dense layer of ``locality`` keeps - rows
+    whose (k+1)-th nearest value is <= their m_(rank+1), i.e. a tie shell at the threshold reaches beyond the list; without a
+    mask (locality 1.0) every row, unless the lists hold all J keys."""
+    n_in = int(mesh_in.shape[-2])
+    if k is None:
+        k = default_neighbors(locality, n_in)
+    k = int(k)
+    need = list_capacity(locality, n_in)
+    if not (need <= k <= n_in):
+        raise ValueError(f"k = {k}: a layer of locality {locality} over {n_in} keys needs between {need} and {n_in} neighbours")
+    batched = mesh_out.dim() == 3 or mesh_in.dim() == 3
+    n_out = int(mesh_out.shape[-2])
+    rank = ops.quantile_rank(float(locality), n_in)[0]
+    with torch.no_grad():
+        mo, mi = mesh_out.detach(), mesh_in.detach()
+        parts, cut = [], None
+        for r0 in range(0, n_out, int(chunk)):
+            m = sqdist(mo[..., r0:r0 + int(chunk), :], mi)
+            vals, ind = torch.topk(m, min(k + 1, n_in), dim=-1, largest=False, sorted=True)
+            parts.append(ind[..., :k])
+            if k < n_in:
+                hit = (vals[..., k] <= vals[..., rank + 1]) if float(locality) < 1.0 else torch.ones_like(vals[..., k], dtype=torch.bool)
+                cut = hit.sum() if cut is None else cut + hit.sum()
+        idx = torch.cat(parts, dim=-2)
+        if cut is None:
+            cut = torch.zeros((), dtype=torch.int64, device=idx.device)
+    s = mesh_out.shape[-1]
+    if batched:
+        b = idx.shape[0]
+        rows = (mesh_out if mesh_out.dim() == 3 else mesh_out.unsqueeze(0).expand(b, -1, -1)).reshape(b * n_out, 1, s)
+        if mesh_in.dim() == 3:
+            keys = mesh_in[torch.arange(b, device=idx.device).view(b, 1, 1), idx]
+        else:
+            keys = mesh_in[idx]
+        keys = keys.reshape(b * n_out, k, s)
+    else:
+        rows, keys = mesh_out.unsqueeze(1), mesh_in[idx]
+    sqd = sqdist(rows, keys).reshape(idx.shape)
+    return NeighborLists(idx, sqd, cut)
+
+
 class posatt_metric(nn.Module):
     """Self attention under ``sqdist``: ``forward(mesh, inputs)`` returns ``cat((inputs, conv), -1)`` as posatt.forward does
     (pit.py:37-44).  A plain module with an ``lmda`` parameter initialised as posatt's is (pit.py:35)."""
@@ -68,8 +143,12 @@ class posatt_metric(nn.Module):
     _PLAN_CACHE = 8
     _self_attn = True
 
-    def __init__(self, n_head, in_dim, locality, sqdist=sqdist_euclid):
+    def __init__(self, n_head, in_dim, locality, sqdist=sqdist_euclid, neighbors=None):
         super().__init__()
+        if not (neighbors is None or neighbors == "auto" or (isinstance(neighbors, int) and neighbors > 0)):
+            raise ValueError(f"neighbors must be None, 'auto' or a positive int, got {neighbors!r}")
+        self.neighbors = neighbors            # None: dense distances; otherwise forward() builds kNN lists of that width
+        self.last_lists = None                # the NeighborLists of the latest forward() on lists (cut_rows is read from here)
         self.locality = locality
         self.n_head = n_head
         self.in_dim = in_dim
@@ -108,9 +187,47 @@ class posatt_metric(nn.Module):
         plan = self._plan(m_dist)
         return ops.posatt_dist_apply(inputs, self.lmda, plan, self.n_head, concat=self._self_attn, m_dist=m_dist)
 
+    def _list_plan(self, idx, sqd, n_in: int) -> ops.ListPlan:
+        """Shared (N, K) lists keep their plan like a shared matrix does: keyed on both addresses, shapes, versions and locality."""
+        if idx.dim() != 2:
+            return ops.ListPlan(idx, sqd, n_in, self.locality)
+        key = ("list", idx.data_ptr(), sqd.data_ptr(), tuple(idx.shape), tuple(idx.stride()), tuple(sqd.stride()), idx._version,
+               sqd._version, int(n_in), float(self.locality), sqd.device.index)
+        plan = self._plans.get(key)
+        if plan is None:
+            plan = ops.ListPlan(idx, sqd, n_in, self.locality)
+            while len(self._plans) >= self._PLAN_CACHE:
+                self._plans.popitem(last=False)
+            self._plans[key] = plan
+        else:
+            self._plans.move_to_end(key)
+        if ops._capturing():
+            ops._pin(plan)
+        return plan
+
+    def forward_list(self, idx, sqd, inputs, lengths=None):
+        """The layer on candidate lists: ``idx`` (int32 / int64) and ``sqd`` (fp32), (N, K) or (b, N, K); slot (i, t) says that
+        key idx[i, t] lies at squared distance sqd[i, t] from row i; a key outside [0, J) marks padding.  K >= list_capacity(
+        locality, J).  The self form (this class) needs N == J and prepends the inputs."""
+        self._refuse_lengths(lengths)
+        ops._check_dist_mode()
+        ops.check_list_shapes(idx, sqd, inputs, self._self_attn)
+        plan = self._list_plan(idx, sqd, inputs.shape[1])
+        return ops.posatt_list_apply(inputs, self.lmda, plan, self.n_head, concat=self._self_attn, sqd=sqd)
+
+    def _on_lists(self, mesh_out, mesh_in, inputs):
+        # lists formed for this call (pit_metric(..., neighbors=...)): their plan is built for this call too
+        lists = knn_lists(self.sqdist, mesh_out, mesh_in, None if self.neighbors == "auto" else self.neighbors, locality=self.locality)
+        self.last_lists = lists
+        ops.check_list_shapes(lists.idx, lists.sqd, inputs, self._self_attn)
+        plan = ops.ListPlan(lists.idx, lists.sqd, inputs.shape[1], self.locality)
+        return ops.posatt_list_apply(inputs, self.lmda, plan, self.n_head, concat=self._self_attn, sqd=lists.sqd)
+
     def forward(self, mesh, inputs, lengths=None):
         self._refuse_lengths(lengths)
         ops._check_dist_mode()
+        if self.neighbors is not None:
+            return self._on_lists(mesh, mesh, inputs)
         return self._on_fresh(self.sqdist(mesh, mesh), inputs)
 
     def _on_fresh(self, m_dist, inputs):
@@ -139,6 +256,8 @@ class posatt_cross_metric(posatt_metric):
     def forward(self, mesh_out, mesh_in, inputs, out_bf16: bool = False, len_out=None, len_in=None):
         self._refuse_lengths(len_out if len_out is not None else len_in)
         ops._check_dist_mode()
+        if self.neighbors is not None:
+            return self._on_lists(mesh_out, mesh_in, inputs)
         return self._on_fresh(self.sqdist(mesh_out, mesh_in), inputs)
 
 
@@ -146,14 +265,16 @@ class pit_metric(_pit.pit):
     """``pit.pit`` whose down / conv[i] / up are the metric layers above.  ``pit.encoder / processor / decoder`` call replaced
     modules as they are; none of the fused launches takes these layers.  ``forward(mesh_in, func_in, mesh_out)`` is the
     fixed-mesh task forward: the coordinates of ``mesh_in`` are prepended to ``func_in`` (train_darcy.py:51-55).
-    ``learn_latent``: the latent mesh becomes a parameter."""
+    ``learn_latent``: the latent mesh becomes a parameter.  ``neighbors``: an int, or "auto" for default_neighbors - down and up
+    then build kNN lists under ``sqdist`` (knn_lists) and run on them (forward_list), O(N k) instead of O(N J); conv stays dense
+    on the latent mesh.  None: dense distances everywhere."""
 
     def __init__(self, space_dim, in_dim, out_dim, hid_dim, n_head, n_blocks, mesh_ltt, en_loc, de_loc, sqdist=sqdist_euclid,
-                 learn_latent: bool = False):
+                 learn_latent: bool = False, neighbors=None):
         super().__init__(space_dim, in_dim, out_dim, hid_dim, n_head, n_blocks, mesh_ltt, en_loc, de_loc)
-        self.down = posatt_cross_metric(self.n_head, self.in_dim, self.en_local, sqdist)
+        self.down = posatt_cross_metric(self.n_head, self.in_dim, self.en_local, sqdist, neighbors)
         self.conv = nn.ModuleList([posatt_metric(self.n_head, self.hid_dim, 1.0, sqdist) for _ in range(self.n_blocks)])
-        self.up = posatt_cross_metric(self.n_head, self.hid_dim, self.de_local, sqdist)
+        self.up = posatt_cross_metric(self.n_head, self.hid_dim, self.de_local, sqdist, neighbors)
         if learn_latent:
             self.mesh_ltt = nn.Parameter(self.mesh_ltt.detach().clone())
 

@@ -1641,6 +1641,215 @@ def posatt_dist_apply(values: torch.Tensor, lmda: torch.Tensor, plan: DistPlan, 
     return _PosAttDist.apply(values, lmda.reshape(-1), plan, n_head, concat, head_is_scale, c, *extra)
 
 
+# ---- the same layer on candidate lists of caller-supplied squared distances (csrc/pit_distlist.hip; metric.py) -------------------
+LIST_MAX_CAP = 2048         # PIT_DISTLIST_MAX_CAP: slots of a row the selection holds in registers
+
+
+def list_capacity(locality: float, n_in: int) -> int:
+    """Least width of the candidate lists of a layer of ``locality`` over ``n_in`` keys: k + 2 slots (the selection needs
+    m_(k) and m_(k+1) and the row's tie at m_(k+1)), 1 without a mask."""
+    if float(locality) >= 1.0:
+        return 1
+    return quantile_rank(float(locality), int(n_in))[0] + 2
+
+
+def check_list_shapes(idx, sqd, values, concat: bool) -> None:
+    """Shape and dtype refusals of a layer on candidate lists, raised before the device check and before anything is launched."""
+    if not torch.is_tensor(idx) or not torch.is_tensor(sqd) or idx.dim() not in (2, 3):
+        raise ValueError("idx and sqd must be (N, K) or (b, N, K) tensors: the keys and squared distances of each row's candidates")
+    if tuple(idx.shape) != tuple(sqd.shape):
+        raise ValueError(f"idx and sqd must have the same shape, got {tuple(idx.shape)} and {tuple(sqd.shape)}")
+    if idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"idx must be int32 or int64, got {idx.dtype}")
+    if sqd.dtype != torch.float32:
+        raise ValueError(f"sqd must be fp32, got {sqd.dtype}")
+    if 0 in idx.shape:
+        raise ValueError(f"the lists have an empty axis: {tuple(idx.shape)}")
+    if values is None:
+        return
+    if not torch.is_tensor(values) or values.dim() != 3:
+        raise ValueError("inputs must be a (batch, J, channels) tensor")
+    if idx.dim() == 3 and idx.shape[0] != values.shape[0]:
+        raise ValueError(f"the lists hold {idx.shape[0]} samples, the inputs {values.shape[0]}")
+    if concat and idx.shape[-2] != values.shape[1]:
+        raise ValueError(f"the self-attention form needs one list per input point (N == J): {idx.shape[-2]} lists, {values.shape[1]} points")
+
+
+class ListPlan:
+    """Candidate lists ``(idx, sqd)`` - (N, K), shared by the whole batch, or (b, N, K) - of a layer of ``locality`` over
+    ``n_in`` keys: an int32 copy of the keys, a detached view of the distances, the selection statistics over the valid slots
+    (pit_distlist_select_fwd; the rank comes from ``n_in``, not from K) and - built when a backward first asks for it - the
+    transposed index that d(values) runs over.  A slot whose key is outside [0, n_in) is padding.  Preconditions, not checked
+    (a check would synchronise): valid distances finite and >= 0, no key twice in a row, at least k + 2 valid slots per row of a
+    masked layer."""
+
+    def __init__(self, idx: torch.Tensor, sqd: torch.Tensor, n_in: int, locality: float):
+        _check_dist_mode()
+        check_list_shapes(idx, sqd, None, False)
+        if not (0.0 <= float(locality) <= 1.0):
+            raise ValueError(f"locality must lie in [0, 1], got {locality}")
+        n_in = int(n_in)
+        if n_in <= 0:
+            raise ValueError(f"n_in must be positive, got {n_in}")
+        n, cap = int(idx.shape[-2]), int(idx.shape[-1])
+        need = list_capacity(locality, n_in)
+        if cap < need:
+            raise ValueError(f"lists of {cap} slots are too narrow for locality {locality} over {n_in} keys: "
+                             f"list_capacity gives {need} (k + 2)")
+        if cap > LIST_MAX_CAP:
+            raise ValueError(f"lists of {cap} slots: at most {LIST_MAX_CAP} are supported")
+        if n * cap >= 2 ** 31:
+            raise ValueError(f"N * K = {n * cap} does not fit 31 bits")
+        _need_gpu(sqd)
+        if idx.device != sqd.device:
+            raise RuntimeError(f"idx lives on {idx.device}, sqd on {sqd.device}")
+        self.source_idx, self.source = idx, sqd.detach()    # (keep the caller's storages - and with them their addresses - alive)
+        i3 = idx.detach() if idx.dim() == 3 else idx.detach().unsqueeze(0)
+        if i3.dtype != torch.int32:
+            i3 = i3.clamp(-1, n_in).to(torch.int32)         # (every out-of-range key is padding: -1 and n_in stand for them all)
+        self.idx = i3.contiguous()
+        s3 = self.source if sqd.dim() == 3 else self.source.unsqueeze(0)
+        self.sqd = s3.contiguous()
+        self.mesh_batch, self.n_out, self.cap, self.n_in = int(i3.shape[0]), n, cap, n_in
+        self.ld = cap
+        self.bstride = n * cap if self.mesh_batch > 1 else 0
+        self.locality = float(locality)
+        self.masked = self.locality < 1.0
+        self.rank_k, self.rank_w = quantile_rank(self.locality, n_in)
+        self.stats = torch.empty((3, self.mesh_batch * n), device=sqd.device, dtype=torch.float32)
+        self._rev = None
+        self.refresh()
+
+    def refresh(self) -> None:
+        """Run the selection on what ``sqd`` holds NOW: for a caller that overwrites the distances in place (the keys unchanged) -
+        one launch, no allocation, so it can be part of a captured step.  Without a mask only the row minima are computed."""
+        src = self.source if self.source.dim() == 3 else self.source.unsqueeze(0)
+        if self.sqd.data_ptr() != src.data_ptr():
+            self.sqd.copy_(src)                             # (the caller's tensor was not contiguous: the plan works on a copy)
+        rc = _lib.lib().pit_distlist_select_fwd(self.idx.data_ptr(), self.sqd.data_ptr(), self.ld, self.bstride, self.cap, self.mesh_batch,
+                                                self.n_out, self.n_in, self.rank_k if self.masked else 0, 1 if self.masked else 0,
+                                                self.stats.data_ptr(), _lib.stream_ptr())
+        _lib.check(rc, "pit_distlist_select_fwd")
+        if _capturing():
+            _pin(self)
+
+    def transposed(self):
+        """(rev_ptr, rev_pos, chunk_ptr, chunk_key) of pit_distlist_bwd, by torch integer ops that do not synchronise: a stable
+        sort of the flattened keys (padding clamped to n_in, so it sorts behind every key) gives, per key, its listing slots
+        row * K + slot in ascending order; searchsorted gives the range starts.  Any n_in."""
+        if self._rev is None:
+            mb, j, dev = self.mesh_batch, self.n_in, self.idx.device
+            flat = self.idx.reshape(mb, -1)
+            keys = torch.where((flat >= 0) & (flat < j), flat, torch.full_like(flat, j))
+            skeys, order = torch.sort(keys, dim=1, stable=True)
+            probe = torch.arange(j + 1, device=dev, dtype=torch.int32).unsqueeze(0).expand(mb, -1).contiguous()
+            rev_ptr = torch.searchsorted(skeys, probe, right=False).to(torch.int32)
+            cnt = rev_ptr[:, 1:] - rev_ptr[:, :-1]
+            chunk = _lib.DISTLIST_CHUNK
+            nch = torch.where(cnt > chunk, (cnt + (chunk - 1)) // chunk, torch.zeros_like(cnt))
+            ends = torch.cumsum(nch, dim=1)
+            chunk_ptr = torch.cat((torch.zeros((mb, 1), device=dev, dtype=ends.dtype), ends), dim=1).to(torch.int32).contiguous()
+            slots = _lib.distlist_chunk_slots(self.n_out, self.cap)
+            probe = torch.arange(slots, device=dev, dtype=ends.dtype).unsqueeze(0).expand(mb, -1).contiguous()
+            chunk_key = torch.searchsorted(ends.contiguous(), probe, right=True).to(torch.int32)
+            self._rev = (rev_ptr.contiguous(), order.to(torch.int32).contiguous(), chunk_ptr, chunk_key.contiguous())
+        return self._rev
+
+
+class _PosAttList(torch.autograd.Function):
+    """pit.py:48-57 (+ the concat of :44) on a ListPlan: pit_distlist_fwd / _bwd, one autograd node.  ``sqd`` arrives only when
+    it requires grad and then receives d loss / d sqd in its own shape (0 at padding)."""
+
+    @staticmethod
+    def forward(ctx, values, head, plan: ListPlan, n_head: int, concat: bool, head_is_scale: bool, scale_in=None, sqd=None):
+        _need_gpu(values, head)
+        values = _row_view(values)
+        b, j, d = values.shape
+        if j != plan.n_in:
+            raise RuntimeError(f"inputs have {j} points but the lists were planned for {plan.n_in} keys")
+        if plan.mesh_batch not in (1, b):
+            raise RuntimeError("list batch and input batch differ")
+        if concat and plan.n_out != plan.n_in:
+            raise RuntimeError("the self-attention form needs one list per input point")
+        head = head.detach().reshape(-1).contiguous()
+        if head.numel() != n_head:
+            raise RuntimeError("lmda must hold one value per head")
+        width = (n_head + (1 if concat else 0)) * d
+        out = torch.empty((b, plan.n_out, width), device=values.device, dtype=torch.float32)
+        rowstat = torch.empty((plan.mesh_batch, n_head, plan.n_out, 4), device=values.device, dtype=torch.float32)
+        scale = torch.empty((n_head,), device=values.device, dtype=torch.float32)
+        k_head, k_is_scale = (scale_in, True) if scale_in is not None else (head, head_is_scale)
+        rc = _lib.lib().pit_distlist_fwd(
+            plan.idx.data_ptr(), plan.sqd.data_ptr(), plan.ld, plan.bstride, plan.cap, plan.n_out, plan.n_in,
+            values.data_ptr(), b, d, values.stride(1), values.stride(0),
+            k_head.data_ptr(), n_head, 1 if k_is_scale else 0,
+            plan.stats.data_ptr(), plan.rank_w, 1 if plan.masked else 0,
+            out.data_ptr(), out.stride(1), out.stride(0), d if concat else 0, 1 if concat else 0,
+            rowstat.data_ptr(), scale.data_ptr(), MATH_MODES["fp32"], _lib.stream_ptr())
+        _lib.check(rc, "pit_distlist_fwd")
+        ctx.plan, ctx.n_head, ctx.concat, ctx.head_is_scale = plan, n_head, concat, head_is_scale
+        ctx.sqd_shape = tuple(sqd.shape) if sqd is not None else None
+        # (d(sqd) needs a_i = g_i . out_i: the result itself is kept then)
+        ctx.save_for_backward(values, head, rowstat, scale, *((out,) if sqd is not None else ()))
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        values, head, rowstat, scale = ctx.saved_tensors[:4]
+        out = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
+        plan, n_head = ctx.plan, ctx.n_head
+        b, j, d = values.shape
+        if d_out.dtype != torch.float32:
+            d_out = d_out.float()
+        d_out = _row_view(d_out)
+        _need_gpu(d_out)
+        need_v, need_h = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_s = ctx.sqd_shape is not None and ctx.needs_input_grad[7]
+        dev = values.device
+        d_values = torch.empty((b, j, d), device=dev, dtype=torch.float32) if need_v else None
+        d_head = torch.empty((n_head,), device=dev, dtype=torch.float32) if need_h else None
+        work = _dscale_workspace(dev, n_head) if need_h else None
+        d_sqd = torch.empty((plan.mesh_batch, plan.n_out, plan.cap), device=dev, dtype=torch.float32) if need_s else None
+        L = _lib.lib()
+        rev = plan.transposed() if need_v else (None, None, None, None)
+        dv_ws = torch.empty(((L.pit_distlist_bwd_workspace(b, plan.n_out, plan.cap, d) + 3) // 4,), device=dev, dtype=torch.float32) if need_v else None
+        if need_v or need_h or need_s:
+            rc = L.pit_distlist_bwd(
+                plan.idx.data_ptr(), plan.sqd.data_ptr(), plan.ld, plan.bstride, plan.cap, plan.n_out, plan.n_in,
+                values.data_ptr(), b, d, values.stride(1), values.stride(0),
+                head.data_ptr(), n_head, 1 if ctx.head_is_scale else 0, scale.data_ptr(),
+                rowstat.data_ptr(), 1 if plan.masked else 0,
+                d_out.data_ptr(), d_out.stride(1), d_out.stride(0), d if ctx.concat else 0,
+                _lib.ptr(d_values), d, j * d, 1 if ctx.concat else 0,
+                _lib.ptr(d_head), 0, _lib.ptr(work),
+                _lib.ptr(d_sqd), _lib.ptr(out) if need_s else None, out.stride(1) if need_s else 0, out.stride(0) if need_s else 0,
+                _lib.ptr(rev[0]), _lib.ptr(rev[1]), _lib.ptr(rev[2]), _lib.ptr(rev[3]), _lib.ptr(dv_ws),
+                MATH_MODES["fp32"], _lib.stream_ptr())
+            _lib.check(rc, "pit_distlist_bwd")
+        return d_values, d_head, None, None, None, None, None, (d_sqd.view(ctx.sqd_shape) if d_sqd is not None else None)
+
+
+@torch.compiler.disable
+def posatt_list_apply(values: torch.Tensor, lmda: torch.Tensor, plan: ListPlan, n_head: int, concat: bool = False,
+                      head_is_scale: bool = False, sqd: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``posatt_dist_apply`` on candidate lists: out[b,n,h*D+d] = sum_t P[n,t] * values[b,idx[n,t],d] over the kept slots of row
+    n (the kept set and the weights of pit.py:48-57 on the matrix that holds the listed distances and a masked value everywhere
+    else); ``concat`` prepends the inputs (pit.py:44).  ``sqd``: the caller's own tensor (the one ``plan`` was built from); when
+    grad mode is on and it requires grad it becomes an input of the node and receives d loss / d sqd in its shape, so autograd
+    carries the gradient on to whatever formed the listed distances.  fp32 math mode only; head-scale routes as in ``posatt_apply``."""
+    _check_dist_mode()
+    if _capturing():
+        _pin(plan)                                 # its buffers' addresses are now baked into a hipGraph: never release them
+    values = materialize_coords(values)
+    c = host_head_scale(lmda) if (not head_is_scale and get_head_scale_route() == "host") else None
+    extra = ()
+    if sqd is not None and torch.is_grad_enabled() and sqd.requires_grad:
+        if tuple(sqd.shape)[-2:] != (plan.n_out, plan.cap) or sqd.numel() != plan.mesh_batch * plan.n_out * plan.cap:
+            raise ValueError("sqd is not the tensor the plan was built from")
+        extra = (sqd,)
+    return _PosAttList.apply(values, lmda.reshape(-1), plan, n_head, concat, head_is_scale, c, *extra)
+
+
 # ---- one-launch MLP chains of the bf16 math mode (csrc/pit_chain.hip): hid 128 / 256 on a few thousand rows ----------------------
 # The chains read their weights as bf16: copies are kept per weight tensor and re-formed when the weight changed (version counter /
 # parameters_changed() epoch) - all requested copies in ONE launch.  Inside a stream capture nothing can be known about the
