@@ -45,6 +45,31 @@ class DecoderWeightsJob(ctypes.Structure):
                 ("pw", _P), ("qw", _P), ("scale_out", _P), ("w1", _P), ("w1f", _P), ("dim", _I)]
 
 
+# The argument groups that recur in the layer entries beside the main mesh path (ragged, distance matrix, candidate lists), in
+# the header's order: their types here, their values in the *_args builders below SIGNATURES.
+_VALUES = [_P, _I, _L, _L]                 # values, dim, ld_values, values_bstride
+_VALUES_B = [_P, _I, _I, _L, _L]           # values, batch, dim, ld_values, values_bstride
+_HEAD = [_P, _I, _I]                       # head, n_head, head_is_scale
+_HEAD_BWD = _HEAD + [_P]                   # ..., scale
+_STATS = [_P, _F, _I]                      # stats, rank_w, masked
+_STATS_RAGGED = [_P, _P, _I]               # (rank_w per sample, on the device)
+_STATS_BWD = [_P, _I]                      # rowstat, masked
+_OUT = [_P, _L, _L, _I, _I, _P, _P]        # out, ld_out, out_bstride, out_col0, copy_inputs, rowstat, scale_out
+_DOUT = [_P, _L, _L, _I]                   # d_out, ld_dout, dout_bstride, out_col0
+_DVALUES = [_P, _L, _L, _I]                # d_values, ld_dvalues, dvalues_bstride, add_residual
+_DHEAD = [_P, _I, _P]                      # d_head, accumulate_head, workspace
+_SAVED_OUT = [_P, _L, _L]                  # out, ld_out, out_bstride (the forward's result, read by d(m) / d(sqd))
+_TAIL = [_I, _P]                           # math_mode, stream
+_RAGGED = [_P, _P, _I, _I, _I, _I, _P, _P]                  # mesh_out, mesh_in, mesh_batch, n_out, n_in, space_dim, len_out, len_in
+_RAGGED_STRIDED = _RAGGED[:6] + [_L, _L] + _RAGGED[6:]      # ..., out_stride, in_stride, len_out, len_in
+_RAGGED_LISTS = [_P, _P, _I]                                # nbr_idx, nbr_cnt, nbr_cap
+_MAT = [_P, _L, _L, _I, _I]                                 # m, ld_m, m_bstride, n_out, n_in
+_LIST = [_P, _P, _L, _L, _I, _I, _I]                        # idx, sqd, ld, bstride, cap, n_out, n_in
+_FWD_RAGGED = _VALUES + _HEAD + _STATS_RAGGED + _OUT + _RAGGED_LISTS + _TAIL
+_BWD_RAGGED = _VALUES + _HEAD_BWD + _STATS_BWD + _DOUT + _DVALUES + _DHEAD + _RAGGED_LISTS + [_P, _P] + _TAIL      # ..., rev_ptr, rev_row
+_FWD_DIST = _VALUES_B + _HEAD + _STATS + _OUT + _TAIL
+_BWD_DIST = _VALUES_B + _HEAD_BWD + _STATS_BWD + _DOUT + _DVALUES + _DHEAD
+
 # name -> argtypes, mirrors include/pit_hip.h one to one
 SIGNATURES = {
     "pit_version": [],
@@ -141,68 +166,21 @@ SIGNATURES = {
     "pit_rel_lp_loss_fwd_grad_ordered": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P],
     "pit_rel_lp_loss_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "pit_plan_ragged_fwd": [_P, _P, _I, _I, _I, _I, _P, _P, _F, _I, _P, _P, _I, _P, _P, _P],
-    "pit_posatt_ragged_fwd": [_P, _P, _I, _I, _I, _I, _P, _P,
-                              _P, _I, _L, _L,
-                              _P, _I, _I,
-                              _P, _P, _I,
-                              _P, _L, _L, _I, _I,
-                              _P, _P, _P, _P, _I, _I, _P],
-    "pit_posatt_ragged_bwd": [_P, _P, _I, _I, _I, _I, _P, _P,
-                              _P, _I, _L, _L,
-                              _P, _I, _I, _P,
-                              _P, _I,
-                              _P, _L, _L, _I,
-                              _P, _L, _L, _I,
-                              _P, _I, _P, _P, _P, _I, _P, _P, _I, _P],
+    "pit_posatt_ragged_fwd": _RAGGED + _FWD_RAGGED,
+    "pit_posatt_ragged_bwd": _RAGGED + _BWD_RAGGED,
     "pit_plan_ragged_strided_fwd": [_P, _P, _I, _I, _I, _I, _L, _L, _P, _P, _F, _I, _P, _P, _I, _P, _P, _P],
-    "pit_posatt_ragged_strided_fwd": [_P, _P, _I, _I, _I, _I, _L, _L, _P, _P,
-                                      _P, _I, _L, _L,
-                                      _P, _I, _I,
-                                      _P, _P, _I,
-                                      _P, _L, _L, _I, _I,
-                                      _P, _P, _P, _P, _I, _I, _P],
-    "pit_posatt_ragged_strided_bwd": [_P, _P, _I, _I, _I, _I, _L, _L, _P, _P,
-                                      _P, _I, _L, _L,
-                                      _P, _I, _I, _P,
-                                      _P, _I,
-                                      _P, _L, _L, _I,
-                                      _P, _L, _L, _I,
-                                      _P, _I, _P, _P, _P, _I, _P, _P, _I, _P],
+    "pit_posatt_ragged_strided_fwd": _RAGGED_STRIDED + _FWD_RAGGED,
+    "pit_posatt_ragged_strided_bwd": _RAGGED_STRIDED + _BWD_RAGGED,
     "pit_rel_lp_loss_ragged_fwd": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "pit_rel_lp_loss_ragged_bwd": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
     "pit_distmat_select_fwd": [_P, _L, _L, _I, _I, _I, _I, _I, _P, _P],
-    "pit_distmat_fwd": [_P, _L, _L, _I, _I,
-                        _P, _I, _I, _L, _L,
-                        _P, _I, _I,
-                        _P, _F, _I,
-                        _P, _L, _L, _I, _I,
-                        _P, _P, _I, _P],
+    "pit_distmat_fwd": _MAT + _FWD_DIST,
     "pit_distmat_bwd_workspace": [_I, _I, _I],
-    "pit_distmat_bwd": [_P, _L, _L, _I, _I,
-                        _P, _I, _I, _L, _L,
-                        _P, _I, _I, _P,
-                        _P, _I,
-                        _P, _L, _L, _I,
-                        _P, _L, _L, _I,
-                        _P, _I, _P,
-                        _P, _P, _L, _L, _P, _I, _P],
+    "pit_distmat_bwd": _MAT + _BWD_DIST + [_P] + _SAVED_OUT + [_P] + _TAIL,                 # ..., d_m, out ..., a_workspace
     "pit_distlist_select_fwd": [_P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _P, _P],
-    "pit_distlist_fwd": [_P, _P, _L, _L, _I, _I, _I,
-                         _P, _I, _I, _L, _L,
-                         _P, _I, _I,
-                         _P, _F, _I,
-                         _P, _L, _L, _I, _I,
-                         _P, _P, _I, _P],
+    "pit_distlist_fwd": _LIST + _FWD_DIST,
     "pit_distlist_bwd_workspace": [_I, _I, _I, _I],
-    "pit_distlist_bwd": [_P, _P, _L, _L, _I, _I, _I,
-                         _P, _I, _I, _L, _L,
-                         _P, _I, _I, _P,
-                         _P, _I,
-                         _P, _L, _L, _I,
-                         _P, _L, _L, _I,
-                         _P, _I, _P,
-                         _P, _P, _L, _L,
-                         _P, _P, _P, _P, _P, _I, _P],
+    "pit_distlist_bwd": _LIST + _BWD_DIST + [_P] + _SAVED_OUT + [_P] * 5 + _TAIL,            # ..., d_sqd, out ..., the transposed index, dv_workspace
     "pit_rel_max_norm": [_P, _P, _I, _I, _I, _P, _P, _P],
     "pit_instance_norm_fwd": [_P, _L, _L, _I, _I, _I, _F, _P, _P, _P],
     "pit_instance_norm_bwd": [_P, _P, _P, _I, _I, _I, _P, _P],
@@ -266,3 +244,34 @@ def stream_ptr() -> int:
 
 def ptr(t) -> int:
     return 0 if t is None else t.data_ptr()
+
+
+# ---- the values of the argument groups above (t: a (batch, points, channels) tensor whose rows are contiguous) --------------------
+def values_args(t, with_batch: bool) -> tuple:
+    b, _, d = t.shape
+    return (t.data_ptr(),) + ((b, d) if with_batch else (d,)) + (t.stride(1), t.stride(0))
+
+
+def head_args(head, n_head: int, is_scale: bool, *scale) -> tuple:
+    """_HEAD; with the forward's scale_out as ``scale``: _HEAD_BWD."""
+    return (head.data_ptr(), n_head, 1 if is_scale else 0) + tuple(c.data_ptr() for c in scale)
+
+
+def out_args(out, d: int, concat: bool, rowstat, scale_out) -> tuple:
+    return (out.data_ptr(), out.stride(1), out.stride(0), d if concat else 0, 1 if concat else 0, rowstat.data_ptr(), scale_out.data_ptr())
+
+
+def dout_args(d_out, d: int, concat: bool) -> tuple:
+    return (d_out.data_ptr(), d_out.stride(1), d_out.stride(0), d if concat else 0)
+
+
+def dvalues_args(d_values, j: int, d: int, concat: bool) -> tuple:
+    return (ptr(d_values), d, j * d, 1 if concat else 0)
+
+
+def dhead_args(d_head, workspace) -> tuple:
+    return (ptr(d_head), 0, ptr(workspace))
+
+
+def saved_out_args(out) -> tuple:
+    return (None, 0, 0) if out is None else (out.data_ptr(), out.stride(1), out.stride(0))

@@ -20,32 +20,23 @@
 // Rows of values, d_out and out are read through sized buffer descriptors (one per sample, wave-uniform): an offset beyond the
 // tensor reads 0, which is also how the tail of a group of four slots is fed.  VEC: 16-byte pieces (lane holds 4 consecutive
 // columns), otherwise 4-byte pieces (lane holds columns lane, lane + 64, ...).
-#include "pit_common.h"
+#include "pit_layer.h"
 
 namespace {
 
 constexpr int LQ = 4;                      // columns per lane and column group (a wave covers 64 * LQ = 256 columns)
 constexpr int CHUNK = PIT_DISTLIST_CHUNK;  // listing slots of a key summed by one wave
 
-struct ListArgs {
+struct ListArgs : LayerIO {
     const int* idx; const float* sqd; long ld, bstride; int cap;     // bstride 0: one list set shared by the batch
     int batch, n_out, n_in;
-    const float* values; int dim; long ld_values, values_bstride;
-    const float* head; int n_head, head_is_scale;
-    const float* stats; float rank_w; int masked;
-    float* out; long ld_out, out_bstride; int out_col0, copy_inputs;
-    float* rowstat; float* scale_out;
-    const float* d_out; long ld_dout, dout_bstride;
-    float* d_values; long ld_dvalues, dvalues_bstride; int add_residual;
-    double* dscale_acc; float* d_sqd;
+    float rank_w;
+    float* d_sqd;
     const int* rev_ptr; const int* rev_pos; const int* chunk_ptr; const int* chunk_key; float* dv_ws;
-    int colgroups, chunk_slots;
-    unsigned values_bytes, dout_bytes, out_bytes;                    // of ONE sample's rows: the sizes of the buffer descriptors
+    int chunk_slots;
+    unsigned out_bytes;                                              // of ONE sample's rows: the size of out's buffer descriptor
 };
 
-__device__ __forceinline__ float head_c(const ListArgs& a, int h) {
-    return a.head_is_scale ? a.head[h] : head_scale_from_lmda(a.head[h]);
-}
 __device__ __forceinline__ bool key_ok(int j, int n_in) { return (unsigned)j < (unsigned)n_in; }
 
 // column u of a lane in column group cg
@@ -148,16 +139,6 @@ __device__ __forceinline__ bool load_slot(const ListArgs& a, long base, int t0, 
     m = valid ? mm : 0.0f;
     return valid;
 }
-// the forward's unnormalised weight of one slot (pit_distmat.hip: exp(S_min - S), kept if S <= T)
-__device__ __forceinline__ float weight_raw(float m, float c, float T, float smin, bool valid, int masked) {
-    const float sv = __fmul_rn(m, c);
-    const bool keep = valid && (!masked || sv <= T);
-    return keep ? __expf(smin - sv) : 0.0f;
-}
-__device__ __forceinline__ float4 row_stat(const ListArgs& a, int mb, int h, int row) {
-    return *reinterpret_cast<const float4*>(a.rowstat + (((long)mb * a.n_head + h) * a.n_out + row) * 4);
-}
-__device__ __forceinline__ float lane_f(float v, int src) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src)); }
 
 // ---- forward --------------------------------------------------------------------------------------------------------------
 // grid (rows / 4, head groups of NH, colgroups)
@@ -260,7 +241,7 @@ __device__ __forceinline__ void dv_range(const ListArgs& a, int mb, __amdgpu_buf
         const float m = valid ? mm : 0.0f;
         for (int h = 0; h < a.n_head; ++h) {
             const float c = head_c(a, h);
-            const float4 rs = row_stat(a, mb, h, row);
+            const float4 rs = row_stat(a.rowstat, a.n_head, a.n_out, mb, h, row);
             const float p = weight_raw(m, c, rs.x, rs.y, valid, a.masked) * rs.z;
             unsigned long long mask = __builtin_amdgcn_ballot_w64(p != 0.0f);
             const unsigned hoff = (unsigned)((a.out_col0 + (long)h * a.dim) * 4);
@@ -365,7 +346,7 @@ __global__ __launch_bounds__(256) void distlist_rows_bwd_kernel(ListArgs a) {
                     const bool hv = h0 + q < a.n_head;
                     const int h = hv ? h0 + q : 0;
                     c[q] = head_c(a, h);
-                    const float4 rs = row_stat(a, mb, h, n);
+                    const float4 rs = row_stat(a.rowstat, a.n_head, a.n_out, mb, h, n);
                     p[q] = weight_raw(m, c[q], rs.x, rs.y, valid && hv, a.masked) * rs.z;
                     mbar[q] = rs.w;
                     any = any || p[q] != 0.0f;
@@ -443,30 +424,19 @@ __global__ __launch_bounds__(256) void distlist_rows_bwd_kernel(ListArgs a) {
     }
 }
 
-unsigned long long rows_bytes(int rows, long ld, long width) { return ((unsigned long long)(rows - 1) * ld + width) * 4ull; }
 bool aligned4(const void* p, long a = 0, long b = 0, long c = 0, long d = 0) {
     return (reinterpret_cast<uintptr_t>(p) & 15u) == 0 && ((a | b | c | d) & 3L) == 0;
 }
 
-// sizes shared by the entries; fills the per-sample descriptor sizes
+// the list operands, then the layer's (pit_layer.h); fills the per-sample descriptor sizes
 int list_check(ListArgs& a, int need_dout) {
     if (a.batch <= 0 || a.n_out <= 0 || a.n_in <= 0 || a.cap <= 0) return PIT_ERR_SIZE;
     if (a.batch > 65535) return PIT_ERR_UNSUPPORTED;
     if (a.ld < a.cap || a.bstride < 0 || (a.bstride != 0 && a.bstride < (long)(a.n_out - 1) * a.ld + a.cap)) return PIT_ERR_SIZE;
     if ((long)a.n_out * a.cap > 0x7fffffffL || (long)a.batch * a.n_out > 0x7fffffffL) return PIT_ERR_UNSUPPORTED;
-    if (a.dim <= 0 || a.n_head <= 0 || a.ld_values < a.dim || a.values_bstride < 0) return PIT_ERR_SIZE;
-    const unsigned long long vb = rows_bytes(a.n_in, a.ld_values, a.dim);
-    if (vb > PIT_MAX_BUFFER_BYTES) return PIT_ERR_UNSUPPORTED;
-    a.values_bytes = (unsigned)vb;
-    a.colgroups = (a.dim + 64 * LQ - 1) / (64 * LQ);
+    if (int rc = layer_check_values(a, a.n_in)) return rc;
     if (a.n_head > 65535 || a.colgroups > 65535) return PIT_ERR_UNSUPPORTED;
-    if (need_dout) {
-        if (a.out_col0 < 0 || a.ld_dout < a.out_col0 + (long)a.n_head * a.dim || a.dout_bstride < 0) return PIT_ERR_SIZE;
-        const unsigned long long db = rows_bytes(std::max(a.n_out, a.add_residual ? a.n_in : 0), a.ld_dout, a.out_col0 + (long)a.n_head * a.dim);
-        if (db > PIT_MAX_BUFFER_BYTES) return PIT_ERR_UNSUPPORTED;
-        a.dout_bytes = (unsigned)db;
-    }
-    return 0;
+    return need_dout ? layer_check_dout(a, std::max(a.n_out, a.add_residual ? a.n_in : 0)) : 0;
 }
 
 template <int NPL>
@@ -510,15 +480,13 @@ extern "C" int pit_distlist_fwd(const int* idx, const float* sqd, long ld, long 
     if (math_mode != PIT_MATH_FP32) return PIT_ERR_UNSUPPORTED;
     ListArgs a = ListArgs();
     a.idx = idx; a.sqd = sqd; a.ld = ld; a.bstride = bstride; a.cap = cap; a.batch = batch; a.n_out = n_out; a.n_in = n_in;
-    a.values = values; a.dim = dim; a.ld_values = ld_values; a.values_bstride = values_bstride;
-    a.head = head; a.n_head = n_head; a.head_is_scale = head_is_scale;
+    a.rank_w = rank_w;
+    layer_set_fwd(a, values, dim, ld_values, values_bstride, head, n_head, head_is_scale, stats, masked, out, ld_out, out_bstride, out_col0,
+                  copy_inputs, rowstat, scale_out);
     if (int rc = list_check(a, 0)) return rc;
     if (out_col0 < 0 || ld_out < out_col0 + (long)n_head * dim || out_bstride < 0 || (copy_inputs && (n_out != n_in || out_col0 < dim)))
         return PIT_ERR_SIZE;
     if (rows_bytes(n_out, ld_out, out_col0 + (long)n_head * dim) > PIT_MAX_BUFFER_BYTES) return PIT_ERR_UNSUPPORTED;
-    a.stats = stats; a.rank_w = rank_w; a.masked = masked ? 1 : 0;
-    a.out = out; a.ld_out = ld_out; a.out_bstride = out_bstride; a.out_col0 = out_col0; a.copy_inputs = copy_inputs ? 1 : 0;
-    a.rowstat = rowstat; a.scale_out = scale_out;
     const bool vec = dim % 4 == 0 && aligned4(values, ld_values, values_bstride) && aligned4(out, ld_out, out_bstride, out_col0);
     const int nh = n_head == 1 ? 1 : n_head == 2 ? 2 : 4;
     const dim3 grid((unsigned)(((long)batch * n_out + 3) / 4), (unsigned)((n_head + nh - 1) / nh), (unsigned)a.colgroups);
@@ -553,16 +521,11 @@ extern "C" int pit_distlist_bwd(const int* idx, const float* sqd, long ld, long 
     if (math_mode != PIT_MATH_FP32) return PIT_ERR_UNSUPPORTED;
     ListArgs a = ListArgs();
     a.idx = idx; a.sqd = sqd; a.ld = ld; a.bstride = bstride; a.cap = cap; a.batch = batch; a.n_out = n_out; a.n_in = n_in;
-    a.values = values; a.dim = dim; a.ld_values = ld_values; a.values_bstride = values_bstride;
-    a.head = scale ? scale : head; a.n_head = n_head; a.head_is_scale = (scale || head_is_scale) ? 1 : 0;
-    a.out_col0 = out_col0; a.ld_dout = ld_dout; a.dout_bstride = dout_bstride; a.add_residual = add_residual ? 1 : 0;
+    layer_set_bwd(a, values, dim, ld_values, values_bstride, head, n_head, head_is_scale, scale, rowstat, masked, d_out, ld_dout, dout_bstride,
+                  out_col0, d_values, ld_dvalues, dvalues_bstride, add_residual, d_head, workspace);
     if (add_residual && (n_out != n_in || out_col0 < dim)) return PIT_ERR_SIZE;
     if (int rc = list_check(a, 1)) return rc;
     if (d_values && (ld_dvalues < dim || dvalues_bstride < 0)) return PIT_ERR_SIZE;
-    a.rowstat = const_cast<float*>(rowstat); a.masked = masked ? 1 : 0;
-    a.d_out = d_out;
-    a.d_values = d_values; a.ld_dvalues = ld_dvalues; a.dvalues_bstride = dvalues_bstride;
-    a.dscale_acc = d_head ? workspace : nullptr;
     a.d_sqd = d_sqd;
     a.rev_ptr = rev_ptr; a.rev_pos = rev_pos; a.chunk_ptr = chunk_ptr; a.chunk_key = chunk_key; a.dv_ws = dv_workspace;
     const long slots = PIT_DISTLIST_CHUNK_SLOTS(n_out, cap);
@@ -599,14 +562,5 @@ extern "C" int pit_distlist_bwd(const int* idx, const float* sqd, long ld, long 
 #undef PIT_LIST_ROWS
         PIT_CHECK_LAUNCH();
     }
-    if (d_head && !(accumulate_head & PIT_HEAD_DEFER)) {  // drain the accumulators, apply d c / d lmda (pit_posatt_dhead_finish)
-        double* ws[1] = {workspace};
-        float* dh[1] = {d_head};
-        const float* hd[1] = {head};
-        const float* sc[1] = {scale};
-        const int nh[1] = {n_head};
-        const int fl[1] = {(accumulate_head & PIT_HEAD_ACCUMULATE) | (head_is_scale ? PIT_HEAD_IS_SCALE : 0)};
-        return pit_posatt_dhead_finish(1, ws, dh, hd, sc, nh, fl, nullptr, stream);
-    }
-    return 0;
+    return layer_finish_head(head, scale, d_head, workspace, n_head, accumulate_head, head_is_scale, stream);
 }

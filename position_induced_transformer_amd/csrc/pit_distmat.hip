@@ -17,13 +17,13 @@
 //               weights (mbar_i = sum_j P_ij m_ij is in rowstat), the contracted rows dotted with d_out.
 //   d(m)        a_i = sum_j P_ij gv_ij = g_i . out_i from the forward's result (a wave per row); then a workgroup owns a 32 x 128
 //               tile of d_m, a wave forms the 32 x 32 tiles of gv = g . v on the matrix pipe (the channel axis contracted;
-//               gv_tile of pit_dmesh.hip) and loops over heads and - for a shared matrix - over the samples in ascending
+//               gv_tile of pit_layer.h) and loops over heads and - for a shared matrix - over the samples in ascending
 //               order: d m_ij = -sum_h c_h P_ij (gv_ij - a_i).  No buffer of per-sample partials exists.
 // Tiles whose weights are all zero (masked layers: most of them) skip their contraction - a wave- or workgroup-uniform branch.
 // Every sum except d(scale)'s fp64 slots (the PIT_DSCALE_SLOTS convention of pit_posatt_bwd) has a fixed order; no atomics
 // otherwise: the same input gives the same bits on every run.  Rows, keys and channels beyond a tensor read 0 through sized
 // buffer descriptors (one per sample, built from workgroup-uniform values).
-#include "pit_common.h"
+#include "pit_layer.h"
 
 namespace {
 
@@ -94,36 +94,14 @@ __global__ __launch_bounds__(256) void distmat_select_kernel(const float* __rest
 }
 
 // ---- attention --------------------------------------------------------------------------------------------------------
-struct DmatArgs {
+struct DmatArgs : LayerIO {
     const float* m; long ld_m, m_bstride;        // m_bstride 0: one matrix shared by the batch
     int batch, n_out, n_in;
-    const float* values; int dim; long ld_values, values_bstride;
-    const float* head; int n_head, head_is_scale;
-    const float* stats; float rank_w; int masked;
-    float* out; long ld_out, out_bstride; int out_col0, copy_inputs;
-    float* rowstat; float* scale_out;
-    const float* d_out; long ld_dout, dout_bstride;
-    float* d_values; long ld_dvalues, dvalues_bstride; int add_residual;
-    double* dscale_acc; float* a_ws;
+    float rank_w;
+    float* a_ws;
     float* d_m;
-    int colgroups;
-    unsigned m_bytes, values_bytes, dout_bytes;  // of ONE sample's rows: the sizes of the buffer descriptors
+    unsigned m_bytes;                            // of ONE sample's rows: the size of its buffer descriptor
 };
-
-__device__ __forceinline__ float head_c(const DmatArgs& a, int h) {
-    return a.head_is_scale ? a.head[h] : head_scale_from_lmda(a.head[h]);
-}
-
-// the forward's unnormalised weight of one pair (pit_posatt.hip: exp(S_min - S), kept if S <= T)
-__device__ __forceinline__ float weight_raw(float m, float c, float T, float smin, bool valid, int masked) {
-    const float sv = __fmul_rn(m, c);
-    const bool keep = valid && (!masked || sv <= T);
-    return keep ? __expf(smin - sv) : 0.0f;
-}
-
-__device__ __forceinline__ float4 row_stat(const DmatArgs& a, int mb, int h, int row) {
-    return *reinterpret_cast<const float4*>(a.rowstat + (((long)mb * a.n_head + h) * a.n_out + row) * 4);
-}
 
 // One tile's contraction for a wave: acc{0,1}[owner][col] += sum_t w[t][owner] * x[t0 + t][col] over the tile's KT items, for
 // the wave's two 32-column tiles at cb and cb + 32 (columns of x from xcol0 on).  A: lane l holds w[2u + half][l & 31] (LDS),
@@ -179,7 +157,7 @@ __global__ __launch_bounds__(256) void distmat_rows_kernel(DmatArgs a) {
     }
     if (MODE == 0 && s == 0 && blockIdx.x == 0 && cg == 0 && tid == 0 && a.scale_out) a.scale_out[h] = c;
     if (MODE == 1) {
-        if (tid < RT) s_rs[tid] = row_stat(a, mb, h, min(r0 + tid, a.n_out - 1));
+        if (tid < RT) s_rs[tid] = row_stat(a.rowstat, a.n_head, a.n_out, mb, h, min(r0 + tid, a.n_out - 1));
     } else if (tid < RT) {
         const long row = (long)mb * a.n_out + min(r0 + tid, a.n_out - 1);
         float4 st;
@@ -294,7 +272,7 @@ __global__ __launch_bounds__(256) void distmat_dv_kernel(DmatArgs a) {
             for (int q = 0; q < KT / 8; ++q) {
                 const int t = tr + 8 * q, row = n0 + t;
                 const bool valid = kv && row < a.n_out;
-                const float4 rs = row_stat(a, mb, h, min(row, a.n_out - 1));
+                const float4 rs = row_stat(a.rowstat, a.n_head, a.n_out, mb, h, min(row, a.n_out - 1));
                 const float mv = buf_load(rm, valid ? (unsigned)(((long)row * a.ld_m + key) * 4) : a.m_bytes);
                 const float p = weight_raw(mv, c, rs.x, rs.y, valid, a.masked) * rs.z;
                 any = any || (p != 0.0f);
@@ -323,33 +301,6 @@ __global__ __launch_bounds__(256) void distmat_dv_kernel(DmatArgs a) {
     }
 }
 
-// gv tile (gv_tile of pit_dmesh.hip on per-sample descriptors): acc[r] of lane l = sum_d g[i0 + acc_row(r, half)][d] *
-// v[j0 + (l & 31)][d] for head h.  A lane holds channels d0 + 4*half + u (u = 0..3) of its row / key; channels, rows and keys
-// out of range read 0.
-__device__ __forceinline__ f32x16 gv_tile(const DmatArgs& a, __amdgpu_buffer_rsrc_t rg, __amdgpu_buffer_rsrc_t rv, int h, int i0, int j0) {
-    const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
-    const int row = i0 + l31, key = j0 + l31;
-    const bool rvalid = row < a.n_out, kvalid = key < a.n_in;
-    const unsigned gbase = rvalid ? (unsigned)(((long)row * a.ld_dout + a.out_col0 + (long)h * a.dim) * 4) : 0u;
-    const unsigned vbase = kvalid ? (unsigned)(((long)key * a.ld_values) * 4) : 0u;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    for (int d0 = 0; d0 < a.dim; d0 += 8) {
-        float ga[4], vb[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int d = d0 + 4 * half + u;
-            const bool ok = d < a.dim;
-            ga[u] = buf_load(rg, (rvalid && ok) ? gbase + (unsigned)d * 4u : a.dout_bytes);
-            vb[u] = buf_load(rv, (kvalid && ok) ? vbase + (unsigned)d * 4u : a.values_bytes);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc = mfma_32x32x2(ga[u], vb[u], acc);
-    }
-    return acc;
-}
-
 // a_i = sum_j P_ij gv_ij = g_i . out_i (out_i = sum_j P_ij v_j is the forward's result): one wave per row and head.
 // grid (ceil(n_out / 4), batch, n_head)
 __global__ __launch_bounds__(256) void distmat_ai_kernel(DmatArgs a) {
@@ -370,8 +321,9 @@ __global__ __launch_bounds__(256) void distmat_dm_kernel(DmatArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
     const int j0 = blockIdx.x * 128 + wave * 32, i0 = blockIdx.y * RT, mb = blockIdx.z;
     if (j0 >= a.n_in) return;                             // (wave-uniform; no barriers below)
-    const int key = j0 + l31;
-    const bool kv = key < a.n_in;
+    const int key = j0 + l31, grow = i0 + l31;            // grow: the row whose d_out this lane feeds to the gv tiles
+    const bool kv = key < a.n_in, gvalid = grow < a.n_out;
+    const unsigned vbase = kv ? (unsigned)(((long)key * a.ld_values) * 4) : 0u;
     const int s_beg = a.m_bstride ? mb : 0, s_end = a.m_bstride ? mb + 1 : a.batch;
     const __amdgpu_buffer_rsrc_t rm = make_rsrc(a.m + (long)mb * a.m_bstride, a.m_bytes);
     float acc[16];
@@ -385,7 +337,7 @@ __global__ __launch_bounds__(256) void distmat_dm_kernel(DmatArgs a) {
         for (int r = 0; r < 16; ++r) {
             const int row = i0 + acc_row(r, half);
             const bool valid = kv && row < a.n_out;
-            const float4 rs = row_stat(a, mb, h, min(row, a.n_out - 1));
+            const float4 rs = row_stat(a.rowstat, a.n_head, a.n_out, mb, h, min(row, a.n_out - 1));
             const float mv = buf_load(rm, valid ? (unsigned)(((long)row * a.ld_m + key) * 4) : a.m_bytes);
             p[r] = -c * (weight_raw(mv, c, rs.x, rs.y, valid, a.masked) * rs.z);
             any = any || (p[r] != 0.0f);
@@ -394,7 +346,8 @@ __global__ __launch_bounds__(256) void distmat_dm_kernel(DmatArgs a) {
         for (int s = s_beg; s < s_end; ++s) {
             const __amdgpu_buffer_rsrc_t rv = make_rsrc(a.values + (long)s * a.values_bstride, a.values_bytes);
             const __amdgpu_buffer_rsrc_t rg = make_rsrc(a.d_out + (long)s * a.dout_bstride, a.dout_bytes);
-            const f32x16 gv = gv_tile(a, rg, rv, h, i0, j0);
+            const unsigned gbase = gvalid ? (unsigned)(((long)grow * a.ld_dout + a.out_col0 + (long)h * a.dim) * 4) : 0u;
+            const f32x16 gv = gv_tile(rg, rv, gbase, gvalid, vbase, kv, a.dim, a.dout_bytes, a.values_bytes);
             const float* ai = a.a_ws + ((long)s * a.n_head + h) * a.n_out;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] += p[r] * (gv[r] - ai[min(i0 + acc_row(r, half), a.n_out - 1)]);
@@ -410,30 +363,18 @@ __global__ __launch_bounds__(256) void distmat_dm_kernel(DmatArgs a) {
     }
 }
 
-// sizes shared by the three entries; fills the per-sample descriptor sizes
-int dmat_check(DmatArgs& a, int need_values, int need_dout) {
+// the matrix operands, then the layer's (pit_layer.h); fills the per-sample descriptor sizes
+int dmat_check(DmatArgs& a, int need_dout) {
     if (a.batch <= 0 || a.n_out <= 0 || a.n_in <= 0) return PIT_ERR_SIZE;
     if (a.batch > 65535) return PIT_ERR_UNSUPPORTED;
     if (a.ld_m < a.n_in) return PIT_ERR_SIZE;
-    const unsigned long long mbytes = ((unsigned long long)(a.n_out - 1) * a.ld_m + a.n_in) * 4ull;
+    const unsigned long long mbytes = rows_bytes(a.n_out, a.ld_m, a.n_in);
     if (a.m_bstride != 0 && (a.m_bstride < 0 || (unsigned long long)a.m_bstride * 4ull < mbytes)) return PIT_ERR_SIZE;
     if (mbytes > PIT_MAX_BUFFER_BYTES) return PIT_ERR_UNSUPPORTED;
     a.m_bytes = (unsigned)mbytes;
-    if (need_values) {
-        if (a.dim <= 0 || a.n_head <= 0 || a.ld_values < a.dim || a.values_bstride < 0) return PIT_ERR_SIZE;
-        const unsigned long long vb = ((unsigned long long)(a.n_in - 1) * a.ld_values + a.dim) * 4ull;
-        if (vb > PIT_MAX_BUFFER_BYTES) return PIT_ERR_UNSUPPORTED;
-        a.values_bytes = (unsigned)vb;
-        a.colgroups = (a.dim + 255) / 256;
-        if ((long)a.n_head * a.colgroups > 65535) return PIT_ERR_UNSUPPORTED;
-    }
-    if (need_dout) {
-        if (a.out_col0 < 0 || a.ld_dout < a.out_col0 + (long)a.n_head * a.dim || a.dout_bstride < 0) return PIT_ERR_SIZE;
-        const unsigned long long db = ((unsigned long long)(a.n_out - 1) * a.ld_dout + a.out_col0 + (unsigned long long)a.n_head * a.dim) * 4ull;
-        if (db > PIT_MAX_BUFFER_BYTES) return PIT_ERR_UNSUPPORTED;
-        a.dout_bytes = (unsigned)db;
-    }
-    return 0;
+    if (int rc = layer_check_values(a, a.n_in)) return rc;
+    if ((long)a.n_head * a.colgroups > 65535) return PIT_ERR_UNSUPPORTED;
+    return need_dout ? layer_check_dout(a, a.n_out) : 0;
 }
 
 }  // namespace
@@ -461,15 +402,12 @@ extern "C" int pit_distmat_fwd(const float* m, long ld_m, long m_bstride, int n_
     if (!m || !values || !head || !stats || !out || !rowstat) return PIT_ERR_NULL;
     if (math_mode != PIT_MATH_FP32) return PIT_ERR_UNSUPPORTED;
     DmatArgs a = DmatArgs();
-    a.m = m; a.ld_m = ld_m; a.m_bstride = m_bstride; a.batch = batch; a.n_out = n_out; a.n_in = n_in;
-    a.values = values; a.dim = dim; a.ld_values = ld_values; a.values_bstride = values_bstride;
-    a.head = head; a.n_head = n_head; a.head_is_scale = head_is_scale;
-    if (int rc = dmat_check(a, 1, 0)) return rc;
+    a.m = m; a.ld_m = ld_m; a.m_bstride = m_bstride; a.batch = batch; a.n_out = n_out; a.n_in = n_in; a.rank_w = rank_w;
+    layer_set_fwd(a, values, dim, ld_values, values_bstride, head, n_head, head_is_scale, stats, masked, out, ld_out, out_bstride, out_col0,
+                  copy_inputs, rowstat, scale_out);
+    if (int rc = dmat_check(a, 0)) return rc;
     if (out_col0 < 0 || ld_out < out_col0 + (long)n_head * dim || out_bstride < 0 || (copy_inputs && (n_out != n_in || out_col0 < dim)))
         return PIT_ERR_SIZE;
-    a.stats = stats; a.rank_w = rank_w; a.masked = masked ? 1 : 0;
-    a.out = out; a.ld_out = ld_out; a.out_bstride = out_bstride; a.out_col0 = out_col0; a.copy_inputs = copy_inputs ? 1 : 0;
-    a.rowstat = rowstat; a.scale_out = scale_out;
     const dim3 grid((unsigned)((n_out + RT - 1) / RT), (unsigned)batch, (unsigned)(n_head * a.colgroups));
     hipLaunchKernelGGL(distmat_rows_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, a);
     PIT_CHECK_LAUNCH();
@@ -495,16 +433,11 @@ extern "C" int pit_distmat_bwd(const float* m, long ld_m, long m_bstride, int n_
     if (math_mode != PIT_MATH_FP32) return PIT_ERR_UNSUPPORTED;
     DmatArgs a = DmatArgs();
     a.m = m; a.ld_m = ld_m; a.m_bstride = m_bstride; a.batch = batch; a.n_out = n_out; a.n_in = n_in;
-    a.values = values; a.dim = dim; a.ld_values = ld_values; a.values_bstride = values_bstride;
-    a.head = scale ? scale : head; a.n_head = n_head; a.head_is_scale = (scale || head_is_scale) ? 1 : 0;
-    a.out_col0 = out_col0; a.ld_dout = ld_dout; a.dout_bstride = dout_bstride;
-    if (int rc = dmat_check(a, 1, 1)) return rc;
+    layer_set_bwd(a, values, dim, ld_values, values_bstride, head, n_head, head_is_scale, scale, rowstat, masked, d_out, ld_dout, dout_bstride,
+                  out_col0, d_values, ld_dvalues, dvalues_bstride, add_residual, d_head, workspace);
+    if (int rc = dmat_check(a, 1)) return rc;
     if (n_head > 65535 || (add_residual && (n_out != n_in || out_col0 < dim))) return PIT_ERR_SIZE;
     if (d_values && (ld_dvalues < dim || dvalues_bstride < 0)) return PIT_ERR_SIZE;
-    a.rowstat = const_cast<float*>(rowstat); a.masked = masked ? 1 : 0;
-    a.d_out = d_out;
-    a.d_values = d_values; a.ld_dvalues = ld_dvalues; a.dvalues_bstride = dvalues_bstride; a.add_residual = add_residual ? 1 : 0;
-    a.dscale_acc = d_head ? workspace : nullptr;
     a.a_ws = d_m ? a_workspace : nullptr;
     a.d_m = d_m;
     hipStream_t st = (hipStream_t)stream;
@@ -528,14 +461,5 @@ extern "C" int pit_distmat_bwd(const float* m, long ld_m, long m_bstride, int n_
         hipLaunchKernelGGL(distmat_dm_kernel, grid, dim3(256), 0, st, a);
         PIT_CHECK_LAUNCH();
     }
-    if (d_head && !(accumulate_head & PIT_HEAD_DEFER)) {  // drain the accumulators, apply d c / d lmda (pit_posatt_dhead_finish)
-        double* ws[1] = {workspace};
-        float* dh[1] = {d_head};
-        const float* hd[1] = {head};
-        const float* sc[1] = {scale};
-        const int nh[1] = {n_head};
-        const int fl[1] = {(accumulate_head & PIT_HEAD_ACCUMULATE) | (head_is_scale ? PIT_HEAD_IS_SCALE : 0)};
-        return pit_posatt_dhead_finish(1, ws, dh, hd, sc, nh, fl, nullptr, stream);
-    }
-    return 0;
+    return layer_finish_head(head, scale, d_head, workspace, n_head, accumulate_head, head_is_scale, stream);
 }

@@ -16,7 +16,7 @@
 //       which are scanned densely as pit_posatt_bwd does); the dot products are wave reductions, the sums fp64.
 // No atomics: every pass writes per-sample partials into the caller's workspace and one reduction kernel per output sums
 // them in sample order, so the result is the same bits on every run.
-#include "pit_common.h"
+#include "pit_layer.h"
 
 namespace {
 
@@ -35,10 +35,8 @@ struct DmArgs {
     unsigned values_bytes, dout_bytes;
 };
 
-__device__ __forceinline__ float head_c(const DmArgs& a, int h) {
-    if (a.scale) return a.scale[h];
-    return a.head_is_scale ? a.head[h] : head_scale_from_lmda(a.head[h]);
-}
+// the forward's scale_out, where the caller kept it, in place of the head
+__device__ __forceinline__ float scale_c(const DmArgs& a, int h) { return a.scale ? a.scale[h] : head_c(a, h); }
 
 __device__ __forceinline__ void load_pt(const float* mesh, long idx, int sdim, float& x, float& y, float& z) {
     const float* p = mesh + idx * sdim;
@@ -54,36 +52,15 @@ __device__ __forceinline__ float weight(float m, float c, float4 rs, bool valid,
     return keep ? __expf(rs.y - sv) * rs.z : 0.0f;
 }
 
-__device__ __forceinline__ float4 row_stat(const DmArgs& a, int mb, int h, int row) {
-    return *reinterpret_cast<const float4*>(a.rowstat + (((long)mb * a.n_head + h) * a.n_out + row) * 4);
-}
-
-// gv tile: acc[r] of lane l = sum_d g[i0 + acc_row(r, half)][d] * v[j0 + (l & 31)][d] for sample s, head h.  A lane holds
-// channels d0 + 4*half + u (u = 0..3) of its row / key: four MFMAs per group of 8 channels; channels, rows and keys out
-// of range read 0 through the buffer descriptors.
-__device__ __forceinline__ f32x16 gv_tile(const DmArgs& a, __amdgpu_buffer_rsrc_t rdo, __amdgpu_buffer_rsrc_t rv,
-                                          int s, int h, int i0, int j0) {
-    const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
+// gv tile (pit_layer.h) for sample s, head h, rows i0 .. i0 + 31 and keys j0 .. j0 + 31; the descriptors span the whole batch
+__device__ __forceinline__ f32x16 gv_tile_at(const DmArgs& a, __amdgpu_buffer_rsrc_t rdo, __amdgpu_buffer_rsrc_t rv,
+                                             int s, int h, int i0, int j0) {
+    const int l31 = threadIdx.x & 31;
     const int row = i0 + l31, key = j0 + l31;
     const bool rvalid = row < a.n_out, kvalid = key < a.n_in;
     const unsigned gbase = rvalid ? (unsigned)(((long)s * a.dout_bstride + (long)row * a.ld_dout + a.out_col0 + (long)h * a.dim) * 4) : 0u;
     const unsigned vbase = kvalid ? (unsigned)(((long)s * a.values_bstride + (long)key * a.ld_values) * 4) : 0u;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    for (int d0 = 0; d0 < a.dim; d0 += 8) {
-        float ga[4], vb[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int d = d0 + 4 * half + u;
-            const bool ok = d < a.dim;
-            ga[u] = buf_load(rdo, (rvalid && ok) ? gbase + (unsigned)d * 4u : a.dout_bytes);
-            vb[u] = buf_load(rv, (kvalid && ok) ? vbase + (unsigned)d * 4u : a.values_bytes);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc = mfma_32x32x2(ga[u], vb[u], acc);
-    }
-    return acc;
+    return gv_tile(rdo, rv, gbase, rvalid, vbase, kvalid, a.dim, a.dout_bytes, a.values_bytes);
 }
 
 // sum over the 32 lanes of a half-wave (lanes l and l ^ 32 keep their own sums)
@@ -112,9 +89,9 @@ __global__ __launch_bounds__(64) void dmesh_rows_dense(DmArgs a) {
         s_x[lane] = p;
     }
     for (int h = 0; h < a.n_head; ++h) {
-        const float c = head_c(a, h);
+        const float c = scale_c(a, h);
         __syncthreads();
-        if (lane < 32) s_rs[lane] = row_stat(a, mb, h, min(i0 + lane, a.n_out - 1));
+        if (lane < 32) s_rs[lane] = row_stat(a.rowstat, a.n_head, a.n_out, mb, h, min(i0 + lane, a.n_out - 1));
         __syncthreads();
         float ap[16];
 #pragma unroll
@@ -124,7 +101,7 @@ __global__ __launch_bounds__(64) void dmesh_rows_dense(DmArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) w2[r][0] = w2[r][1] = w2[r][2] = 0.0f;
             for (int j0 = 0; j0 < a.n_in; j0 += 32) {
-                const f32x16 gv = gv_tile(a, rdo, rv, s, h, i0, j0);
+                const f32x16 gv = gv_tile_at(a, rdo, rv, s, h, i0, j0);
                 const int key = j0 + l31;
                 const bool kv = key < a.n_in;
                 float yx, yy, yz;
@@ -194,7 +171,7 @@ __global__ __launch_bounds__(64) void dmesh_cols_dense(DmArgs a) {
     load_pt(a.mesh_in, (long)mb * a.n_in + (kv ? key : 0), a.sdim, yx, yy, yz);
     float dy[3] = {0.0f, 0.0f, 0.0f};
     for (int h = 0; h < a.n_head; ++h) {
-        const float c = head_c(a, h);
+        const float c = scale_c(a, h);
         float acc[3] = {0.0f, 0.0f, 0.0f};
         for (int i0 = 0; i0 < a.n_out; i0 += 32) {
             __syncthreads();
@@ -202,11 +179,11 @@ __global__ __launch_bounds__(64) void dmesh_cols_dense(DmArgs a) {
                 const int row = min(i0 + lane, a.n_out - 1);
                 float4 p; load_pt(a.mesh_out, (long)mb * a.n_out + row, a.sdim, p.x, p.y, p.z); p.w = 0.0f;
                 s_x[lane] = p;
-                s_rs[lane] = row_stat(a, mb, h, row);
+                s_rs[lane] = row_stat(a.rowstat, a.n_head, a.n_out, mb, h, row);
                 s_a[lane] = a.a_ws[((long)s * a.n_head + h) * a.n_out + row];
             }
             __syncthreads();
-            const f32x16 gv = gv_tile(a, rdo, rv, s, h, i0, j0);
+            const f32x16 gv = gv_tile_at(a, rdo, rv, s, h, i0, j0);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int ri = acc_row(r, half);
@@ -255,8 +232,8 @@ __global__ __launch_bounds__(256) void dmesh_rows_lists(DmArgs a) {
     const int* list = a.nbr_idx + rid * a.cap;
     double dx[3] = {0.0, 0.0, 0.0};
     for (int h = 0; h < a.n_head; ++h) {
-        const float c = head_c(a, h);
-        const float4 rs = row_stat(a, mb, h, row);
+        const float c = scale_c(a, h);
+        const float4 rs = row_stat(a.rowstat, a.n_head, a.n_out, mb, h, row);
         double A = 0.0, B[3] = {0.0, 0.0, 0.0}, C[3] = {0.0, 0.0, 0.0};
         for (int base = 0; base < total; base += 64) {
             const int e = base + lane;
@@ -271,10 +248,10 @@ __global__ __launch_bounds__(256) void dmesh_rows_lists(DmArgs a) {
                 const int src = __builtin_ctzll(mask);
                 mask &= mask - 1ull;
                 const int jj = __builtin_amdgcn_readlane(j, src);
-                const double pp = (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), src));
-                const float d0 = __fsub_rn(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(yx), src)), xx);
-                const float d1 = __fsub_rn(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(yy), src)), xy);
-                const float d2 = __fsub_rn(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(yz), src)), xz);
+                const double pp = (double)lane_f(p, src);
+                const float d0 = __fsub_rn(lane_f(yx, src), xx);
+                const float d1 = __fsub_rn(lane_f(yy, src), xy);
+                const float d2 = __fsub_rn(lane_f(yz, src), xz);
                 const double gv = (double)wave_dot(a, s, h, row, jj);
                 A += pp * gv;
                 B[0] += pp * gv * d0; B[1] += pp * gv * d1; B[2] += pp * gv * d2;
@@ -302,7 +279,7 @@ __global__ __launch_bounds__(256) void dmesh_cols_lists(DmArgs a) {
     const int* rrow = a.rev_row + (long)mb * a.n_out * a.cap;
     double dy[3] = {0.0, 0.0, 0.0};
     for (int h = 0; h < a.n_head; ++h) {
-        const float c = head_c(a, h);
+        const float c = scale_c(a, h);
         const float* arow = a.a_ws + ((long)s * a.n_head + h) * a.n_out;
         double acc[3] = {0.0, 0.0, 0.0};
         auto add = [&](int nrow, float p, float xx, float xy, float xz) {
@@ -311,10 +288,10 @@ __global__ __launch_bounds__(256) void dmesh_cols_lists(DmArgs a) {
                 const int src = __builtin_ctzll(mask);
                 mask &= mask - 1ull;
                 const int ii = __builtin_amdgcn_readlane(nrow, src);
-                const double pp = (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), src));
-                const float d0 = __fsub_rn(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(xx), src)), yx);
-                const float d1 = __fsub_rn(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(xy), src)), yy);
-                const float d2 = __fsub_rn(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(xz), src)), yz);
+                const double pp = (double)lane_f(p, src);
+                const float d0 = __fsub_rn(lane_f(xx, src), yx);
+                const float d1 = __fsub_rn(lane_f(xy, src), yy);
+                const float d2 = __fsub_rn(lane_f(xz, src), yz);
                 const double t = pp * ((double)wave_dot(a, s, h, ii, key) - (double)arow[ii]);
                 acc[0] += t * d0; acc[1] += t * d1; acc[2] += t * d2;
             }
@@ -327,7 +304,7 @@ __global__ __launch_bounds__(256) void dmesh_cols_lists(DmArgs a) {
             float xx, xy, xz;
             load_pt(a.mesh_out, (long)mb * a.n_out + nrow, a.sdim, xx, xy, xz);
             const float m = sq_dist3(xx, xy, xz, yx, yy, yz, false, 0.0f);
-            add(nrow, weight(m, c, row_stat(a, mb, h, nrow), valid, 1), xx, xy, xz);
+            add(nrow, weight(m, c, row_stat(a.rowstat, a.n_head, a.n_out, mb, h, nrow), valid, 1), xx, xy, xz);
         }
         if (!a.complete) {                                         // rows that overflowed are not in the transposed lists
             for (int base = 0; base < a.n_out; base += 64) {
@@ -337,7 +314,7 @@ __global__ __launch_bounds__(256) void dmesh_cols_lists(DmArgs a) {
                 float xx, xy, xz;
                 load_pt(a.mesh_out, (long)mb * a.n_out + nrow, a.sdim, xx, xy, xz);
                 const float m = sq_dist3(xx, xy, xz, yx, yy, yz, false, 0.0f);
-                add(nrow, weight(m, c, row_stat(a, mb, h, nrow), valid, 1), xx, xy, xz);
+                add(nrow, weight(m, c, row_stat(a.rowstat, a.n_head, a.n_out, mb, h, nrow), valid, 1), xx, xy, xz);
             }
         }
         const double c2 = 2.0 * (double)c;
@@ -376,8 +353,8 @@ __global__ __launch_bounds__(256) void dmesh_rows_wide(DmArgs a) {
     const int masked = sparse ? 1 : a.masked;
     double dx[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int h = 0; h < a.n_head; ++h) {
-        const float c = head_c(a, h);
-        const float4 rs = row_stat(a, mb, h, row);
+        const float c = scale_c(a, h);
+        const float4 rs = row_stat(a.rowstat, a.n_head, a.n_out, mb, h, row);
         double A = 0.0, B[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, C[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         for (int base = 0; base < total; base += 64) {
             const int e = base + lane;
@@ -390,12 +367,12 @@ __global__ __launch_bounds__(256) void dmesh_rows_wide(DmArgs a) {
                 const int src = __builtin_ctzll(mask);
                 mask &= mask - 1ull;
                 const int jj = __builtin_amdgcn_readlane(j, src);
-                const double pp = (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), src));
+                const double pp = (double)lane_f(p, src);
                 const double gv = (double)wave_dot(a, s, h, row, jj);
                 A += pp * gv;
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
-                    const float yk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pt8_at(y, k)), src));
+                    const float yk = lane_f(pt8_at(y, k), src);
                     const float d = __fsub_rn(yk, pt8_at(x, k));
                     B[k] += pp * gv * d;
                     C[k] += pp * d;
@@ -422,22 +399,22 @@ __global__ __launch_bounds__(256) void dmesh_cols_wide(DmArgs a) {
     const int masked = sparse ? 1 : a.masked;
     double dy[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int h = 0; h < a.n_head; ++h) {
-        const float c = head_c(a, h);
+        const float c = scale_c(a, h);
         const float* arow = a.a_ws + ((long)s * a.n_head + h) * a.n_out;
         double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         auto add = [&](int nrow, bool valid) {
             const pt8 x = load_pt8(a.mesh_out, (long)mb * a.n_out + nrow, a.sdim, a.sdim);
-            const float p = weight(sq_dist8t<false>(x, y, a.sdim, 0.0f), c, row_stat(a, mb, h, nrow), valid, masked);
+            const float p = weight(sq_dist8t<false>(x, y, a.sdim, 0.0f), c, row_stat(a.rowstat, a.n_head, a.n_out, mb, h, nrow), valid, masked);
             unsigned long long mask = __builtin_amdgcn_ballot_w64(p != 0.0f);
             while (mask) {
                 const int src = __builtin_ctzll(mask);
                 mask &= mask - 1ull;
                 const int ii = __builtin_amdgcn_readlane(nrow, src);
-                const double pp = (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), src));
+                const double pp = (double)lane_f(p, src);
                 const double t = pp * ((double)wave_dot(a, s, h, ii, key) - (double)arow[ii]);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
-                    const float xk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pt8_at(x, k)), src));
+                    const float xk = lane_f(pt8_at(x, k), src);
                     acc[k] += t * __fsub_rn(xk, pt8_at(y, k));
                 }
             }

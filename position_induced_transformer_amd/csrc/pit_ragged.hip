@@ -21,7 +21,7 @@
 // per mesh - 0 reads the one (n, space_dim) mesh in place for every sample, no expanded copy exists - and a length pointer that may
 // be NULL (every sample has the full width: the shared side has no padding).  Both are kernel arguments, so the branch is uniform
 // and the stride-0 address is the same for every sample; statistics, lists, rowstat, values and d(values) stay per sample.
-#include "pit_common.h"
+#include "pit_layer.h"
 
 namespace {
 
@@ -122,20 +122,12 @@ __global__ __launch_bounds__(256) void ragged_select_kernel(RagSelectArgs a) {
 }
 
 // ---- attention ------------------------------------------------------------------------------------------------------
-struct RagArgs {
+struct RagArgs : LayerIO {
     const float* mesh_out; const float* mesh_in;
     long mo_stride, mi_stride;   // as in RagSelectArgs
     const int* len_out; const int* len_in;
     int batch, n_out, n_in, sdim;
-    const float* values; int dim; long ld_values, values_bstride;
-    const float* head; int n_head, head_is_scale;
-    const float* stats; const float* rank_w; int masked;
-    float* out; long ld_out, out_bstride; int out_col0, copy_inputs;
-    float* rowstat; float* scale_out;
-    const float* d_out; long ld_dout, dout_bstride;
-    float* d_values; long ld_dvalues, dvalues_bstride; int add_residual;
-    double* dscale_acc;
-    int colgroups;       // groups of 256 value columns
+    const float* rank_w;
 };
 
 // the tile's contraction for one wave: acc[r] += w[t][r] * x[t][col] over the tile's first `cnt` items; x rows ldx apart.
@@ -175,7 +167,7 @@ __global__ __launch_bounds__(256) void ragged_rows_kernel(RagArgs a) {
     const bool cvalid = col < a.dim;
     const int rows_here = min(RT, a.n_out - r0);          // rows of this tile inside the padded width
     const int live = max(0, min(RT, lo - r0));            // ... inside the sample
-    const float c = a.head_is_scale ? a.head[h] : head_scale_from_lmda(a.head[h]);
+    const float c = head_c(a, h);
 
     if (MODE == 0) {
         if (a.copy_inputs && h == 0 && cvalid)            // torch.cat((inputs, conv), -1): the copied columns as they are
@@ -203,7 +195,7 @@ __global__ __launch_bounds__(256) void ragged_rows_kernel(RagArgs a) {
             st.y = __fmul_rn(c, a.stats[2 * rows_total + row]);
             st.z = 0.0f; st.w = 0.0f;
         } else {
-            st = *reinterpret_cast<const float4*>(a.rowstat + (((long)s * a.n_head + h) * a.n_out + r0 + r) * 4);
+            st = row_stat(a.rowstat, a.n_head, a.n_out, s, h, r0 + r);
         }
         s_rs[tid] = st;
     }
@@ -306,7 +298,7 @@ __global__ __launch_bounds__(256) void ragged_cols_kernel(RagArgs a) {
 #pragma unroll
     for (int r = 0; r < RT; ++r) tot[r] = 0.0;
     for (int h = 0; h < a.n_head; ++h) {
-        const float c = a.head_is_scale ? a.head[h] : head_scale_from_lmda(a.head[h]);
+        const float c = head_c(a, h);
         const float* go = a.d_out + (long)s * a.dout_bstride + a.out_col0 + (long)h * a.dim + col;
         for (int n0 = 0; n0 < lo; n0 += KT) {
             const int cnt = min(KT, lo - n0);
@@ -383,7 +375,7 @@ __global__ __launch_bounds__(256) void ragged_list_rows_kernel(RagArgs a, RagLis
     const int s = (int)(row / a.n_out), n = (int)(row - (long)s * a.n_out);
     const int h = blockIdx.y, cg = blockIdx.z;
     const int lo = clamp_len(a.len_out, s, a.n_out), li = clamp_len(a.len_in, s, a.n_in);
-    const float c = a.head_is_scale ? a.head[h] : head_scale_from_lmda(a.head[h]);
+    const float c = head_c(a, h);
     int col[LQ]; bool cv[LQ];
 #pragma unroll
     for (int q = 0; q < LQ; ++q) { col[q] = cg * 64 * LQ + q * 64 + lane; cv[q] = col[q] < a.dim; }
@@ -436,7 +428,7 @@ __global__ __launch_bounds__(256) void ragged_list_rows_kernel(RagArgs a, RagLis
             const int src = __builtin_ctzll(mask);
             mask &= mask - 1ull;
             const int jj = __builtin_amdgcn_readlane(j, src);
-            const float pv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), src));
+            const float pv = lane_f(p, src);
             const float* vr = vals + (long)jj * a.ld_values;
 #pragma unroll
             for (int q = 0; q < LQ; ++q) acc[q] += pv * (cv[q] ? vr[col[q]] : 0.0f);
@@ -484,10 +476,10 @@ __global__ __launch_bounds__(256) void ragged_list_cols_kernel(RagArgs a, RagLis
     const int* cnts = L.cnt + (long)s * a.n_out;
     float acc[LQ] = {0.0f, 0.0f, 0.0f, 0.0f};
     for (int h = 0; h < a.n_head; ++h) {
-        const float c = a.head_is_scale ? a.head[h] : head_scale_from_lmda(a.head[h]);
+        const float c = head_c(a, h);
         const float* go = a.d_out + (long)s * a.dout_bstride + a.out_col0 + (long)h * a.dim;
         auto add_row = [&](int n) {
-            const float4 rs = *reinterpret_cast<const float4*>(a.rowstat + (((long)s * a.n_head + h) * a.n_out + n) * 4);
+            const float4 rs = row_stat(a.rowstat, a.n_head, a.n_out, s, h, n);
             const float m = dist3(load_pt3(a.mesh_out + (long)s * a.mo_stride + (long)n * a.sdim, a.sdim), xi);
             const float sv = __fmul_rn(m, c);
             if (sv <= rs.x) {
@@ -750,11 +742,9 @@ static int posatt_ragged_fwd(const float* mesh_out, const float* mesh_in, int me
     a.mesh_out = mesh_out; a.mesh_in = mesh_in; a.len_out = len_out; a.len_in = len_in;
     a.mo_stride = out_stride * space_dim; a.mi_stride = in_stride * space_dim;
     a.batch = mesh_batch; a.n_out = n_out; a.n_in = n_in; a.sdim = space_dim;
-    a.values = values; a.dim = dim; a.ld_values = ld_values; a.values_bstride = values_bstride;
-    a.head = head; a.n_head = n_head; a.head_is_scale = head_is_scale;
-    a.stats = stats; a.rank_w = rank_w; a.masked = masked;
-    a.out = out; a.ld_out = ld_out; a.out_bstride = out_bstride; a.out_col0 = out_col0; a.copy_inputs = copy_inputs;
-    a.rowstat = rowstat; a.scale_out = scale_out;
+    a.rank_w = rank_w;
+    layer_set_fwd(a, values, dim, ld_values, values_bstride, head, n_head, head_is_scale, stats, masked, out, ld_out, out_bstride, out_col0,
+                  copy_inputs, rowstat, scale_out);
     a.colgroups = (dim + 255) / 256;
     if ((long)n_head * a.colgroups > 65535) return PIT_ERR_SIZE;
     if (nbr_idx && masked) {
@@ -792,12 +782,8 @@ static int posatt_ragged_bwd(const float* mesh_out, const float* mesh_in, int me
     a.mesh_out = mesh_out; a.mesh_in = mesh_in; a.len_out = len_out; a.len_in = len_in;
     a.mo_stride = out_stride * space_dim; a.mi_stride = in_stride * space_dim;
     a.batch = mesh_batch; a.n_out = n_out; a.n_in = n_in; a.sdim = space_dim;
-    a.values = values; a.dim = dim; a.ld_values = ld_values; a.values_bstride = values_bstride;
-    a.head = scale ? scale : head; a.n_head = n_head; a.head_is_scale = (scale || head_is_scale) ? 1 : 0;
-    a.masked = masked; a.rowstat = const_cast<float*>(rowstat);
-    a.d_out = d_out; a.ld_dout = ld_dout; a.dout_bstride = dout_bstride; a.out_col0 = out_col0;
-    a.d_values = d_values; a.ld_dvalues = ld_dvalues; a.dvalues_bstride = dvalues_bstride; a.add_residual = add_residual;
-    a.dscale_acc = workspace;
+    layer_set_bwd(a, values, dim, ld_values, values_bstride, head, n_head, head_is_scale, scale, rowstat, masked, d_out, ld_dout, dout_bstride,
+                  out_col0, d_values, ld_dvalues, dvalues_bstride, add_residual, d_head, workspace);
     a.colgroups = (dim + 255) / 256;
     if ((long)n_head * a.colgroups > 65535) return PIT_ERR_SIZE;
     hipStream_t s = (hipStream_t)stream;
@@ -823,17 +809,8 @@ static int posatt_ragged_bwd(const float* mesh_out, const float* mesh_in, int me
             hipLaunchKernelGGL(ragged_rows_kernel<1>, grid, dim3(256), 0, s, a);
         }
         PIT_CHECK_LAUNCH();
-        if (!(accumulate_head & PIT_HEAD_DEFER)) {        // drain the accumulators, apply d c / d lmda (pit_posatt_dhead_finish)
-            double* ws[1] = {workspace};
-            float* dh[1] = {d_head};
-            const float* hd[1] = {head};
-            const float* sc[1] = {scale};
-            const int nh[1] = {n_head};
-            const int fl[1] = {(accumulate_head & PIT_HEAD_ACCUMULATE) | (head_is_scale ? PIT_HEAD_IS_SCALE : 0)};
-            return pit_posatt_dhead_finish(1, ws, dh, hd, sc, nh, fl, nullptr, stream);
-        }
     }
-    return 0;
+    return layer_finish_head(head, scale, d_head, workspace, n_head, accumulate_head, head_is_scale, stream);
 }
 
 extern "C" int pit_plan_ragged_fwd(const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,

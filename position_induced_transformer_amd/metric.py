@@ -161,15 +161,14 @@ class posatt_metric(nn.Module):
         if lengths is not None:
             raise NotImplementedError("lengths (ragged batches) with a caller-supplied distance matrix are not implemented")
 
-    def _plan(self, m_dist: torch.Tensor) -> ops.DistPlan:
-        """A shared (N, J) matrix keeps its plan: keyed on address, shape, version and locality, least recently used first out
-        (the plan holds the tensor, so its address cannot be handed to another tensor while the entry lives)."""
-        if m_dist.dim() != 2:
-            return ops.DistPlan(m_dist, self.locality)
-        key = (m_dist.data_ptr(), tuple(m_dist.shape), tuple(m_dist.stride()), m_dist._version, float(self.locality), m_dist.device.index)
+    def _cached_plan(self, key, build):
+        """A plan of tensors the caller keeps and shares over the batch stays: least recently used first out (the plan holds
+        its tensors, so their addresses cannot be handed to other tensors while the entry lives).  key None: not kept."""
+        if key is None:
+            return build()
         plan = self._plans.get(key)
         if plan is None:
-            plan = ops.DistPlan(m_dist, self.locality)
+            plan = build()
             while len(self._plans) >= self._PLAN_CACHE:
                 self._plans.popitem(last=False)
             self._plans[key] = plan
@@ -178,6 +177,12 @@ class posatt_metric(nn.Module):
         if ops._capturing():
             ops._pin(plan)
         return plan
+
+    def _plan(self, m_dist: torch.Tensor) -> ops.DistPlan:
+        """A shared (N, J) matrix keeps its plan: keyed on address, shape, version and locality."""
+        key = None if m_dist.dim() != 2 else (m_dist.data_ptr(), tuple(m_dist.shape), tuple(m_dist.stride()), m_dist._version,
+                                              float(self.locality), m_dist.device.index)
+        return self._cached_plan(key, lambda: ops.DistPlan(m_dist, self.locality))
 
     def forward_dist(self, m_dist, inputs, lengths=None):
         """The layer on a precomputed matrix of squared distances, (N, J) or (b, N, J)."""
@@ -189,21 +194,9 @@ class posatt_metric(nn.Module):
 
     def _list_plan(self, idx, sqd, n_in: int) -> ops.ListPlan:
         """Shared (N, K) lists keep their plan like a shared matrix does: keyed on both addresses, shapes, versions and locality."""
-        if idx.dim() != 2:
-            return ops.ListPlan(idx, sqd, n_in, self.locality)
-        key = ("list", idx.data_ptr(), sqd.data_ptr(), tuple(idx.shape), tuple(idx.stride()), tuple(sqd.stride()), idx._version,
-               sqd._version, int(n_in), float(self.locality), sqd.device.index)
-        plan = self._plans.get(key)
-        if plan is None:
-            plan = ops.ListPlan(idx, sqd, n_in, self.locality)
-            while len(self._plans) >= self._PLAN_CACHE:
-                self._plans.popitem(last=False)
-            self._plans[key] = plan
-        else:
-            self._plans.move_to_end(key)
-        if ops._capturing():
-            ops._pin(plan)
-        return plan
+        key = None if idx.dim() != 2 else ("list", idx.data_ptr(), sqd.data_ptr(), tuple(idx.shape), tuple(idx.stride()),
+                                           tuple(sqd.stride()), idx._version, sqd._version, int(n_in), float(self.locality), sqd.device.index)
+        return self._cached_plan(key, lambda: ops.ListPlan(idx, sqd, n_in, self.locality))
 
     def forward_list(self, idx, sqd, inputs, lengths=None):
         """The layer on candidate lists: ``idx`` (int32 / int64) and ``sqd`` (fp32), (N, K) or (b, N, K); slot (i, t) says that
@@ -215,27 +208,24 @@ class posatt_metric(nn.Module):
         plan = self._list_plan(idx, sqd, inputs.shape[1])
         return ops.posatt_list_apply(inputs, self.lmda, plan, self.n_head, concat=self._self_attn, sqd=sqd)
 
-    def _on_lists(self, mesh_out, mesh_in, inputs):
-        # lists formed for this call (pit_metric(..., neighbors=...)): their plan is built for this call too
-        lists = knn_lists(self.sqdist, mesh_out, mesh_in, None if self.neighbors == "auto" else self.neighbors, locality=self.locality)
-        self.last_lists = lists
-        ops.check_list_shapes(lists.idx, lists.sqd, inputs, self._self_attn)
-        plan = ops.ListPlan(lists.idx, lists.sqd, inputs.shape[1], self.locality)
-        return ops.posatt_list_apply(inputs, self.lmda, plan, self.n_head, concat=self._self_attn, sqd=lists.sqd)
+    def _on_meshes(self, mesh_out, mesh_in, inputs):
+        # distances formed for this call - kNN lists (pit_metric(..., neighbors=...)) or the whole matrix: their plan is built
+        # for this call too, like every per-sample mesh plan (the cache of forward_dist / forward_list is for what the caller keeps)
+        if self.neighbors is not None:
+            lists = knn_lists(self.sqdist, mesh_out, mesh_in, None if self.neighbors == "auto" else self.neighbors, locality=self.locality)
+            self.last_lists = lists
+            ops.check_list_shapes(lists.idx, lists.sqd, inputs, self._self_attn)
+            plan = ops.ListPlan(lists.idx, lists.sqd, inputs.shape[1], self.locality)
+            return ops.posatt_list_apply(inputs, self.lmda, plan, self.n_head, concat=self._self_attn, sqd=lists.sqd)
+        m_dist = self.sqdist(mesh_out, mesh_in)
+        ops.check_dist_shapes(m_dist, inputs, self._self_attn)
+        plan = ops.DistPlan(m_dist, self.locality)
+        return ops.posatt_dist_apply(inputs, self.lmda, plan, self.n_head, concat=self._self_attn, m_dist=m_dist)
 
     def forward(self, mesh, inputs, lengths=None):
         self._refuse_lengths(lengths)
         ops._check_dist_mode()
-        if self.neighbors is not None:
-            return self._on_lists(mesh, mesh, inputs)
-        return self._on_fresh(self.sqdist(mesh, mesh), inputs)
-
-    def _on_fresh(self, m_dist, inputs):
-        # a matrix formed for this call: its plan is built for this call too, like every per-sample mesh plan (the cache of
-        # forward_dist is for matrices the caller keeps)
-        ops.check_dist_shapes(m_dist, inputs, self._self_attn)
-        plan = ops.DistPlan(m_dist, self.locality)
-        return ops.posatt_dist_apply(inputs, self.lmda, plan, self.n_head, concat=self._self_attn, m_dist=m_dist)
+        return self._on_meshes(mesh, mesh, inputs)
 
     def dist2att(self, m_dist, scale, locality):
         """Dense attention weights ((b,) H, N, J) of pit.py:48-52 on ``m_dist``: the fused kernel run on the identity as values,
@@ -256,9 +246,7 @@ class posatt_cross_metric(posatt_metric):
     def forward(self, mesh_out, mesh_in, inputs, out_bf16: bool = False, len_out=None, len_in=None):
         self._refuse_lengths(len_out if len_out is not None else len_in)
         ops._check_dist_mode()
-        if self.neighbors is not None:
-            return self._on_lists(mesh_out, mesh_in, inputs)
-        return self._on_fresh(self.sqdist(mesh_out, mesh_in), inputs)
+        return self._on_meshes(mesh_out, mesh_in, inputs)
 
 
 class pit_metric(_pit.pit):

@@ -11,6 +11,7 @@ import ctypes
 import math
 import os
 import threading
+import types
 from collections import OrderedDict
 from typing import Optional
 
@@ -986,37 +987,70 @@ def _mesh_grads(ctx, values, head, rowstat, scale, d_out):
             d_mi.view(ctx.mesh_shapes[1]) if d_mi is not None else None)
 
 
+def _layer_outputs(values, head, plan, n_head: int, concat: bool, refusals, shared_ok: bool):
+    """What a layer node on a plan beside the main path does before its launch: checks (values, head, plan, n_head, concat) and
+    allocates out, rowstat and scale.  ``refusals``: the plan's words for a wrong point count, a wrong batch and a concat whose
+    two sides differ (None: not checked); ``shared_ok``: one geometry may serve the whole batch.  Returns the row view of the
+    values and the flat head with them."""
+    _need_gpu(values, head)
+    values = _row_view(values)
+    b, j, d = values.shape
+    points, batch, square = refusals
+    if j != plan.n_in:
+        raise RuntimeError(points.format(j=j, n_in=plan.n_in))
+    if plan.mesh_batch != b and not (shared_ok and plan.mesh_batch == 1):
+        raise RuntimeError(batch)
+    if square is not None and concat and plan.n_out != plan.n_in:
+        raise RuntimeError(square)
+    head = head.detach().reshape(-1).contiguous()
+    if head.numel() != n_head:
+        raise RuntimeError("lmda must hold one value per head")
+    width = (n_head + (1 if concat else 0)) * d
+    out = torch.empty((b, plan.n_out, width), device=values.device, dtype=torch.float32)
+    rowstat = torch.empty((plan.mesh_batch, n_head, plan.n_out, 4), device=values.device, dtype=torch.float32)
+    scale = torch.empty((n_head,), device=values.device, dtype=torch.float32)
+    return values, head, out, rowstat, scale
+
+
+def _layer_io(values, head, n_head: int, is_scale: bool, concat: bool, with_batch: bool, rowstat, scale, out=None,
+              d_out=None, d_values=None, d_head=None, work=None):
+    """The argument groups of a layer entry (_lib.values_args ...) around which a plan places its geometry and extras: of a
+    forward entry when ``out`` is given, of a backward entry when ``d_out`` is."""
+    b, j, d = values.shape
+    io = types.SimpleNamespace(batch=b, dim=d, n_head=n_head, values=_lib.values_args(values, with_batch),
+                               tail=(MATH_MODES["fp32"], _lib.stream_ptr()))
+    if d_out is None:
+        io.head = _lib.head_args(head, n_head, is_scale)
+        io.out = _lib.out_args(out, d, concat, rowstat, scale)
+    else:
+        io.head = _lib.head_args(head, n_head, is_scale, scale)
+        io.rowstat = rowstat.data_ptr()
+        io.d_out = _lib.dout_args(d_out, d, concat)
+        io.d_values = _lib.dvalues_args(d_values, j, d, concat)
+        io.d_head = _lib.dhead_args(d_head, work)
+    return io
+
+
 class _PosAttRagged(torch.autograd.Function):
     """_PosAtt on a ragged plan (MeshPlan with lengths): pit_posatt_ragged_fwd / _bwd, one launch per layer and direction
     (+ the d(lmda) finish); none of the fused / union / tiled / paired launches is taken."""
 
     @staticmethod
-    def forward(ctx, values, head, plan: MeshPlan, n_head: int, concat: bool, head_is_scale: bool):
-        _need_gpu(values, head)
-        values = _row_view(values)
-        b, j, d = values.shape
-        if j != plan.n_in:
-            raise RuntimeError(f"inputs have {j} points but mesh_in has {plan.n_in}")
-        if plan.mesh_batch != b:
-            raise RuntimeError("mesh batch and input batch differ")
-        head = head.detach().reshape(-1).contiguous()
-        if head.numel() != n_head:
-            raise RuntimeError("lmda must hold one value per head")
-        width = (n_head + (1 if concat else 0)) * d
-        out = torch.empty((b, plan.n_out, width), device=values.device, dtype=torch.float32)
-        rowstat = torch.empty((b, n_head, plan.n_out, 4), device=values.device, dtype=torch.float32)
-        scale = torch.empty((n_head,), device=values.device, dtype=torch.float32)
+    def _geometry(plan: MeshPlan, direction: str):
         # (a shared mesh against ragged clouds: the strided entries - stride 0, no length on the shared side)
-        entry, extra = ("pit_posatt_ragged_fwd", ()) if plan.shared is None else ("pit_posatt_ragged_strided_fwd", plan.sample_strides())
+        entry, extra = ("pit_posatt_ragged_", ()) if plan.shared is None else ("pit_posatt_ragged_strided_", plan.sample_strides())
+        return entry + direction, (plan.mesh_out.data_ptr(), plan.mesh_in.data_ptr(), plan.mesh_batch, plan.n_out, plan.n_in, plan.sdim,
+                                   *extra, _lib.ptr(plan.len_out), _lib.ptr(plan.len_in))
+
+    @staticmethod
+    def forward(ctx, values, head, plan: MeshPlan, n_head: int, concat: bool, head_is_scale: bool):
+        refusals = ("inputs have {j} points but mesh_in has {n_in}", "mesh batch and input batch differ", None)
+        values, head, out, rowstat, scale = _layer_outputs(values, head, plan, n_head, concat, refusals, False)
+        io = _layer_io(values, head, n_head, head_is_scale, concat, False, rowstat, scale, out=out)
+        entry, geometry = _PosAttRagged._geometry(plan, "fwd")
         rc = getattr(_lib.lib(), entry)(
-            plan.mesh_out.data_ptr(), plan.mesh_in.data_ptr(), b, plan.n_out, plan.n_in, plan.sdim, *extra,
-            _lib.ptr(plan.len_out), _lib.ptr(plan.len_in),
-            values.data_ptr(), d, values.stride(1), values.stride(0),
-            head.data_ptr(), n_head, 1 if head_is_scale else 0,
-            plan.stats.data_ptr(), plan.rank_w_dev.data_ptr(), 1 if plan.masked else 0,
-            out.data_ptr(), out.stride(1), out.stride(0), d if concat else 0, 1 if concat else 0,
-            rowstat.data_ptr(), scale.data_ptr(), _lib.ptr(plan.nbr_idx), _lib.ptr(plan.nbr_cnt), plan.nbr_cap,
-            MATH_MODES["fp32"], _lib.stream_ptr())
+            *geometry, *io.values, *io.head, plan.stats.data_ptr(), plan.rank_w_dev.data_ptr(), 1 if plan.masked else 0, *io.out,
+            _lib.ptr(plan.nbr_idx), _lib.ptr(plan.nbr_cnt), plan.nbr_cap, *io.tail)
         _lib.check(rc, entry)
         ctx.plan, ctx.n_head, ctx.concat, ctx.head_is_scale = plan, n_head, concat, head_is_scale
         ctx.save_for_backward(values, head, rowstat, scale)
@@ -1034,17 +1068,12 @@ class _PosAttRagged(torch.autograd.Function):
         d_head = torch.empty((n_head,), device=values.device, dtype=torch.float32) if need_h else None
         work = _dscale_workspace(values.device, n_head) if need_h else None
         if need_v or need_h:
-            entry, extra = ("pit_posatt_ragged_bwd", ()) if plan.shared is None else ("pit_posatt_ragged_strided_bwd", plan.sample_strides())
+            io = _layer_io(values, head, n_head, ctx.head_is_scale, ctx.concat, False, rowstat, scale, d_out=d_out,
+                           d_values=d_values, d_head=d_head, work=work)
+            entry, geometry = _PosAttRagged._geometry(plan, "bwd")
             rc = getattr(_lib.lib(), entry)(
-                plan.mesh_out.data_ptr(), plan.mesh_in.data_ptr(), b, plan.n_out, plan.n_in, plan.sdim, *extra,
-                _lib.ptr(plan.len_out), _lib.ptr(plan.len_in),
-                values.data_ptr(), d, values.stride(1), values.stride(0),
-                head.data_ptr(), n_head, 1 if ctx.head_is_scale else 0, scale.data_ptr(),
-                rowstat.data_ptr(), 1 if plan.masked else 0,
-                d_out.data_ptr(), d_out.stride(1), d_out.stride(0), d if ctx.concat else 0,
-                _lib.ptr(d_values), d, j * d, 1 if ctx.concat else 0,
-                _lib.ptr(d_head), 0, _lib.ptr(work), _lib.ptr(plan.nbr_idx), _lib.ptr(plan.nbr_cnt), plan.nbr_cap,
-                _lib.ptr(plan.rev_ptr), _lib.ptr(plan.rev_row), MATH_MODES["fp32"], _lib.stream_ptr())
+                *geometry, *io.values, *io.head, io.rowstat, 1 if plan.masked else 0, *io.d_out, *io.d_values, *io.d_head,
+                _lib.ptr(plan.nbr_idx), _lib.ptr(plan.nbr_cnt), plan.nbr_cap, _lib.ptr(plan.rev_ptr), _lib.ptr(plan.rev_row), *io.tail)
             _lib.check(rc, entry)
         return d_values, d_head, None, None, None, None
 
@@ -1547,49 +1576,53 @@ class DistPlan:
         if _capturing():
             _pin(self)
 
+    REFUSALS = ("inputs have {j} points but the distance matrix has {n_in} columns", "distance-matrix batch and input batch differ",
+                "the self-attention form needs a square distance matrix")
+    NOT_THE_SOURCE = "m_dist is not the matrix the plan was built from"
 
-class _PosAttDist(torch.autograd.Function):
-    """pit.py:48-57 (+ the concat of :44) on a DistPlan: pit_distmat_fwd / _bwd, one autograd node.  ``m_dist`` arrives only
-    when it requires grad and then receives d loss / d m."""
+    def source_grad_shape(self):
+        return (self.mesh_batch, self.n_out, self.n_in)
+
+    def _geometry(self):
+        return (self.m.data_ptr(), self.ld_m, self.m_bstride, self.n_out, self.n_in)
+
+    def launch_fwd(self, io) -> None:
+        rc = _lib.lib().pit_distmat_fwd(*self._geometry(), *io.values, *io.head, self.stats.data_ptr(), self.rank_w, 1 if self.masked else 0,
+                                        *io.out, *io.tail)
+        _lib.check(rc, "pit_distmat_fwd")
+
+    def launch_bwd(self, io, grads) -> None:
+        """``grads``: d_source (None: not wanted), the forward's result with it, and whether d(values) is wanted."""
+        L = _lib.lib()
+        a_ws = None
+        if grads.d_source is not None:
+            a_ws = torch.empty(((L.pit_distmat_bwd_workspace(io.batch, self.n_out, io.n_head) + 3) // 4,), device=self.m.device, dtype=torch.float32)
+        rc = L.pit_distmat_bwd(*self._geometry(), *io.values, *io.head, io.rowstat, 1 if self.masked else 0, *io.d_out, *io.d_values, *io.d_head,
+                               _lib.ptr(grads.d_source), *_lib.saved_out_args(grads.out), _lib.ptr(a_ws), *io.tail)
+        _lib.check(rc, "pit_distmat_bwd")
+
+
+class _PosAttSupplied(torch.autograd.Function):
+    """pit.py:48-57 (+ the concat of :44) on supplied squared distances - a DistPlan (pit_distmat_fwd / _bwd) or a ListPlan
+    (pit_distlist_fwd / _bwd) - as one autograd node; the plan places its geometry around the shared argument groups.
+    ``source`` (the caller's m_dist / sqd) arrives only when it requires grad and then receives d loss / d source in its own
+    shape (for lists: 0 at padding)."""
 
     @staticmethod
-    def forward(ctx, values, head, plan: DistPlan, n_head: int, concat: bool, head_is_scale: bool, scale_in=None, m_dist=None):
-        _need_gpu(values, head)
-        values = _row_view(values)
-        b, j, d = values.shape
-        if j != plan.n_in:
-            raise RuntimeError(f"inputs have {j} points but the distance matrix has {plan.n_in} columns")
-        if plan.mesh_batch not in (1, b):
-            raise RuntimeError("distance-matrix batch and input batch differ")
-        if concat and plan.n_out != plan.n_in:
-            raise RuntimeError("the self-attention form needs a square distance matrix")
-        head = head.detach().reshape(-1).contiguous()
-        if head.numel() != n_head:
-            raise RuntimeError("lmda must hold one value per head")
-        width = (n_head + (1 if concat else 0)) * d
-        out = torch.empty((b, plan.n_out, width), device=values.device, dtype=torch.float32)
-        rowstat = torch.empty((plan.mesh_batch, n_head, plan.n_out, 4), device=values.device, dtype=torch.float32)
-        scale = torch.empty((n_head,), device=values.device, dtype=torch.float32)
+    def forward(ctx, values, head, plan, n_head: int, concat: bool, head_is_scale: bool, scale_in=None, source=None):
+        values, head, out, rowstat, scale = _layer_outputs(values, head, plan, n_head, concat, plan.REFUSALS, True)
         # route 'host': the kernels are handed the scale the host evaluated for lmda (scale_in), as in _PosAtt
         k_head, k_is_scale = (scale_in, True) if scale_in is not None else (head, head_is_scale)
-        rc = _lib.lib().pit_distmat_fwd(
-            plan.m.data_ptr(), plan.ld_m, plan.m_bstride, plan.n_out, plan.n_in,
-            values.data_ptr(), b, d, values.stride(1), values.stride(0),
-            k_head.data_ptr(), n_head, 1 if k_is_scale else 0,
-            plan.stats.data_ptr(), plan.rank_w, 1 if plan.masked else 0,
-            out.data_ptr(), out.stride(1), out.stride(0), d if concat else 0, 1 if concat else 0,
-            rowstat.data_ptr(), scale.data_ptr(), MATH_MODES["fp32"], _lib.stream_ptr())
-        _lib.check(rc, "pit_distmat_fwd")
+        plan.launch_fwd(_layer_io(values, k_head, n_head, k_is_scale, concat, True, rowstat, scale, out=out))
         ctx.plan, ctx.n_head, ctx.concat, ctx.head_is_scale = plan, n_head, concat, head_is_scale
-        ctx.m_shape = tuple(m_dist.shape) if m_dist is not None else None
-        # (d(m) needs a_i = g_i . out_i: the result itself is kept then)
-        ctx.save_for_backward(values, head, rowstat, scale, *((out,) if m_dist is not None else ()))
+        ctx.source_shape = tuple(source.shape) if source is not None else None
+        # (d(source) needs a_i = g_i . out_i: the result itself is kept then)
+        ctx.save_for_backward(values, head, rowstat, scale, *((out,) if source is not None else ()))
         return out
 
     @staticmethod
     def backward(ctx, d_out):
         values, head, rowstat, scale = ctx.saved_tensors[:4]
-        out = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
         plan, n_head = ctx.plan, ctx.n_head
         b, j, d = values.shape
         if d_out.dtype != torch.float32:
@@ -1597,27 +1630,32 @@ class _PosAttDist(torch.autograd.Function):
         d_out = _row_view(d_out)
         _need_gpu(d_out)
         need_v, need_h = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        need_m = ctx.m_shape is not None and ctx.needs_input_grad[7]
+        need_s = ctx.source_shape is not None and ctx.needs_input_grad[7]
         dev = values.device
         d_values = torch.empty((b, j, d), device=dev, dtype=torch.float32) if need_v else None
         d_head = torch.empty((n_head,), device=dev, dtype=torch.float32) if need_h else None
         work = _dscale_workspace(dev, n_head) if need_h else None
-        d_m = torch.empty((plan.mesh_batch, plan.n_out, plan.n_in), device=dev, dtype=torch.float32) if need_m else None
-        L = _lib.lib()
-        a_ws = torch.empty(((L.pit_distmat_bwd_workspace(b, plan.n_out, n_head) + 3) // 4,), device=dev, dtype=torch.float32) if need_m else None
-        if need_v or need_h or need_m:
-            rc = L.pit_distmat_bwd(
-                plan.m.data_ptr(), plan.ld_m, plan.m_bstride, plan.n_out, plan.n_in,
-                values.data_ptr(), b, d, values.stride(1), values.stride(0),
-                head.data_ptr(), n_head, 1 if ctx.head_is_scale else 0, scale.data_ptr(),
-                rowstat.data_ptr(), 1 if plan.masked else 0,
-                d_out.data_ptr(), d_out.stride(1), d_out.stride(0), d if ctx.concat else 0,
-                _lib.ptr(d_values), d, j * d, 1 if ctx.concat else 0,
-                _lib.ptr(d_head), 0, _lib.ptr(work),
-                _lib.ptr(d_m), _lib.ptr(out) if need_m else None, out.stride(1) if need_m else 0, out.stride(0) if need_m else 0,
-                _lib.ptr(a_ws), MATH_MODES["fp32"], _lib.stream_ptr())
-            _lib.check(rc, "pit_distmat_bwd")
-        return d_values, d_head, None, None, None, None, None, (d_m.view(ctx.m_shape) if d_m is not None else None)
+        d_source = torch.empty(plan.source_grad_shape(), device=dev, dtype=torch.float32) if need_s else None
+        if need_v or need_h or need_s:
+            io = _layer_io(values, head, n_head, ctx.head_is_scale, ctx.concat, True, rowstat, scale, d_out=d_out,
+                           d_values=d_values, d_head=d_head, work=work)
+            plan.launch_bwd(io, types.SimpleNamespace(d_source=d_source, out=ctx.saved_tensors[4] if need_s else None, need_values=need_v))
+        return d_values, d_head, None, None, None, None, None, (d_source.view(ctx.source_shape) if need_s else None)
+
+
+def _posatt_supplied_apply(values, lmda, plan, n_head: int, concat: bool, head_is_scale: bool, source):
+    _check_dist_mode()
+    if _capturing():
+        _pin(plan)                                 # its buffers' addresses are now baked into a hipGraph: never release them
+    values = materialize_coords(values)
+    c = host_head_scale(lmda) if (not head_is_scale and get_head_scale_route() == "host") else None
+    extra = ()
+    if source is not None and torch.is_grad_enabled() and source.requires_grad:
+        shape = plan.source_grad_shape()
+        if tuple(source.shape)[-2:] != shape[1:] or source.numel() != shape[0] * shape[1] * shape[2]:
+            raise ValueError(plan.NOT_THE_SOURCE)
+        extra = (source,)
+    return _PosAttSupplied.apply(values, lmda.reshape(-1), plan, n_head, concat, head_is_scale, c, *extra)
 
 
 @torch.compiler.disable
@@ -1628,17 +1666,7 @@ def posatt_dist_apply(values: torch.Tensor, lmda: torch.Tensor, plan: DistPlan, 
     (pit.py:44).  ``m_dist``: the caller's own tensor (the one ``plan`` was built from); when grad mode is on and it requires
     grad it becomes an input of the node and receives d loss / d m - autograd then carries the gradient on through whatever torch
     code formed the distances, for any metric.  fp32 math mode only; head-scale routes as in ``posatt_apply``."""
-    _check_dist_mode()
-    if _capturing():
-        _pin(plan)                                 # its buffers' addresses are now baked into a hipGraph: never release them
-    values = materialize_coords(values)
-    c = host_head_scale(lmda) if (not head_is_scale and get_head_scale_route() == "host") else None
-    extra = ()
-    if m_dist is not None and torch.is_grad_enabled() and m_dist.requires_grad:
-        if tuple(m_dist.shape)[-2:] != (plan.n_out, plan.n_in) or m_dist.numel() != plan.mesh_batch * plan.n_out * plan.n_in:
-            raise ValueError("m_dist is not the matrix the plan was built from")
-        extra = (m_dist,)
-    return _PosAttDist.apply(values, lmda.reshape(-1), plan, n_head, concat, head_is_scale, c, *extra)
+    return _posatt_supplied_apply(values, lmda, plan, n_head, concat, head_is_scale, m_dist)
 
 
 # ---- the same layer on candidate lists of caller-supplied squared distances (csrc/pit_distlist.hip; metric.py) -------------------
@@ -1755,78 +1783,32 @@ class ListPlan:
             self._rev = (rev_ptr.contiguous(), order.to(torch.int32).contiguous(), chunk_ptr, chunk_key.contiguous())
         return self._rev
 
+    REFUSALS = ("inputs have {j} points but the lists were planned for {n_in} keys", "list batch and input batch differ",
+                "the self-attention form needs one list per input point")
+    NOT_THE_SOURCE = "sqd is not the tensor the plan was built from"
 
-class _PosAttList(torch.autograd.Function):
-    """pit.py:48-57 (+ the concat of :44) on a ListPlan: pit_distlist_fwd / _bwd, one autograd node.  ``sqd`` arrives only when
-    it requires grad and then receives d loss / d sqd in its own shape (0 at padding)."""
+    def source_grad_shape(self):
+        return (self.mesh_batch, self.n_out, self.cap)
 
-    @staticmethod
-    def forward(ctx, values, head, plan: ListPlan, n_head: int, concat: bool, head_is_scale: bool, scale_in=None, sqd=None):
-        _need_gpu(values, head)
-        values = _row_view(values)
-        b, j, d = values.shape
-        if j != plan.n_in:
-            raise RuntimeError(f"inputs have {j} points but the lists were planned for {plan.n_in} keys")
-        if plan.mesh_batch not in (1, b):
-            raise RuntimeError("list batch and input batch differ")
-        if concat and plan.n_out != plan.n_in:
-            raise RuntimeError("the self-attention form needs one list per input point")
-        head = head.detach().reshape(-1).contiguous()
-        if head.numel() != n_head:
-            raise RuntimeError("lmda must hold one value per head")
-        width = (n_head + (1 if concat else 0)) * d
-        out = torch.empty((b, plan.n_out, width), device=values.device, dtype=torch.float32)
-        rowstat = torch.empty((plan.mesh_batch, n_head, plan.n_out, 4), device=values.device, dtype=torch.float32)
-        scale = torch.empty((n_head,), device=values.device, dtype=torch.float32)
-        k_head, k_is_scale = (scale_in, True) if scale_in is not None else (head, head_is_scale)
-        rc = _lib.lib().pit_distlist_fwd(
-            plan.idx.data_ptr(), plan.sqd.data_ptr(), plan.ld, plan.bstride, plan.cap, plan.n_out, plan.n_in,
-            values.data_ptr(), b, d, values.stride(1), values.stride(0),
-            k_head.data_ptr(), n_head, 1 if k_is_scale else 0,
-            plan.stats.data_ptr(), plan.rank_w, 1 if plan.masked else 0,
-            out.data_ptr(), out.stride(1), out.stride(0), d if concat else 0, 1 if concat else 0,
-            rowstat.data_ptr(), scale.data_ptr(), MATH_MODES["fp32"], _lib.stream_ptr())
+    def _geometry(self):
+        return (self.idx.data_ptr(), self.sqd.data_ptr(), self.ld, self.bstride, self.cap, self.n_out, self.n_in)
+
+    def launch_fwd(self, io) -> None:
+        rc = _lib.lib().pit_distlist_fwd(*self._geometry(), *io.values, *io.head, self.stats.data_ptr(), self.rank_w, 1 if self.masked else 0,
+                                         *io.out, *io.tail)
         _lib.check(rc, "pit_distlist_fwd")
-        ctx.plan, ctx.n_head, ctx.concat, ctx.head_is_scale = plan, n_head, concat, head_is_scale
-        ctx.sqd_shape = tuple(sqd.shape) if sqd is not None else None
-        # (d(sqd) needs a_i = g_i . out_i: the result itself is kept then)
-        ctx.save_for_backward(values, head, rowstat, scale, *((out,) if sqd is not None else ()))
-        return out
 
-    @staticmethod
-    def backward(ctx, d_out):
-        values, head, rowstat, scale = ctx.saved_tensors[:4]
-        out = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
-        plan, n_head = ctx.plan, ctx.n_head
-        b, j, d = values.shape
-        if d_out.dtype != torch.float32:
-            d_out = d_out.float()
-        d_out = _row_view(d_out)
-        _need_gpu(d_out)
-        need_v, need_h = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        need_s = ctx.sqd_shape is not None and ctx.needs_input_grad[7]
-        dev = values.device
-        d_values = torch.empty((b, j, d), device=dev, dtype=torch.float32) if need_v else None
-        d_head = torch.empty((n_head,), device=dev, dtype=torch.float32) if need_h else None
-        work = _dscale_workspace(dev, n_head) if need_h else None
-        d_sqd = torch.empty((plan.mesh_batch, plan.n_out, plan.cap), device=dev, dtype=torch.float32) if need_s else None
+    def launch_bwd(self, io, grads) -> None:
+        """``grads``: as DistPlan.launch_bwd; d(values) runs over the transposed index and a workspace of partial rows."""
         L = _lib.lib()
-        rev = plan.transposed() if need_v else (None, None, None, None)
-        dv_ws = torch.empty(((L.pit_distlist_bwd_workspace(b, plan.n_out, plan.cap, d) + 3) // 4,), device=dev, dtype=torch.float32) if need_v else None
-        if need_v or need_h or need_s:
-            rc = L.pit_distlist_bwd(
-                plan.idx.data_ptr(), plan.sqd.data_ptr(), plan.ld, plan.bstride, plan.cap, plan.n_out, plan.n_in,
-                values.data_ptr(), b, d, values.stride(1), values.stride(0),
-                head.data_ptr(), n_head, 1 if ctx.head_is_scale else 0, scale.data_ptr(),
-                rowstat.data_ptr(), 1 if plan.masked else 0,
-                d_out.data_ptr(), d_out.stride(1), d_out.stride(0), d if ctx.concat else 0,
-                _lib.ptr(d_values), d, j * d, 1 if ctx.concat else 0,
-                _lib.ptr(d_head), 0, _lib.ptr(work),
-                _lib.ptr(d_sqd), _lib.ptr(out) if need_s else None, out.stride(1) if need_s else 0, out.stride(0) if need_s else 0,
-                _lib.ptr(rev[0]), _lib.ptr(rev[1]), _lib.ptr(rev[2]), _lib.ptr(rev[3]), _lib.ptr(dv_ws),
-                MATH_MODES["fp32"], _lib.stream_ptr())
-            _lib.check(rc, "pit_distlist_bwd")
-        return d_values, d_head, None, None, None, None, None, (d_sqd.view(ctx.sqd_shape) if d_sqd is not None else None)
+        rev, dv_ws = (None, None, None, None), None
+        if grads.need_values:
+            rev = self.transposed()
+            dv_ws = torch.empty(((L.pit_distlist_bwd_workspace(io.batch, self.n_out, self.cap, io.dim) + 3) // 4,), device=self.idx.device,
+                                dtype=torch.float32)
+        rc = L.pit_distlist_bwd(*self._geometry(), *io.values, *io.head, io.rowstat, 1 if self.masked else 0, *io.d_out, *io.d_values, *io.d_head,
+                                _lib.ptr(grads.d_source), *_lib.saved_out_args(grads.out), *(_lib.ptr(t) for t in rev), _lib.ptr(dv_ws), *io.tail)
+        _lib.check(rc, "pit_distlist_bwd")
 
 
 @torch.compiler.disable
@@ -1837,17 +1819,7 @@ def posatt_list_apply(values: torch.Tensor, lmda: torch.Tensor, plan: ListPlan, 
     else); ``concat`` prepends the inputs (pit.py:44).  ``sqd``: the caller's own tensor (the one ``plan`` was built from); when
     grad mode is on and it requires grad it becomes an input of the node and receives d loss / d sqd in its shape, so autograd
     carries the gradient on to whatever formed the listed distances.  fp32 math mode only; head-scale routes as in ``posatt_apply``."""
-    _check_dist_mode()
-    if _capturing():
-        _pin(plan)                                 # its buffers' addresses are now baked into a hipGraph: never release them
-    values = materialize_coords(values)
-    c = host_head_scale(lmda) if (not head_is_scale and get_head_scale_route() == "host") else None
-    extra = ()
-    if sqd is not None and torch.is_grad_enabled() and sqd.requires_grad:
-        if tuple(sqd.shape)[-2:] != (plan.n_out, plan.cap) or sqd.numel() != plan.mesh_batch * plan.n_out * plan.cap:
-            raise ValueError("sqd is not the tensor the plan was built from")
-        extra = (sqd,)
-    return _PosAttList.apply(values, lmda.reshape(-1), plan, n_head, concat, head_is_scale, c, *extra)
+    return _posatt_supplied_apply(values, lmda, plan, n_head, concat, head_is_scale, sqd)
 
 
 # ---- one-launch MLP chains of the bf16 math mode (csrc/pit_chain.hip): hid 128 / 256 on a few thousand rows ----------------------
