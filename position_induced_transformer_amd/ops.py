@@ -124,22 +124,31 @@ def _flush_head_finishes(task: int) -> None:
         grp = [p for p in pend if p[0].device.index == dev]
         for i in range(0, len(grp), 32):
             part = grp[i:i + 32]
-            n = len(part)
             rider = None
             if job is not None and job[2].device.index == dev and job[2] == torch.cuda.current_stream(job[2].device):
                 rider, job = job, None
                 _PENDING_DW[task] = None
-            ws = (ctypes.c_void_p * n)(*[p[0].data_ptr() for p in part])
-            dh = (ctypes.c_void_p * n)(*[p[1].data_ptr() for p in part])
-            hd = (ctypes.c_void_p * n)(*[p[2].data_ptr() for p in part])
-            sc = (ctypes.c_void_p * n)(*[p[3].data_ptr() for p in part])
-            nh = (ctypes.c_int * n)(*[p[4] for p in part])
-            fl = (ctypes.c_int * n)(*[p[5] for p in part])
             with torch.cuda.device(dev):
-                rc = _lib.lib().pit_posatt_dhead_finish(n, ws, dh, hd, sc, nh, fl,
-                                                        ctypes.cast(ctypes.pointer(rider[0]), ctypes.c_void_p) if rider is not None else None,
-                                                        _lib.stream_ptr())
-            _lib.check(rc, "pit_posatt_dhead_finish")
+                _launch_head_finishes(part, rider)
+
+
+def _launch_head_finishes(entries, rider=None) -> None:
+    """ONE pit_posatt_dhead_finish launch on the current device and stream: d(lmda) of every layer in ``entries`` =
+    [(work, d_head, head, scale, n_head, flags), ...] from its accumulators ``work`` (flags: 1 = add into d_head in place,
+    4 = the head is the scale itself), with the postponed weight-gradient job ``rider`` (_PENDING_DW's form) riding along."""
+    n = len(entries)
+    ws, dh, hd, sc = ((ctypes.c_void_p * n)(*[_lib.ptr(e[i]) for e in entries]) for i in range(4))
+    nh = (ctypes.c_int * n)(*[e[4] for e in entries])
+    fl = (ctypes.c_int * n)(*[e[5] for e in entries])
+    rc = _lib.lib().pit_posatt_dhead_finish(n, ws, dh, hd, sc, nh, fl,
+                                            ctypes.cast(ctypes.pointer(rider[0]), ctypes.c_void_p) if rider is not None else None,
+                                            _lib.stream_ptr())
+    _lib.check(rc, "pit_posatt_dhead_finish")
+
+
+def _finish_heads_now(work, d_head, head, scale, n_head: int, flags: int) -> None:
+    """d(lmda) of ONE layer from freshly loaded accumulators, now."""
+    _launch_head_finishes([(work, d_head, head, scale, n_head, flags)])
 
 
 def _defer_head_begin(work: torch.Tensor) -> None:
@@ -167,6 +176,64 @@ def _defer_head_begin(work: torch.Tensor) -> None:
 def _defer_head_finish(work, d_head, head, scale, n_head: int, flags: int) -> None:
     _defer_head_begin(work)
     _PENDING_HEADS[_graph_task()].append((work, d_head, head, scale, n_head, flags))
+
+
+class _HeadGrad:
+    """Where ONE attention layer's d(lmda) goes, decided BEFORE the layer's backward launch (which adds d(scale) partial sums into
+    ``work``) and carried out by ``finish`` after it:
+      returned   lmda did not opt in (_grad_slot): ``d_head`` is a fresh tensor, finished now, handed to autograd;
+      in place   ``d_head`` is lmda.grad itself (``slot``), finished now, autograd gets None;
+      deferred   in place under DEFER_HEAD_FINISH: the layer's own accumulators (_layer_workspace), finished by the pass's ONE
+                 finishing launch (_flush_head_finishes); constructing the object performs _defer_head_begin.
+    What differs between the nodes is spelled at their call:
+      shared_workspace     the not-deferred accumulators are the stream's _dscale_workspace, which the kernels leave zeroed and
+                           which exists whether or not lmda needs a gradient (_PosAtt); otherwise a fresh torch.zeros buffer;
+      always_accumulators  accumulators although ``need`` is false: the launch reduces d(scale) unconditionally (_Encoder);
+      kernel_finishes      the launch itself forms d(lmda) unless deferred (_PosAtt's candidate-list / dense launch): it is handed
+                           ``d_head`` and ``acc`` (bit 1: add in place, bit 2: PIT_HEAD_DEFER) and ``finish`` only queues."""
+    __slots__ = ("need", "n_head", "scale_bit", "kernel_finishes", "slot", "defer", "work", "d_head")
+
+    def __init__(self, head_param, need: bool, n_head: int, device, head_is_scale: bool, *, shared_workspace: bool = False,
+                 always_accumulators: bool = False, kernel_finishes: bool = False):
+        self.need, self.n_head, self.kernel_finishes = bool(need), n_head, kernel_finishes
+        self.scale_bit = 4 if head_is_scale else 0
+        self.slot = _grad_slot(head_param) if need else None
+        self.defer = bool(DEFER_HEAD_FINISH and self.slot is not None)
+        if self.defer:
+            self.work = _layer_workspace(self.slot, n_head)
+            _defer_head_begin(self.work)            # (clears what an aborted pass left, before the kernel adds)
+        elif shared_workspace:
+            self.work = _dscale_workspace(device, n_head)
+        elif need or always_accumulators:
+            self.work = torch.zeros(n_head * 1024, device=device, dtype=torch.float64)
+        else:
+            self.work = None
+        if self.slot is not None:
+            self.d_head = self.slot                 # accumulate into lmda.grad in place
+        else:
+            self.d_head = torch.empty((n_head,), device=device, dtype=torch.float32) if need else None
+
+    @property
+    def acc(self) -> int:
+        return (1 if self.slot is not None else 0) | (2 if self.defer else 0)
+
+    def finish(self, head, scale):
+        """After the launch: what the backward returns to autograd for lmda (None: not wanted, or it went in place)."""
+        return _HeadGrad.finish_all([(self, head, scale)])[0]
+
+    @staticmethod
+    def finish_all(layers):
+        """``finish`` for [(_HeadGrad, head, scale), ...] of one node: the deferred layers are queued, all others share ONE launch."""
+        now = []
+        for g, head, scale in layers:
+            entry = (g.work, g.d_head, head, scale, g.n_head, (1 if g.slot is not None else 0) | g.scale_bit)
+            if g.defer:
+                _defer_head_finish(*entry)
+            elif g.need and not g.kernel_finishes:
+                now.append(entry)
+        if now:
+            _launch_head_finishes(now)
+        return [None if g.slot is not None else g.d_head for g, _, _ in layers]
 
 
 # The weight-gradient reductions of an MLP backward (dW2|db2, dW1|db1: nothing downstream in the pass reads
@@ -272,6 +339,13 @@ def _dw_take(device):
     return job
 
 
+def _dw_run_pending(device) -> None:
+    """For a backward whose launch carries no rider: the job the pass has postponed, if any, is performed now."""
+    job = _dw_take(device)
+    if job is not None:
+        _dw_run(job)
+
+
 BIG_RIDER_ROWS = 8192
 
 
@@ -322,6 +396,39 @@ def _grad_slot(param) -> Optional[torch.Tensor]:
     if param._backward_hooks or getattr(param, "_post_accumulate_grad_hooks", None):
         return None                      # hooks must see the gradient: return it to autograd
     return g
+
+
+def _mlp_grad_slots(params, shapes, needs, device, fresh: str = "zeros"):
+    """([d_w1, d_b1, d_w2, d_b2], in place?) for an MLP's weight gradients: the parameters' own .grad (the kernels accumulate) when
+    every one of them opted in and needs a gradient, else fresh tensors returned to autograd - ``fresh`` = "zeros": zeroed, the
+    kernels add into them (accumulate = 1); "empty": uninitialised, the kernels overwrite them (accumulate = 0: _Mlp)."""
+    slots = [_grad_slot(p) if isinstance(p, torch.nn.Parameter) else None for p in params]
+    if all(s is not None for s in slots) and all(needs):
+        return slots, True
+    new = torch.zeros if fresh == "zeros" else torch.empty
+    return [new(tuple(sh), device=device, dtype=torch.float32) for sh in shapes], False
+
+
+def _params_job(x, h, d_y, scratch, grads, dims, out_gelu: int, math: int, ld_dy=None):
+    """(MlpParamsJob, the tensors it points into) of an MLP's weight-gradient reductions (pit_mlp_bwd_params' argument list):
+    ``x`` (rows, n0) and ``h`` (rows, n1) the forward's operands, ``d_y`` the output gradient with row stride ``ld_dy``, ``scratch``
+    the data path's dZ1 (| dZ2), ``grads`` = (d_w1, d_b1, d_w2, d_b2) which it adds to, ``dims`` = (rows, n0, n1, n2)."""
+    d_w1, d_b1, d_w2, d_b2 = grads
+    st = _lib.MlpParamsJob(x.data_ptr(), x.stride(-2), *dims, h.data_ptr(), out_gelu, d_y.data_ptr(),
+                           d_y.stride(0) if ld_dy is None else ld_dy, d_w1.data_ptr(), d_b1.data_ptr(), d_w2.data_ptr(),
+                           d_b2.data_ptr(), 1, scratch.data_ptr(), math)
+    return st, (x, h, d_y, scratch, d_w1, d_b1, d_w2, d_b2)
+
+
+def _dw_deliver(job, inplace: bool, device):
+    """The weight-gradient tail of a fused edge node: ``job`` (_params_job) is postponed and carried by a later launch of the pass
+    in the in-place mode, performed now otherwise; returns the four gradients for autograd (None each when they went in place)."""
+    st, keep = job
+    if inplace and MLP_PARAMS_RIDER and _dw_deferrable(st.rows, st.n0, st.n1, st.n2, st.out_gelu, st.ld_dy):
+        _dw_defer(st, keep, device)
+    else:
+        _dw_run((st, keep, torch.cuda.current_stream(device)))
+    return (None,) * 4 if inplace else tuple(keep[4:])
 
 
 # bf16 STORAGE flags of the `math_mode` argument (include/pit_hip.h, PIT_IO_*)
@@ -1233,77 +1340,11 @@ class _PosAtt(torch.autograd.Function):
             raise NotImplementedError("the reproducible mode takes an fp32 d_out only")
         ordered_lists = repro and need_v and plan.nbr_idx is not None and plan.masked and plan.rev_ptr is not None and not io
         d_values = torch.empty((b, j, dv), device=values.device, dtype=torch.float32) if need_v else None
-        slot = _grad_slot(ctx.head_param) if need_h else None
-        if slot is not None:
-            d_head, acc_head = slot, 1                  # accumulate into lmda.grad in place
-        else:
-            d_head = torch.empty((n_head,), device=values.device, dtype=torch.float32) if need_h else None
-            acc_head = 0
-        defer = DEFER_HEAD_FINISH and slot is not None
-        work = _layer_workspace(slot, n_head) if defer else _dscale_workspace(values.device, n_head)
-        if defer:
-            acc_head |= 2                               # PIT_HEAD_DEFER: finished by _flush_head_finishes
-            _defer_head_begin(work)                     # (clears what an aborted pass left, before the kernel adds)
-
-        # an MLP's postponed weight-gradient reductions ride along - unless this is a candidate-list layer and the job is
-        # LARGE (the decoder MLP's: inside that launch it costs more than a launch of its own, measured 34.7 vs 16.1 +
-        # 15.7 us at Darcy b=8); left pending, the fused processor spreads it over its block launches (_Processor.backward)
-        # or the next MLP backward / the end of the pass runs it
-        rider = None if (repro or (plan.nbr_idx is not None and _dw_pending_rows(values.device) >= BIG_RIDER_ROWS)) \
-            else _dw_take(values.device)
-        if getattr(ctx, "satt", None) is not None:       # dense self-attention on bf16 MFMA (csrc/pit_satt.hip)
-            job = None
-            if rider is not None:
-                if SATT_DW_RIDER:
-                    job = rider                          # (carried by the backward launch below; `rider[1]` keeps its tensors alive)
-                else:
-                    _dw_run(rider)
-            if d_out.dtype != torch.float32 or d_out.stride(1) % 4 or d_out.stride(0) % 4 or d_out.data_ptr() % 16:
-                d_out = d_out.float().contiguous()
-            lk = getattr(ctx, "satt_link", None)
-            g16 = lk.get("g16") if lk is not None else None
-            g16_ready = _handoff_g16_ready(lk, d_out, (b, n_head, j, dv))
-            if lk is not None:
-                lk["g16"] = None                         # (consumed)
-            if not g16_ready:
-                g16 = torch.empty((b, n_head, j, dv), device=values.device, dtype=torch.bfloat16)
-            rc = _lib.lib().pit_satt_bwd(plan.mesh_in.data_ptr(), plan.mesh_batch, plan.n_in, plan.sdim, plan.metric_id, plan.period,
-                                         b, dv, scale.data_ptr(), n_head, rowstat.data_ptr(), ctx.satt.data_ptr(), g16.data_ptr(),
-                                         d_out.data_ptr(), d_out.stride(1), d_out.stride(0), dv,
-                                         _lib.ptr(d_values), d_values.stride(1) if d_values is not None else 0,
-                                         d_values.stride(0) if d_values is not None else 0, 1,
-                                         work.data_ptr() if need_h else None, _lib.ptr(getattr(ctx, "satt_tiles", None)),
-                                         1 if g16_ready else 0, ctypes.byref(job[0]) if job is not None else None, _lib.stream_ptr())
-            _lib.check(rc, "pit_satt_bwd")
-            if need_h:
-                flags = (1 if slot is not None else 0) | (4 if ctx.head_is_scale else 0)
-                if defer:
-                    _defer_head_finish(work, d_head, head, scale, n_head, 1 | (4 if ctx.head_is_scale else 0))
-                else:
-                    _finish_heads_now(work, d_head, head, scale, n_head, flags)
-            return (d_values, (None if slot is not None else d_head), None, None, None, None, None, None, None, None, None, None) \
-                + _mesh_grads(ctx, values, head, rowstat, scale, d_out)
-        if ctx.uatt is not None:                         # the union-tile backward: d_out read once, d(values) added from the tiles
-            if rider is not None:
-                _dw_run(rider)
-            w = ctx.uatt
-            if d_values is not None:
-                d_values.zero_()
-            sp, max_union = plan.slab_plan()[0], plan.slab_plan()[1]
-            rc = _lib.lib().pit_union_att_bwd(ctypes.byref(sp), values.data_ptr(), values.stride(1), values.stride(0), b, n_head, dv,
-                                              w.pw.data_ptr(), w.qw.data_ptr(), d_out.data_ptr(), d_out.stride(1), d_out.stride(0),
-                                              1 if io else 0, _lib.ptr(d_values), d_values.stride(1) if d_values is not None else 0,
-                                              d_values.stride(0) if d_values is not None else 0, work.data_ptr() if need_h else None,
-                                              max_union, _lib.stream_ptr())
-            _lib.check(rc, "pit_union_att_bwd")
-            flags = (1 if slot is not None else 0) | (4 if ctx.head_is_scale else 0)
-            if need_h:
-                if defer:
-                    _defer_head_finish(work, d_head, head, w.scale, n_head, 1 | (4 if ctx.head_is_scale else 0))
-                else:
-                    _finish_heads_now(work, d_head, head, w.scale, n_head, flags)
-            return (d_values, (None if slot is not None else d_head), None, None, None, None, None, None, None, None, None, None) \
-                + _mesh_grads(ctx, values, head, rowstat, scale, d_out)
+        uatt, satt = ctx.uatt, getattr(ctx, "satt", None)
+        # (the candidate-list / dense launch forms d(lmda) itself unless deferred; the other two leave it to the finishing kernel)
+        hg = _HeadGrad(ctx.head_param, need_h, n_head, values.device, ctx.head_is_scale, shared_workspace=True,
+                       kernel_finishes=uatt is None and satt is None)
+        work = hg.work
 
         def launch(dv, dh, stream_ptr, job=None):
             rc = _lib.lib().pit_posatt_bwd(
@@ -1315,7 +1356,7 @@ class _PosAtt(torch.autograd.Function):
                 d_out.data_ptr(), d_out.stride(1), d_out.stride(0), d if concat else 0,
                 _lib.ptr(dv), dv.stride(1) if dv is not None else 0, dv.stride(0) if dv is not None else 0,
                 1 if concat else 0,
-                _lib.ptr(dh), acc_head, work.data_ptr(),
+                _lib.ptr(dh), hg.acc, work.data_ptr(),
                 _lib.ptr(plan.nbr_idx), _lib.ptr(plan.nbr_cnt), plan.nbr_cap, 1 if ordered_lists else plan.lists_complete(),
                 _lib.ptr(plan.rev_ptr), _lib.ptr(rev_row),
                 ctypes.cast(ctypes.pointer(job[0]), ctypes.c_void_p) if job is not None else None,
@@ -1330,11 +1371,52 @@ class _PosAtt(torch.autograd.Function):
                     dv.data_ptr(), dv.stride(1), dv.stride(0), plan.nbr_cnt.data_ptr(), plan.nbr_cap, ctx.coord_dims, stream_ptr)
                 _lib.check(rc, "pit_posatt_overflow_dv_ordered")
 
-        launch(d_values, d_head, _lib.stream_ptr(), rider)
-        if defer:
-            _defer_head_finish(work, d_head, head, scale, n_head, 1 | (4 if ctx.head_is_scale else 0))
-        return (d_values, (None if slot is not None else d_head), None, None, None, None, None, None, None, None, None, None) \
-            + _mesh_grads(ctx, values, head, rowstat, scale, d_out)
+        # an MLP's postponed weight-gradient reductions ride along - unless this is a candidate-list layer and the job is
+        # LARGE (the decoder MLP's: inside that launch it costs more than a launch of its own, measured 34.7 vs 16.1 +
+        # 15.7 us at Darcy b=8); left pending, the fused processor spreads it over its block launches (_Processor.backward)
+        # or the next MLP backward / the end of the pass runs it
+        carry = not (repro or (plan.nbr_idx is not None and _dw_pending_rows(values.device) >= BIG_RIDER_ROWS))
+        fscale = scale                                   # (the scale c the finishing kernel's chain rule reads)
+        if uatt is not None:                             # the union-tile backward: d_out read once, d(values) added from the tiles
+            if carry:
+                _dw_run_pending(values.device)           # (this launch carries nothing)
+            if d_values is not None:
+                d_values.zero_()
+            sp, max_union = plan.slab_plan()[0], plan.slab_plan()[1]
+            rc = _lib.lib().pit_union_att_bwd(ctypes.byref(sp), values.data_ptr(), values.stride(1), values.stride(0), b, n_head, dv,
+                                              uatt.pw.data_ptr(), uatt.qw.data_ptr(), d_out.data_ptr(), d_out.stride(1), d_out.stride(0),
+                                              1 if io else 0, _lib.ptr(d_values), d_values.stride(1) if d_values is not None else 0,
+                                              d_values.stride(0) if d_values is not None else 0, work.data_ptr() if need_h else None,
+                                              max_union, _lib.stream_ptr())
+            _lib.check(rc, "pit_union_att_bwd")
+            fscale = uatt.scale
+        elif satt is not None:                           # dense self-attention on bf16 MFMA (csrc/pit_satt.hip)
+            job = _dw_take(values.device) if carry else None
+            if job is not None and not SATT_DW_RIDER:    # (else carried by the launch below; `job[1]` keeps its tensors alive)
+                _dw_run(job)
+                job = None
+            if d_out.dtype != torch.float32 or d_out.stride(1) % 4 or d_out.stride(0) % 4 or d_out.data_ptr() % 16:
+                d_out = d_out.float().contiguous()
+            lk = getattr(ctx, "satt_link", None)
+            g16 = lk.get("g16") if lk is not None else None
+            g16_ready = _handoff_g16_ready(lk, d_out, (b, n_head, j, dv))
+            if lk is not None:
+                lk["g16"] = None                         # (consumed)
+            if not g16_ready:
+                g16 = torch.empty((b, n_head, j, dv), device=values.device, dtype=torch.bfloat16)
+            rc = _lib.lib().pit_satt_bwd(plan.mesh_in.data_ptr(), plan.mesh_batch, plan.n_in, plan.sdim, plan.metric_id, plan.period,
+                                         b, dv, scale.data_ptr(), n_head, rowstat.data_ptr(), satt.data_ptr(), g16.data_ptr(),
+                                         d_out.data_ptr(), d_out.stride(1), d_out.stride(0), dv,
+                                         _lib.ptr(d_values), d_values.stride(1) if d_values is not None else 0,
+                                         d_values.stride(0) if d_values is not None else 0, 1,
+                                         work.data_ptr() if need_h else None, _lib.ptr(getattr(ctx, "satt_tiles", None)),
+                                         1 if g16_ready else 0, ctypes.byref(job[0]) if job is not None else None, _lib.stream_ptr())
+            _lib.check(rc, "pit_satt_bwd")
+        else:
+            launch(d_values, hg.d_head, _lib.stream_ptr(), _dw_take(values.device) if carry else None)
+        # (forward's inputs: values, head, then plan, n_head, concat, head_is_scale, head_param, out_slot, coord_dims, scale_in,
+        # out_bf16, link - and the two meshes)
+        return (d_values, hg.finish(head, fscale)) + (None,) * 10 + _mesh_grads(ctx, values, head, rowstat, scale, d_out)
 
 
 # Where the head scale c = tan(0.25*pi*(1-1e-7)*(1+sin(lmda))) (pit.py:48) is evaluated.
@@ -1973,19 +2055,17 @@ class _Mlp(torch.autograd.Function):
             d_y2 = d_y2.contiguous()
         need_x = ctx.needs_input_grad[0]
         d_x = torch.empty((rows, n0), device=dev, dtype=torch.bfloat16 if ctx.x16 else torch.float32) if need_x else None
-        slots = [_grad_slot(p) if isinstance(p, torch.nn.Parameter) else None for p in ctx.params]
-        inplace = all(s is not None for s in slots) and all(ctx.needs_input_grad[1:5])
-        if inplace:
-            d_w1, d_b1, d_w2, d_b2 = slots
-        else:
-            d_w1 = torch.empty((n1, n0), device=dev, dtype=torch.float32)
-            d_b1 = torch.empty((n1,), device=dev, dtype=torch.float32)
-            d_w2 = torch.empty((n2, n1), device=dev, dtype=torch.float32)
-            d_b2 = torch.empty((n2,), device=dev, dtype=torch.float32)
+        # (fresh="empty": gradients returned to autograd are overwritten - accumulate = 0 - by the calls below; every postponed job
+        # adds into the parameters' own .grad)
+        grads, inplace = _mlp_grad_slots(ctx.params, ((n1, n0), (n1,), (n2, n1), (n2,)), ctx.needs_input_grad[1:5], dev, fresh="empty")
+        d_w1, d_b1, d_w2, d_b2 = grads
         scratch = torch.empty((rows * (n1 + n2),), device=dev, dtype=torch.float32)
         L = _lib.lib()
         z2p = z2.data_ptr() if ctx.out_gelu else 0
         og = 1 if ctx.out_gelu else 0
+
+        def postpone(math):                          # the weight-gradient reductions, handed to a later launch of the pass
+            _dw_defer(*_params_job(x2, h, d_y2, scratch, grads, ctx.dims, og, math), dev)
         if ctx.ordered:
             # the data path, then both weight-gradient reductions slab by slab in a fixed order: the same bits on every run
             rc = L.pit_mlp_bwd_data(rows, n0, n1, n2, w1.data_ptr(), w2.data_ptr(), z1.data_ptr(), z2p, og,
@@ -2017,10 +2097,7 @@ class _Mlp(torch.autograd.Function):
             if lk is not None and inplace and SATT_DW_RIDER and lk.get("rowstat") is not None:
                 # the weight-gradient reductions depend on this launch only: they ride in the attention layer's ONE backward launch
                 # (pit_satt_bwd's rider) instead of standing between the two
-                st = _lib.MlpParamsJob(x2.data_ptr(), x2.stride(0), rows, n0, n1, n2, h.data_ptr(), og, d_y2.data_ptr(),
-                                       d_y2.stride(0), d_w1.data_ptr(), d_b1.data_ptr(), d_w2.data_ptr(), d_b2.data_ptr(),
-                                       1, scratch.data_ptr(), ctx.math)
-                _dw_defer(st, (x2, h, d_y2, scratch, d_w1, d_b1, d_w2, d_b2), dev)
+                postpone(ctx.math)
             else:
                 rc = L.pit_mlp_bwd_params(x2.data_ptr(), x2.stride(0), rows, n0, n1, n2, h.data_ptr(), og, d_y2.data_ptr(),
                                           d_y2.stride(0), d_w1.data_ptr(), d_b1.data_ptr(), d_w2.data_ptr(), d_b2.data_ptr(),
@@ -2035,10 +2112,7 @@ class _Mlp(torch.autograd.Function):
             # (the postponed reductions of a small-regime MLP contract in fp32 in every math mode, like its fused data-path
             # kernels: as LDS-staged fp32 tiles they ride in the block launches at a third of the cost of the register-direct
             # bf16 form - bf16 mode at batch 8 was 5 % slower than fp32 for this alone)
-            st = _lib.MlpParamsJob(x2.data_ptr(), x2.stride(0), rows, n0, n1, n2, h.data_ptr(), og, d_y2.data_ptr(),
-                                   d_y2.stride(0), d_w1.data_ptr(), d_b1.data_ptr(), d_w2.data_ptr(), d_b2.data_ptr(),
-                                   1, scratch.data_ptr(), 0)
-            _dw_defer(st, (x2, h, d_y2, scratch, d_w1, d_b1, d_w2, d_b2), dev)
+            postpone(0)
         elif (WIDE_DW_RIDER and inplace and ctx.after_dense_att and not ctx.x16 and rows >= 1024 and n1 >= 128 and n1 % 64 == 0
               and n2 % 64 == 0 and n0 % 64 == 0 and (not og or d_y2.stride(0) == n2)):
             # x is the output of a dense self-attention layer (pit.py:116-121): the same split in the large regime - the reductions
@@ -2050,10 +2124,7 @@ class _Mlp(torch.autograd.Function):
                                     d_y2.data_ptr(), d_y2.stride(0), _lib.ptr(d_x), n0, scratch.data_ptr(),
                                     ctx.math, _lib.stream_ptr())
             _lib.check(rc, "pit_mlp_bwd_data")
-            st = _lib.MlpParamsJob(x2.data_ptr(), x2.stride(0), rows, n0, n1, n2, h.data_ptr(), og, d_y2.data_ptr(),
-                                   d_y2.stride(0), d_w1.data_ptr(), d_b1.data_ptr(), d_w2.data_ptr(), d_b2.data_ptr(),
-                                   1, scratch.data_ptr(), ctx.math)
-            _dw_defer(st, (x2, h, d_y2, scratch, d_w1, d_b1, d_w2, d_b2), dev)
+            postpone(ctx.math)
         else:
             # one call: dZ1, then dX and both weight-gradient reductions (merged into one launch when small)
             # (small regime: fp32 in every math mode, like the postponed form above - the two must agree)
@@ -2064,9 +2135,8 @@ class _Mlp(torch.autograd.Function):
                                1 if inplace else 0, scratch.data_ptr(), 0 if small else ctx.math, _lib.stream_ptr())
             _lib.check(rc, "pit_mlp_bwd")
         dx = d_x.reshape(ctx.in_shape) if need_x else None
-        if inplace:
-            return dx, None, None, None, None, None, None, None, None, None, None
-        return dx, d_w1, d_b1, d_w2, d_b2, None, None, None, None, None, None
+        # (forward's inputs: x, then w1, b1, w2, b2, then out_gelu, concat_heads, satt_link, y16_slot, after_dense_att, ordered)
+        return (dx,) + ((None,) * 4 if inplace else tuple(grads)) + (None,) * 6
 
 
 @torch.compiler.disable
@@ -2179,37 +2249,18 @@ class _PosAttPre(torch.autograd.Function):
         need_v, need_h = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         dev = values.device
         d_values = torch.empty((b, L, D), device=dev, dtype=torch.float32)
-        slot = _grad_slot(ctx.head_param) if need_h else None
-        defer = DEFER_HEAD_FINISH and slot is not None
-        work = None
-        if need_h:
-            if q is None:
-                raise RuntimeError("d(lmda) needs the d(scale) weights: block_weights(..., need_q=True)")
-            if defer:
-                work = _layer_workspace(slot, n_head)
-                _defer_head_begin(work)
-            else:
-                work = torch.zeros(n_head * 1024, device=dev, dtype=torch.float64)
-        rider = _dw_take(dev)                       # (a postponed MLP job: these launches carry nothing - run it now)
-        if rider is not None:
-            _dw_run(rider)
+        if need_h and q is None:
+            raise RuntimeError("d(lmda) needs the d(scale) weights: block_weights(..., need_q=True)")
+        # (head_is_scale=False: `head` is always lmda here - block_weights hands the kernels a host-evaluated scale beside it, never
+        # in its place - so the finishing kernel applies the chain rule through lmda on either route)
+        hg = _HeadGrad(ctx.head_param, need_h, n_head, dev, head_is_scale=False)
+        _dw_run_pending(dev)                        # (a postponed MLP job: these launches carry nothing)
         rc = _lib.lib().pit_posatt_pre_bwd(e.data_ptr(), _lib.ptr(q), rowstat.data_ptr(), L, n_head, D, b, values.data_ptr(),
                                            values.stride(1), values.stride(0), d_out.data_ptr(), d_out.stride(1), d_out.stride(0),
-                                           D, d_values.data_ptr(), D, L * D, 1, _lib.ptr(work), ctx.math, _lib.stream_ptr())
+                                           D, d_values.data_ptr(), D, L * D, 1, _lib.ptr(hg.work), ctx.math, _lib.stream_ptr())
         _lib.check(rc, "pit_posatt_pre_bwd")
-        d_head = None
-        if need_h:
-            if defer:
-                _defer_head_finish(work, slot, head, scale, n_head, 1)
-            else:
-                d_head = slot if slot is not None else torch.empty((n_head,), device=dev, dtype=torch.float32)
-                one = lambda t: (ctypes.c_void_p * 1)(t.data_ptr())
-                _lib.check(_lib.lib().pit_posatt_dhead_finish(1, one(work), one(d_head), one(head), one(scale), (ctypes.c_int * 1)(n_head),
-                                                              (ctypes.c_int * 1)(1 if slot is not None else 0), None, _lib.stream_ptr()),
-                           "pit_posatt_dhead_finish")
-                if slot is not None:
-                    d_head = None
-        return (d_values if need_v else None), d_head, None, None, None, None, None, None, None
+        # (forward's inputs: values, head, then e, q, rowstat, scale, n_head, head_param, out_slot)
+        return ((d_values if need_v else None), hg.finish(head, scale)) + (None,) * 7
 
 
 @torch.compiler.disable
@@ -2377,26 +2428,10 @@ class _Processor(torch.autograd.Function):
         scratch = [torch.empty((rows * 2 * D,), device=dev, dtype=torch.float32) for _ in range(n)]
         dx = torch.empty((b, L, D), device=dev, dtype=torch.float32)
         # gradient destinations: the parameters' own .grad slots (in place, nothing returned) or fresh tensors
-        lm_slots = [_grad_slot(p) if isinstance(p, torch.nn.Parameter) else None for p in lm_params]
-        w_slots, w_grads = [], []
-        for i in range(n):
-            sl = [_grad_slot(p) if isinstance(p, torch.nn.Parameter) else None for p in mlp_params[i]]
-            if all(s is not None for s in sl):
-                w_slots.append(sl)
-                w_grads.append(None)
-            else:
-                g = [torch.zeros_like(t) for t in wts[i]]
-                w_slots.append(g)
-                w_grads.append(g)
-        defer = [DEFER_HEAD_FINISH and s is not None for s in lm_slots]
-        work = []
-        for i in range(n):
-            if defer[i]:
-                ws = _layer_workspace(lm_slots[i], H)
-                _defer_head_begin(ws)
-            else:
-                ws = torch.zeros(H * 1024, device=dev, dtype=torch.float64)
-            work.append(ws)
+        # (needs: not consulted here - a block whose four parameters all opted in accumulates in place)
+        w_grads = [_mlp_grad_slots(mlp_params[i], [t.shape for t in wts[i]], (True,) * 4, dev) for i in range(n)]
+        # (head_is_scale=False: `heads` are the lmda's themselves on either route; d(lmda) of every block is always formed)
+        hgs = [_HeadGrad(p if isinstance(p, torch.nn.Parameter) else None, True, H, dev, head_is_scale=False) for p in lm_params]
         # a large job the pass has postponed (the decoder MLP's weight gradients): one row slice per block launch
         extra = _dw_take(dev)
         slices = []
@@ -2415,10 +2450,7 @@ class _Processor(torch.autograd.Function):
                                  _lib.stream_ptr())
         _lib.check(rc, "pit_mlp_bwd_data")
         for i in range(n - 1, -1, -1):
-            dw1, db1, dw2, db2 = w_slots[i]
-            job = _lib.MlpParamsJob(bufs[i].data_ptr(), W, rows, W, D, D, hh[i].data_ptr(), 1, scratch[i].data_ptr(), D,
-                                    dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(), db2.data_ptr(), 1,
-                                    scratch[i].data_ptr(), ctx.math)
+            job = _params_job(bufs[i], hh[i], scratch[i], scratch[i], w_grads[i][0], (rows, W, D, D), 1, ctx.math, ld_dy=D)[0]
             if i > 0:
                 pw1, _, pw2, _ = wts[i - 1]
                 prev = (pw1.data_ptr(), pw2.data_ptr(), z1[i - 1].data_ptr(), z2[i - 1].data_ptr(), 1, W,
@@ -2428,36 +2460,19 @@ class _Processor(torch.autograd.Function):
             k = n - 1 - i                              # launch order
             job2 = ctypes.cast(ctypes.pointer(slices[k]), ctypes.c_void_p) if k < len(slices) else None
             rc = L_.pit_block_bwd(E[i].data_ptr(), inv[i].data_ptr(), Q[i].data_ptr(), L, H, D, b, dxc[i].data_ptr(),
-                                  bufs[i].data_ptr(), work[i].data_ptr(), *prev,
+                                  bufs[i].data_ptr(), hgs[i].work.data_ptr(), *prev,
                                   ctypes.cast(ctypes.pointer(job), ctypes.c_void_p), job2, ctx.math,
                                   _lib.stream_ptr())
             _lib.check(rc, "pit_block_bwd")
             if ctx.hook is not None:
                 ctx.hook[0](i)                              # (block i's weight gradients are now enqueued)
         # d(lmda): deferred layers are finished by the pass's one finishing launch; the others here, in one launch
-        d_heads = [None] * n
-        now = [i for i in range(n) if not defer[i]]
-        for i in range(n):
-            if defer[i]:
-                _defer_head_finish(work[i], lm_slots[i], heads[i], scale[i], H, 1)
-        if now:
-            m = len(now)
-            for i in now:
-                d_heads[i] = lm_slots[i] if lm_slots[i] is not None else torch.empty((H,), device=dev, dtype=torch.float32)
-            ws = (ctypes.c_void_p * m)(*[work[i].data_ptr() for i in now])
-            dh = (ctypes.c_void_p * m)(*[d_heads[i].data_ptr() for i in now])
-            hd = (ctypes.c_void_p * m)(*[heads[i].data_ptr() for i in now])
-            sc = (ctypes.c_void_p * m)(*[scale[i].data_ptr() for i in now])
-            nh = (ctypes.c_int * m)(*[H] * m)
-            fl = (ctypes.c_int * m)(*[1 if lm_slots[i] is not None else 0 for i in now])
-            _lib.check(L_.pit_posatt_dhead_finish(m, ws, dh, hd, sc, nh, fl, None, _lib.stream_ptr()), "pit_posatt_dhead_finish")
-        grads = [dx, None, None, None, None, None]
-        for i in range(n):
-            g = None if lm_slots[i] is not None else d_heads[i]
-            grads.append(g)
-        for i in range(n):
-            grads.extend(w_grads[i] if w_grads[i] is not None else [None, None, None, None])
-        return tuple(grads)
+        d_heads = _HeadGrad.finish_all([(hgs[i], heads[i], scale[i]) for i in range(n)])
+        # (forward's inputs: x, then plan, n_head, scales, params, early - then the n lmda's - then (w1, b1, w2, b2) per block)
+        grads = (dx,) + (None,) * 5 + tuple(d_heads)
+        for g, inplace in w_grads:
+            grads += (None,) * 4 if inplace else tuple(g)
+        return grads
 
 
 # engine.TrainStep(all_reduce_buckets=2) sets step_state(processor_hook=(callback, complete_by)): the callback is called
@@ -2496,23 +2511,6 @@ def edge_fusion_supported(plan: MeshPlan, n_head: int, dim: int, batch: int, nee
         return False
     sp = plan.slab_plan(patch=needs_union)          # (needs_union: the fused decoder, the one consumer of patch plans)
     return sp is not None and (not needs_union or sp[1] <= SLAB_UNION_MAX)
-
-
-def _finish_heads_now(work, d_head, head, scale, n_head: int, flags: int) -> None:
-    """d(lmda) of ONE layer from freshly loaded accumulators, now (the gradient is returned to autograd, not accumulated in place)."""
-    one = lambda t: (ctypes.c_void_p * 1)(_lib.ptr(t))
-    rc = _lib.lib().pit_posatt_dhead_finish(1, one(work), one(d_head), one(head), one(scale), (ctypes.c_int * 1)(n_head),
-                                            (ctypes.c_int * 1)(flags), None, _lib.stream_ptr())
-    _lib.check(rc, "pit_posatt_dhead_finish")
-
-
-def _mlp_grad_slots(params, shapes, needs, device):
-    """([d_w1, d_b1, d_w2, d_b2], in place?) for an MLP's weight gradients: the parameters' own .grad (the kernels accumulate) when
-    every one of them opted in, else fresh ZEROED tensors returned to autograd."""
-    slots = [_grad_slot(p) if isinstance(p, torch.nn.Parameter) else None for p in params]
-    if all(s is not None for s in slots) and all(needs):
-        return slots, True
-    return [torch.zeros(tuple(sh), device=device, dtype=torch.float32) for sh in shapes], False
 
 
 class LossSpec:
@@ -2663,49 +2661,25 @@ class _Decoder(torch.autograd.Function):
             if d_pred.stride(1) != 1 or d_pred.stride(0) < n2:
                 d_pred = d_pred.contiguous()
             dyp, ld = d_pred, d_pred.stride(0)
-        need_h = ctx.needs_input_grad[1]
-        slot = _grad_slot(ctx.head_param) if need_h else None
-        defer = DEFER_HEAD_FINISH and slot is not None
-        work = None
-        if need_h:
-            work = _layer_workspace(slot, n_head) if defer else torch.zeros(n_head * 1024, device=dev, dtype=torch.float64)
-            if defer:
-                _defer_head_begin(work)
+        hg = _HeadGrad(ctx.head_param, ctx.needs_input_grad[1], n_head, dev, ctx.head_is_scale)
         L = _lib.lib()
         rc = L.pit_decoder_bwd(ctypes.byref(sp), values.data_ptr(), values.stride(1), values.stride(0), b, n_head, d,
                                weights.pw.data_ptr(), weights.qw.data_ptr(), w1.data_ptr(), w2.data_ptr(), n2, z1.data_ptr(),
-                               _lib.ptr(dyp), ld, dz1.data_ptr(), dvals.data_ptr(), dvals.stride(0), _lib.ptr(work),
+                               _lib.ptr(dyp), ld, dz1.data_ptr(), dvals.data_ptr(), dvals.stride(0), _lib.ptr(hg.work),
                                loss.pred.data_ptr() if inside else None, _lib.ptr(loss.true) if inside else None,
                                _lib.ptr(loss.scale) if inside else None, _lib.ptr(loss.shift) if inside else None,
                                _lib.ptr(loss.seed) if inside else None, loss.p if inside else 0,
                                _lib.ptr(loss.partials) if inside else None, d_pred.data_ptr() if inside else None,
                                loss.value.data_ptr() if inside else None, None, weights.max_union, _lib.stream_ptr())
         _lib.check(rc, "pit_decoder_bwd")
-        d_head = None
-        if need_h:
-            flags = 1 | (4 if ctx.head_is_scale else 0)
-            if defer:
-                _defer_head_finish(work, slot, head, scale, n_head, flags)
-            else:
-                d_head = slot if slot is not None else torch.empty((n_head,), device=dev, dtype=torch.float32)
-                _finish_heads_now(work, d_head, head, scale, n_head, flags if slot is not None else flags & ~1)
-                if slot is not None:
-                    d_head = None
+        d_head = hg.finish(head, scale)
         # weight gradients: the reductions over all rows are postponed and carried by a later launch of the pass (_dw_defer) in the
         # in-place mode, performed now otherwise
         grads, inplace = _mlp_grad_slots(ctx.params, (w1.shape, (d,), w2.shape, (n2,)), ctx.needs_input_grad[9:13], dev)
-        d_w1, d_b1, d_w2, d_b2 = grads
-        st = _lib.MlpParamsJob(x.data_ptr(), x.stride(0), rows, n_head * d, d, n2, h.data_ptr(), 0, d_pred.data_ptr(),
-                               d_pred.stride(0), d_w1.data_ptr(), d_b1.data_ptr(), d_w2.data_ptr(), d_b2.data_ptr(), 1,
-                               dz1.data_ptr(), 0)
-        keep = (x, h, d_pred, dz1, d_w1, d_b1, d_w2, d_b2)
-        if inplace and MLP_PARAMS_RIDER and _dw_deferrable(rows, n_head * d, d, n2, 0, d_pred.stride(0)):
-            _dw_defer(st, keep, dev)
-        else:
-            _dw_run((st, keep, torch.cuda.current_stream(dev)))
+        d_w = _dw_deliver(_params_job(x, h, d_pred, dz1, grads, (rows, n_head * d, d, n2), 0, 0), inplace, dev)
         dv = dvals if ctx.needs_input_grad[0] else None
-        w = (None, None, None, None) if inplace else (d_w1, d_b1, d_w2, d_b2)
-        return (dv, d_head, None, None, None, None, None, None, None) + w
+        # (forward's inputs: values, head, then plan, n_head, head_is_scale, head_param, weights, params, loss - and w1, b1, w2, b2)
+        return (dv, d_head) + (None,) * 7 + d_w
 
 
 @torch.compiler.disable
@@ -2903,35 +2877,18 @@ class _FoldAtt(torch.autograd.Function):
             d_vw = torch.empty((b, j, hd), device=vw.device, dtype=torch.float32)
         else:
             d_vw = torch.zeros((b, j, hd), device=vw.device, dtype=torch.float32) if need_v else None
-        slot = _grad_slot(ctx.head_param) if need_h else None
-        defer = DEFER_HEAD_FINISH and slot is not None
-        work = None
-        if need_h:
-            work = _layer_workspace(slot, n_head) if defer else torch.zeros(n_head * 1024, device=vw.device, dtype=torch.float64)
-            if defer:
-                _defer_head_begin(work)
-        rider = _dw_take(vw.device)                  # (a postponed weight-gradient job: nothing here carries it - run it now)
-        if rider is not None:
-            _dw_run(rider)
+        hg = _HeadGrad(ctx.head_param, need_h, n_head, vw.device, ctx.head_is_scale)
+        _dw_run_pending(vw.device)                   # (a postponed weight-gradient job: nothing here carries it)
         sp, max_union = plan.fold_plan()[0], plan.fold_plan()[1]
         pw = w.pw16 if w.pw16 is not None else w.pw    # (bf16 math mode: the bf16 tiles)
         qw = (w.qw16 if w.qw16 is not None else pw) if w.pw16 is not None else (w.qw if w.qw is not None else w.pw)      # (read only for d(scale))
         rc = _lib.lib().pit_fold_att_bwd(ctypes.byref(sp), vw.data_ptr(), vw.stride(1), vw.stride(0), b, n_head, d, pw.data_ptr(),
                                          qw.data_ptr(), dz.data_ptr(), dz.stride(1), dz.stride(0),
-                                         _lib.ptr(d_vw), hd, j * hd, _lib.ptr(work), _lib.ptr(tiles), _lib.ptr(rev_ptr),
+                                         _lib.ptr(d_vw), hd, j * hd, _lib.ptr(hg.work), _lib.ptr(tiles), _lib.ptr(rev_ptr),
                                          _lib.ptr(rev_ent), max_union, ctx.math | io, _lib.stream_ptr())
         _lib.check(rc, "pit_fold_att_bwd")
-        d_head = None
-        if need_h:
-            flags = 1 | (4 if ctx.head_is_scale else 0)
-            if defer:
-                _defer_head_finish(work, slot, head, w.scale, n_head, flags)
-            else:
-                d_head = slot if slot is not None else torch.empty((n_head,), device=vw.device, dtype=torch.float32)
-                _finish_heads_now(work, d_head, head, w.scale, n_head, flags if slot is not None else flags & ~1)
-                if slot is not None:
-                    d_head = None
-        return d_vw, d_head, None, None, None, None, None, None, None
+        # (forward's inputs: vw, head, then plan, n_head, head_is_scale, head_param, scale_in, out_bf16, need_q)
+        return (d_vw, hg.finish(head, w.scale)) + (None,) * 7
 
 
 _TAIL_WS = {}       # (device index, stream) -> the thin tail's slotted partial sums (self-cleaning)
@@ -3075,40 +3032,19 @@ class _Encoder(torch.autograd.Function):
         if d_y2.stride(1) != 1 or d_y2.stride(0) < d:
             d_y2 = d_y2.contiguous()
         scratch = torch.empty((rows * 2 * d,), device=dev, dtype=torch.float32)
-        need_h = ctx.needs_input_grad[1]
-        slot = _grad_slot(ctx.head_param) if need_h else None
-        defer = DEFER_HEAD_FINISH and slot is not None
         # (the launch always reduces d(scale): accumulators of its own when lmda needs no gradient)
-        work = _layer_workspace(slot, n_head) if defer else torch.zeros(n_head * 1024, device=dev, dtype=torch.float64)
-        if defer:
-            _defer_head_begin(work)
+        hg = _HeadGrad(ctx.head_param, ctx.needs_input_grad[1], n_head, dev, ctx.head_is_scale, always_accumulators=True)
         rc = _lib.lib().pit_encoder_bwd(ctypes.byref(sp), plan.mesh_in.data_ptr(), plan.sdim, kd, values.data_ptr(), values.stride(1),
                                         values.stride(0), dv, b, n_head, d, scale.data_ptr(), rowstat.data_ptr(), w1.data_ptr(),
                                         w2.data_ptr(), z1.data_ptr(), z2.data_ptr(), d_y2.data_ptr(), d_y2.stride(0),
-                                        scratch.data_ptr(), _lib.ptr(work), _lib.stream_ptr())
+                                        scratch.data_ptr(), _lib.ptr(hg.work), _lib.stream_ptr())
         _lib.check(rc, "pit_encoder_bwd")
-        d_head = None
-        if need_h:
-            flags = 1 | (4 if ctx.head_is_scale else 0)
-            if defer:
-                _defer_head_finish(work, slot, head, scale, n_head, flags)
-            else:
-                d_head = slot if slot is not None else torch.empty((n_head,), device=dev, dtype=torch.float32)
-                _finish_heads_now(work, d_head, head, scale, n_head, flags if slot is not None else flags & ~1)
-                if slot is not None:
-                    d_head = None
+        d_head = hg.finish(head, scale)
         grads, inplace = _mlp_grad_slots(ctx.params, (w1.shape, (d,), w2.shape, (d,)), ctx.needs_input_grad[12:16], dev)
-        d_w1, d_b1, d_w2, d_b2 = grads
-        k0 = n_head * (kd + dv)
-        st = _lib.MlpParamsJob(x.data_ptr(), x.stride(0), rows, k0, d, d, h.data_ptr(), 1, d_y2.data_ptr(), d_y2.stride(0),
-                               d_w1.data_ptr(), d_b1.data_ptr(), d_w2.data_ptr(), d_b2.data_ptr(), 1, scratch.data_ptr(), 0)
-        keep = (x, h, d_y2, scratch, d_w1, d_b1, d_w2, d_b2)
-        if inplace and MLP_PARAMS_RIDER and _dw_deferrable(rows, k0, d, d, 1, d_y2.stride(0)):
-            _dw_defer(st, keep, dev)
-        else:
-            _dw_run((st, keep, torch.cuda.current_stream(dev)))
-        w = (None, None, None, None) if inplace else (d_w1, d_b1, d_w2, d_b2)
-        return (None, d_head, None, None, None, None, None, None, None, None, None, None) + w + (None, None)
+        d_w = _dw_deliver(_params_job(x, h, d_y2, scratch, grads, (rows, n_head * (kd + dv), d, d), 1, 0), inplace, dev)
+        # (forward's inputs: values, head, then plan, n_head, head_is_scale, head_param, scale_in, params, coord_dims, concat_heads,
+        # wjob, clear - then w1, b1, w2, b2 - then djob, need)
+        return (None, d_head) + (None,) * 10 + d_w + (None, None)
 
 
 @torch.compiler.disable

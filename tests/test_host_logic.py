@@ -333,3 +333,161 @@ def test_fused_processor_gate_refuses_more_blocks_than_one_weights_launch_forms(
     finally:
         ops.block_fusion_supported = orig
     assert not calls
+
+
+# --------------------------------------------------------------------------- where d(lmda) and an MLP's weight gradients go
+# (the keywords a backward node constructs ops._HeadGrad with, as the seven nodes spell them)
+HEAD_KINDS = {"fresh": {}, "encoder": {"always_accumulators": True}, "shared": {"shared_workspace": True},
+              "kernel": {"shared_workspace": True, "kernel_finishes": True}}
+
+
+@pytest.mark.parametrize("is_scale", [False, True])
+@pytest.mark.parametrize("mode", ["unwanted", "returned", "inplace", "deferred"])
+def test_head_gradient_object_over_delivery_modes_and_node_kinds(mode, is_scale, monkeypatch):
+    """ops._HeadGrad over {no gradient wanted, returned to autograd, in place now, in place deferred} x {head is lmda, head is the
+    scale} x the nodes' keywords: the flags that reach the one finishing launcher (in place = 1 only with a slot, 4 = head is the
+    scale), which accumulators the kernel is handed, what finish() returns, what the self-finishing launch gets, and
+    _defer_head_begin run by the constructor exactly when deferring."""
+    from position_induced_transformer_amd import ops
+    slot, param = torch.zeros(2), object()
+    shared = torch.zeros(8, dtype=torch.float64)
+    launched, flushed, begun = [], [], []
+    monkeypatch.setattr(ops, "_grad_slot", lambda p: slot if (p is param and mode in ("inplace", "deferred")) else None)
+    monkeypatch.setattr(ops, "DEFER_HEAD_FINISH", mode == "deferred")
+    monkeypatch.setattr(ops, "_launch_head_finishes", lambda entries, rider=None: launched.append(list(entries)))
+    monkeypatch.setattr(ops, "_flush_head_finishes", lambda task: flushed.extend(ops._PENDING_HEADS.pop(task)))
+    monkeypatch.setattr(ops, "_dscale_workspace", lambda device, n_head: shared)
+    real_begin = ops._defer_head_begin
+    monkeypatch.setattr(ops, "_defer_head_begin", lambda work: (begun.append(work), real_begin(work))[1])
+    ops._PENDING_HEADS.clear()
+    head, scale = torch.ones(2), torch.ones(2)
+    seen = {}
+
+    class Layer(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x):
+            return x * 2
+
+        @staticmethod
+        def backward(ctx, g):
+            for kind, kw in HEAD_KINDS.items():
+                n0, l0 = len(begun), len(launched)
+                hg = ops._HeadGrad(param, mode != "unwanted", 2, torch.device("cpu"), is_scale, **kw)
+                begins = len(begun) - n0
+                ret = hg.finish(head, scale)
+                seen[kind] = (hg, begins, ret, launched[l0:])
+            return g * 2
+
+    Layer.apply(torch.ones(3, requires_grad=True)).sum().backward()
+    bit = 4 if is_scale else 0
+    own = ops._layer_workspace(slot, 2)                              # (cached per gradient slot: the object the constructor took)
+    for kind, (hg, begins, ret, launches) in seen.items():
+        assert begins == (1 if mode == "deferred" else 0), (kind, "_defer_head_begin")
+        assert (hg.slot is slot) == (mode in ("inplace", "deferred")) and hg.defer == (mode == "deferred")
+        # accumulators
+        if mode == "deferred":
+            assert hg.work is own, kind
+        elif kind in ("shared", "kernel"):
+            assert hg.work is shared, kind
+        elif mode == "unwanted" and kind == "fresh":
+            assert hg.work is None
+        else:
+            assert hg.work.dtype == torch.float64 and hg.work.numel() == 2 * 1024 and float(hg.work.abs().sum()) == 0.0, kind
+            assert hg.work is not own and hg.work is not shared
+        # the gradient tensor and what autograd receives
+        if mode == "unwanted":
+            assert hg.d_head is None and ret is None and launches == []
+            continue
+        assert (hg.d_head is slot) if hg.slot is not None else (tuple(hg.d_head.shape) == (2,) and hg.d_head.dtype == torch.float32)
+        assert (ret is None) if hg.slot is not None else (ret is hg.d_head), kind
+        assert hg.acc == {"returned": 0, "inplace": 1, "deferred": 3}[mode]
+        # the finishing launch
+        if mode == "deferred" or kind == "kernel":
+            assert launches == [], kind
+        else:
+            (entry,), = launches
+            assert entry[0] is hg.work and entry[1] is hg.d_head and entry[2] is head and entry[3] is scale and entry[4] == 2
+            assert entry[5] == (1 if mode == "inplace" else 0) | bit, (kind, entry[5])
+    if mode == "deferred":                                           # one entry per layer, drained by the pass's one flush
+        assert len(flushed) == len(HEAD_KINDS)
+        for e in flushed:
+            assert e[0] is own and e[1] is slot and e[5] == 1 | bit
+    else:
+        assert flushed == [] and not ops._PENDING_HEADS
+
+
+def test_head_gradients_of_one_node_share_one_finishing_launch(monkeypatch):
+    """_HeadGrad.finish_all (the fused processor): layers whose gradient is returned or goes in place now are finished by ONE
+    launch, in layer order, each with its own flags."""
+    from position_induced_transformer_amd import ops
+    slot, marked = torch.zeros(2), object()
+    launched = []
+    monkeypatch.setattr(ops, "_grad_slot", lambda p: slot if p is marked else None)
+    monkeypatch.setattr(ops, "DEFER_HEAD_FINISH", False)
+    monkeypatch.setattr(ops, "_launch_head_finishes", lambda entries, rider=None: launched.append(list(entries)))
+    hgs = [ops._HeadGrad(p, True, 2, torch.device("cpu"), False) for p in (None, marked, None)]
+    heads, scales = [torch.ones(2) for _ in hgs], [torch.ones(2) for _ in hgs]
+    out = ops._HeadGrad.finish_all(list(zip(hgs, heads, scales)))
+    assert len(launched) == 1 and [e[5] for e in launched[0]] == [0, 1, 0]
+    assert [e[2] for e in launched[0]] == heads and [e[0] for e in launched[0]] == [g.work for g in hgs]
+    assert out[0] is hgs[0].d_head and out[1] is None and out[2] is hgs[2].d_head
+
+
+@pytest.mark.parametrize("fresh", ["empty", "zeros"])
+@pytest.mark.parametrize("case", ["all_slots", "one_slot_missing", "needs_partly_false"])
+def test_weight_gradient_tail_over_slots_and_fresh_kinds(case, fresh, monkeypatch):
+    """ops._mlp_grad_slots / _params_job / _dw_deliver over {every parameter opted in, one did not, one needs no gradient} x {fresh
+    tensors uninitialised (the caller's kernels overwrite them, accumulate 0: _Mlp) or zeroed (the kernels add, accumulate 1: the
+    fused nodes)}: the four gradient tensors, the in-place verdict, the job's fields (a job always adds), postponed exactly when in
+    place and deferrable, and the four-tuple handed to autograd."""
+    from position_induced_transformer_amd import ops
+    rows, n0, n1, n2 = 6, 5, 4, 3
+    shapes = ((n1, n0), (n1,), (n2, n1), (n2,))
+    params = [torch.nn.Parameter(torch.zeros(s)) for s in shapes]
+    slots = {id(p): torch.ones(s) for p, s in zip(params, shapes)}
+    if case == "one_slot_missing":
+        del slots[id(params[2])]
+    needs = (True, True, True, case != "needs_partly_false")
+    monkeypatch.setattr(ops, "_grad_slot", lambda p: slots.get(id(p)))
+    made = {"zeros": 0, "empty": 0}
+    real = {"zeros": torch.zeros, "empty": torch.empty}
+    for kind in made:
+        monkeypatch.setattr(torch, kind, lambda *a, _k=kind, **k: (made.__setitem__(_k, made[_k] + 1), real[_k](*a, **k))[1])
+    grads, inplace = ops._mlp_grad_slots(params, shapes, needs, torch.device("cpu"), fresh=fresh)
+    monkeypatch.undo()
+    assert inplace == (case == "all_slots")
+    if inplace:
+        assert all(g is slots[id(p)] for g, p in zip(grads, params)) and made == {"zeros": 0, "empty": 0}
+    else:
+        assert made == {fresh: 4, ("empty" if fresh == "zeros" else "zeros"): 0}
+        assert [tuple(g.shape) for g in grads] == [tuple(s) for s in shapes] and all(g.dtype == torch.float32 for g in grads)
+        assert all(all(g is not s for s in slots.values()) for g in grads)
+        if fresh == "zeros":
+            assert all(float(g.abs().sum()) == 0.0 for g in grads)
+    x, h, d_y, scratch = torch.zeros(rows, 8)[:, :n0], torch.zeros(rows, n1), torch.zeros(rows, n2), torch.zeros(rows * (n1 + n2))
+    st, keep = ops._params_job(x, h, d_y, scratch, grads, (rows, n0, n1, n2), 1, 0x100)
+    assert (st.x, st.ldx, st.rows, st.n0, st.n1, st.n2, st.h, st.out_gelu) == (x.data_ptr(), 8, rows, n0, n1, n2, h.data_ptr(), 1)
+    assert (st.d_y, st.ld_dy, st.accumulate, st.scratch, st.math_mode) == (d_y.data_ptr(), n2, 1, scratch.data_ptr(), 0x100)
+    assert (st.d_w1, st.d_b1, st.d_w2, st.d_b2) == tuple(g.data_ptr() for g in grads)
+    assert all(a is b for a, b in zip(keep, (x, h, d_y, scratch) + tuple(grads)))
+    assert ops._params_job(x, h, scratch, scratch, grads, (rows, n0, n1, n2), 1, 0, ld_dy=7)[0].ld_dy == 7
+    for deferrable in (True, False):
+        for rider in (True, False):
+            calls = []
+            monkeypatch.setattr(ops, "MLP_PARAMS_RIDER", rider)
+            monkeypatch.setattr(ops, "_dw_deferrable", lambda *key: calls.append(("deferrable", key)) or deferrable)
+            monkeypatch.setattr(ops, "_dw_defer", lambda st_, keep_, dev: calls.append(("defer", st_, keep_)))
+            monkeypatch.setattr(ops, "_dw_run", lambda job: calls.append(("run", job[0], job[1], job[2])))
+            monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: "the current stream")
+            out = ops._dw_deliver((st, keep), inplace, torch.device("cpu"))
+            monkeypatch.undo()
+            what = [c for c in calls if c[0] != "deferrable"]
+            assert len(what) == 1 and what[0][1] is st and what[0][2] is keep
+            assert what[0][0] == ("defer" if (inplace and rider and deferrable) else "run")
+            if what[0][0] == "run":
+                assert what[0][3] == "the current stream"
+            for c in calls:
+                if c[0] == "deferrable":
+                    assert c[1] == (rows, n0, n1, n2, 1, n2)
+            assert isinstance(out, tuple) and len(out) == 4
+            assert all(a is None for a in out) if inplace else all(a is b for a, b in zip(out, grads))
