@@ -934,6 +934,36 @@ int pit_distlist_bwd(const int* idx, const float* sqd, long ld, long bstride, in
                      const int* rev_ptr, const int* rev_pos, const int* chunk_ptr, const int* chunk_key, float* dv_workspace,
                      int math_mode, void* stream);
 
+/* ---- A training step and the evaluation metric on ragged batches (additions to ABI 31; csrc/pit_ragged_step.hip) -----------------
+ * utils.py:59-98 (RelMaxNorm, RelLpNorm) on every sample TRUNCATED to its first len[s] points, as engine.TrainStep and
+ * utils.RelMaxNorm use them with lengths.  A library built from this header defines PIT_HAS_RAGGED_STEP; PIT_ABI_VERSION is
+ * unchanged (nothing that existed changed).  true / pred (batch, npts, nch) contiguous fp32, len (batch) int32 on the device,
+ * clamped into [1, npts] where it is read; padded points are never read (they may hold NaN).  No host synchronisation, no
+ * allocation, capturable; every sum has a fixed order: same input, same bits.
+ *
+ * pit_rel_lp_loss_ragged_fwd_grad - ONE launch for what pit_rel_lp_loss_ragged_fwd, pit_rel_lp_loss_ragged_bwd(gloss = NULL) and a
+ *   memset do in four:
+ *     norms (batch, nch, 2) and *loss  exactly as pit_rel_lp_loss_ragged_fwd writes them (the same summation order, the same bits);
+ *     d_pred_unit (batch, npts, nch)   the gradient for d loss = 1, as pit_rel_lp_loss_ragged_bwd writes it for gloss = NULL (the
+ *                                      same bits), exact zeros on padded points.                              NULL = not wanted
+ *     clear_buf                        clear_n floats are zeroed (the step's flat gradient accumulators; any 4-byte alignment);
+ *                                      clear_n = 0: nothing is cleared
+ *     workspace                        ONE unsigned word, the arrival ticket: zero before the first call, left zero by every call
+ *                                      (calls that share it must be stream-ordered)
+ *   A (sample, channel) series is never split over workgroups; the pairs' terms are added in index order by the workgroup that
+ *   arrives last.  PIT_ERR_NULL for a missing tru, pred, len, norms, loss or workspace; PIT_ERR_SIZE for batch <= 0,
+ *   batch > 65535, npts <= 0, nch <= 0, p < 1, clear_n < 0, or clear_buf == NULL with clear_n > 0.
+ * pit_rel_max_norm_ragged - *out = sum_s mean_c max_{l < len[s]} |true - pred| / max_{l < len[s]} |true| (utils.py:59-77 per
+ *   truncated sample; fp32 division as in the reference, NaN in a real point propagates).  Forward only, no workspace, one
+ *   workgroup: an evaluation metric.  PIT_ERR_NULL for a missing pointer; PIT_ERR_SIZE for batch <= 0, batch > 65535, npts <= 0,
+ *   nch <= 0. */
+#define PIT_HAS_RAGGED_STEP 1
+int pit_rel_lp_loss_ragged_fwd_grad(const float* tru, const float* pred, const int* len, int batch, int npts, int nch, int p,
+                                    float* norms, float* loss, unsigned* workspace, float* d_pred_unit, float* clear_buf,
+                                    long clear_n, void* stream);
+int pit_rel_max_norm_ragged(const float* tru, const float* pred, const int* len, int batch, int npts, int nch, float* out,
+                            void* stream);
+
 /* Layout probe used by the tests: D = A(32x8) * B(8x32) through the same
  * v_mfma_f32_32x32x2_f32 fragment maps the kernels use. */
 int pit_debug_mfma_tile(const float* a, const float* b, float* d, void* stream);

@@ -173,6 +173,8 @@ SIGNATURES = {
     "pit_posatt_ragged_strided_bwd": _RAGGED_STRIDED + _BWD_RAGGED,
     "pit_rel_lp_loss_ragged_fwd": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "pit_rel_lp_loss_ragged_bwd": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
+    "pit_rel_lp_loss_ragged_fwd_grad": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P],
+    "pit_rel_max_norm_ragged": [_P, _P, _P, _I, _I, _I, _P, _P],
     "pit_distmat_select_fwd": [_P, _L, _L, _I, _I, _I, _I, _I, _P, _P],
     "pit_distmat_fwd": _MAT + _FWD_DIST,
     "pit_distmat_bwd_workspace": [_I, _I, _I],
@@ -194,7 +196,8 @@ LONG_RETURN = {"pit_satt_tiles_elems", "pit_posatt_dmesh_workspace", "pit_mlp_bw
                "pit_mlp_bwd_params_ordered_mfma_workspace", "pit_distmat_bwd_workspace", "pit_distlist_bwd_workspace"}
 # entries added to an ABI version after its first release (PIT_HAS_* in the header): a library of the same version built before
 # them lacks the symbols
-ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_workspace", "pit_distlist_bwd"}
+ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_workspace", "pit_distlist_bwd",
+               "pit_rel_lp_loss_ragged_fwd_grad", "pit_rel_max_norm_ragged"}       # PIT_HAS_DISTLIST, PIT_HAS_RAGGED_STEP
 DISTLIST_CHUNK = 512   # PIT_DISTLIST_CHUNK
 
 

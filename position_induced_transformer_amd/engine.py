@@ -8,6 +8,7 @@ in one flat buffer (ddp.FlatGradients) so a data-parallel step is ONE all-reduce
 """
 from __future__ import annotations
 
+import inspect
 from typing import Optional, Sequence
 
 import torch
@@ -34,15 +35,26 @@ class TrainStep:
     def __init__(self, model: torch.nn.Module, batch: Sequence[torch.Tensor], out_dim: int, p: int,
                  pred_affine: Optional[Sequence[torch.Tensor]] = None, all_reduce: bool = False,
                  optimizer: Optional[torch.optim.Optimizer] = None, flat: Optional[FlatGradients] = None,
-                 all_reduce_buckets: int = 1):
+                 all_reduce_buckets: int = 1, len_in=None, len_out=None):
         """``all_reduce_buckets=2``: the gradient exchange is split - the bucket of weights whose gradients are
         complete half-way through the backward pass (early_gradient_parameters) is all-reduced on a second stream
         while the rest of the backward runs, the remainder after the pass; needs a ``flat`` built with that
-        bucket as its ``tail`` (done here when ``flat`` is None)."""
+        bucket as its ``tail`` (done here when ``flat`` is None).
+
+        ``len_in`` / ``len_out`` (lists or tensors, one entry per sample): a ragged batch of padded clouds
+        (tasks.pit_elasticity, tasks.pit_cloud_latent).  Each becomes a static int32 device tensor (``self.len_in`` /
+        ``self.len_out``) the model is called with and ``set_batch`` overwrites in place, so one captured graph serves every
+        mix of sizes up to the padded width.  The loss runs over ``len_out`` - over ``len_in`` when only that is given and
+        ``mesh_out`` is ``mesh_in``, the rule of the two task forwards - in ONE launch that also writes its own gradient
+        and clears the flat gradient buffer (ops.rel_lp_loss_ragged)."""
         self.model = model
         self.mesh_in, self.func_in, self.mesh_out, self.target = batch
         self.out_dim, self.p = out_dim, p
         self.affine = pred_affine
+        self.len_in = self.len_out = self._len_loss = None
+        self._len_kw = {}
+        if len_in is not None or len_out is not None:
+            self._init_lengths(len_in, len_out)
         self.all_reduce = all_reduce
         self.optimizer = optimizer
         self.buckets = 1
@@ -74,6 +86,39 @@ class TrainStep:
         self._seed = torch.ones((), device=self.func_in.device)      # d loss / d loss, allocated once
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._agree_early()                  # (a collective when the process group has more than one rank: every rank builds its step)
+
+    def _init_lengths(self, len_in, len_out) -> None:
+        """The checks of a ragged step (before any launch) and its static length tensors."""
+        if self.affine is not None:
+            raise ValueError("pred_affine with lengths: a per-pixel affine has no meaning on ragged clouds")
+        if isinstance(self, RolloutStep):
+            raise ValueError("RolloutStep with lengths: the rollout runs on one fixed mesh")
+        params = inspect.signature(self.model.forward).parameters
+        any_kw = any(q.kind is inspect.Parameter.VAR_KEYWORD for q in params.values())
+        batch = self.func_in.shape[0]
+        for name, given in (("len_in", len_in), ("len_out", len_out)):
+            if given is None:
+                continue
+            if not any_kw and name not in params:
+                raise ValueError(f"{type(self.model).__name__}.forward does not accept the keyword {name}")
+            width = (self.mesh_in if name == "len_in" else self.mesh_out).shape[-2]
+            self._check_length_list(name, given, width)
+            t = ops.as_lengths(given, self.func_in.device, batch)      # (an int32 device tensor is used as it is)
+            setattr(self, name, t)
+            self._len_kw[name] = t
+        if self.len_out is not None:
+            self._len_loss = self.len_out
+        elif self.mesh_out is self.mesh_in or (self.mesh_out.data_ptr() == self.mesh_in.data_ptr()
+                                                and self.mesh_out.shape == self.mesh_in.shape):
+            self._len_loss = self.len_in
+
+    @staticmethod
+    def _check_length_list(name: str, lengths, width: int) -> None:
+        # a Python sequence is checked on the host; a tensor is taken as it is (a check would synchronise; the kernels clamp)
+        if not torch.is_tensor(lengths):
+            for n in lengths:
+                if not 1 <= int(n) <= width:
+                    raise ValueError(f"{name}: length {int(n)} outside [1, {width}]")
 
     # two-bucket exchange: when the gradient of the marker module's output arrives, everything after it in the forward
     # has been back-propagated (launches enqueued) - fork the second stream there and reduce the early bucket on it
@@ -158,16 +203,20 @@ class TrainStep:
         # the loss the step applies to the prediction: a fused decoder accumulates its partial sums in the forward launch and
         # forms d(pred) in the backward launch - no loss launch (ops.LossSpec; any other model, and the reproducible mode, run the
         # loss kernel below)
-        spec = ops.LossSpec(self.target, sc, sh, self.out_dim, self.p) if self.p in (1, 2) and ops.EDGE_FUSION and not ops.reproducible_wanted() else None
+        # (a ragged step builds none: its loss runs over the lengths)
+        spec = ops.LossSpec(self.target, sc, sh, self.out_dim, self.p) if self.p in (1, 2) and ops.EDGE_FUSION and not ops.reproducible_wanted() and not self._len_kw else None
         # per-thread state, read by the autograd nodes in their forward (ops._STEP)
         with ops.step_state(processor_hook=(self._on_processor_block, self._early_block) if early else None, loss=spec, clear=clear):
             self._step_body(sc, sh)
 
     def _step_body(self, sc, sh) -> None:
-        out = self.model(self.mesh_in, self.func_in, self.mesh_out)
+        out = self.model(self.mesh_in, self.func_in, self.mesh_out, **self._len_kw)
         clear = ops.take_pending_clear()         # None when a launch of the forward already zeroed the buffer
         # the loss launch also writes its own gradient for the seed of ones below: no loss-backward launch
-        loss = ops.rel_lp_loss(self.target, out, self.out_dim, self.p, sc, sh, unit_seed=self._seed, clear=clear)
+        if self._len_loss is not None:
+            loss = ops.rel_lp_loss_ragged(self.target, out, self._len_loss, self.out_dim, self.p, unit_seed=self._seed, clear=clear)
+        else:
+            loss = ops.rel_lp_loss(self.target, out, self.out_dim, self.p, sc, sh, unit_seed=self._seed, clear=clear)
         torch.autograd.backward(loss, grad_tensors=self._seed)        # no ones_like fill per step
         self.loss = loss.detach()            # same storage every replay (graph-private pool): no copy
         self.out = out.detach()              # (the prediction of the last step / replay: parity checks read it)
@@ -230,15 +279,25 @@ class TrainStep:
             ops.parameters_changed()          # the replay rewrote the parameters behind autograd's back
 
     def set_batch(self, func_in: torch.Tensor, target: torch.Tensor, mesh_in: Optional[torch.Tensor] = None,
-                  mesh_out: Optional[torch.Tensor] = None) -> None:
+                  mesh_out: Optional[torch.Tensor] = None, len_in=None, len_out=None) -> None:
         """Copy a new batch into the captured static buffers.  Tasks with per-sample meshes
         (train_elasticity.py:46, train_naca.py:62-65) also pass the batch's meshes: the captured step
         rebuilds its selection plans from the static mesh buffers on every replay, so a replay after
         ``set_batch`` computes on the new clouds.  (When mesh_in and func_in are one tensor, as in
-        NACA, one copy serves both.)"""
+        NACA, one copy serves both.)  ``len_in`` / ``len_out``: the new clouds' point counts, copied into the
+        step's static length tensors; a list is range-checked here, a tensor is copied unchecked (a check would
+        synchronise; the kernels clamp)."""
         if (mesh_in is not None or mesh_out is not None) and not getattr(self.model.down, "_batched", True):
             raise ValueError("this model's meshes are batch-free (fixed): their selection plans were built once and "
                              "are part of the captured step; only per-sample meshes can change between replays")
+        for name, given in (("len_in", len_in), ("len_out", len_out)):
+            if given is None:
+                continue
+            static = getattr(self, name)
+            if static is None:
+                raise ValueError(f"set_batch({name}=...): this step was built without {name}")
+            self._check_length_list(name, given, (self.mesh_in if name == "len_in" else self.mesh_out).shape[-2])
+            static.copy_(ops.as_lengths(given, static.device, static.numel()))
         self.func_in.copy_(func_in)
         self.target.copy_(target)
         if mesh_in is not None and self.mesh_in.data_ptr() != self.func_in.data_ptr():

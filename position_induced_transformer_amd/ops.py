@@ -3209,12 +3209,20 @@ def rel_lp_loss(true, pred, out_dim: int, p: int, pred_scale=None, pred_shift=No
     return _RelLpLoss.apply(pred, true, out_dim, p, pred_scale, pred_shift, unit_seed, clear)
 
 
+_RAGGED_LOSS_WS = {}       # (device index, stream) -> the arrival ticket of pit_rel_lp_loss_ragged_fwd_grad (zero between calls)
+
+
 class _RelLpLossRagged(torch.autograd.Function):
     """RelLpNorm of every sample truncated to its first lengths[s] points (pit_rel_lp_loss_ragged_*): padded points are
-    skipped and get a zero gradient; ``true`` gets none (data)."""
+    skipped and get a zero gradient; ``true`` gets none (data).
+
+    With ``unit_seed`` / ``clear`` (see _RelLpLoss: the seed of ones of a training step, its flat gradient accumulators) ONE
+    launch - pit_rel_lp_loss_ragged_fwd_grad - writes the norms, the loss, the gradient for d loss = 1 and the zeros; backward
+    returns that gradient without a launch when it is handed the seed itself and runs pit_rel_lp_loss_ragged_bwd on the saved
+    norms otherwise.  The values are the same bits either way."""
 
     @staticmethod
-    def forward(ctx, pred, true, lengths, out_dim: int, p: int):
+    def forward(ctx, pred, true, lengths, out_dim: int, p: int, unit_seed=None, clear=None):
         _need_gpu(pred, true)
         b = true.size(0)
         t = true.detach().reshape(b, -1, out_dim).contiguous()
@@ -3224,11 +3232,30 @@ class _RelLpLossRagged(torch.autograd.Function):
         npts = t.shape[1]
         norms = torch.empty((b, out_dim, 2), device=t.device, dtype=torch.float32)
         loss = torch.empty((), device=t.device, dtype=torch.float32)
-        rc = _lib.lib().pit_rel_lp_loss_ragged_fwd(t.data_ptr(), q.data_ptr(), lengths.data_ptr(), b, npts, out_dim, int(p),
-                                                   norms.data_ptr(), loss.data_ptr(), _lib.stream_ptr())
-        _lib.check(rc, "pit_rel_lp_loss_ragged_fwd")
+        unit_p = None
+        if unit_seed is None and clear is None:
+            rc = _lib.lib().pit_rel_lp_loss_ragged_fwd(t.data_ptr(), q.data_ptr(), lengths.data_ptr(), b, npts, out_dim, int(p),
+                                                       norms.data_ptr(), loss.data_ptr(), _lib.stream_ptr())
+            _lib.check(rc, "pit_rel_lp_loss_ragged_fwd")
+        else:
+            if clear is not None and (not clear.is_contiguous() or clear.dtype != torch.float32):
+                raise RuntimeError("clear must be a contiguous fp32 tensor")
+            wkey = _ws_key(t.device)
+            ws = _RAGGED_LOSS_WS.get(wkey)
+            if ws is None:
+                ws = _RAGGED_LOSS_WS[wkey] = torch.zeros(4, device=t.device, dtype=torch.int32)
+            if _capturing():
+                _pin(ws)
+            if unit_seed is not None and pred.requires_grad:
+                unit_p = torch.empty_like(q)
+            rc = _lib.lib().pit_rel_lp_loss_ragged_fwd_grad(t.data_ptr(), q.data_ptr(), lengths.data_ptr(), b, npts, out_dim, int(p),
+                                                            norms.data_ptr(), loss.data_ptr(), ws.data_ptr(), _lib.ptr(unit_p),
+                                                            _lib.ptr(clear), clear.numel() if clear is not None else 0,
+                                                            _lib.stream_ptr())
+            _lib.check(rc, "pit_rel_lp_loss_ragged_fwd_grad")
         ctx.meta = (b, npts, out_dim, int(p), pred.shape)
         ctx.save_for_backward(t, q, norms, lengths)
+        ctx.unit = (unit_seed.data_ptr() if unit_seed is not None else 0, unit_p)
         return loss
 
     @staticmethod
@@ -3236,25 +3263,30 @@ class _RelLpLossRagged(torch.autograd.Function):
         t, q, norms, lengths = ctx.saved_tensors
         b, npts, out_dim, p, shape = ctx.meta
         if not ctx.needs_input_grad[0]:
-            return None, None, None, None, None
+            return None, None, None, None, None, None, None
+        seed_ptr, unit_p = ctx.unit
+        if seed_ptr and g.data_ptr() == seed_ptr and unit_p is not None:
+            # d loss is the step's tensor of ones: the forward launch already wrote this gradient
+            return unit_p.reshape(shape), None, None, None, None, None, None
         g = g.contiguous()
         d_pred = torch.empty_like(q)
         rc = _lib.lib().pit_rel_lp_loss_ragged_bwd(t.data_ptr(), q.data_ptr(), lengths.data_ptr(), b, npts, out_dim, p,
                                                    norms.data_ptr(), g.data_ptr(), d_pred.data_ptr(), _lib.stream_ptr())
         _lib.check(rc, "pit_rel_lp_loss_ragged_bwd")
-        return d_pred.reshape(shape), None, None, None, None
+        return d_pred.reshape(shape), None, None, None, None, None, None
 
 
 @torch.compiler.disable
-def rel_lp_loss_ragged(true, pred, lengths, out_dim: int, p: int) -> torch.Tensor:
-    """sum_s mean_c ||true_s - pred_s||_p / ||true_s||_p over the first lengths[s] points of every sample."""
+def rel_lp_loss_ragged(true, pred, lengths, out_dim: int, p: int, unit_seed=None, clear=None) -> torch.Tensor:
+    """sum_s mean_c ||true_s - pred_s||_p / ||true_s||_p over the first lengths[s] points of every sample.
+    ``unit_seed`` / ``clear``: see _RelLpLossRagged (used by engine.TrainStep: no loss-backward launch, no memset)."""
     if torch.is_grad_enabled() and true.requires_grad:
         raise NotImplementedError("RelLpNorm with lengths gives `true` no gradient (it is data)")
     _need_gpu(pred, true)
     lengths = as_lengths(lengths, pred.device, true.size(0))
     if _capturing():
         _pin(lengths)
-    return _RelLpLossRagged.apply(pred, true, lengths, out_dim, p)
+    return _RelLpLossRagged.apply(pred, true, lengths, out_dim, p, unit_seed, clear)
 
 
 _RELMAX_WS = {}
@@ -3282,6 +3314,28 @@ def rel_max_norm(true: torch.Tensor, pred: torch.Tensor, out_dim: int) -> torch.
     out = torch.empty((), device=t.device, dtype=torch.float32)
     _lib.check(_lib.lib().pit_rel_max_norm(t.data_ptr(), q.data_ptr(), b, t.shape[1], out_dim, out.data_ptr(),
                                            ws.data_ptr(), _lib.stream_ptr()), "pit_rel_max_norm")
+    return out
+
+
+@torch.compiler.disable
+def rel_max_norm_ragged(true: torch.Tensor, pred: torch.Tensor, lengths, out_dim: int) -> torch.Tensor:
+    """RelMaxNorm (utils.py:59-77) of every sample truncated to its first lengths[s] points: sum_s mean_c max|true-pred| / max|true|
+    over the real points; padded points are never read.  Forward only, device tensors only."""
+    _need_gpu(true, pred)
+    if torch.is_grad_enabled() and (true.requires_grad or pred.requires_grad):
+        raise NotImplementedError("RelMaxNorm on device tensors is forward-only (an evaluation metric in the reference "
+                                  "scripts): call it under torch.no_grad() or on detached tensors")
+    b = true.size(0)
+    t = true.detach().reshape(b, -1, out_dim).contiguous()
+    q = pred.detach().reshape(b, -1, out_dim).contiguous()
+    if t.shape != q.shape:
+        raise RuntimeError(f"true {tuple(true.shape)} and pred {tuple(pred.shape)} do not match")
+    lengths = as_lengths(lengths, t.device, b)
+    if _capturing():
+        _pin(lengths)
+    out = torch.empty((), device=t.device, dtype=torch.float32)
+    _lib.check(_lib.lib().pit_rel_max_norm_ragged(t.data_ptr(), q.data_ptr(), lengths.data_ptr(), b, t.shape[1], out_dim,
+                                                  out.data_ptr(), _lib.stream_ptr()), "pit_rel_max_norm_ragged")
     return out
 
 

@@ -77,7 +77,11 @@ class RelMaxNorm:
     def __init__(self, out_dim):
         self._out_dim = out_dim
 
-    def __call__(self, true, pred):
+    def __call__(self, true, pred, lengths=None):
+        """``lengths`` (ragged batches; as for RelLpNorm): the maxima of sample s run over its first lengths[s] points only -
+        utils.py:64-77 on the truncated sample; padded points are never read.  Device tensors only."""
+        if lengths is not None:
+            return ops.rel_max_norm_ragged(true, pred, lengths, self._out_dim)
         if pred.is_cuda or true.is_cuda:
             return ops.rel_max_norm(true, pred, self._out_dim)      # HIP kernel (forward only, as the scripts use it)
         # host tensors (offline evaluation of saved predictions)
