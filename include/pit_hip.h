@@ -964,6 +964,23 @@ int pit_rel_lp_loss_ragged_fwd_grad(const float* tru, const float* pred, const i
 int pit_rel_max_norm_ragged(const float* tru, const float* pred, const int* len, int batch, int npts, int nch, float* out,
                             void* stream);
 
+/* ---- The two slab forms of pit_block_fwd (additions to ABI 31; csrc/pit_block.hip) ------------------------------------------------
+ * pit_block_fwd runs 16-row slabs, or - n_head = 2, n_pts = 256, the weights through LDS, and 8 * ceil(batch / 8) * n_pts / 8
+ * workgroups no more than the device has CUs (batch <= 8 on MI355X) - 8-row slabs with the two heads stacked in the M dimension of
+ * one MFMA (both heads contract the same value rows).  Every per-element sum keeps its order, so the two forms write the same
+ * bits to xcat, z1, h, z2 and y.  A library built from this header defines PIT_HAS_BLOCK_ROWS8; PIT_ABI_VERSION is unchanged
+ * (nothing that existed changed; pit_block_fwd keeps its signature).  The environment variable PIT_BLOCK_ROWS8=0 (read once)
+ * keeps the automatic choice on the 16-row form.  Host-side and process-global, no device work, nothing read by a kernel:
+ *
+ * pit_block_fwd_set_form - 0: automatic (the rule above), 16: always the 16-row form, 8: the stacked form wherever the rule
+ *   above admits it (PIT_BLOCK_ROWS8 notwithstanding), 16 rows elsewhere.  Returns the previous value, PIT_ERR_SIZE (nothing
+ *   changed) for any other argument.  Meant for tests and A/B runs: a graph captured earlier keeps the form it was captured with.
+ * pit_block_fwd_last_rows - the slab height (8 or 16) of the most recent pit_block_fwd launch of this process, 0 before the
+ *   first. */
+#define PIT_HAS_BLOCK_ROWS8 1
+int pit_block_fwd_set_form(int form);
+int pit_block_fwd_last_rows(void);
+
 /* Layout probe used by the tests: D = A(32x8) * B(8x32) through the same
  * v_mfma_f32_32x32x2_f32 fragment maps the kernels use. */
 int pit_debug_mfma_tile(const float* a, const float* b, float* d, void* stream);

@@ -190,6 +190,8 @@ SIGNATURES = {
     "pit_debug_mfma_tile": [_P, _P, _P, _P],
     "pit_debug_rider_counts": [_P, _I, _I],
     "pit_debug_gemm_counts": [_P, _I, _I],
+    "pit_block_fwd_set_form": [_I],
+    "pit_block_fwd_last_rows": [],
 }
 
 LONG_RETURN = {"pit_satt_tiles_elems", "pit_posatt_dmesh_workspace", "pit_mlp_bwd_params_ordered_workspace",
@@ -197,7 +199,8 @@ LONG_RETURN = {"pit_satt_tiles_elems", "pit_posatt_dmesh_workspace", "pit_mlp_bw
 # entries added to an ABI version after its first release (PIT_HAS_* in the header): a library of the same version built before
 # them lacks the symbols
 ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_workspace", "pit_distlist_bwd",
-               "pit_rel_lp_loss_ragged_fwd_grad", "pit_rel_max_norm_ragged"}       # PIT_HAS_DISTLIST, PIT_HAS_RAGGED_STEP
+               "pit_rel_lp_loss_ragged_fwd_grad", "pit_rel_max_norm_ragged",       # PIT_HAS_DISTLIST, PIT_HAS_RAGGED_STEP
+               "pit_block_fwd_set_form", "pit_block_fwd_last_rows"}                # PIT_HAS_BLOCK_ROWS8
 DISTLIST_CHUNK = 512   # PIT_DISTLIST_CHUNK
 
 

@@ -27,6 +27,7 @@
 #include "pit_common.h"
 #include "pit_gemm_rd.h"
 #include "pit_block_dev.h"
+#include <atomic>
 #include <cstdlib>
 
 namespace {
@@ -149,33 +150,44 @@ struct BlockFwdArgs {
 // look-ups per workgroup for W1 | W2 against 512 when all eight waves copy the 64 KB with unit-stride 16-byte loads; the copy lands
 // in LDS before the barrier in front of GEMM1 and the fragments are ds_read_b128s.  Needs 64 KB more LDS (one workgroup per CU):
 // taken when the launch has no more workgroups than the chip has CUs.
-template <int H, bool WLDS>
+//
+// R8 (round 8; H = 2, WLDS, L = 256 only): an 8-row slab with the two heads STACKED in M.  Both heads contract the same value rows
+// (the B operand), so the A operand of one v_mfma_f32_16x16x4_f32 holds the slab's 8 rows of head 0 in matrix rows 0..7 and the same
+// 8 rows of head 1 in rows 8..15: one MFMA where the 16-row form issues two, one accumulator set, one parked tile per wave, half the
+// E bytes per workgroup and twice the workgroups (a batch of 8 fills all 256 CUs).  C row r = head r >> 3, slab row r & 7.  MFMA
+// output rows do not mix and every per-element sum keeps its order (k-steps of a wave, waves 0..7, * 1/rowsum), so xcat, z1, h, z2 and
+// y are the 16-row form's bit for bit.  The MLP runs on the same 16-row tiles with rows 8..15 zero (half of M idle), stores rows 0..7.
+template <int H, bool WLDS, bool R8 = false>
 __global__ __launch_bounds__(512, WLDS ? 1 : 2) void block_fwd_kernel(BlockFwdArgs g) {      // (WLDS: one workgroup per CU, 256 registers)
+    static_assert(!R8 || (H == 2 && WLDS), "the stacked form: two heads, weights and E through LDS");
     constexpr int W = (1 + H) * BD;                     // concat width = K of the first contraction
     constexpr int XP = W + 4, HP = BD + 4;              // LDS pitches
     constexpr int KS = W / 16;
     constexpr int NW1 = BD * W / 4 / 512, NW2 = BD * BD / 4 / 512;      // 16-byte pieces of W1 / W2 per thread (6 / 2 at H = 2)
+    constexpr int RS = R8 ? 8 : 16;                     // slab rows
+    constexpr int NA = R8 ? 1 : H;                      // accumulator sets = parked tiles per wave
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* pk = smem;                                   // [H * PARK_FLOATS]: slot wave*H + head
-    float* xs = smem + H * PARK_FLOATS;                 // [16][XP] concat tile
+    float* pk = smem;                                   // [NA * PARK_FLOATS]: slot wave*H + head (R8: slot wave)
+    float* xs = smem + NA * PARK_FLOATS;                // [16][XP] concat tile
     float* hs = xs + 16 * XP;                           // [16][HP] hidden tile
     float* w1s = hs + 16 * HP;                          // WLDS: [64][XP] image of W1, then [64][HP] image of W2
     float* w2s = w1s + BD * XP;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, kq = lane >> 4;
-    const int slabs = g.L / 16;
+    const int slabs = g.L / RS;
     int b, slab;
     if (!slab_of(blockIdx.x, g.batch, slabs, b, slab)) return;
-    const int n0 = slab * 16;
-    const long m0 = ((long)b * slabs + slab) * 16;      // first row of the slab in the (batch*L) row space
+    const int n0 = slab * RS;
+    const long m0 = ((long)b * slabs + slab) * RS;      // first row of the slab in the (batch*L) row space
     const int klen = g.L / BW;                          // every wave: its eighth of the keys, all heads
 
     // the slab's own X rows (first 64 columns of the concat tile): requested first, parked after the attention loads
     float4 xown = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (tid < 256) xown = *reinterpret_cast<const float4*>(g.xcat + (m0 + (tid >> 4)) * W + 4 * (tid & 15));
+    if (tid < RS * 16) xown = *reinterpret_cast<const float4*>(g.xcat + (m0 + (tid >> 4)) * W + 4 * (tid & 15));
     // 1 / rowsum of the row this thread normalises after the reduction (item = tid when H = 2: one per thread): requested here -
     // round 5: loaded inside the reduction it was a dependent memory round trip in the middle of the chain
-    const float rinv0 = g.inv[(long)((tid >> 8) % H) * g.L + n0 + 4 * ((tid & 63) >> 4) + ((tid >> 6) & 3)];
+    const int r0 = 4 * ((tid & 63) >> 4) + ((tid >> 6) & 3);           // C row of item = tid
+    const float rinv0 = R8 ? g.inv[(long)(r0 >> 3) * g.L + n0 + (r0 & 7)] : g.inv[(long)((tid >> 8) % H) * g.L + n0 + r0];
 
     BSTAMP(0);
     // MLP operands (waves 0..3 own the four hidden / output tiles): requested before (EARLYW) or after the attention
@@ -205,25 +217,26 @@ __global__ __launch_bounds__(512, WLDS ? 1 : 2) void block_fwd_kernel(BlockFwdAr
         for (int p = 0; p < NW2; ++p) wq2[p] = reinterpret_cast<const f32x4_t*>(g.w2)[p * 512 + tid];
         load_weights();
     }
-    f32x4_t acc[H][4];
+    f32x4_t acc[NA][4];
 #pragma unroll
-    for (int hh = 0; hh < H; ++hh)
+    for (int hh = 0; hh < NA; ++hh)
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc[hh][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     // ELDS: the slab's E rows (A operand) through LDS as well, when they fit the region the weights take later (L <= 256: one
     // 32-key trip per wave).  As fragments, lane = row: 16 cache lines per wave instruction (2 048 look-ups per workgroup); as
     // unit-stride copies 256.  The value rows (B operand: lanes along the row) are requested first, in the same round trip.
     constexpr int EP = 256 + 4;
-    const bool elds = WLDS && g.L == 256 && !(PIT_BLOCK_EXP & 64);
+    const bool elds = R8 || (WLDS && g.L == 256 && !(PIT_BLOCK_EXP & 64));
     if (elds) {
-        float* es = w1s;                                // [H][16][EP], overwritten by the weights after the next barrier but one
+        float* es = w1s;                                // [H][RS][EP], overwritten by the weights after the next barrier but one
         const float* vp = g.xcat + (long)b * g.L * W + 4 * l15;
         const int j0 = wave * 32;
-        f32x4_t eq[H * 2];
+        constexpr int NE = H * RS / 8;                  // 16-byte pieces of the E rows per thread
+        f32x4_t eq[NE];
 #pragma unroll
-        for (int p = 0; p < H * 2; ++p) {               // piece q: head q >> 10, row (q >> 6) & 15, keys 4 (q & 63) ..
+        for (int p = 0; p < NE; ++p) {                  // piece q: head q / (64 RS), row (q >> 6) & (RS - 1), keys 4 (q & 63) ..
             const int q = p * 512 + tid;
-            eq[p] = *reinterpret_cast<const f32x4_t*>(g.e + (long)(q >> 10) * g.L * g.L + (long)(n0 + ((q >> 6) & 15)) * g.L + 4 * (q & 63));
+            eq[p] = *reinterpret_cast<const f32x4_t*>(g.e + (long)(q / (64 * RS)) * g.L * g.L + (long)(n0 + ((q >> 6) & (RS - 1))) * g.L + 4 * (q & 63));
         }
         f32x4_t bvv[2][4];
 #pragma unroll
@@ -232,44 +245,54 @@ __global__ __launch_bounds__(512, WLDS ? 1 : 2) void block_fwd_kernel(BlockFwdAr
             for (int m = 0; m < 4; ++m) bvv[s][m] = *reinterpret_cast<const f32x4_t*>(vp + (long)(j0 + 16 * s + 4 * kq + m) * W);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int p = 0; p < H * 2; ++p) {
+        for (int p = 0; p < NE; ++p) {                  // image row (head * RS + row) = q >> 6
             const int q = p * 512 + tid;
-            *reinterpret_cast<f32x4_t*>(es + ((q >> 10) * 16 + ((q >> 6) & 15)) * EP + 4 * (q & 63)) = eq[p];
+            *reinterpret_cast<f32x4_t*>(es + (q >> 6) * EP + 4 * (q & 63)) = eq[p];
         }
         __syncthreads();
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            f32x4_t av[H];
+            f32x4_t av[NA];                             // (R8: matrix row l15 = head l15 >> 3, slab row l15 & 7 = image row l15)
 #pragma unroll
-            for (int hh = 0; hh < H; ++hh) av[hh] = *reinterpret_cast<const f32x4_t*>(es + (hh * 16 + l15) * EP + j0 + 16 * s + 4 * kq);
+            for (int hh = 0; hh < NA; ++hh) av[hh] = *reinterpret_cast<const f32x4_t*>(es + (hh * 16 + l15) * EP + j0 + 16 * s + 4 * kq);
 #pragma unroll
             for (int m = 0; m < 4; ++m)
 #pragma unroll
-                for (int hh = 0; hh < H; ++hh) {
+                for (int hh = 0; hh < NA; ++hh) {
                     acc[hh][0] = mfma_16x16x4(av[hh][m], bvv[s][m][0], acc[hh][0]);
                     acc[hh][1] = mfma_16x16x4(av[hh][m], bvv[s][m][1], acc[hh][1]);
                     acc[hh][2] = mfma_16x16x4(av[hh][m], bvv[s][m][2], acc[hh][2]);
                     acc[hh][3] = mfma_16x16x4(av[hh][m], bvv[s][m][3], acc[hh][3]);
                 }
         }
-    } else {
+    } else if constexpr (!R8) {
         slab_contract<H, true>(g.e + (long)n0 * g.L, (long)g.L * g.L, g.L, g.xcat + (long)b * g.L * W, W, 0, nullptr,
                                wave * klen, (wave + 1) * klen, l15, kq, acc);
     }
     BSTAMP(1);
     if (!WLDS) load_weights();
 #pragma unroll
-    for (int hh = 0; hh < H; ++hh) park(pk, wave * H + hh, lane, acc[hh]);
-    if (tid < 256) *reinterpret_cast<float4*>(xs + (tid >> 4) * XP + 4 * (tid & 15)) = xown;
+    for (int hh = 0; hh < NA; ++hh) park(pk, wave * NA + hh, lane, acc[hh]);
+    if (tid < RS * 16) *reinterpret_cast<float4*>(xs + (tid >> 4) * XP + 4 * (tid & 15)) = xown;
+    if (R8)                                             // rows 8..15 of the concat tile: the MLP's idle half of M contracts zeros
+        for (int q = tid; q < 8 * XP / 4; q += 512) reinterpret_cast<float4*>(xs + 8 * XP)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
     __syncthreads();
     BSTAMP(2);
     // reduce over the key splits, normalise, -> concat tile (LDS) and concat buffer (memory: the backward needs it)
-    for (int item = tid; item < H * 256; item += 512) {
-        const int hh = item >> 8, i = (item >> 6) & 3, ln = item & 63;
-        const int r = 4 * (ln >> 4) + i, col = 4 * (ln & 15);
-        float4 s = parked_sum(pk, hh, BW, H, i, ln);
-        const float rinv = item == tid ? rinv0 : g.inv[(long)hh * g.L + n0 + r];
-        s.x *= rinv; s.y *= rinv; s.z *= rinv; s.w *= rinv;
+    if (!R8) {
+        for (int item = tid; item < H * 256; item += 512) {
+            const int hh = item >> 8, i = (item >> 6) & 3, ln = item & 63;
+            const int r = 4 * (ln >> 4) + i, col = 4 * (ln & 15);
+            float4 s = parked_sum(pk, hh, BW, H, i, ln);
+            const float rinv = item == tid ? rinv0 : g.inv[(long)hh * g.L + n0 + r];
+            s.x *= rinv; s.y *= rinv; s.z *= rinv; s.w *= rinv;
+            *reinterpret_cast<float4*>(xs + r * XP + BD + hh * BD + col) = s;
+            *reinterpret_cast<float4*>(g.xcat + (m0 + r) * W + BD + hh * BD + col) = s;
+        }
+    } else if (tid < 256) {                             // one item per thread: C row r0 = head r0 >> 3, slab row r0 & 7
+        const int hh = r0 >> 3, r = r0 & 7, col = 4 * (tid & 15);
+        float4 s = parked_sum(pk, 0, BW, 1, (tid >> 6) & 3, tid & 63);
+        s.x *= rinv0; s.y *= rinv0; s.z *= rinv0; s.w *= rinv0;
         *reinterpret_cast<float4*>(xs + r * XP + BD + hh * BD + col) = s;
         *reinterpret_cast<float4*>(g.xcat + (m0 + r) * W + BD + hh * BD + col) = s;
     }
@@ -307,9 +330,11 @@ __global__ __launch_bounds__(512, WLDS ? 1 : 2) void block_fwd_kernel(BlockFwdAr
             const int r = 4 * kq + i;
             const float z = a0[i] + a1[i] + bias;
             const float hv = gelu_erf(z);
-            hs[r * HP + c1] = hv;
-            g.z1[(m0 + r) * BD + c1] = z;
-            g.h[(m0 + r) * BD + c1] = hv;
+            hs[r * HP + c1] = hv;                       // (R8: rows 8..15 hold gelu(bias) - finite, never stored)
+            if (!R8 || kq < 2) {
+                g.z1[(m0 + r) * BD + c1] = z;
+                g.h[(m0 + r) * BD + c1] = hv;
+            }
         }
     }
     BSTAMP(6);
@@ -329,6 +354,7 @@ __global__ __launch_bounds__(512, WLDS ? 1 : 2) void block_fwd_kernel(BlockFwdAr
     BSTAMP(8);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
+        if (R8 && kq >= 2) break;                       // (tile rows 8..15 are not the slab's)
         const long r = m0 + 4 * kq + i;
         float v = o0[i] + o1[i] + bias2;
         if (g.out_gelu) { g.z2[r * BD + c1] = v; v = gelu_erf(v); }
@@ -548,13 +574,17 @@ __global__ __launch_bounds__(512) void block_bwd_kernel(BlockBwdArgs g, pit_deta
     BREC(1);
 }
 
-constexpr size_t fwd_smem(int H, bool wlds) {
-    return ((size_t)H * PARK_FLOATS + 16 * ((1 + H) * BD + 4) + 16 * (BD + 4) + (wlds ? BD * ((1 + H) * BD + 4) + BD * (BD + 4) : 0)) * sizeof(float);
+constexpr size_t fwd_smem(int H, bool wlds, bool r8) {
+    return ((size_t)(r8 ? 1 : H) * PARK_FLOATS + 16 * ((1 + H) * BD + 4) + 16 * (BD + 4) + (wlds ? BD * ((1 + H) * BD + 4) + BD * (BD + 4) : 0)) * sizeof(float);
 }
 constexpr size_t bwd_smem(int H, bool dscale) {
     return std::max((size_t)(PARK_FLOATS + 2 * 16 * (BD + 4)) * sizeof(float),
                     dscale ? ((size_t)H * PARK_FLOATS) * sizeof(float) + BW * sizeof(double) : (size_t)0);
 }
+
+// pit_block_fwd_set_form / pit_block_fwd_last_rows (include/pit_hip.h): host-side, process-global, read by no kernel
+std::atomic<int> block_fwd_form{0};                     // 0 = automatic, 16 = the 16-row form, 8 = stacked where eligible
+std::atomic<int> block_fwd_rows{0};                     // slab height of the most recent pit_block_fwd launch
 
 }  // namespace
 
@@ -591,28 +621,42 @@ extern "C" int pit_block_fwd(const float* e, const float* inv, int n_pts, int n_
     g.e = e; g.inv = inv; g.L = n_pts; g.batch = batch; g.xcat = xcat;
     g.w1 = w1; g.b1 = b1; g.w2 = w2; g.b2 = b2; g.out_gelu = out_gelu;
     g.z1 = z1; g.h = h; g.z2 = z2; g.y = y; g.ldy = ldy;
-    const dim3 grid((unsigned)slab_grid(batch, n_pts / 16)), block(64 * BW);
     static const bool no_wlds = getenv("PIT_NO_BLOCK_WLDS") != nullptr;                  // (A/B switch, read once)
+    static const bool no_rows8 = [] { const char* v = getenv("PIT_BLOCK_ROWS8"); return v && v[0] == '0'; }();      // (A/B switch, read once)
     static const int n_cus = [] {                       // (one device per process: read once)
         int dev = 0, cus = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
         return cus;
     }();
-    const bool earlyw = !no_wlds && (int)grid.x <= n_cus;      // WLDS: the weights through LDS (one workgroup per CU: 64 KB more LDS)
-    const size_t FWD_SMEM = fwd_smem(n_head, earlyw);
-#define PIT_BLOCK_FWD(H_, E_)                                                                                              \
+    // R8: 8-row slabs with the two heads stacked in M, while the twice as many workgroups still get a CU each (batch <= 8 on 256 CUs)
+    const int form = block_fwd_form.load(std::memory_order_relaxed);
+    const bool rows8 = n_head == 2 && n_pts == 256 && !no_wlds && form != 16 && (form == 8 || !no_rows8) &&
+                       slab_grid(batch, n_pts / 8) <= n_cus;
+    const dim3 grid((unsigned)slab_grid(batch, n_pts / (rows8 ? 8 : 16))), block(64 * BW);
+    const bool earlyw = rows8 || (!no_wlds && (int)grid.x <= n_cus);      // WLDS: the weights through LDS (one workgroup per CU: 64 KB more LDS)
+    const size_t FWD_SMEM = fwd_smem(n_head, earlyw, rows8);
+#define PIT_BLOCK_FWD(...)                                                                                                 \
     do {                                                                                                                   \
-        static bool once = ((void)hipFuncSetAttribute((const void*)block_fwd_kernel<H_, E_>,                              \
+        static bool once = ((void)hipFuncSetAttribute((const void*)block_fwd_kernel<__VA_ARGS__>,                         \
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), true);            \
         (void)once;                                                                                                        \
-        hipLaunchKernelGGL((block_fwd_kernel<H_, E_>), grid, block, FWD_SMEM, (hipStream_t)stream, g);                     \
+        hipLaunchKernelGGL((block_fwd_kernel<__VA_ARGS__>), grid, block, FWD_SMEM, (hipStream_t)stream, g);                \
     } while (0)
     if (n_head == 1) { if (earlyw) PIT_BLOCK_FWD(1, true); else PIT_BLOCK_FWD(1, false); }
+    else if (rows8) PIT_BLOCK_FWD(2, true, true);
     else { if (earlyw) PIT_BLOCK_FWD(2, true); else PIT_BLOCK_FWD(2, false); }
 #undef PIT_BLOCK_FWD
     PIT_CHECK_LAUNCH();
+    block_fwd_rows.store(rows8 ? 8 : 16, std::memory_order_relaxed);
     return 0;
 }
+
+extern "C" int pit_block_fwd_set_form(int form) {
+    if (form != 0 && form != 8 && form != 16) return PIT_ERR_SIZE;
+    return block_fwd_form.exchange(form, std::memory_order_relaxed);
+}
+
+extern "C" int pit_block_fwd_last_rows(void) { return block_fwd_rows.load(std::memory_order_relaxed); }
 
 #ifdef PIT_WGREC
 extern "C" int pit_block_read_wgrec(unsigned long long* out, int n) {
