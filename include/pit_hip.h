@@ -981,6 +981,28 @@ int pit_rel_max_norm_ragged(const float* tru, const float* pred, const int* len,
 int pit_block_fwd_set_form(int form);
 int pit_block_fwd_last_rows(void);
 
+/* The weight-gradient riders of pit_block_bwd (`rider`, `rider2`; fp32 math mode) run in three forms: register-direct MFMA tiles
+ * split over the rows, LDS-staged 64 x 64 tiles per row slab, and - a dW2 | db2 with n2 <= 4 and n1 in {32, 64, 128} - a vector-ALU
+ * row reduction on at most 16 workgroups (one add per output element and workgroup).  When `rider` is the block's own MLP (rows =
+ * batch * n_pts), both its reductions are 64 x 64 tiles and batch is a multiple of 8, a row slab's tiles run on the XCD that the
+ * chain gives the slab's sample.  With d(scale) wanted and at most an eighth of the riders beyond the d(scale) slabs' count, the
+ * d(scale) slabs take the launch's first workgroup ids and the chain slabs the second range: riders share the compute units of
+ * the first range, and the chain is the longer of the two.  Only the summation order of the thin dW2 | db2 differs from the older
+ * plan; the environment variable PIT_RIDER_TAIL=0 (read once) keeps that plan, the id-order tile map and the chain slabs first.  A library built from this header defines
+ * PIT_HAS_RIDER_TAIL; PIT_ABI_VERSION is unchanged (nothing that existed changed).
+ *
+ * pit_block_bwd_last_riders - rider workgroups of the most recent pit_block_bwd launch of this process by form, whether the
+ *   XCD-local map was used and which range came first: copies min(n, PIT_BLOCK_RIDER_SLOTS) values to out (host array), returns PIT_BLOCK_RIDER_SLOTS.
+ *   Host-side and process-global, no device work, nothing read by a kernel. */
+#define PIT_HAS_RIDER_TAIL 1
+#define PIT_BLOCK_RIDER_RD    0   /* workgroups of register-direct reductions (gemm_rd_body)              */
+#define PIT_BLOCK_RIDER_TILE  1   /* gemm_rr_tile tiles                                                  */
+#define PIT_BLOCK_RIDER_THIN  2   /* thin_rider workgroups                                               */
+#define PIT_BLOCK_RIDER_LOCAL 3   /* 1: `rider`'s tiles were dealt to their sample's XCD, 0: by id alone */
+#define PIT_BLOCK_RIDER_DS_FIRST 4 /* 1: the d(scale) slabs had the launch's first workgroup ids, 0: the chain slabs */
+#define PIT_BLOCK_RIDER_SLOTS 5
+int pit_block_bwd_last_riders(int* out, int n);
+
 /* Layout probe used by the tests: D = A(32x8) * B(8x32) through the same
  * v_mfma_f32_32x32x2_f32 fragment maps the kernels use. */
 int pit_debug_mfma_tile(const float* a, const float* b, float* d, void* stream);

@@ -376,6 +376,7 @@ struct BlockBwdArgs {
     float *dz1, *dz2;                   // scratch of that MLP's backward: (rows, 64) each
     float* d_values; long ld_dvalues;   // (rows, 64) when there is no previous MLP
     int n_chain, n_ds;                  // workgroup ranges: [0, n_chain) chain slabs, then n_ds d(scale) slabs, then the rider
+    int ds_first;                       // 1: the d(scale) slabs take the first range, the chain slabs the second
 };
 
 template <int H>
@@ -563,14 +564,15 @@ __global__ __launch_bounds__(512) void block_bwd_kernel(BlockBwdArgs g, pit_deta
     // (placement, tools/stamp_block.py: the dispatcher deals workgroup ids to the CUs of an XCD in turn and starts over after one
     //  each, so the riders - dealt third - share the compute units of the FIRST range.  d(scale) slabs first, i.e. riders beside
     //  the 5 us d(scale) workgroups instead of the 7 us chain workgroups, was measured: 11.4 against 11.1 us in the step - a rider
-    //  beside a d(scale) slab lives 8 us, 4.8 alone)
-    if (id < g.n_chain) { block_bwd_chain<H>(g, smem, id); BREC(1); return; }
-    id -= g.n_chain;
-    if (id < g.n_ds) { block_bwd_dscale<H>(g, smem, id); BREC(1); return; }
-    id -= g.n_ds;
+    //  beside a d(scale) slab lives 8 us, 4.8 alone.  That was with 209 riders, 81 of which still sat beside chain slabs; with the
+    //  thin riders of round 9 nearly all fit beside the d(scale) slabs and g.ds_first, set by pit_block_bwd, swaps the two ranges)
+    const int c0 = g.ds_first ? g.n_ds : 0, d0 = g.ds_first ? 0 : g.n_chain;
+    if (id >= c0 && id < c0 + g.n_chain) { block_bwd_chain<H>(g, smem, id - c0); BREC(1); return; }
+    if (id >= d0 && id < d0 + g.n_ds) { block_bwd_dscale<H>(g, smem, id - d0); BREC(1); return; }
+    id -= g.n_chain + g.n_ds;
     if (PIT_BLOCK_EXP & 32) return;                     // (experiment: riders leave at once - the launch without their work)
-    if (NDW >= 1 && id < w.n1 + w.n2) { dw_pair_body(w, id, smem); BREC(1); return; }
-    if (NDW >= 2) dw_pair_body(w2, id - (w.n1 + w.n2), smem);
+    if (NDW >= 1 && id < w.n1 + w.n2) { dw_pair_body<true, true>(w, id, smem); BREC(1); return; }
+    if (NDW >= 2) dw_pair_body<true>(w2, id - (w.n1 + w.n2), smem);
     BREC(1);
 }
 
@@ -585,6 +587,8 @@ constexpr size_t bwd_smem(int H, bool dscale) {
 // pit_block_fwd_set_form / pit_block_fwd_last_rows (include/pit_hip.h): host-side, process-global, read by no kernel
 std::atomic<int> block_fwd_form{0};                     // 0 = automatic, 16 = the 16-row form, 8 = stacked where eligible
 std::atomic<int> block_fwd_rows{0};                     // slab height of the most recent pit_block_fwd launch
+// pit_block_bwd_last_riders: rider workgroups of the most recent pit_block_bwd launch by kind (PIT_BLOCK_RIDER_*)
+std::atomic<int> block_bwd_riders[PIT_BLOCK_RIDER_SLOTS];
 
 }  // namespace
 
@@ -658,6 +662,11 @@ extern "C" int pit_block_fwd_set_form(int form) {
 
 extern "C" int pit_block_fwd_last_rows(void) { return block_fwd_rows.load(std::memory_order_relaxed); }
 
+extern "C" int pit_block_bwd_last_riders(int* out, int n) {
+    for (int k = 0; out && k < n && k < PIT_BLOCK_RIDER_SLOTS; ++k) out[k] = block_bwd_riders[k].load(std::memory_order_relaxed);
+    return PIT_BLOCK_RIDER_SLOTS;
+}
+
 #ifdef PIT_WGREC
 extern "C" int pit_block_read_wgrec(unsigned long long* out, int n) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pit_block_wgrec), (size_t)n * 4 * sizeof(unsigned long long));
@@ -705,8 +714,34 @@ extern "C" int pit_block_bwd(const float* e, const float* inv, const float* qw, 
     pit_detail::DwPair* plans[2] = {&dw, &dw2};
     int ndw = 0;                                        // carried riders are packed into dw, dw2 in order
     bool carried[2] = {false, false};
+    // PIT_RIDER_TAIL=0 (A/B switch, read once): thin dW2 | db2 on MFMA tiles split over the rows, riders dealt to the XCDs by id alone
+    static const bool rider_tail = [] { const char* v = getenv("PIT_RIDER_TAIL"); return !(v && v[0] == '0'); }();
     for (int r = 0; r < 2; ++r)
-        if (jobs[r] && pit_detail::plan_dw_pair(*jobs[r], BW, plans[ndw], 768, true)) { carried[r] = true; ++ndw; }
+        if (jobs[r] && pit_detail::plan_dw_pair(*jobs[r], BW, plans[ndw], 768, rider_tail ? 2 : 1)) { carried[r] = true; ++ndw; }
+    // the tiles of the block's own MLP (`rider`: its rows are the launch's, sample after sample) go to the XCD whose L2 holds their
+    // sample's xcat, h, dZ1 and dZ2 rows (slab_of_xcd) when every XCD then gets the same number: whole slabs per sample, a batch
+    // that is a multiple of 8.  The pair's first workgroup id, n_chain + n_ds, is a multiple of 8 (slab_grid).  A row slice of a
+    // larger job (`rider2`) covers a sample or two: pinned to their XCDs it would unbalance the launch
+    if (rider_tail && carried[0] && dw.rr1 == 1 && dw.rr2 == 1 && dw.slabs1 == dw.slabs2 && rider->rows == rows && batch % 8 == 0 &&
+        rows % pit_detail::RR_BK == 0 && dw.nchunks % dw.slabs1 == 0 && dw.slabs1 % batch == 0)
+        dw.xcd_spb = dw.slabs1 / batch;
+    // Riders are dealt third and share the compute units of the FIRST range in id order, the rest those of the second.  A chain
+    // slab beside a rider tile lives 8.6-8.8 us, alone 7.2; a d(scale) slab 4.9 against 4.4 - so when (nearly) all riders fit beside
+    // the d(scale) slabs, those take the first range.  (With the 209 riders of the older plan 81 still sat beside chain slabs and
+    // this order measured slower, 11.4 against 11.1 us: that plan keeps the chain first.)
+    const int n_riders = (ndw >= 1 ? dw.n1 + dw.n2 : 0) + (ndw >= 2 ? dw2.n1 + dw2.n2 : 0);
+    g.ds_first = rider_tail && g.n_ds > 0 && n_riders > 0 && n_riders - g.n_ds <= n_riders / 8 ? 1 : 0;
+    {
+        int kinds[PIT_BLOCK_RIDER_SLOTS] = {0, 0, 0, 0, 0};
+        for (int p = 0; p < ndw; ++p) {
+            const pit_detail::DwPair& d = *plans[p];
+            kinds[d.rr1 == 2 ? PIT_BLOCK_RIDER_THIN : (d.rr1 ? PIT_BLOCK_RIDER_TILE : PIT_BLOCK_RIDER_RD)] += d.n1;
+            kinds[d.rr2 ? PIT_BLOCK_RIDER_TILE : PIT_BLOCK_RIDER_RD] += d.n2;
+        }
+        kinds[PIT_BLOCK_RIDER_LOCAL] = dw.xcd_spb ? 1 : 0;
+        kinds[PIT_BLOCK_RIDER_DS_FIRST] = g.ds_first;
+        for (int k = 0; k < PIT_BLOCK_RIDER_SLOTS; ++k) block_bwd_riders[k].store(kinds[k], std::memory_order_relaxed);
+    }
     const int n_dw = (ndw >= 1 ? dw.n1 + dw.n2 : 0) + (ndw >= 2 ? dw2.n1 + dw2.n2 : 0);
     const bool any_rr = (ndw >= 1 && (dw.rr1 || dw.rr2)) || (ndw >= 2 && (dw2.rr1 || dw2.rr2));
     const size_t sm = std::max(std::max(bwd_smem(n_head, dscale != nullptr), ndw ? (size_t)BW * 16 * 64 * sizeof(float) : (size_t)0),

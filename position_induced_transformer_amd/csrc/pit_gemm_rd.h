@@ -46,16 +46,22 @@ struct GemmArgs {
 // workgroups [0, n1) run g1 on a (gx1, gy1, .) grid, [n1, n1 + n2) run g2
 // rr1 / rr2 (pit_block.hip's riders): that reduction runs as gemm_rr_tile tiles - workgroup id -> (slab = id / tiles, tile = id % tiles),
 // slab s = chunks [s nchunks / slabs, (s+1) nchunks / slabs) of RR_BK rows
-struct DwPair { GemmArgs g1, g2; int n1, n2, gx1, gy1, gx2, gy2; int rr1, rr2, tx1, tiles1, slabs1, tx2, tiles2, slabs2, nchunks; };
+// rr1 == 2 (plan_dw_pair with allow_rr == 2: pit_block.hip's riders): a dW2 | db2 with at most THIN_RIDER_ROWS output rows runs as
+// thin_rider workgroups - slabs1 of them, workgroup id = rows [id K / slabs1, (id + 1) K / slabs1)
+// xcd_spb > 0 (set by pit_block_bwd for the block's own MLP, both reductions tiles over the same slabs): the pair's workgroup id ->
+// (slab, tile of either reduction) map that keeps a slab's tiles on the XCD of the slab's sample, xcd_spb slabs per sample
+struct DwPair { GemmArgs g1, g2; int n1, n2, gx1, gy1, gx2, gy2; int rr1, rr2, tx1, tiles1, slabs1, tx2, tiles2, slabs2, nchunks, xcd_spb; };
 constexpr int RR_BK = 64;
+constexpr int THIN_RIDER_ROWS = 4, THIN_RIDER_WGS = 16;
 
 // fills `out` and returns true when the job is small enough to ride along in another launch (pit_mlp.hip);
 // `waves` = waves per workgroup of the carrying launch (the row slabs are sized so that a wave reduces as many rows
 // as in the reductions' own 8-wave launch)
 // `target_wgs`: workgroups each of the two reductions aims for (its K range is split accordingly; 768 = the reductions' own
 // launch)
-// `allow_rr`: the caller's kernel runs rr1 / rr2 reductions through gemm_rr_tile (>= 64 KiB of LDS, >= 4 waves)
-bool plan_dw_pair(const pit_mlp_params_job& job, int waves, DwPair* out, int target_wgs = 768, bool allow_rr = false);
+// `allow_rr`: 1 = the caller's kernel runs rr1 / rr2 reductions through gemm_rr_tile (>= 64 KiB of LDS, >= 4 waves); 2 = and a thin
+// dW2 | db2 through thin_rider (dw_pair_body<true>, 8 waves)
+bool plan_dw_pair(const pit_mlp_params_job& job, int waves, DwPair* out, int target_wgs = 768, int allow_rr = 0);
 // both reductions as gemm_rr_tile tiles (fp32 or - bf16 math mode - bf16 MFMA operands) for a carrying launch that has 64 KiB of LDS
 // and at least four waves (pit_satt.hip's backward launch): any size, `budget_wgs` workgroups in all
 bool plan_rr_rider(const pit_mlp_params_job& job, DwPair* out, int budget_wgs);
@@ -406,10 +412,94 @@ __device__ __forceinline__ float* pit_dyn_smem() {
     extern __shared__ __attribute__((aligned(16))) float pit_dyn_lds[];
     return pit_dyn_lds;
 }
+// dW2 | db2 of a thin output layer (DwPair::rr1 == 2: M = n2 <= 4 output rows, N = n1 + 1 with n1 in {32, 64, 128}) as a row
+// reduction on the vector ALU, all waves of the workgroup: C[m][c] += sum over the workgroup's rows k of d_y[k][m] H[k][c], the ones
+// column is sum_k d_y[k][m].  On 16-row MFMA tiles (gemm_rd_body) M = 1 fills a sixteenth of every instruction and the rows are
+// split 87 ways at the flagship slice (3 698 rows), i.e. 87 adds to each of 65 addresses; here workgroup `id` of `nwg` (<= 16) takes
+// rows [id K / nwg, (id + 1) K / nwg), a wave a contiguous share of them, and a wave instruction reads 256 / n1 whole H rows with
+// 16-byte lanes.  Two stages of U instructions are in flight (at up to 256 rows per workgroup that is every load before the first
+// use); a row beyond the wave's share is an out-of-range buffer offset (reads 0), so no load is conditional.  Sums: per lane in row
+// order, then the lanes that hold the same columns, then the waves in order through LDS; one add per output element and workgroup.
+// smem: 4 (n1 + 1) floats per wave.
+template <int MR, int U>
+__device__ __forceinline__ void thin_rider(const pit_detail::GemmArgs& g, int id, int nwg, float* smem) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
+    const int n1 = g.N - 1, lpr = n1 >> 2, lsh = 31 - __clz(lpr);       // lanes per H row
+    const int rpi = 64 >> lsh, sub = lane >> lsh, c4 = (lane & (lpr - 1)) * 4;
+    const int r0 = (int)((long)id * g.K / nwg), r1 = (int)((long)(id + 1) * g.K / nwg);
+    const int per_wave = ((r1 - r0 + nwaves * rpi - 1) / (nwaves * rpi)) * rpi;
+    const int wb = r0 + wave * per_wave, we = min(r1, wb + per_wave);
+    const __amdgpu_buffer_rsrc_t ra = make_rsrc(g.A, g.a_bytes);
+    const __amdgpu_buffer_rsrc_t rb = make_rsrc(g.B, g.b_bytes);
+    float hv[2][U][4], dv[2][U][MR], acc[MR][4], dbs[MR];
+#pragma unroll
+    for (int m = 0; m < MR; ++m) {
+        dbs[m] = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[m][c] = 0.0f;
+    }
+    auto load = [&](float (&h_)[U][4], float (&d_)[U][MR], int q0) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int row = wb + (q0 + u) * rpi + sub;
+            const bool ok = row < we;
+            buf_load4(rb, ok ? ((unsigned)row * (unsigned)g.b_rs + (unsigned)c4) * 4u : g.b_bytes, h_[u]);
+            // (one offset per row: the MR - M values behind a row's d_y are the next row's, or beyond the buffer, and dropped in `add`)
+            const unsigned doff = ok ? (unsigned)row * (unsigned)g.a_cs * 4u : g.a_bytes;
+#pragma unroll
+            for (int m = 0; m < MR; ++m) d_[u][m] = buf_load(ra, doff + 4u * m);
+        }
+        __builtin_amdgcn_sched_barrier(0);               // (left to itself the scheduler sinks every load to its use)
+    };
+    auto add = [&](const float (&h_)[U][4], const float (&d_)[U][MR]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int m = 0; m < MR; ++m) {
+                const float d = m < g.M ? d_[u][m] : 0.0f;
+                dbs[m] += d;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc[m][c] = __builtin_fmaf(d, h_[u][c], acc[m][c]);
+            }
+    };
+    const int trips = (per_wave / rpi + U - 1) / U;      // the same for every wave of the workgroup
+    load(hv[0], dv[0], 0);
+    for (int t = 0; t < trips; t += 2) {
+        load(hv[1], dv[1], (t + 1) * U);
+        add(hv[0], dv[0]);
+        load(hv[0], dv[0], (t + 2) * U);
+        add(hv[1], dv[1]);
+    }
+    for (int off = lpr; off < 64; off <<= 1) {
+#pragma unroll
+        for (int m = 0; m < MR; ++m) {
+            dbs[m] += __shfl_xor(dbs[m], off);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) acc[m][c] += __shfl_xor(acc[m][c], off);
+        }
+    }
+    if (sub == 0) {
+#pragma unroll
+        for (int m = 0; m < MR; ++m) {
+            float* dst = smem + (wave * MR + m) * g.N;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) dst[c4 + c] = acc[m][c];
+            if (lane == 0) dst[n1] = dbs[m];
+        }
+    }
+    __syncthreads();
+    for (int o = tid; o < g.M * g.N; o += blockDim.x) {
+        const int m = o / g.N, c = o - m * g.N;
+        float v = 0.0f;
+        for (int w = 0; w < nwaves; ++w) v += smem[(w * MR + m) * g.N + c];
+        if (c == n1) PIT_RR_ADD(g.C2 + m, v);
+        else PIT_RR_ADD(g.C + (long)m * g.ldc + c, v);
+    }
+}
+
 // one reduction of a rider as a gemm_rr_tile tile (DwPair::rr1 / rr2): the first four waves, 64 KiB of the launch's LDS
-__device__ __forceinline__ void rr_rider(const pit_detail::GemmArgs& g, int id, int tx, int tiles, int slabs, int nchunks, float* smem) {
+__device__ __forceinline__ void rr_rider(const pit_detail::GemmArgs& g, int slab, int tile, int tx, int slabs, int nchunks, float* smem) {
     if (threadIdx.x >= 256) return;                       // (ended waves do not take part in the tile's barriers)
-    const int slab = id / tiles, tile = id % tiles;
     const int kbeg = (int)((long)slab * nchunks / slabs) * pit_detail::RR_BK;
     const int kend = min(g.K, (int)((long)(slab + 1) * nchunks / slabs) * pit_detail::RR_BK);
     gemm_rr_tile<1, 1, pit_detail::RR_BK, false>(g, tile % tx, tile / tx, kbeg, kend, smem, smem + 2 * pit_detail::RR_BK * 64);
@@ -431,13 +521,36 @@ __device__ __forceinline__ void rr_rider_pair(const pit_detail::DwPair& w, int i
 // allowed rr reductions, see plan_dw_pair)
 // (ONE instance of each reduction body per call site: the job's arguments are selected first.  With a body per reduction -
 // and block_bwd_kernel calling this for two pairs - that kernel carried eight inlined reduction bodies, 14.8 k instructions)
+// TAIL (pit_block.hip's riders, 8 waves): the kernel also runs thin_rider reductions and honours DwPair::xcd_spb.  The XCD-local
+// map relies on what slab_of_xcd (pit_block_dev.h) relies on - workgroup ids are dealt round-robin to the 8 XCDs - and on the
+// pair's first workgroup having an id that is a multiple of 8: id & 7 is the XCD, which holds samples x, x + 8, ...; the k-th
+// workgroup of an XCD is tile k % T of the k / T-th slab of those samples (T = tiles1 + tiles2: a bijection on (slab, tile) when
+// the batch is a multiple of 8)
+template <bool TAIL = false, bool LOCAL = false>
 __device__ __forceinline__ void dw_pair_body(const pit_detail::DwPair& w, int id, float* smem) {
-    const bool second = id >= w.n1;
-    if (second) id -= w.n1;
+    bool second;
+    int slab = 0, tile = 0;
+    if (LOCAL && w.xcd_spb) {
+        const int T = w.tiles1 + w.tiles2, per = w.xcd_spb * T;
+        const int k = id >> 3, r = k % per;
+        slab = ((id & 7) + 8 * (k / per)) * w.xcd_spb + r / T;
+        tile = r % T;
+        second = tile >= w.tiles1;
+        if (second) tile -= w.tiles1;
+    } else {
+        second = id >= w.n1;
+        if (second) id -= w.n1;
+        const int tiles = second ? w.tiles2 : w.tiles1;
+        if (tiles) { slab = id / tiles; tile = id % tiles; }
+    }
     const GemmArgs& g = second ? w.g2 : w.g1;
-    const int rr = second ? w.rr2 : w.rr1, tx = second ? w.tx2 : w.tx1, tiles = second ? w.tiles2 : w.tiles1;
+    const int rr = second ? w.rr2 : w.rr1, tx = second ? w.tx2 : w.tx1;
     const int slabs = second ? w.slabs2 : w.slabs1, gx = second ? w.gx2 : w.gx1, gy = second ? w.gy2 : w.gy1;
-    if (rr) rr_rider(g, id, tx, tiles, slabs, w.nchunks, smem);
+    if (TAIL && rr == 2) {
+        if (g.M == 1) thin_rider<1, 4>(g, id, slabs, smem);
+        else thin_rider<pit_detail::THIN_RIDER_ROWS, 2>(g, id, slabs, smem);
+    }
+    else if (rr) rr_rider(g, slab, tile, tx, slabs, w.nchunks, smem);
     else gemm_rd_body<1, EPI_ATOMIC>(g, id % gx, (id / gx) % gy, id / (gx * gy));
 }
 

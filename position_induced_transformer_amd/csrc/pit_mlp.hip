@@ -1688,7 +1688,7 @@ int launch_dz1(int rows, int n1, int n2, const float* w2, const float* z1, const
 
 // the reductions of a postponed pit_mlp_bwd_params, laid out for a launch that carries them along
 // (pit_posatt.hip: posatt_bwd_pair_dw_kernel); same tiling as launch_gemm_pair_atomic
-bool pit_detail::plan_dw_pair(const pit_mlp_params_job& j, int waves, DwPair* out, int target_wgs, bool allow_rr) {
+bool pit_detail::plan_dw_pair(const pit_mlp_params_job& j, int waves, DwPair* out, int target_wgs, int allow_rr) {
     static const bool off = exp_env("PIT_NO_DW_RIDER") != nullptr;
     if (off || !j.accumulate) return false;
     if (!j.x || !j.h || !j.d_y || !j.d_w1 || !j.d_b1 || !j.d_w2 || !j.d_b2 || !j.scratch) return false;
@@ -1708,7 +1708,7 @@ bool pit_detail::plan_dw_pair(const pit_mlp_params_job& j, int waves, DwPair* ou
     out->n1 = L1.grid.x * L1.grid.y * L1.grid.z; out->n2 = L2.grid.x * L2.grid.y * L2.grid.z;
     out->gx1 = L1.grid.x; out->gy1 = L1.grid.y; out->gx2 = L2.grid.x; out->gy2 = L2.grid.y;
     out->rr1 = out->rr2 = 0;
-    out->tx1 = out->tiles1 = out->slabs1 = out->tx2 = out->tiles2 = out->slabs2 = 0;
+    out->tx1 = out->tiles1 = out->slabs1 = out->tx2 = out->tiles2 = out->slabs2 = out->xcd_spb = 0;
     out->nchunks = (j.rows + RR_BK - 1) / RR_BK;
     // a reduction with full 64-wide tiles rides as gemm_rr_tile tiles when the carrying kernel can run them: LDS-staged,
     // coalesced, a few chunks per workgroup - the register-direct form of the same reduction keeps 6-12x as many
@@ -1727,6 +1727,19 @@ bool pit_detail::plan_dw_pair(const pit_mlp_params_job& j, int waves, DwPair* ou
         };
         as_rr(out->g1, out->rr1, out->tx1, out->tiles1, out->slabs1, out->n1);
         as_rr(out->g2, out->rr2, out->tx2, out->tiles2, out->slabs2, out->n2);
+        // a thin output layer's dW2 | db2 (M = n2 <= 4: a quarter or less of a 16-row MFMA tile, and the register-direct form
+        // splits the rows until ~90 workgroups add to the same n2 (n1 + 1) addresses) rides as thin_rider workgroups: at most
+        // THIN_RIDER_WGS adders per address - the depth the 16 slabs of a block's own tiles have - and never fewer rows per
+        // workgroup than one stage of loads (four wave instructions of 256 / n1 rows) for each of its 8 waves: below that a
+        // further workgroup shortens nothing (the rows arrive in one round trip either way) and only adds an adder
+        const GemmArgs& t = out->g1;
+        const int tn1 = t.N - 1;
+        if (allow_rr >= 2 && waves == 8 && !out->rr1 && t.M <= THIN_RIDER_ROWS && (tn1 == 32 || tn1 == 64 || tn1 == 128) &&
+            t.ones_col == tn1 && t.a_rs == 1 && t.b_cs == 1 && t.b_rs % 4 == 0 && aligned16(t.B)) {
+            out->rr1 = 2;
+            out->slabs1 = std::max(1, std::min(THIN_RIDER_WGS, t.K / (8 * 4 * (256 / tn1))));
+            out->n1 = out->slabs1;
+        }
     }
     return true;
 }

@@ -33,6 +33,12 @@ assert L.pit_block_read_wgrec(rec, n) == 0
 rows = [(rec[4 * i], rec[4 * i + 1], rec[4 * i + 2], rec[4 * i + 3], i) for i in range(n) if rec[4 * i + 1] >= rec[4 * i] > 0]
 t0 = min(r[0] for r in rows)
 n_chain = 8 * ((batch + 7) // 8) * 16
+first, second = "chain", "dscale"
+if hasattr(L, "pit_block_bwd_last_riders"):       # (PIT_HAS_RIDER_TAIL: the d(scale) slabs may hold the first range)
+    kinds = (ctypes.c_int * 5)()
+    L.pit_block_bwd_last_riders(kinds, 5)
+    if kinds[4]:
+        first, second = second, first
 
 
 def place(hw, xcc):
@@ -41,7 +47,7 @@ def place(hw, xcc):
 
 percu = collections.defaultdict(list)
 for a, b, hw, xcc, i in rows:
-    kind = "chain" if i < n_chain else ("dscale" if i < 2 * n_chain else "rider")      # (block_bwd's ranges: chain, d(scale) slabs, riders)
+    kind = first if i < n_chain else (second if i < 2 * n_chain else "rider")      # (block_bwd's ranges: chain, d(scale) slabs, riders)
     percu[place(hw, xcc)].append((kind, (a - t0) * 10, (b - t0) * 10, i))
 print(f"{len(rows)} workgroups on {len(percu)} distinct CUs; per CU: {dict(collections.Counter(len(v) for v in percu.values()))}")
 mix = collections.Counter(tuple(sorted(k for k, _, _, _ in v)) for v in percu.values())
