@@ -1061,6 +1061,46 @@ int pit_debug_rider_counts(int* out, int n, int reset);
 #define PIT_GEMM_KINDS            30
 int pit_debug_gemm_counts(int* out, int n, int reset);
 
+/* Which kernels the masked-layer dispatcher of csrc/pit_posatt.hip (pit_posatt_fwd_job, pit_posatt_bwd: the candidate-list and
+ * union-tile kernels) launched: host-side counters of the CALLING THREAD, one per kind below, incremented by the host code after
+ * the launch call at every launch site.  The PIT_ATT_LAST_* slots are not counters: they hold the template arguments (and the
+ * column blocks) of the most recent launch of their family.  PIT_ATT_DENSE is one coarse counter for every dense (MFMA) launcher.
+ * Copies min(n, PIT_ATT_KINDS) slots to out (host array) and zeroes them all when reset != 0; returns PIT_ATT_KINDS.  No device
+ * work, nothing read by a kernel.  A library built from this header defines PIT_HAS_ATT_COUNTS; PIT_ABI_VERSION is unchanged
+ * (nothing that existed changed).  (PIT_ATT_UNION_FWD / _DSCALE / _DV / _ZERO below are SLOTS of this record; PIT_ATT_UNION
+ * above, 0x2000, is the math_mode flag and no slot.) */
+#define PIT_HAS_ATT_COUNTS 1
+#define PIT_ATT_LIST_ROWS_FWD      0   /* posatt_sparse_rows<NH, CR, 0>: plain grid                                        */
+#define PIT_ATT_LIST_ROWS_DSCALE   1   /* posatt_sparse_rows<NH, CR, 1>: plain grid                                        */
+#define PIT_ATT_LIST_ROWS_X        2   /* posatt_sparse_rows_x<NH, CR, *>: XCD-remapped, either mode                       */
+#define PIT_ATT_LIST_ROWS_W        3   /* posatt_sparse_rows_w<NH, CR>: forward carrying the block weights                 */
+#define PIT_ATT_LIST_ROWS_DW       4   /* posatt_sparse_rows_dw<NH, CR>: d(scale) carrying a weight-gradient rider         */
+#define PIT_ATT_LIST_COLS          5   /* posatt_sparse_cols<CR, false>: plain grid                                        */
+#define PIT_ATT_LIST_COLS_X        6   /* posatt_sparse_cols_x<CR, *>: XCD-remapped                                        */
+#define PIT_ATT_LIST_COLS_D16      7   /* posatt_sparse_cols<CR, true> / posatt_sparse_cols_x<CR, true>: bf16 d_out        */
+#define PIT_ATT_LIST_PAIR          8   /* posatt_sparse_bwd_kernel<NH, CRR, CRC, false>                                    */
+#define PIT_ATT_LIST_PAIR_DW       9   /* posatt_sparse_bwd_dw_kernel<NH, CRR, CRC>: the pair carrying a rider             */
+#define PIT_ATT_LIST_PAIR_D16     10   /* posatt_sparse_bwd_kernel<NH, CRR, CRR, true>: bf16 d_out                         */
+#define PIT_ATT_LIST_OVERFLOW     11   /* posatt_sparse_overflow_cols                                                      */
+#define PIT_ATT_LIST_ROWS8        12   /* posatt_sparse_rows8<NH, MODE>: 4..8 coordinates                                  */
+#define PIT_ATT_LIST_COLS8        13   /* posatt_sparse_cols8<*, *>                                                        */
+#define PIT_ATT_LIST_OVERFLOW8    14   /* posatt_sparse_overflow_cols8                                                     */
+#define PIT_ATT_UNION_FWD         15   /* posatt_union_kernel<NH, 0, EPL>                                                  */
+#define PIT_ATT_UNION_DSCALE      16   /* posatt_union_kernel<NH, 1, EPL>                                                  */
+#define PIT_ATT_UNION_DV          17   /* posatt_union_dv_kernel<NH, EPL>                                                  */
+#define PIT_ATT_UNION_ZERO        18   /* zero_f32_kernel in front of posatt_union_dv_kernel                               */
+#define PIT_ATT_DHEAD_FINISH      19   /* posatt_dhead_finish of a non-deferred pit_posatt_bwd                             */
+#define PIT_ATT_HEAD_SCALE        20   /* pit_head_scale up front in pit_posatt_fwd_job (union tiles, rows > 8192)         */
+#define PIT_ATT_DENSE             21   /* launch_rows, launch_cols, launch_bwd_pair: any dense kernel                      */
+#define PIT_ATT_LAST_ROWS         22   /* last list rows launch (plain, _x, _w, _dw): NH * 100 + CR                        */
+#define PIT_ATT_LAST_COLS         23   /* last posatt_sparse_cols* launch: CR                                              */
+#define PIT_ATT_LAST_PAIR         24   /* last pair launch: NH * 10000 + CRR * 100 + CRC                                   */
+#define PIT_ATT_LAST_UNION        25   /* last union launch (either kernel): NH * 100 + EPL                                */
+#define PIT_ATT_LAST_UNION_PER    26   /* last posatt_union_kernel launch: column passes per wavefront                     */
+#define PIT_ATT_LAST_GRID_Y       27   /* column blocks of the last list rows / cols launch (grid.y before any remap)      */
+#define PIT_ATT_KINDS             28
+int pit_debug_att_counts(int* out, int n, int reset);
+
 #ifdef __cplusplus
 }
 #endif

@@ -190,6 +190,7 @@ SIGNATURES = {
     "pit_debug_mfma_tile": [_P, _P, _P, _P],
     "pit_debug_rider_counts": [_P, _I, _I],
     "pit_debug_gemm_counts": [_P, _I, _I],
+    "pit_debug_att_counts": [_P, _I, _I],
     "pit_block_fwd_set_form": [_I],
     "pit_block_fwd_last_rows": [],
     "pit_block_bwd_last_riders": [_P, _I],
@@ -202,7 +203,8 @@ LONG_RETURN = {"pit_satt_tiles_elems", "pit_posatt_dmesh_workspace", "pit_mlp_bw
 ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_workspace", "pit_distlist_bwd",
                "pit_rel_lp_loss_ragged_fwd_grad", "pit_rel_max_norm_ragged",       # PIT_HAS_DISTLIST, PIT_HAS_RAGGED_STEP
                "pit_block_fwd_set_form", "pit_block_fwd_last_rows",                # PIT_HAS_BLOCK_ROWS8
-               "pit_block_bwd_last_riders"}                                        # PIT_HAS_RIDER_TAIL
+               "pit_block_bwd_last_riders",                                        # PIT_HAS_RIDER_TAIL
+               "pit_debug_att_counts"}                                             # PIT_HAS_ATT_COUNTS
 DISTLIST_CHUNK = 512   # PIT_DISTLIST_CHUNK
 
 

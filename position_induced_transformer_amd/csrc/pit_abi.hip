@@ -22,6 +22,7 @@ extern "C" int pit_version(void) { return PIT_ABI_VERSION; }
 namespace {
 thread_local int t_rider_counts[PIT_RIDER_KINDS];
 thread_local int t_gemm_counts[PIT_GEMM_KINDS];
+thread_local int t_att_counts[PIT_ATT_KINDS];
 }  // namespace
 
 void pit_rider_note(int kind) {
@@ -47,6 +48,20 @@ extern "C" int pit_debug_gemm_counts(int* out, int n, int reset) {
     if (reset)
         for (int k = 0; k < PIT_GEMM_KINDS; ++k) t_gemm_counts[k] = 0;
     return PIT_GEMM_KINDS;
+}
+
+void pit_att_note(int kind) {
+    if (kind >= 0 && kind < PIT_ATT_LAST_ROWS) ++t_att_counts[kind];
+}
+void pit_att_note_last(int slot, int value) {
+    if (slot >= PIT_ATT_LAST_ROWS && slot < PIT_ATT_KINDS) t_att_counts[slot] = value;
+}
+
+extern "C" int pit_debug_att_counts(int* out, int n, int reset) {
+    for (int k = 0; out && k < n && k < PIT_ATT_KINDS; ++k) out[k] = t_att_counts[k];
+    if (reset)
+        for (int k = 0; k < PIT_ATT_KINDS; ++k) t_att_counts[k] = 0;
+    return PIT_ATT_KINDS;
 }
 
 extern "C" const char* pit_error_string(int code) {

@@ -1703,7 +1703,7 @@ void launch_cols8(AttArgs a, hipStream_t s) {
 
 template <int MODE>
 void launch_rows(const AttArgs& a0, hipStream_t s) {
-    if (a0.sdim > 3) { launch_rows8(a0, MODE, s); return; }
+    if (a0.sdim > 3) { launch_rows8(a0, MODE, s); pit_att_note(PIT_ATT_DENSE); return; }   // (pit_debug_att_counts: one coarse kind for every dense launcher)
     AttArgs a = a0;
     const bool bf = (MODE == 0) && a.bf16 != 0;
     const int n_tiles = (a.n_out + 31) / 32;
@@ -1730,6 +1730,7 @@ void launch_rows(const AttArgs& a0, hipStream_t s) {
         else { if (tpwg == 32) PIT_RT(1, 4); else if (tpwg == 16) PIT_RT(1, 2); else PIT_RT(1, 1); }
 #undef PIT_RT
 #undef PIT_RT_BF
+        pit_att_note(PIT_ATT_DENSE);
         return;
     }
     int ct = choose_ct(a.ncols, (long)n_tiles * a.n_head * a.mesh_batch);
@@ -1768,10 +1769,11 @@ void launch_rows(const AttArgs& a0, hipStream_t s) {
 #undef PIT_ROWS_IL_BF
 #undef PIT_ROWS
 #undef PIT_ROWS_BF
+    pit_att_note(PIT_ATT_DENSE);
 }
 
 void launch_cols(const AttArgs& a0, hipStream_t s) {
-    if (a0.sdim > 3) { launch_cols8(a0, s); return; }
+    if (a0.sdim > 3) { launch_cols8(a0, s); pit_att_note(PIT_ATT_DENSE); return; }
     AttArgs a = a0;
     const bool bf = a.bf16 != 0;
     const int j_tiles = (a.n_in + 31) / 32;
@@ -1789,6 +1791,7 @@ void launch_cols(const AttArgs& a0, hipStream_t s) {
         if (tpwg == 32) PIT_CT(4); else if (tpwg == 16) PIT_CT(2); else PIT_CT(1);
 #undef PIT_CT
 #undef PIT_CT_BF
+        pit_att_note(PIT_ATT_DENSE);
         return;
     }
     int ct = choose_ct(a.ncols, (long)j_tiles * a.mesh_batch);
@@ -1827,6 +1830,7 @@ void launch_cols(const AttArgs& a0, hipStream_t s) {
 #undef PIT_COLS_IL_BF
 #undef PIT_COLS
 #undef PIT_COLS_BF
+    pit_att_note(PIT_ATT_DENSE);
 }
 
 // d(scale) + d(values) in one launch (posatt_bwd_pair_kernel) when both are in the small regime
@@ -1896,6 +1900,7 @@ bool launch_bwd_pair(const AttArgs& a0, hipStream_t s, const pit_mlp_params_job*
 #undef PIT_PAIR_DW
         *rider_done = true;
         pit_rider_note(PIT_RIDER_PAIR_DW);
+        pit_att_note(PIT_ATT_DENSE);
         return true;
     }
 #define PIT_PAIR_K(M_, BF_)                                                                                   \
@@ -1949,6 +1954,7 @@ bool launch_bwd_pair(const AttArgs& a0, hipStream_t s, const pit_mlp_params_job*
 #undef PIT_PAIR_IL
 #undef PIT_PAIR_W
 #undef PIT_PAIR_K
+    pit_att_note(PIT_ATT_DENSE);
     return true;
 }
 
@@ -3022,6 +3028,9 @@ void launch_union(const AttArgs& a, const SparseArgs& sp, hipStream_t s) {
     if (a.n_head == 2) { if (sp.cap <= 32) PIT_UN(2, 8); else PIT_UN(2, 16); }
     else               { if (sp.cap <= 32) PIT_UN(1, 8); else PIT_UN(1, 16); }
 #undef PIT_UN
+    pit_att_note(MODE == 0 ? PIT_ATT_UNION_FWD : PIT_ATT_UNION_DSCALE);
+    pit_att_note_last(PIT_ATT_LAST_UNION, (a.n_head == 2 ? 2 : 1) * 100 + (sp.cap <= 32 ? 8 : 16));
+    pit_att_note_last(PIT_ATT_LAST_UNION_PER, per);
 }
 // d(values) of the union-tile form (posatt_union_dv_kernel); the caller zeroed d_values
 void launch_union_dv(const AttArgs& a, const SparseArgs& sp, hipStream_t s) {
@@ -3036,6 +3045,8 @@ void launch_union_dv(const AttArgs& a, const SparseArgs& sp, hipStream_t s) {
     if (a.n_head == 2) { if (sp.cap <= 32) PIT_UNDV(2, 8); else PIT_UNDV(2, 16); }
     else               { if (sp.cap <= 32) PIT_UNDV(1, 8); else PIT_UNDV(1, 16); }
 #undef PIT_UNDV
+    pit_att_note(PIT_ATT_UNION_DV);
+    pit_att_note_last(PIT_ATT_LAST_UNION, (a.n_head == 2 ? 2 : 1) * 100 + (sp.cap <= 32 ? 8 : 16));
 }
 
 // columns per lane: as many as the column count allows, fewer when the launch would otherwise
@@ -3082,10 +3093,13 @@ void launch_sparse_rows(const AttArgs& a, const SparseArgs& sp, hipStream_t s, c
         const dim3 grid8((unsigned)((rows + 3) / 4), (a.ncols + 63) / 64, a.n_head / nh), block8(256);
         if (nh == 2) hipLaunchKernelGGL((posatt_sparse_rows8<2, MODE>), grid8, block8, 0, s, a, sp);
         else hipLaunchKernelGGL((posatt_sparse_rows8<1, MODE>), grid8, block8, 0, s, a, sp);
+        pit_att_note(PIT_ATT_LIST_ROWS8);
         return;
     }
     const int cr = cr_for(a.ncols, rows * (a.n_head / nh));
     dim3 grid((unsigned)((rows + 3) / 4), (a.ncols + 64 * cr - 1) / (64 * cr), a.n_head / nh), block(256);
+    pit_att_note_last(PIT_ATT_LAST_ROWS, nh * 100 + cr);          // (pit_debug_att_counts: the instance all three launches below share)
+    pit_att_note_last(PIT_ATT_LAST_GRID_Y, (int)grid.y);
     if (MODE == 0 && wjob && (long)grid.x * grid.y * grid.z <= 4096) {       // small launch: carry the processor's weights
         const int n_att = (int)(grid.x * grid.y * grid.z);
         dim3 gridw((unsigned)(n_att + block_weights_wgs(wjob->n_layers, wjob->n_head, wjob->L)));
@@ -3094,6 +3108,7 @@ void launch_sparse_rows(const AttArgs& a, const SparseArgs& sp, hipStream_t s, c
         if (nh == 2) PIT_SRW_CR(2); else PIT_SRW_CR(1);
 #undef PIT_SRW_CR
 #undef PIT_SRW
+        pit_att_note(PIT_ATT_LIST_ROWS_W);
         *rider_done = true;
         return;
     }
@@ -3111,6 +3126,7 @@ void launch_sparse_rows(const AttArgs& a, const SparseArgs& sp, hipStream_t s, c
 #undef PIT_SRW
         *rider_done = true;
         pit_rider_note(PIT_RIDER_SPARSE_ROWS);
+        pit_att_note(PIT_ATT_LIST_ROWS_DW);
         return;
     }
     const long xtotal = 8L * grid.x * ((grid.y + 7) / 8) * grid.z;
@@ -3125,6 +3141,7 @@ void launch_sparse_rows(const AttArgs& a, const SparseArgs& sp, hipStream_t s, c
     if (nh == 2) PIT_SR_CR(2); else PIT_SR_CR(1);
 #undef PIT_SR_CR
 #undef PIT_SR
+    pit_att_note(remap ? PIT_ATT_LIST_ROWS_X : (MODE == 0 ? PIT_ATT_LIST_ROWS_FWD : PIT_ATT_LIST_ROWS_DSCALE));
 }
 
 // merged d(values) + d(scale) launch for a sparse layer; false when the launch would be large or
@@ -3160,7 +3177,12 @@ bool launch_sparse_bwd_pair(const AttArgs& a, const SparseArgs& sp, bool complet
 #undef PIT_SBW
         *rider_done = true;
         pit_rider_note(PIT_RIDER_SPARSE_PAIR);
-        if (!complete) hipLaunchKernelGGL(posatt_sparse_overflow_cols, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a, sp);
+        pit_att_note(PIT_ATT_LIST_PAIR_DW);
+        pit_att_note_last(PIT_ATT_LAST_PAIR, nh * 10000 + crr * 100 + (crr == 1 ? 1 : crc));
+        if (!complete) {
+            hipLaunchKernelGGL(posatt_sparse_overflow_cols, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a, sp);
+            pit_att_note(PIT_ATT_LIST_OVERFLOW);
+        }
         return true;
     }
 #define PIT_SB(NH_, CRR_, CRC_) hipLaunchKernelGGL((posatt_sparse_bwd_kernel<NH_, CRR_, CRC_>), grid, block, 0, s, a, sp, (int)n_cols, (int)cgx, (int)rgx, rblocks)
@@ -3172,7 +3194,12 @@ bool launch_sparse_bwd_pair(const AttArgs& a, const SparseArgs& sp, bool complet
 #undef PIT_SB_C
 #undef PIT_SB16
 #undef PIT_SB
-    if (!complete) hipLaunchKernelGGL(posatt_sparse_overflow_cols, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a, sp);
+    pit_att_note(a.dout16 ? PIT_ATT_LIST_PAIR_D16 : PIT_ATT_LIST_PAIR);
+    pit_att_note_last(PIT_ATT_LAST_PAIR, nh * 10000 + crr * 100 + (crr == 1 ? 1 : crc));
+    if (!complete) {
+        hipLaunchKernelGGL(posatt_sparse_overflow_cols, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a, sp);
+        pit_att_note(PIT_ATT_LIST_OVERFLOW);
+    }
     return true;
 }
 
@@ -3184,7 +3211,11 @@ void launch_sparse_cols(const AttArgs& a, const SparseArgs& sp, bool complete, h
         if (a.dout16) hipLaunchKernelGGL((posatt_sparse_cols8<2, true>), grid8, block8, 0, s, a, sp);
         else hipLaunchKernelGGL((posatt_sparse_cols8<1, false>), grid8, block8, 0, s, a, sp);
         const long rows8 = (long)a.mesh_batch * a.n_out;
-        if (!complete) hipLaunchKernelGGL(posatt_sparse_overflow_cols8, dim3((unsigned)((rows8 + 3) / 4)), dim3(256), 0, s, a, sp);
+        pit_att_note(PIT_ATT_LIST_COLS8);
+        if (!complete) {
+            hipLaunchKernelGGL(posatt_sparse_overflow_cols8, dim3((unsigned)((rows8 + 3) / 4)), dim3(256), 0, s, a, sp);
+            pit_att_note(PIT_ATT_LIST_OVERFLOW8);
+        }
         return;
     }
     const int cr = a.dout16 ? std::max(2, cr_for(a.ncols, keys)) : cr_for(a.ncols, keys);
@@ -3207,8 +3238,16 @@ void launch_sparse_cols(const AttArgs& a, const SparseArgs& sp, bool complete, h
     else if (cr == 8) PIT_SC(8); else if (cr == 4) PIT_SC(4); else if (cr == 2) PIT_SC(2); else PIT_SC(1);
 #undef PIT_SC16
 #undef PIT_SC
+    if (a.dout16) pit_att_note(PIT_ATT_LIST_COLS_D16);
+    if (remap) pit_att_note(PIT_ATT_LIST_COLS_X);
+    if (!a.dout16 && !remap) pit_att_note(PIT_ATT_LIST_COLS);
+    pit_att_note_last(PIT_ATT_LAST_COLS, cr);
+    pit_att_note_last(PIT_ATT_LAST_GRID_Y, (int)grid.y);
     const long rows = (long)a.mesh_batch * a.n_out;
-    if (!complete) hipLaunchKernelGGL(posatt_sparse_overflow_cols, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a, sp);
+    if (!complete) {
+        hipLaunchKernelGGL(posatt_sparse_overflow_cols, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a, sp);
+        pit_att_note(PIT_ATT_LIST_OVERFLOW);
+    }
 }
 
 int fill_common(AttArgs& a, const float* mesh_out, const float* mesh_in, int mesh_batch, int n_out, int n_in,
@@ -3430,6 +3469,7 @@ extern "C" int pit_posatt_fwd_job(const float* mesh_out, const float* mesh_in, i
         if (union_ok(a, spu) && aligned_rows(out, ld_out, out_bstride, out_col0, a.out16 ? 8 : 4)) {   // coherent row ordering (the caller's plan says so): union tiles
             if (!head_is_scale) {
                 if (int rc2 = pit_head_scale(head, n_head, scale_out, stream)) return rc2;
+                pit_att_note(PIT_ATT_HEAD_SCALE);
                 a.head = scale_out; a.head_is_scale = 1;
                 a.scale_out = nullptr;
             }
@@ -3443,6 +3483,7 @@ extern "C" int pit_posatt_fwd_job(const float* mesh_out, const float* mesh_in, i
         if (!head_is_scale && scale_out && (long)mesh_batch * n_out > 8192) {
             // one wave per row: evaluate c once up front instead of fp64 sin/tan in every wave
             if (int rc2 = pit_head_scale(head, n_head, scale_out, stream)) return rc2;
+            pit_att_note(PIT_ATT_HEAD_SCALE);
             a.head = scale_out; a.head_is_scale = 1;
         }
         launch_sparse_rows<0>(a, sp, (hipStream_t)stream, nullptr, &wdone, job ? &wargs : nullptr);
@@ -3519,6 +3560,7 @@ extern "C" int pit_posatt_bwd(const float* mesh_out, const float* mesh_in, int m
             PIT_CHECK_LAUNCH();
             if (!(accumulate_head & PIT_HEAD_DEFER)) {
                 hipLaunchKernelGGL(posatt_dhead_finish, dim3(n_head), dim3(256), 0, s, a);
+                pit_att_note(PIT_ATT_DHEAD_FINISH);
                 PIT_CHECK_LAUNCH();
             }
         }
@@ -3530,6 +3572,7 @@ extern "C" int pit_posatt_bwd(const float* mesh_out, const float* mesh_in, int m
         } else if (d_values) {
             const long nv = (long)batch * n_in * dim;
             hipLaunchKernelGGL(zero_f32_kernel, dim3((unsigned)std::min<long>((nv + 1023) / 1024, 2048L)), dim3(256), 0, s, d_values, nv);
+            pit_att_note(PIT_ATT_UNION_ZERO);
             PIT_CHECK_LAUNCH();
             launch_union_dv(a, sp, s);
             PIT_CHECK_LAUNCH();
@@ -3560,6 +3603,7 @@ extern "C" int pit_posatt_bwd(const float* mesh_out, const float* mesh_in, int m
         PIT_CHECK_LAUNCH();
         if (!defer) {
             hipLaunchKernelGGL(posatt_dhead_finish, dim3(n_head), dim3(256), 0, s, a);
+            pit_att_note(PIT_ATT_DHEAD_FINISH);
             PIT_CHECK_LAUNCH();
         }
         if (paired) return rd.finish();

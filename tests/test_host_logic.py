@@ -293,6 +293,33 @@ def test_build_is_stale_after_a_build_with_other_flags_and_the_binding_checks_th
     assert _lib.lib() is not None
 
 
+def test_attention_launch_record_reports_its_kinds_and_copies_what_fits():
+    """pit_debug_att_counts (PIT_HAS_ATT_COUNTS, an addition to ABI 31): returns the number of PIT_ATT_* slots of the header, copies
+    min(n, kinds) of them, accepts out = NULL, and every thread reads a record of its own (all zero here: nothing was launched).
+    The non-zero record, its reset and its thread locality are asserted on the GPU (tests/test_gpu_att_edges.py)."""
+    import ctypes
+    import re
+    from position_induced_transformer_amd import _lib, ops
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "pit_hip.h")).read()
+    assert re.search(r"#define PIT_HAS_ATT_COUNTS 1", header)
+    assert "pit_debug_att_counts" in _lib.SIGNATURES and "pit_debug_att_counts" in _lib.ADDED_LATER
+    slots = {name: int(v) for name, v in re.findall(r"#define PIT_ATT_(\w+)\s+(\d+)\b", header[header.index("#define PIT_HAS_ATT_COUNTS"):])}   # (after the block's marker: the PIT_ATT_UNION math_mode flag stands far above it)
+    kinds = slots.pop("KINDS")
+    assert sorted(slots.values()) == list(range(kinds))                    # one slot per kind, none twice
+    fn = _lib.lib().pit_debug_att_counts
+    assert fn(None, 0, 0) == kinds and fn(None, kinds, 1) == kinds
+    for n in (0, 3, kinds, kinds + 5):
+        buf = (ctypes.c_int * (kinds + 5))(*([-1] * (kinds + 5)))
+        assert fn(buf, n, 0) == kinds
+        assert list(buf) == [0] * min(n, kinds) + [-1] * (kinds + 5 - min(n, kinds))
+    assert ops.att_launch_counts() == [0] * kinds
+    seen = []
+    t = threading.Thread(target=lambda: seen.append(ops.att_launch_counts(reset=True)))
+    t.start()
+    t.join()
+    assert seen == [[0] * kinds]
+
+
 def test_postponed_job_slices_cover_the_rows_once_and_respect_the_early_bucket():
     """ops._dw_slices: a postponed weight-gradient job cut into row slices for the fused processor's launches - every row
     exactly once, slices 16-row aligned, operand pointers advanced by whole rows; and the number of parts a two-bucket step
