@@ -363,7 +363,18 @@ __global__ __launch_bounds__(NTB, 4) void fold_bwd_kernel(FoldArgs g) {
     T* pt = vt + H * umk * VP;                          // [H][SR][PP]    P of this pass, read as the [k = row][i = slot] image
     T* qt = pt + H * SR * PP;                           // [H][SR][PP]    Q = P (m - mbar)
     T* dt = qt + H * SR * PP;                           // [SR][VP]       this pass's rows of dZ
-    double* wred = reinterpret_cast<double*>(dt + SR * VP);      // [8]      (dt's end is 16-byte aligned: SR * VP * sizeof(T) is)
+    // wred and keys_s are still live when the epilogue lays its exchange tile ex[EU][CW * H + 4] (fp32) over the dead tiles, so they
+    // sit behind the LONGER of the two layouts (both ends are multiples of 16 bytes).  End of the tiles / end of ex, bytes:
+    //   fp32  H=1  um 32 / 48 / 64:  26 624 / 35 072 / 43 520  | 17 408      H=2:  44 544 / 61 440 / 78 336  | 33 792
+    //   bf16  H=1  um 32 / 48, 64:   14 336 / 23 040           | 17 408      H=2:  24 064 / 41 472           | 33 792
+    // (bf16 pads 48 slots to umk = 64).  Only bf16 with um = 32 has tiles shorter than ex: with both arrays right behind the
+    // tiles, ex's rows >= 32 - the zero accumulators of the skipped MFMA tiles, stored all the same - cleared keys_s before the
+    // atomic epilogue read it (every d(VW) row of the slab was added to key 0) and raced with the other waves' wred stores (a
+    // head's d(scale) partial could be lost).  fold_smem adds their 320 bytes to whichever layout is longer: at most 34 112 bytes
+    // where ex decides (bf16, um = 32, H = 2), under the 40 960 that four workgroups per CU leave each.
+    constexpr size_t EX_BYTES = (size_t)EU * (CW * H + 4) * sizeof(float);
+    const size_t tiles_bytes = ((size_t)H * umk * VP + 2 * (size_t)H * SR * PP + (size_t)SR * VP) * sizeof(T);
+    double* wred = reinterpret_cast<double*>(smem_raw + (tiles_bytes > EX_BYTES ? tiles_bytes : EX_BYTES));      // [8]
     int* keys_s = reinterpret_cast<int*>(wred + 8);              // [EU]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, kq = lane >> 4;
     const int gsel = wave >> 2, w4 = wave & 3;
@@ -504,7 +515,8 @@ size_t fold_smem(int H, bool bf, int um, bool bwd) {
     const int es = bf ? 2 : 4, pade = bf ? 8 : 4, umk = bf ? ((um + 31) & ~31) : um;
     const size_t vt = (size_t)H * umk * (CW + pade) * es, wt = (size_t)H * SR * (umk + pade) * es;
     if (!bwd) return vt + wt + (size_t)SR * (CW + 4) * 4;
-    return std::max(vt + 2 * wt + (size_t)SR * (CW + pade) * es + 8 * 8 + EU * 4, (size_t)EU * (CW * H + 4) * 4);   // (the epilogue's exchange tile)
+    // the tiles or the epilogue's exchange tile, whichever ends later, then wred[8] and keys_s[EU] (fold_bwd_kernel places them so)
+    return std::max(vt + 2 * wt + (size_t)SR * (CW + pade) * es, (size_t)EU * (CW * H + 4) * 4) + 8 * 8 + EU * 4;
 }
 
 bool fold_plan_ok(const pit_slab_plan* p) {

@@ -119,7 +119,7 @@ def test_folded_decoder_against_the_oracle(metric, n_out_side, n_in_side, dim, h
     assert float((p1["lmda"].grad.cpu().reshape(-1) - p0["lmda"].grad.reshape(-1)).norm()) <= 1e-4 * float(p0["lmda"].grad.norm())
 
 
-@pytest.mark.parametrize("metric,n_out_side,n_in_side,dim,heads,batch,loc,n2", CASES[:3])
+@pytest.mark.parametrize("metric,n_out_side,n_in_side,dim,heads,batch,loc,n2", CASES)
 def test_folded_decoder_in_bf16_mode(metric, n_out_side, n_in_side, dim, heads, batch, loc, n2):
     """The same in the bf16 math mode: tiles rounded to bf16 in LDS, v_mfma_f32_16x16x32_bf16 (the [k][n] images through
     ds_read_b64_tr_b16), z / dz stored as bf16 - within the mode's tolerances against the fp32 oracle (tests/test_gpu_bf16.py)."""
