@@ -23,6 +23,7 @@
 #include "pit_common.h"
 #include "pit_block_dev.h"      // block_weights_body: the processor's weights as a rider of the down-projection launch
 #include "pit_gemm_rd.h"
+#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
@@ -1597,16 +1598,27 @@ __global__ __launch_bounds__(512) void posatt_bwd_pair_wide_kernel(AttArgs ar, A
     }
 }
 
-// tuning overrides for experiments (tools/microbench.py): PIT_FORCE_CT, PIT_FORCE_WAVES, PIT_NO_TILES_KERNEL
+// PIT_FORCE_TILES, PIT_FORCE_RT and PIT_NO_FAST_LOADS are live in the production library (tests/test_gpu_ops.py sets them)
 int env_int(const char* name) {
     const char* v = getenv(name);
     return v ? atoi(v) : 0;
 }
+// A/B switches (PIT_FORCE_CT, PIT_FORCE_WAVES, PIT_NO_BWD_PAIR, PIT_NO_TILES_KERNEL, PIT_NO_UNION_TILES, PIT_NO_XCD_REMAP,
+// PIT_NO_INTERLEAVE, PIT_NO_PRE_WEIGHTS, PIT_NO_WIDE_DW_RIDER: force another kernel family or tile shape for a measurement)
+// are compiled in only with -DPIT_EXPERIMENTS, as in pit_mlp.hip: the production library reads no environment variable
+// for them.
+#ifdef PIT_EXPERIMENTS
+const char* exp_env(const char* name) { return getenv(name); }
+int exp_int(const char* name) { return env_int(name); }
+#else
+const char* exp_env(const char*) { return nullptr; }
+int exp_int(const char*) { return 0; }
+#endif
 
 // tiles per workgroup for the large-regime kernels (0 = use the J-split kernels): they pay off
 // only when the launch has real work (MFMA-instruction count), small layers stay latency-bound
 int tiles_per_wg_for(int ncols, long units, long work_mfma, int mesh_batch) {
-    if (env_int("PIT_NO_TILES_KERNEL")) return 0;
+    if (exp_int("PIT_NO_TILES_KERNEL")) return 0;
     const int ntiles = (ncols + 31) / 32;
     if (ntiles < 8) return 0;
     // measured (MI355X): wins for batch-free meshes with the batch folded into >= 32 column tiles
@@ -1618,8 +1630,86 @@ int tiles_per_wg_for(int ncols, long units, long work_mfma, int mesh_batch) {
     return tpw;
 }
 
+// rt = 32-row tiles per workgroup of posatt_rows_tiles, tpwg = column tiles per workgroup; tpwg == 0 = the J-split kernels
+struct TilesRegime { int rt, tpwg; };
+// The regime of a rows launch (forward, d(scale)).  The ONE statement of the rule: the dense launcher,
+// the merged backward, the precomputed-weights launcher and pit_posatt_pre_supported must agree on it.
+TilesRegime rows_tiles_regime(int ncols, int n_tiles, int n_head, int mesh_batch, int n_in) {
+    const long work = (long)n_tiles * n_head * mesh_batch * ((ncols + 31) / 32) * ((n_in + 1) / 2);
+    // row tiles per workgroup: more reuse of every value fragment, as long as the grid still fills the chip
+    int rt = 4;
+    while (rt > 1 && (n_tiles < rt || (long)((n_tiles + rt - 1) / rt) * n_head * mesh_batch * (((long)ncols + 255) / 256) < 256)) rt >>= 1;
+    if (int f = env_int("PIT_FORCE_RT")) rt = f;                // (tests: 1, 2 or 4; any other value takes the RT = 1 kernels, as it always did)
+    int tpwg = tiles_per_wg_for(ncols, (long)((n_tiles + rt - 1) / rt) * n_head * mesh_batch, work, mesh_batch);
+    if (tpwg && rt == 4) tpwg = 8;                             // registers: RT*TPW accumulator tiles <= 4
+    else if (rt == 2 && tpwg > 16) tpwg = 16;
+    return {rt, tpwg};
+}
+// the same for a columns launch (d(values)): column tiles per workgroup of posatt_cols_tiles, 0 = the J-split kernels
+int cols_tiles_regime(int ncols, int j_tiles, int n_head, int mesh_batch, int n_out) {
+    const long work = (long)j_tiles * mesh_batch * ((ncols + 31) / 32) * ((n_out + 1) / 2) * n_head;
+    return tiles_per_wg_for(ncols, (long)j_tiles * mesh_batch, work, mesh_batch);
+}
+
 int pow2_floor(int v) { int p = 1; while (p * 2 <= v) p *= 2; return p; }
 
+// Launch of kernel K with up to 96 KiB of dynamic LDS: the limit is raised once per kernel instantiation, before its first
+// launch (a function-local static keyed on K alone: thread-safe), never per launch.
+template <auto K> void raise_lds96() {
+    static const bool once = ((void)hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, 98304), true);
+    (void)once;
+}
+template <auto K, typename... Args>
+void launch_lds96(dim3 grid, dim3 block, size_t smem, hipStream_t s, const Args&... args) {
+    raise_lds96<K>();
+    hipLaunchKernelGGL(K, grid, block, smem, s, args...);
+}
+// The ladders below leave combinations that have no kernel instance out with `if constexpr`; no caller reaches one today (the
+// dispatch rules above each ladder say why).  One that did would otherwise launch nothing, silently: it ends the process instead.
+[[noreturn]] void no_instance(const char* kernel) {
+    fprintf(stderr, "pit_posatt: no instance of %s for this combination of template arguments\n", kernel);
+    abort();
+}
+// A run-time bool, or an int out of a fixed list (any other value takes the LAST entry), as a compile-time constant for a
+// generic lambda: with_bool(a.masked, [&](auto M) { ... decltype(M)::value ... }), with_int<8, 4, 2, 1>(cr, ...)
+template <class F> void with_bool(bool v, F&& f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
+template <int V0, int... Vs, class F> void with_int(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V0>{});
+    else if (v == V0) f(std::integral_constant<int, V0>{});
+    else with_int<Vs...>(v, f);
+}
+
+// The (RT, TPW) ladder over posatt_rows_tiles, once: `r` from rows_tiles_regime (r.tpwg != 0).  PRE (precomputed weights)
+// exists unmasked only; its callers pass mesh_batch == 1 and masked == 0.  bf16 math is the forward's (MODE 0) only.
+template <int MODE>
+void launch_rows_tiles(AttArgs a, TilesRegime r, bool pre, hipStream_t s) {
+    const bool bf = (MODE == 0) && a.bf16 != 0;
+    const int n_tiles = (a.n_out + 31) / 32;
+    a.tiles_per_wg = r.tpwg;
+    a.colgroups = ((a.ncols + 31) / 32 + r.tpwg - 1) / r.tpwg;
+    dim3 grid(a.mesh_batch * a.colgroups, a.n_head, (n_tiles + r.rt - 1) / r.rt), block(512);
+    // TPW = tiles per wave (8 waves); the regime's clamps keep RT * TPW <= 4 accumulator tiles, the instances that exist
+    with_int<4, 2, 1>(r.rt, [&](auto RT) { with_int<4, 2, 1>(r.tpwg / 8, [&](auto TPW) {
+        with_bool(pre, [&](auto PRE) { with_bool(a.masked, [&](auto M) { with_bool(bf, [&](auto BF) {
+            if constexpr (RT() * TPW() <= 4 && !(PRE() && M()) && !(BF() && MODE != 0))
+                hipLaunchKernelGGL((posatt_rows_tiles<RT(), TPW(), MODE, M(), BF(), PRE()>), grid, block, 0, s, a);
+            else no_instance("posatt_rows_tiles");
+        }); }); });
+    }); });
+}
+
+// the TPW ladder over posatt_cols_tiles, once: `tpwg` from cols_tiles_regime (!= 0)
+void launch_cols_tiles(AttArgs a, int tpwg, bool pre, hipStream_t s) {
+    const int j_tiles = (a.n_in + 31) / 32;
+    a.tiles_per_wg = tpwg;
+    a.colgroups = ((a.ncols + 31) / 32 + tpwg - 1) / tpwg;
+    dim3 grid(a.colgroups, j_tiles, a.mesh_batch), block(512);
+    with_int<32, 16, 8>(tpwg, [&](auto TPWG) { with_bool(pre, [&](auto PRE) { with_bool(a.masked, [&](auto M) { with_bool(a.bf16, [&](auto BF) {
+        if constexpr (!(PRE() && M()))
+            hipLaunchKernelGGL((posatt_cols_tiles<TPWG() / 8, M(), BF(), PRE()>), grid, block, 0, s, a);
+        else no_instance("posatt_cols_tiles");
+    }); }); }); });
+}
 
 
 // column-tile count per workgroup: least padding, then enough workgroups to cover the chip
@@ -1650,7 +1740,7 @@ size_t cols_smem(int ct, int nwaves, int n_out) {
 // a lane's four columns must belong to one sample.  mode 0: forward (values, out), 1: d(scale) (values, d_out),
 // 2: d(values) (d_out, d_values)
 bool interleave_ok(const AttArgs& a, int mode) {
-    static const bool off = getenv("PIT_NO_INTERLEAVE") != nullptr;
+    static const bool off = exp_env("PIT_NO_INTERLEAVE") != nullptr;
     auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     if (off || a.dim % 4 != 0 || a.ncols % 4 != 0) return false;
     const bool vals = al(a.values) && a.ld_values % 4 == 0 && a.values_bstride % 4 == 0;
@@ -1670,17 +1760,11 @@ void launch_rows8(AttArgs a, int mode, hipStream_t s) {
     const dim3 grid(a.mesh_batch * a.colgroups, a.n_head, n_tiles), block(64 * nwaves);
     const size_t stage = (size_t)min(KEY_CHUNK, a.n_in) * sizeof(pt8), red = (size_t)nwaves * (16 + 2) * 64 * sizeof(float);
     const size_t sm = stage > red ? stage : red;
-#define PIT_R8(MODE_, MASKED_, BF_)                                                                                    \
-    do {                                                                                                               \
-        static bool once = ((void)hipFuncSetAttribute((const void*)posatt_rows_kernel8<MODE_, MASKED_, BF_>,           \
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, 98304), true);       \
-        (void)once;                                                                                                    \
-        hipLaunchKernelGGL((posatt_rows_kernel8<MODE_, MASKED_, BF_>), grid, block, sm, s, a);                         \
-    } while (0)
-    if (mode == 1) { if (a.masked) PIT_R8(1, true, false); else PIT_R8(1, false, false); }
-    else if (bf) { if (a.masked) PIT_R8(0, true, true); else PIT_R8(0, false, true); }
-    else { if (a.masked) PIT_R8(0, true, false); else PIT_R8(0, false, false); }
-#undef PIT_R8
+    with_int<1, 0>(mode, [&](auto MODE) { with_bool(a.masked, [&](auto M) { with_bool(bf, [&](auto BF) {
+        if constexpr (!(BF() && MODE() == 1))                       // (d(scale) is always exact fp32)
+            launch_lds96<posatt_rows_kernel8<MODE(), M(), BF()>>(grid, block, sm, s, a);
+        else no_instance("posatt_rows_kernel8");
+    }); }); });
 }
 void launch_cols8(AttArgs a, hipStream_t s) {
     const int j_tiles = (a.n_in + 31) / 32;
@@ -1689,16 +1773,9 @@ void launch_cols8(AttArgs a, hipStream_t s) {
     const dim3 grid(a.colgroups, j_tiles, a.mesh_batch), block(64 * nwaves);
     const size_t stage = (size_t)ROW_CHUNK * (sizeof(rec8) + sizeof(float2)), red = (size_t)nwaves * 16 * 64 * sizeof(float);
     const size_t sm = stage > red ? stage : red;
-#define PIT_C8(MASKED_, BF_)                                                                                           \
-    do {                                                                                                               \
-        static bool once = ((void)hipFuncSetAttribute((const void*)posatt_cols_kernel8<MASKED_, BF_>,                  \
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, 98304), true);       \
-        (void)once;                                                                                                    \
-        hipLaunchKernelGGL((posatt_cols_kernel8<MASKED_, BF_>), grid, block, sm, s, a);                                \
-    } while (0)
-    if (a.bf16) { if (a.masked) PIT_C8(true, true); else PIT_C8(false, true); }
-    else { if (a.masked) PIT_C8(true, false); else PIT_C8(false, false); }
-#undef PIT_C8
+    with_bool(a.masked, [&](auto M) { with_bool(a.bf16, [&](auto BF) {
+        launch_lds96<posatt_cols_kernel8<M(), BF()>>(grid, block, sm, s, a);
+    }); });
 }
 
 template <int MODE>
@@ -1707,68 +1784,26 @@ void launch_rows(const AttArgs& a0, hipStream_t s) {
     AttArgs a = a0;
     const bool bf = (MODE == 0) && a.bf16 != 0;
     const int n_tiles = (a.n_out + 31) / 32;
-    const long work = (long)n_tiles * a.n_head * a.mesh_batch * ((a.ncols + 31) / 32) * ((a.n_in + 1) / 2);
-    // row tiles per workgroup: more reuse of every value fragment, as long as the grid still fills the chip
-    int rt = 4;
-    while (rt > 1 && (n_tiles < rt || (long)((n_tiles + rt - 1) / rt) * a.n_head * a.mesh_batch * ((a.ncols + 255) / 256) < 256)) rt >>= 1;
-    if (int f = env_int("PIT_FORCE_RT")) rt = f;
-    if (const int tpwg0 = tiles_per_wg_for(a.ncols, (long)((n_tiles + rt - 1) / rt) * a.n_head * a.mesh_batch, work, a.mesh_batch)) {
-        int tpwg = tpwg0;
-        if (rt == 4) tpwg = 8;                                 // registers: RT*TPW accumulator tiles <= 4
-        else if (rt == 2 && tpwg > 16) tpwg = 16;
-        a.tiles_per_wg = tpwg;
-        a.colgroups = ((a.ncols + 31) / 32 + tpwg - 1) / tpwg;
-        dim3 grid(a.mesh_batch * a.colgroups, a.n_head, (n_tiles + rt - 1) / rt), block(512);
-#define PIT_RT_BF(RT_, TPW_, BF_)                                                                                 \
-        do {                                                                                                      \
-            if (a.masked) hipLaunchKernelGGL((posatt_rows_tiles<RT_, TPW_, MODE, true, BF_>), grid, block, 0, s, a); \
-            else hipLaunchKernelGGL((posatt_rows_tiles<RT_, TPW_, MODE, false, BF_>), grid, block, 0, s, a);      \
-        } while (0)
-#define PIT_RT(RT_, TPW_) do { if (bf) PIT_RT_BF(RT_, TPW_, (MODE == 0)); else PIT_RT_BF(RT_, TPW_, false); } while (0)
-        if (rt == 4) PIT_RT(4, 1);
-        else if (rt == 2) { if (tpwg == 16) PIT_RT(2, 2); else PIT_RT(2, 1); }
-        else { if (tpwg == 32) PIT_RT(1, 4); else if (tpwg == 16) PIT_RT(1, 2); else PIT_RT(1, 1); }
-#undef PIT_RT
-#undef PIT_RT_BF
+    const TilesRegime regime = rows_tiles_regime(a.ncols, n_tiles, a.n_head, a.mesh_batch, a.n_in);
+    if (regime.tpwg) {
+        launch_rows_tiles<MODE>(a, regime, false, s);
         pit_att_note(PIT_ATT_DENSE);
         return;
     }
     int ct = choose_ct(a.ncols, (long)n_tiles * a.n_head * a.mesh_batch);
-    if (int f = env_int("PIT_FORCE_CT")) ct = f;
+    if (int f = exp_int("PIT_FORCE_CT")) ct = f;
     a.colgroups = (a.ncols + 32 * ct - 1) / (32 * ct);
     const int wmax = (ct == 4) ? 4 : 8;                                  // parked tiles must fit 96 KiB of LDS
     int nwaves = max(1, min(wmax, pow2_floor(a.n_in / 32)));
-    if (int f = env_int("PIT_FORCE_WAVES")) nwaves = pow2_floor(max(1, min(f, wmax)));     // (the epilogue is specialised for 1/2/4/8)
+    if (int f = exp_int("PIT_FORCE_WAVES")) nwaves = pow2_floor(max(1, min(f, wmax)));     // (the epilogue is specialised for 1/2/4/8)
     dim3 grid(a.mesh_batch * a.colgroups, a.n_head, n_tiles), block(64 * nwaves);
     const size_t sm = rows_smem(ct, nwaves, a.n_in);
-#define PIT_ROWS_BF(CT_, BF_)                                                                               \
-    do {                                                                                                    \
-        static bool once = ((void)hipFuncSetAttribute((const void*)posatt_rows_kernel<CT_, MODE, true, BF_>,      \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 98304),         \
-                            (void)hipFuncSetAttribute((const void*)posatt_rows_kernel<CT_, MODE, false, BF_>,     \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 98304), true);  \
-        (void)once;                                                                                         \
-        if (a.masked) hipLaunchKernelGGL((posatt_rows_kernel<CT_, MODE, true, BF_>), grid, block, sm, s, a); \
-        else hipLaunchKernelGGL((posatt_rows_kernel<CT_, MODE, false, BF_>), grid, block, sm, s, a);        \
-    } while (0)
-#define PIT_ROWS(CT_) do { if (bf) PIT_ROWS_BF(CT_, (MODE == 0)); else PIT_ROWS_BF(CT_, false); } while (0)
-#define PIT_ROWS_IL_BF(BF_)                                                                                 \
-    do {                                                                                                    \
-        static bool once = ((void)hipFuncSetAttribute((const void*)posatt_rows_kernel<4, MODE, true, BF_, true>,  \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 98304),         \
-                            (void)hipFuncSetAttribute((const void*)posatt_rows_kernel<4, MODE, false, BF_, true>, \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 98304), true);  \
-        (void)once;                                                                                         \
-        if (a.masked) hipLaunchKernelGGL((posatt_rows_kernel<4, MODE, true, BF_, true>), grid, block, sm, s, a); \
-        else hipLaunchKernelGGL((posatt_rows_kernel<4, MODE, false, BF_, true>), grid, block, sm, s, a);    \
-    } while (0)
-    if (ct == 4 && interleave_ok(a, MODE)) { if (bf) PIT_ROWS_IL_BF((MODE == 0)); else PIT_ROWS_IL_BF(false); }
-    else if (ct == 4) PIT_ROWS(4);
-    else if (ct == 2) PIT_ROWS(2);
-    else PIT_ROWS(1);
-#undef PIT_ROWS_IL_BF
-#undef PIT_ROWS
-#undef PIT_ROWS_BF
+    const bool il = ct == 4 && interleave_ok(a, MODE);
+    with_int<4, 2, 1>(ct, [&](auto CT) { with_bool(il, [&](auto IL) { with_bool(a.masked, [&](auto M) { with_bool(bf, [&](auto BF) {
+        if constexpr (!(IL() && CT() != 4) && !(BF() && MODE != 0))
+            launch_lds96<posatt_rows_kernel<CT(), MODE, M(), BF(), IL()>>(grid, block, sm, s, a);
+        else no_instance("posatt_rows_kernel");
+    }); }); }); });
     pit_att_note(PIT_ATT_DENSE);
 }
 
@@ -1777,59 +1812,25 @@ void launch_cols(const AttArgs& a0, hipStream_t s) {
     AttArgs a = a0;
     const bool bf = a.bf16 != 0;
     const int j_tiles = (a.n_in + 31) / 32;
-    const long work = (long)j_tiles * a.mesh_batch * ((a.ncols + 31) / 32) * ((a.n_out + 1) / 2) * a.n_head;
-    if (const int tpwg = tiles_per_wg_for(a.ncols, (long)j_tiles * a.mesh_batch, work, a.mesh_batch)) {
-        a.tiles_per_wg = tpwg;
-        a.colgroups = ((a.ncols + 31) / 32 + tpwg - 1) / tpwg;
-        dim3 grid(a.colgroups, j_tiles, a.mesh_batch), block(512);
-#define PIT_CT_BF(TPW_, BF_)                                                                             \
-        do {                                                                                             \
-            if (a.masked) hipLaunchKernelGGL((posatt_cols_tiles<TPW_, true, BF_>), grid, block, 0, s, a); \
-            else hipLaunchKernelGGL((posatt_cols_tiles<TPW_, false, BF_>), grid, block, 0, s, a);        \
-        } while (0)
-#define PIT_CT(TPW_) do { if (bf) PIT_CT_BF(TPW_, true); else PIT_CT_BF(TPW_, false); } while (0)
-        if (tpwg == 32) PIT_CT(4); else if (tpwg == 16) PIT_CT(2); else PIT_CT(1);
-#undef PIT_CT
-#undef PIT_CT_BF
+    if (const int tpwg = cols_tiles_regime(a.ncols, j_tiles, a.n_head, a.mesh_batch, a.n_out)) {
+        launch_cols_tiles(a, tpwg, false, s);
         pit_att_note(PIT_ATT_DENSE);
         return;
     }
     int ct = choose_ct(a.ncols, (long)j_tiles * a.mesh_batch);
-    if (int f = env_int("PIT_FORCE_CT")) ct = f;
+    if (int f = exp_int("PIT_FORCE_CT")) ct = f;
     a.colgroups = (a.ncols + 32 * ct - 1) / (32 * ct);
     const int wmax = (ct == 4) ? 4 : 8;
     int nwaves = max(1, min(wmax, pow2_floor(a.n_out * a.n_head / 32)));
-    if (int f = env_int("PIT_FORCE_WAVES")) nwaves = pow2_floor(max(1, min(f, wmax)));
+    if (int f = exp_int("PIT_FORCE_WAVES")) nwaves = pow2_floor(max(1, min(f, wmax)));
     dim3 grid(a.colgroups, j_tiles, a.mesh_batch), block(64 * nwaves);
     const size_t sm = cols_smem(ct, nwaves, a.n_out);
-#define PIT_COLS_BF(CT_, BF_)                                                                          \
-    do {                                                                                               \
-        static bool once = ((void)hipFuncSetAttribute((const void*)posatt_cols_kernel<CT_, true, BF_>,       \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 98304),    \
-                            (void)hipFuncSetAttribute((const void*)posatt_cols_kernel<CT_, false, BF_>,      \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 98304), true); \
-        (void)once;                                                                                    \
-        if (a.masked) hipLaunchKernelGGL((posatt_cols_kernel<CT_, true, BF_>), grid, block, sm, s, a);  \
-        else hipLaunchKernelGGL((posatt_cols_kernel<CT_, false, BF_>), grid, block, sm, s, a);         \
-    } while (0)
-#define PIT_COLS(CT_) do { if (bf) PIT_COLS_BF(CT_, true); else PIT_COLS_BF(CT_, false); } while (0)
-#define PIT_COLS_IL_BF(BF_)                                                                            \
-    do {                                                                                               \
-        static bool once = ((void)hipFuncSetAttribute((const void*)posatt_cols_kernel<4, true, BF_, true>,   \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 98304),    \
-                            (void)hipFuncSetAttribute((const void*)posatt_cols_kernel<4, false, BF_, true>,  \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 98304), true); \
-        (void)once;                                                                                    \
-        if (a.masked) hipLaunchKernelGGL((posatt_cols_kernel<4, true, BF_, true>), grid, block, sm, s, a); \
-        else hipLaunchKernelGGL((posatt_cols_kernel<4, false, BF_, true>), grid, block, sm, s, a);     \
-    } while (0)
-    if (ct == 4 && interleave_ok(a, 2)) { if (bf) PIT_COLS_IL_BF(true); else PIT_COLS_IL_BF(false); }
-    else if (ct == 4) PIT_COLS(4);
-    else if (ct == 2) PIT_COLS(2);
-    else PIT_COLS(1);
-#undef PIT_COLS_IL_BF
-#undef PIT_COLS
-#undef PIT_COLS_BF
+    const bool il = ct == 4 && interleave_ok(a, 2);
+    with_int<4, 2, 1>(ct, [&](auto CT) { with_bool(il, [&](auto IL) { with_bool(a.masked, [&](auto M) { with_bool(bf, [&](auto BF) {
+        if constexpr (!(IL() && CT() != 4))
+            launch_lds96<posatt_cols_kernel<CT(), M(), BF(), IL()>>(grid, block, sm, s, a);
+        else no_instance("posatt_cols_kernel");
+    }); }); }); });
     pit_att_note(PIT_ATT_DENSE);
 }
 
@@ -1857,16 +1858,11 @@ __global__ __launch_bounds__(512, 4) void posatt_bwd_pair_dw_kernel(AttArgs ar, 
 
 // `rider` (may be null) is carried along when the narrow-tile kernel is the one chosen; *rider_done says so
 bool launch_bwd_pair(const AttArgs& a0, hipStream_t s, const pit_mlp_params_job* job = nullptr, bool* rider_done = nullptr) {
-    if (env_int("PIT_NO_BWD_PAIR") || env_int("PIT_FORCE_CT") || env_int("PIT_FORCE_WAVES") || a0.sdim > 3) return false;
+    if (exp_int("PIT_NO_BWD_PAIR") || exp_int("PIT_FORCE_CT") || exp_int("PIT_FORCE_WAVES") || a0.sdim > 3) return false;
     const int n_tiles = (a0.n_out + 31) / 32, j_tiles = (a0.n_in + 31) / 32;
-    {   // either part would take the large-regime kernels: keep them separate
-        const long work_r = (long)n_tiles * a0.n_head * a0.mesh_batch * ((a0.ncols + 31) / 32) * ((a0.n_in + 1) / 2);
-        const long work_c = (long)j_tiles * a0.mesh_batch * ((a0.ncols + 31) / 32) * ((a0.n_out + 1) / 2) * a0.n_head;
-        int rt = 4;
-        while (rt > 1 && (n_tiles < rt || (long)((n_tiles + rt - 1) / rt) * a0.n_head * a0.mesh_batch * ((a0.ncols + 255) / 256) < 256)) rt >>= 1;
-        if (tiles_per_wg_for(a0.ncols, (long)((n_tiles + rt - 1) / rt) * a0.n_head * a0.mesh_batch, work_r, a0.mesh_batch)) return false;
-        if (tiles_per_wg_for(a0.ncols, (long)j_tiles * a0.mesh_batch, work_c, a0.mesh_batch)) return false;
-    }
+    // either part would take the large-regime kernels: keep them separate
+    if (rows_tiles_regime(a0.ncols, n_tiles, a0.n_head, a0.mesh_batch, a0.n_in).tpwg ||
+        cols_tiles_regime(a0.ncols, j_tiles, a0.n_head, a0.mesh_batch, a0.n_out)) return false;
     const int ct = choose_ct(a0.ncols, (long)n_tiles * a0.n_head * a0.mesh_batch);
     if (ct != choose_ct(a0.ncols, (long)j_tiles * a0.mesh_batch)) return false;
     AttArgs ar = a0, ac = a0;
@@ -1887,53 +1883,22 @@ bool launch_bwd_pair(const AttArgs& a0, hipStream_t s, const pit_mlp_params_job*
         const int n_att = (int)(rows_wgs + cols_wgs);
         const size_t smw = std::max(sm, (size_t)nwaves * 16 * 64 * sizeof(float));
         dim3 gridw((unsigned)(n_att + rider->n1 + rider->n2));
-#define PIT_PAIR_DW(M_, BF_)                                                                                  \
-    do {                                                                                                      \
-        static bool once = ((void)hipFuncSetAttribute((const void*)posatt_bwd_pair_dw_kernel<M_, BF_>,        \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 98304), true);    \
-        (void)once;                                                                                           \
-        hipLaunchKernelGGL((posatt_bwd_pair_dw_kernel<M_, BF_>), gridw, block, smw, s, ar, ac, (int)cols_wgs, \
-                           ac.colgroups, j_tiles, a0.mesh_batch * ar.colgroups, a0.n_head, n_att, *rider);    \
-    } while (0)
-        if (a0.masked) { if (a0.bf16) PIT_PAIR_DW(true, true); else PIT_PAIR_DW(true, false); }
-        else { if (a0.bf16) PIT_PAIR_DW(false, true); else PIT_PAIR_DW(false, false); }
-#undef PIT_PAIR_DW
+        with_bool(a0.masked, [&](auto M) { with_bool(a0.bf16, [&](auto BF) {
+            launch_lds96<posatt_bwd_pair_dw_kernel<M(), BF()>>(gridw, block, smw, s, ar, ac, (int)cols_wgs, ac.colgroups, j_tiles,
+                                                               a0.mesh_batch * ar.colgroups, a0.n_head, n_att, *rider);
+        }); });
         *rider_done = true;
         pit_rider_note(PIT_RIDER_PAIR_DW);
         pit_att_note(PIT_ATT_DENSE);
         return true;
     }
-#define PIT_PAIR_K(M_, BF_)                                                                                   \
-    do {                                                                                                      \
-        static bool once = ((void)hipFuncSetAttribute((const void*)posatt_bwd_pair_kernel<M_, BF_>,                 \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 98304), true);    \
-        (void)once;                                                                                           \
-        hipLaunchKernelGGL((posatt_bwd_pair_kernel<M_, BF_>), grid, block, sm, s, ar, ac, (int)cols_wgs,      \
-                           ac.colgroups, j_tiles, a0.mesh_batch * ar.colgroups, a0.n_head);                   \
-    } while (0)
-#define PIT_PAIR_W(CT_, M_, BF_)                                                                              \
-    do {                                                                                                      \
-        static bool once = ((void)hipFuncSetAttribute((const void*)posatt_bwd_pair_wide_kernel<CT_, M_, BF_>,       \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 98304), true);    \
-        (void)once;                                                                                           \
-        hipLaunchKernelGGL((posatt_bwd_pair_wide_kernel<CT_, M_, BF_>), wgrid, block, wsm, s, ar, ac, (int)cols_wgs, \
-                           ac.colgroups, j_tiles, a0.mesh_batch * ar.colgroups, a0.n_head, (int)(rows_wgs + cols_wgs), wdw); \
-    } while (0)
-#define PIT_PAIR_IL(M_, BF_)                                                                                  \
-    do {                                                                                                      \
-        static bool once = ((void)hipFuncSetAttribute((const void*)posatt_bwd_pair_wide_kernel<4, M_, BF_, true>,   \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 98304), true);    \
-        (void)once;                                                                                           \
-        hipLaunchKernelGGL((posatt_bwd_pair_wide_kernel<4, M_, BF_, true>), wgrid, block, wsm, s, ar, ac, (int)cols_wgs, \
-                           ac.colgroups, j_tiles, a0.mesh_batch * ar.colgroups, a0.n_head, (int)(rows_wgs + cols_wgs), wdw); \
-    } while (0)
     const bool il = ct == 4 && interleave_ok(a0, 1) && interleave_ok(a0, 2);
     // the wide kernels (four or eight waves, 96 KiB of LDS allowed) carry the job as gemm_rr_tile tiles whatever its size; the tiles contract in
     // the kernel's math mode, which is the job's
     pit_detail::DwPair wdw = pit_detail::DwPair();
     dim3 wgrid = grid;
     size_t wsm = sm;
-    static const bool no_wide_rider = getenv("PIT_NO_WIDE_DW_RIDER") != nullptr;
+    static const bool no_wide_rider = exp_env("PIT_NO_WIDE_DW_RIDER") != nullptr;
     // (... while the attention itself is latency-bound: same-box A/B per fp32 step, carried / own launch - NACA 728 points x hid 128
     // 1.419 / 1.465 ms, Vorticity 256 x 256 x 2 heads 1.219 / 1.231, Elasticity 972 x 256 x 2 2.460 / 2.393: there the attention
     // workgroups run the fp32 matrix pipe at 62 % and the tiles compete for it)
@@ -1947,13 +1912,15 @@ bool launch_bwd_pair(const AttArgs& a0, hipStream_t s, const pit_mlp_params_job*
     } else {
         wdw = pit_detail::DwPair();
     }
-#define PIT_PAIR_CT(M_, BF_) do { if (ct == 1) PIT_PAIR_K(M_, BF_); else if (ct == 2) PIT_PAIR_W(2, M_, BF_); else if (il) PIT_PAIR_IL(M_, BF_); else PIT_PAIR_W(4, M_, BF_); } while (0)
-    if (a0.masked) { if (a0.bf16) PIT_PAIR_CT(true, true); else PIT_PAIR_CT(true, false); }
-    else { if (a0.bf16) PIT_PAIR_CT(false, true); else PIT_PAIR_CT(false, false); }
-#undef PIT_PAIR_CT
-#undef PIT_PAIR_IL
-#undef PIT_PAIR_W
-#undef PIT_PAIR_K
+    with_int<1, 2, 4>(ct, [&](auto CT) { with_bool(il, [&](auto IL) { with_bool(a0.masked, [&](auto M) { with_bool(a0.bf16, [&](auto BF) {
+        if constexpr (CT() == 1)
+            launch_lds96<posatt_bwd_pair_kernel<M(), BF()>>(grid, block, sm, s, ar, ac, (int)cols_wgs, ac.colgroups, j_tiles,
+                                                            a0.mesh_batch * ar.colgroups, a0.n_head);
+        else if constexpr (!(IL() && CT() != 4))
+            launch_lds96<posatt_bwd_pair_wide_kernel<CT(), M(), BF(), IL()>>(wgrid, block, wsm, s, ar, ac, (int)cols_wgs, ac.colgroups, j_tiles,
+                                                                             a0.mesh_batch * ar.colgroups, a0.n_head, (int)(rows_wgs + cols_wgs), wdw);
+        else no_instance("posatt_bwd_pair_wide_kernel");
+    }); }); }); });
     pit_att_note(PIT_ATT_DENSE);
     return true;
 }
@@ -3004,7 +2971,7 @@ int union_wave_lds(int nh, int n_in) {
 bool union_ok(const AttArgs& a, const SparseArgs& sp) {
     return a.sdim <= 3 && a.masked && sp.nbr_idx && sp.nbr_cnt && a.n_in <= 4096 && a.n_head <= 2 && a.coord_dims == 0 && sp.cap <= 64 &&
            a.n_out >= 16 && a.dim % 8 == 0 && a.ld_values % 4 == 0 && a.values_bstride % 4 == 0 &&
-           (reinterpret_cast<uintptr_t>(a.values) & 15) == 0 && !env_int("PIT_NO_UNION_TILES");
+           (reinterpret_cast<uintptr_t>(a.values) & 15) == 0 && !exp_int("PIT_NO_UNION_TILES");
 }
 bool aligned_rows(const void* p, long ld, long bstride, int col0, int elems16) {   // 16-byte pieces of `elems16` elements
     return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && ld % elems16 == 0 && bstride % elems16 == 0 && col0 % elems16 == 0;
@@ -3020,31 +2987,22 @@ void launch_union(const AttArgs& a, const SparseArgs& sp, hipStream_t s) {
     while (per < ncb && (long)rtiles * a.mesh_batch * ((ncb + 2 * per - 1) / (2 * per)) >= 2048) per *= 2;
     dim3 grid((unsigned)((ncb + per - 1) / per), (unsigned)((rtiles + 3) / 4), (unsigned)a.mesh_batch), block(256);
     const int wl = union_wave_lds(a.n_head, a.n_in);
-#define PIT_UN(NH_, EPL_) do {                                                                                             \
-        static bool once = ((void)hipFuncSetAttribute((const void*)posatt_union_kernel<NH_, MODE, EPL_>,                   \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 98304), true);                 \
-        (void)once;                                                                                                        \
-        hipLaunchKernelGGL((posatt_union_kernel<NH_, MODE, EPL_>), grid, block, (size_t)4 * wl, s, a, sp, per, wl); } while (0)
-    if (a.n_head == 2) { if (sp.cap <= 32) PIT_UN(2, 8); else PIT_UN(2, 16); }
-    else               { if (sp.cap <= 32) PIT_UN(1, 8); else PIT_UN(1, 16); }
-#undef PIT_UN
+    with_int<2, 1>(a.n_head, [&](auto NH) { with_int<8, 16>(sp.cap <= 32 ? 8 : 16, [&](auto EPL) {
+        launch_lds96<posatt_union_kernel<NH(), MODE, EPL()>>(grid, block, (size_t)4 * wl, s, a, sp, per, wl);
+    }); });
     pit_att_note(MODE == 0 ? PIT_ATT_UNION_FWD : PIT_ATT_UNION_DSCALE);
     pit_att_note_last(PIT_ATT_LAST_UNION, (a.n_head == 2 ? 2 : 1) * 100 + (sp.cap <= 32 ? 8 : 16));
     pit_att_note_last(PIT_ATT_LAST_UNION_PER, per);
 }
+
 // d(values) of the union-tile form (posatt_union_dv_kernel); the caller zeroed d_values
 void launch_union_dv(const AttArgs& a, const SparseArgs& sp, hipStream_t s) {
     const int ncb = (a.ncols + UW_CB - 1) / UW_CB;
     const size_t sm = (size_t)DV_KC * DV_PS * sizeof(float) + 256 * sizeof(unsigned) + 16 + (size_t)a.n_in * sizeof(unsigned short) + 16;
     dim3 grid((unsigned)std::min(ncb, 64), (unsigned)((a.n_out + DV_RB - 1) / DV_RB), (unsigned)a.mesh_batch), block(512);
-#define PIT_UNDV(NH_, EPL_) do {                                                                                           \
-        static bool once = ((void)hipFuncSetAttribute((const void*)posatt_union_dv_kernel<NH_, EPL_>,                      \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 98304), true);                 \
-        (void)once;                                                                                                        \
-        hipLaunchKernelGGL((posatt_union_dv_kernel<NH_, EPL_>), grid, block, sm, s, a, sp); } while (0)
-    if (a.n_head == 2) { if (sp.cap <= 32) PIT_UNDV(2, 8); else PIT_UNDV(2, 16); }
-    else               { if (sp.cap <= 32) PIT_UNDV(1, 8); else PIT_UNDV(1, 16); }
-#undef PIT_UNDV
+    with_int<2, 1>(a.n_head, [&](auto NH) { with_int<8, 16>(sp.cap <= 32 ? 8 : 16, [&](auto EPL) {
+        launch_lds96<posatt_union_dv_kernel<NH(), EPL()>>(grid, block, sm, s, a, sp);
+    }); });
     pit_att_note(PIT_ATT_UNION_DV);
     pit_att_note_last(PIT_ATT_LAST_UNION, (a.n_head == 2 ? 2 : 1) * 100 + (sp.cap <= 32 ? 8 : 16));
 }
@@ -3091,8 +3049,7 @@ void launch_sparse_rows(const AttArgs& a, const SparseArgs& sp, hipStream_t s, c
     const long rows = (long)a.mesh_batch * a.n_out;
     if (a.sdim > 3) {                                 // 4..8 coordinates: one column per lane, nothing carried along
         const dim3 grid8((unsigned)((rows + 3) / 4), (a.ncols + 63) / 64, a.n_head / nh), block8(256);
-        if (nh == 2) hipLaunchKernelGGL((posatt_sparse_rows8<2, MODE>), grid8, block8, 0, s, a, sp);
-        else hipLaunchKernelGGL((posatt_sparse_rows8<1, MODE>), grid8, block8, 0, s, a, sp);
+        with_int<2, 1>(nh, [&](auto NH) { hipLaunchKernelGGL((posatt_sparse_rows8<NH(), MODE>), grid8, block8, 0, s, a, sp); });
         pit_att_note(PIT_ATT_LIST_ROWS8);
         return;
     }
@@ -3100,47 +3057,43 @@ void launch_sparse_rows(const AttArgs& a, const SparseArgs& sp, hipStream_t s, c
     dim3 grid((unsigned)((rows + 3) / 4), (a.ncols + 64 * cr - 1) / (64 * cr), a.n_head / nh), block(256);
     pit_att_note_last(PIT_ATT_LAST_ROWS, nh * 100 + cr);          // (pit_debug_att_counts: the instance all three launches below share)
     pit_att_note_last(PIT_ATT_LAST_GRID_Y, (int)grid.y);
-    if (MODE == 0 && wjob && (long)grid.x * grid.y * grid.z <= 4096) {       // small launch: carry the processor's weights
-        const int n_att = (int)(grid.x * grid.y * grid.z);
-        dim3 gridw((unsigned)(n_att + block_weights_wgs(wjob->n_layers, wjob->n_head, wjob->L)));
-#define PIT_SRW(NH_, CR_) hipLaunchKernelGGL((posatt_sparse_rows_w<NH_, CR_>), gridw, block, 0, s, a, sp, (int)grid.x, (int)grid.y, n_att, *wjob)
-#define PIT_SRW_CR(NH_) do { if (cr == 8) PIT_SRW(NH_, 8); else if (cr == 4) PIT_SRW(NH_, 4); else if (cr == 2) PIT_SRW(NH_, 2); else PIT_SRW(NH_, 1); } while (0)
-        if (nh == 2) PIT_SRW_CR(2); else PIT_SRW_CR(1);
-#undef PIT_SRW_CR
-#undef PIT_SRW
-        pit_att_note(PIT_ATT_LIST_ROWS_W);
-        *rider_done = true;
-        return;
+    // every ladder below: NH in {2, 1} x CR in {8, 4, 2, 1}
+    auto ladder = [&](auto&& launch) { with_int<2, 1>(nh, [&](auto NH) { with_int<8, 4, 2, 1>(cr, [&](auto CR) { launch(NH, CR); }); }); };
+    if constexpr (MODE == 0) {
+        if (wjob && (long)grid.x * grid.y * grid.z <= 4096) {       // small launch: carry the processor's weights
+            const int n_att = (int)(grid.x * grid.y * grid.z);
+            dim3 gridw((unsigned)(n_att + block_weights_wgs(wjob->n_layers, wjob->n_head, wjob->L)));
+            ladder([&](auto NH, auto CR) {
+                hipLaunchKernelGGL((posatt_sparse_rows_w<NH(), CR()>), gridw, block, 0, s, a, sp, (int)grid.x, (int)grid.y, n_att, *wjob);
+            });
+            pit_att_note(PIT_ATT_LIST_ROWS_W);
+            *rider_done = true;
+            return;
+        }
     }
-    pit_detail::DwPair dw;
-    const pit_detail::DwPair* rider = &dw;
-    if (MODE == 1 && job && (long)grid.x * grid.y * grid.z <= 16384 && pit_detail::plan_dw_pair(*job, 4, &dw)) {   // small launch: carry the reductions
-        const int n_att = (int)(grid.x * grid.y * grid.z);
-        dim3 gridw((unsigned)(n_att + rider->n1 + rider->n2));
-        // (gemm_rr tiles for this rider - the encoder MLP's 64 x 64 reduction - measured neutral: 0.1985 vs 0.1994 ms)
-#define PIT_SRW(NH_, CR_) hipLaunchKernelGGL((posatt_sparse_rows_dw<NH_, CR_>), gridw, block, DW_SMEM_4WAVES, s, a, sp, \
-                                             (int)grid.x, (int)grid.y, rider->n1 + rider->n2, *rider)
-#define PIT_SRW_CR(NH_) do { if (cr == 8) PIT_SRW(NH_, 8); else if (cr == 4) PIT_SRW(NH_, 4); else if (cr == 2) PIT_SRW(NH_, 2); else PIT_SRW(NH_, 1); } while (0)
-        if (nh == 2) PIT_SRW_CR(2); else PIT_SRW_CR(1);
-#undef PIT_SRW_CR
-#undef PIT_SRW
-        *rider_done = true;
-        pit_rider_note(PIT_RIDER_SPARSE_ROWS);
-        pit_att_note(PIT_ATT_LIST_ROWS_DW);
-        return;
+    if constexpr (MODE == 1) {
+        pit_detail::DwPair dw;
+        if (job && (long)grid.x * grid.y * grid.z <= 16384 && pit_detail::plan_dw_pair(*job, 4, &dw)) {   // small launch: carry the reductions
+            const int n_att = (int)(grid.x * grid.y * grid.z);
+            dim3 gridw((unsigned)(n_att + dw.n1 + dw.n2));
+            // (gemm_rr tiles for this rider - the encoder MLP's 64 x 64 reduction - measured neutral: 0.1985 vs 0.1994 ms)
+            ladder([&](auto NH, auto CR) {
+                hipLaunchKernelGGL((posatt_sparse_rows_dw<NH(), CR()>), gridw, block, DW_SMEM_4WAVES, s, a, sp,
+                                   (int)grid.x, (int)grid.y, dw.n1 + dw.n2, dw);
+            });
+            *rider_done = true;
+            pit_rider_note(PIT_RIDER_SPARSE_ROWS);
+            pit_att_note(PIT_ATT_LIST_ROWS_DW);
+            return;
+        }
     }
     const long xtotal = 8L * grid.x * ((grid.y + 7) / 8) * grid.z;
-    const bool remap = grid.y >= 16 && xtotal < 0x7fffffffL && !env_int("PIT_NO_XCD_REMAP");   // (few blocks: padding costs more than locality gains)
-#define PIT_SR(NH_, CR_)                                                                                              \
-    do {                                                                                                              \
-        if (remap) hipLaunchKernelGGL((posatt_sparse_rows_x<NH_, CR_, MODE>), dim3((unsigned)xtotal), block, 0, s, a, sp, \
-                                      (int)grid.x, (int)grid.y);                                                      \
-        else hipLaunchKernelGGL((posatt_sparse_rows<NH_, CR_, MODE>), grid, block, 0, s, a, sp);                      \
-    } while (0)
-#define PIT_SR_CR(NH_) do { if (cr == 8) PIT_SR(NH_, 8); else if (cr == 4) PIT_SR(NH_, 4); else if (cr == 2) PIT_SR(NH_, 2); else PIT_SR(NH_, 1); } while (0)
-    if (nh == 2) PIT_SR_CR(2); else PIT_SR_CR(1);
-#undef PIT_SR_CR
-#undef PIT_SR
+    const bool remap = grid.y >= 16 && xtotal < 0x7fffffffL && !exp_int("PIT_NO_XCD_REMAP");   // (few blocks: padding costs more than locality gains)
+    ladder([&](auto NH, auto CR) {
+        if (remap) hipLaunchKernelGGL((posatt_sparse_rows_x<NH(), CR(), MODE>), dim3((unsigned)xtotal), block, 0, s, a, sp,
+                                      (int)grid.x, (int)grid.y);
+        else hipLaunchKernelGGL((posatt_sparse_rows<NH(), CR(), MODE>), grid, block, 0, s, a, sp);
+    });
     pit_att_note(remap ? PIT_ATT_LIST_ROWS_X : (MODE == 0 ? PIT_ATT_LIST_ROWS_FWD : PIT_ATT_LIST_ROWS_DSCALE));
 }
 
@@ -3149,7 +3102,7 @@ void launch_sparse_rows(const AttArgs& a, const SparseArgs& sp, hipStream_t s, c
 // parts separately)
 bool launch_sparse_bwd_pair(const AttArgs& a, const SparseArgs& sp, bool complete, hipStream_t s,
                             const pit_mlp_params_job* job = nullptr, bool* rider_done = nullptr) {
-    if (env_int("PIT_NO_BWD_PAIR") || a.sdim > 3) return false;
+    if (exp_int("PIT_NO_BWD_PAIR") || a.sdim > 3) return false;
     const int nh = (a.n_head % 2 == 0) ? 2 : 1;
     const long rows = (long)a.mesh_batch * a.n_out, keys = (long)a.mesh_batch * a.n_in;
     const int crr = cr_for(a.ncols, rows * (a.n_head / nh));
@@ -3164,42 +3117,37 @@ bool launch_sparse_bwd_pair(const AttArgs& a, const SparseArgs& sp, bool complet
     const long n_rows = rgx * rblocks * (a.n_head / nh), n_cols = cgx * cblocks;
     if (n_rows + n_cols > 16384) return false;            // big launches gain nothing from merging
     dim3 grid((unsigned)(n_rows + n_cols)), block(256);
+    auto overflow = [&]() {
+        if (complete) return;
+        hipLaunchKernelGGL(posatt_sparse_overflow_cols, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a, sp);
+        pit_att_note(PIT_ATT_LIST_OVERFLOW);
+    };
+    // the ladders: NH in {2, 1} x CRR x (d(values) columns per lane the same as d(scale)'s, or 1)
+    const bool same = crc == crr;
     pit_detail::DwPair dw;
     if (job && crr <= 4 && pit_detail::plan_dw_pair(*job, 4, &dw)) {
         const int n_dw = dw.n1 + dw.n2;
         dim3 gridw((unsigned)(n_rows + n_cols + n_dw));
-#define PIT_SBW(NH_, CRR_, CRC_) hipLaunchKernelGGL((posatt_sparse_bwd_dw_kernel<NH_, CRR_, CRC_>), gridw, block, DW_SMEM_4WAVES, s, a, sp, (int)n_cols, (int)cgx, (int)rgx, rblocks, n_dw, dw)
-#define PIT_SBW_C(NH_, CRR_) do { if (crc == CRR_) PIT_SBW(NH_, CRR_, CRR_); else PIT_SBW(NH_, CRR_, 1); } while (0)
-#define PIT_SBW_CR(NH_) do { if (crr == 4) PIT_SBW_C(NH_, 4); else if (crr == 2) PIT_SBW_C(NH_, 2); else PIT_SBW(NH_, 1, 1); } while (0)
-        if (nh == 2) PIT_SBW_CR(2); else PIT_SBW_CR(1);
-#undef PIT_SBW_CR
-#undef PIT_SBW_C
-#undef PIT_SBW
+        with_int<2, 1>(nh, [&](auto NH) { with_int<4, 2, 1>(crr, [&](auto CRR) { with_bool(same, [&](auto SAME) {
+            constexpr int CRC = SAME() ? CRR() : 1;
+            hipLaunchKernelGGL((posatt_sparse_bwd_dw_kernel<NH(), CRR(), CRC>), gridw, block, DW_SMEM_4WAVES, s, a, sp, (int)n_cols, (int)cgx, (int)rgx, rblocks, n_dw, dw);
+        }); }); });
         *rider_done = true;
         pit_rider_note(PIT_RIDER_SPARSE_PAIR);
         pit_att_note(PIT_ATT_LIST_PAIR_DW);
         pit_att_note_last(PIT_ATT_LAST_PAIR, nh * 10000 + crr * 100 + (crr == 1 ? 1 : crc));
-        if (!complete) {
-            hipLaunchKernelGGL(posatt_sparse_overflow_cols, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a, sp);
-            pit_att_note(PIT_ATT_LIST_OVERFLOW);
-        }
+        overflow();
         return true;
     }
-#define PIT_SB(NH_, CRR_, CRC_) hipLaunchKernelGGL((posatt_sparse_bwd_kernel<NH_, CRR_, CRC_>), grid, block, 0, s, a, sp, (int)n_cols, (int)cgx, (int)rgx, rblocks)
-#define PIT_SB16(NH_, CRR_) hipLaunchKernelGGL((posatt_sparse_bwd_kernel<NH_, CRR_, CRR_, true>), grid, block, 0, s, a, sp, (int)n_cols, (int)cgx, (int)rgx, rblocks)
-#define PIT_SB_C(NH_, CRR_) do { if (a.dout16) PIT_SB16(NH_, CRR_); else if (crc == CRR_) PIT_SB(NH_, CRR_, CRR_); else PIT_SB(NH_, CRR_, 1); } while (0)
-#define PIT_SB_CR(NH_) do { if (crr == 8) PIT_SB_C(NH_, 8); else if (crr == 4) PIT_SB_C(NH_, 4); else if (crr == 2) PIT_SB_C(NH_, 2); else PIT_SB(NH_, 1, 1); } while (0)
-    if (nh == 2) PIT_SB_CR(2); else PIT_SB_CR(1);
-#undef PIT_SB_CR
-#undef PIT_SB_C
-#undef PIT_SB16
-#undef PIT_SB
+    with_int<2, 1>(nh, [&](auto NH) { with_int<8, 4, 2, 1>(crr, [&](auto CRR) { with_bool(same, [&](auto SAME) { with_bool(a.dout16, [&](auto D16) {
+        constexpr int CRC = SAME() ? CRR() : 1;
+        if constexpr (!(D16() && (!SAME() || CRR() == 1)))          // (bf16 d_out: column pairs, crc == crr >= 2)
+            hipLaunchKernelGGL((posatt_sparse_bwd_kernel<NH(), CRR(), CRC, D16()>), grid, block, 0, s, a, sp, (int)n_cols, (int)cgx, (int)rgx, rblocks);
+        else no_instance("posatt_sparse_bwd_kernel");
+    }); }); }); });
     pit_att_note(a.dout16 ? PIT_ATT_LIST_PAIR_D16 : PIT_ATT_LIST_PAIR);
     pit_att_note_last(PIT_ATT_LAST_PAIR, nh * 10000 + crr * 100 + (crr == 1 ? 1 : crc));
-    if (!complete) {
-        hipLaunchKernelGGL(posatt_sparse_overflow_cols, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a, sp);
-        pit_att_note(PIT_ATT_LIST_OVERFLOW);
-    }
+    overflow();
     return true;
 }
 
@@ -3221,23 +3169,14 @@ void launch_sparse_cols(const AttArgs& a, const SparseArgs& sp, bool complete, h
     const int cr = a.dout16 ? std::max(2, cr_for(a.ncols, keys)) : cr_for(a.ncols, keys);
     dim3 grid((unsigned)((keys + 3) / 4), (a.ncols + 64 * cr - 1) / (64 * cr)), block(256);
     const long xtotal = 8L * grid.x * ((grid.y + 7) / 8);
-    const bool remap = grid.y >= 16 && xtotal < 0x7fffffffL && !env_int("PIT_NO_XCD_REMAP");   // (few blocks: padding costs more than locality gains)
-#define PIT_SC(CR_)                                                                                                   \
-    do {                                                                                                              \
-        if (remap) hipLaunchKernelGGL((posatt_sparse_cols_x<CR_>), dim3((unsigned)xtotal), block, 0, s, a, sp,        \
-                                      (int)grid.x, (int)grid.y);                                                      \
-        else hipLaunchKernelGGL((posatt_sparse_cols<CR_>), grid, block, 0, s, a, sp);                                 \
-    } while (0)
-#define PIT_SC16(CR_)                                                                                                 \
-    do {                                                                                                              \
-        if (remap) hipLaunchKernelGGL((posatt_sparse_cols_x<CR_, true>), dim3((unsigned)xtotal), block, 0, s, a, sp,  \
-                                      (int)grid.x, (int)grid.y);                                                      \
-        else hipLaunchKernelGGL((posatt_sparse_cols<CR_, true>), grid, block, 0, s, a, sp);                           \
-    } while (0)
-    if (a.dout16) { if (cr == 8) PIT_SC16(8); else if (cr == 4) PIT_SC16(4); else PIT_SC16(2); }
-    else if (cr == 8) PIT_SC(8); else if (cr == 4) PIT_SC(4); else if (cr == 2) PIT_SC(2); else PIT_SC(1);
-#undef PIT_SC16
-#undef PIT_SC
+    const bool remap = grid.y >= 16 && xtotal < 0x7fffffffL && !exp_int("PIT_NO_XCD_REMAP");   // (few blocks: padding costs more than locality gains)
+    with_int<8, 4, 2, 1>(cr, [&](auto CR) { with_bool(a.dout16, [&](auto D16) {
+        if constexpr (!(D16() && CR() == 1)) {                      // (bf16 d_out: column pairs)
+            if (remap) hipLaunchKernelGGL((posatt_sparse_cols_x<CR(), D16()>), dim3((unsigned)xtotal), block, 0, s, a, sp,
+                                          (int)grid.x, (int)grid.y);
+            else hipLaunchKernelGGL((posatt_sparse_cols<CR(), D16()>), grid, block, 0, s, a, sp);
+        } else no_instance("posatt_sparse_cols");
+    }); });
     if (a.dout16) pit_att_note(PIT_ATT_LIST_COLS_D16);
     if (remap) pit_att_note(PIT_ATT_LIST_COLS_X);
     if (!a.dout16 && !remap) pit_att_note(PIT_ATT_LIST_COLS);
@@ -3294,43 +3233,18 @@ int fill_pre(AttArgs& a, int n_pts, int n_head, int dim, int batch, const float*
     a.no_fast_loads = env_int("PIT_NO_FAST_LOADS");
     return 0;
 }
-// grid of posatt_rows_tiles for this shape (as launch_rows chooses it); false = the shape is not in the tiles regime
+// the rows / cols launch of such a layer (fill_pre: mesh_batch 1, nothing masked); false = the shape is not in the tiles regime
 template <int MODE>
-bool launch_rows_pre(AttArgs& a, hipStream_t s) {
-    const bool bf = (MODE == 0) && a.bf16 != 0;
-    const int n_tiles = (a.n_out + 31) / 32;
-    const long work = (long)n_tiles * a.n_head * ((a.ncols + 31) / 32) * ((a.n_in + 1) / 2);
-    int rt = 4;
-    while (rt > 1 && (n_tiles < rt || (long)((n_tiles + rt - 1) / rt) * a.n_head * ((a.ncols + 255) / 256) < 256)) rt >>= 1;
-    const int tpwg0 = tiles_per_wg_for(a.ncols, (long)((n_tiles + rt - 1) / rt) * a.n_head, work, 1);
-    if (!tpwg0) return false;
-    int tpwg = tpwg0;
-    if (rt == 4) tpwg = 8;
-    else if (rt == 2 && tpwg > 16) tpwg = 16;
-    a.tiles_per_wg = tpwg;
-    a.colgroups = ((a.ncols + 31) / 32 + tpwg - 1) / tpwg;
-    dim3 grid(a.colgroups, a.n_head, (n_tiles + rt - 1) / rt), block(512);
-#define PIT_RTP(RT_, TPW_) do { if (bf) hipLaunchKernelGGL((posatt_rows_tiles<RT_, TPW_, MODE, false, (MODE == 0), true>), grid, block, 0, s, a); \
-                                else hipLaunchKernelGGL((posatt_rows_tiles<RT_, TPW_, MODE, false, false, true>), grid, block, 0, s, a); } while (0)
-    if (rt == 4) PIT_RTP(4, 1);
-    else if (rt == 2) { if (tpwg == 16) PIT_RTP(2, 2); else PIT_RTP(2, 1); }
-    else { if (tpwg == 32) PIT_RTP(1, 4); else if (tpwg == 16) PIT_RTP(1, 2); else PIT_RTP(1, 1); }
-#undef PIT_RTP
+bool launch_rows_pre(const AttArgs& a, hipStream_t s) {
+    const TilesRegime r = rows_tiles_regime(a.ncols, (a.n_out + 31) / 32, a.n_head, 1, a.n_in);
+    if (!r.tpwg) return false;
+    launch_rows_tiles<MODE>(a, r, true, s);
     return true;
 }
-bool launch_cols_pre(AttArgs& a, hipStream_t s) {
-    const bool bf = a.bf16 != 0;
-    const int j_tiles = (a.n_in + 31) / 32;
-    const long work = (long)j_tiles * ((a.ncols + 31) / 32) * ((a.n_out + 1) / 2) * a.n_head;
-    const int tpwg = tiles_per_wg_for(a.ncols, (long)j_tiles, work, 1);
+bool launch_cols_pre(const AttArgs& a, hipStream_t s) {
+    const int tpwg = cols_tiles_regime(a.ncols, (a.n_in + 31) / 32, a.n_head, 1, a.n_out);
     if (!tpwg) return false;
-    a.tiles_per_wg = tpwg;
-    a.colgroups = ((a.ncols + 31) / 32 + tpwg - 1) / tpwg;
-    dim3 grid(a.colgroups, j_tiles, 1), block(512);
-#define PIT_CTP(TPW_) do { if (bf) hipLaunchKernelGGL((posatt_cols_tiles<TPW_, false, true, true>), grid, block, 0, s, a); \
-                           else hipLaunchKernelGGL((posatt_cols_tiles<TPW_, false, false, true>), grid, block, 0, s, a); } while (0)
-    if (tpwg == 32) PIT_CTP(4); else if (tpwg == 16) PIT_CTP(2); else PIT_CTP(1);
-#undef PIT_CTP
+    launch_cols_tiles(a, tpwg, true, s);
     return true;
 }
 
@@ -3338,16 +3252,13 @@ bool launch_cols_pre(AttArgs& a, hipStream_t s) {
 
 // include/pit_hip.h: 1 when pit_posatt_pre_fwd / _bwd run this shape (the large regime of a batch-free self-attention layer)
 extern "C" int pit_posatt_pre_supported(int n_pts, int n_head, int dim, int batch) {
-    static const bool off = getenv("PIT_NO_PRE_WEIGHTS") != nullptr;        // (diagnostic switch, read once)
+    static const bool off = exp_env("PIT_NO_PRE_WEIGHTS") != nullptr;       // (diagnostic switch, read once)
     if (n_pts <= 0 || n_head <= 0 || dim <= 0 || batch <= 0 || off) return 0;
     const long ncols = (long)batch * dim;
     if (ncols > 0x7fffffffL || n_pts % 4 != 0 || n_pts > 2048) return 0;          // (E and Q: n_head * n_pts^2 floats per layer)
     const int n_tiles = (n_pts + 31) / 32;
-    int rt = 4;
-    while (rt > 1 && (n_tiles < rt || (long)((n_tiles + rt - 1) / rt) * n_head * ((ncols + 255) / 256) < 256)) rt >>= 1;
-    const long work = (long)n_tiles * n_head * ((ncols + 31) / 32) * ((n_pts + 1) / 2);
-    return tiles_per_wg_for((int)ncols, (long)((n_tiles + rt - 1) / rt) * n_head, work, 1) != 0 &&
-           tiles_per_wg_for((int)ncols, (long)n_tiles, work, 1) != 0;
+    return rows_tiles_regime((int)ncols, n_tiles, n_head, 1, n_pts).tpwg != 0 &&
+           cols_tiles_regime((int)ncols, n_tiles, n_head, 1, n_pts) != 0;
 }
 
 extern "C" int pit_posatt_pre_fwd(const float* e, const float* rowstat, int n_pts, int n_head, int dim, int batch,

@@ -17,7 +17,8 @@ weight gradients between modes 5e-7 (both rel-L2 against (a)), the doubled pass 
 
 Shapes: the lower edges of the support predicates - the 20 x 20 <-> 16 x 16 jittered pair of test_gpu_fused_envelope (PAIRS / UNIONS)
 for the edge launches, the fold and the candidate-list layers, 256 latent points x batch 2 x two blocks for the fused processor, 64
-points x hid 256 for the bf16 dense self-attention, the smallest shapes pit_posatt_pre_supported takes for _PosAttPre."""
+points x hid 256 for the bf16 dense self-attention, the smallest shapes pit_posatt_pre_supported takes for _PosAttPre, and
+the two at which its rows launch takes two and four row tiles per workgroup."""
 import contextlib
 
 import pytest
@@ -137,6 +138,17 @@ def pre_two_heads():
 def pre_one_head():
     """One head: 1024 points, hid 128, batch 8."""
     return _pre((32, 32), 1, 128, 8)
+
+
+def pre_rt2():
+    """Two 32-row tiles per workgroup (the two cases above run one): 1024 points, two heads, hid 256, batch 8 = 2048 columns - the
+    regime rule (csrc/pit_posatt.hip: rows_tiles_regime) gives rt = 2 with 8 column tiles per workgroup."""
+    return _pre((32, 32), 2, 256, 8)
+
+
+def pre_rt4():
+    """Four row tiles per workgroup: the same layer at batch 16 = 4096 columns - rt = 4, 8 column tiles per workgroup."""
+    return _pre((32, 32), 2, 256, 16)
 
 
 # --------------------------------------------------------------------------- _Processor
@@ -288,7 +300,7 @@ def mlp_one_call():
                 torch.randn(2, 50, 3, generator=g), "_MlpBackward", _mlp_entries(False), (0, 0, 0))
 
 
-CASES = [posatt_lists, posatt_satt, posatt_union, pre_two_heads, pre_one_head, processor, decoder_lmda, decoder_scale, fold_lmda,
+CASES = [posatt_lists, posatt_satt, posatt_union, pre_two_heads, pre_one_head, pre_rt2, pre_rt4, processor, decoder_lmda, decoder_scale, fold_lmda,
          fold_scale, encoder_lmda, encoder_scale, encoder_one_head, mlp_small_rider, mlp_wide_rider, mlp_one_call]
 
 
