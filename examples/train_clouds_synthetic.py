@@ -7,7 +7,11 @@ Adam (ddp.FlatAdam(zero_grads=True)).
 
 The step is captured once for the padded width; every batch then brings its own point counts through
 ``set_batch(..., len_in=...)`` - the lengths live in a static device tensor the kernels read, so no replay waits for the
-host.  The evaluation metric is the reference's for clouds, RelMaxNorm (train_elasticity.py:118), over the real points only."""
+host.  The evaluation metric is the reference's for clouds, RelMaxNorm (train_elasticity.py:118), over the real points only.
+
+After every epoch a held-out set of ragged batches is evaluated through one captured graph (engine.EvalStep with lengths): both
+metrics add up on the device, the last batch is only partly filled (``n_valid``), and ``result()`` is the pass's one
+synchronisation."""
 import argparse
 import os
 import sys
@@ -18,7 +22,7 @@ import torch  # noqa: E402
 
 from position_induced_transformer_amd import tasks  # noqa: E402
 from position_induced_transformer_amd.ddp import FlatAdam, FlatGradients  # noqa: E402
-from position_induced_transformer_amd.engine import TrainStep  # noqa: E402
+from position_induced_transformer_amd.engine import EvalStep, TrainStep  # noqa: E402
 from position_induced_transformer_amd.utils import RelMaxNorm, count_params  # noqa: E402
 
 
@@ -50,6 +54,13 @@ def main():
     step = TrainStep(model, (mesh, func, mesh, target), 1, 2, optimizer=opt, flat=flat, len_in=lens)
     step.capture()
     metric = RelMaxNorm(1)
+    # the held-out set: nbatches // 4 + 1 batches, the last of which holds batch // 2 clouds only
+    held_out = list(batches(args.nbatches // 4 + 1, args.batch, args.width, seed=99))
+    last_valid = max(1, args.batch // 2)
+    n_test = (len(held_out) - 1) * args.batch + last_valid
+    emesh = mesh.clone()                                             # (static buffers of its own; queries = the clouds themselves)
+    evaluate = EvalStep(model, (emesh, func.clone(), emesh, target.clone()), 1, 2, capacity=n_test, len_in=lens.clone())
+    evaluate.capture()
     for ep in range(args.epochs):
         t1 = default_timer()
         train_l2 = torch.zeros((), device="cuda")
@@ -62,7 +73,13 @@ def main():
         torch.cuda.synchronize()
         t2 = default_timer()
         n = args.nbatches * args.batch
-        print(ep, f"{t2 - t1:.3f}s", "rel-L2", float(train_l2) / n, "rel-max", float(train_max) / n)
+        evaluate.reset()
+        for i, (m, f, t, _, lengths) in enumerate(held_out):
+            evaluate.set_batch(f, t, mesh_in=m, len_in=lengths, n_valid=last_valid if i == len(held_out) - 1 else args.batch)
+            evaluate.replay()
+        test = evaluate.result()                                     # the pass's only synchronisation
+        print(ep, f"{t2 - t1:.3f}s", "rel-L2", float(train_l2) / n, "rel-max", float(train_max) / n,
+              "| test rel-L2", test.rel_lp / test.count, "rel-max", test.rel_max / test.count, "samples", test.count)
 
 
 if __name__ == "__main__":

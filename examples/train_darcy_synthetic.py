@@ -6,7 +6,11 @@ forward, Adam + CosineAnnealingLR, RelLpNorm - but importing the MI355X modules 
     python examples/train_darcy_synthetic.py [--epochs 2] [--graph]
 
 `--graph` replaces the inner loop by the hipGraph-captured step (engine.TrainStep) with the
-fused Adam; without it the loop is literally the reference's eager loop."""
+fused Adam; without it the loop is literally the reference's eager loop.
+
+After every epoch a held-out synthetic set is evaluated as train_darcy.py:136-144 does, through one captured
+graph per batch (engine.EvalStep): the errors add up on the device, the last batch is only partly filled
+(``n_valid``), and ``result()`` is the one synchronisation of the pass."""
 import argparse
 import os
 import sys
@@ -39,6 +43,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--ntrain", type=int, default=256)
+    ap.add_argument("--ntest", type=int, default=100)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--graph", action="store_true")
     args = ap.parse_args()
@@ -46,10 +51,14 @@ def main():
     s = 43
     # synthetic "dataset": smooth random coefficient fields and a fixed smoothing of them as targets
     x_train = torch.randn(args.ntrain, s, s, 1)  # noqa: F405
+    x_test = torch.randn(args.ntest, s, s, 1)  # noqa: F405
     k = torch.ones(1, 1, 5, 5) / 25.0  # noqa: F405
     y_train = torch.nn.functional.conv2d(x_train.permute(0, 3, 1, 2), k, padding=2).permute(0, 2, 3, 1)  # noqa: F405
+    y_test = torch.nn.functional.conv2d(x_test.permute(0, 3, 1, 2), k, padding=2).permute(0, 2, 3, 1)  # noqa: F405
     x_normalizer = PixelWiseNormalization(x_train)  # noqa: F405
     x_train = x_normalizer.normalize(x_train)
+    x_test = x_normalizer.normalize(x_test).cuda()
+    y_test = y_test.cuda()
     y_normalizer = PixelWiseNormalization(y_train)  # noqa: F405
     mesh, mesh_ltt = grid(s), grid(16)
     loader = torch.utils.data.DataLoader(torch.utils.data.TensorDataset(x_train, y_train),  # noqa: F405
@@ -73,6 +82,12 @@ def main():
         optimizer = torch.optim.Adam(model.parameters(), lr=1e-3)  # noqa: F405
         scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=iterations)  # noqa: F405
 
+    # the evaluation pass (built after FlatGradients re-homed the parameters: the graph reads them where they live now)
+    from position_induced_transformer_amd.engine import EvalStep
+    evaluate = EvalStep(model, (mesh, x_test[:args.batch].clone(), mesh, y_test[:args.batch].clone()), 1, 2,
+                        pred_affine=y_normalizer.affine(), capacity=args.ntest)
+    evaluate.capture()
+
     for ep in range(args.epochs):
         model.train()
         t1 = default_timer()
@@ -94,7 +109,16 @@ def main():
                 train_l2 += loss.detach()
         torch.cuda.synchronize()  # noqa: F405
         t2 = default_timer()
-        print(ep, f"{t2 - t1:.3f}s", float(train_l2) / args.ntrain)
+        model.eval()
+        evaluate.reset()
+        for i in range(0, args.ntest, args.batch):
+            x, y = x_test[i:i + args.batch], y_test[i:i + args.batch]
+            evaluate.set_batch(x, y, n_valid=x.shape[0])              # (the last batch brings fewer rows)
+            evaluate.replay()
+        test = evaluate.result()                                      # the pass's only synchronisation
+        t3 = default_timer()
+        print(ep, f"{t2 - t1:.3f}s", float(train_l2) / args.ntrain, "| test", f"{t3 - t2:.3f}s", test.rel_lp / test.count,
+              "worst sample", test.worst_rel_lp)
     torch.save({"model_state": model.state_dict()}, "/tmp/model.pth")  # noqa: F405
 
 

@@ -964,6 +964,56 @@ int pit_rel_lp_loss_ragged_fwd_grad(const float* tru, const float* pred, const i
 int pit_rel_max_norm_ragged(const float* tru, const float* pred, const int* len, int batch, int npts, int nch, float* out,
                             void* stream);
 
+/* ---- The metrics of an evaluation pass, kept on the device (additions to ABI 31; csrc/pit_eval.hip) -------------------------------
+ * The reference scripts evaluate after every epoch: under no_grad they loop over the test loader and add
+ * myloss(y, out).item() per batch (train_darcy.py:136-144; train_vorticity.py:131-141 around a 20-step rollout, with the model
+ * output in the `true` slot, line 139), report utils.RelMaxNorm beside it (train_burgers.py:80, train_naca.py:132) and write each
+ * batch's prediction into pred[batch_size*i : ...] (train_darcy.py:167-177).  pit_eval_metrics is one launch per batch for all of
+ * that, with totals that live in `state` from launch to launch, so a pass needs ONE device->host copy at its end.  A library
+ * built from this header defines PIT_HAS_EVAL_METRICS; PIT_ABI_VERSION is unchanged (nothing that existed changed).
+ *
+ * tru / pred (batch, npts, nch) contiguous fp32; pred' = pred*pred_scale + pred_shift ((npts, nch) each, both or neither; two fp32
+ * roundings, as the loss kernels form it).  For every valid sample s and channel c, over the sample's first len[s] points:
+ *   ||tru - pred'||_p / ||tru||_p   (any integer p >= 1, as pit_rel_lp_loss_fwd)   and   max|tru - pred'| / max|tru|;
+ * their means over c are RelLp_s and RelMax_s (utils.py:59-98).  A zero denominator gets no special case (the reference has
+ * none); NaN in a real point propagates.
+ *   len        (batch) int32 on the device, clamped into [0, npts] where it is read; NULL = npts.  Padded points are never read.
+ *   n_valid    one int32 on the device, clamped into [0, batch]: samples s >= *n_valid are skipped - never read, no row written
+ *              (a last batch that is only partly filled).  NULL = batch.
+ *   state      PIT_EVAL_STATE_DOUBLES doubles on the device, zeroed by the caller to start a pass:
+ *                [0] += sum_s RelLp_s      [1] += sum_s RelMax_s      [2] = max(old, max_s RelLp_s)      [3] = max(old, max_s RelMax_s)
+ *                [4] the cursor: rows consumed so far (+= *n_valid when advance != 0)      [5] += 1 per launch      [6], [7] stay 0
+ *   per_sample optional table: row r = cursor + s at per_sample + r * ps_stride receives {RelLp_s, RelMax_s} (ps_stride >= 2)
+ *   pred_store optional: row r at pred_store + r * store_stride receives the sample's (npts, nch) values of pred', zeros in the
+ *              padded points (store_stride >= npts * nch)
+ *   advance    PIT_EVAL_ADVANCE (1): this launch moves the cursor on by *n_valid; 0: it stays (further launches of the same batch
+ *              follow, e.g. the steps of a rollout).  | PIT_EVAL_STORE_TRUE (2): pred_store receives the `tru` slot instead of
+ *              pred' - for callers that put the model output there (the argument order of train_vorticity.py:139).  Any other
+ *              bit: PIT_ERR_SIZE.
+ *   capacity   rows of the two optional outputs: rows r >= capacity are not written (nothing out of range is touched); the
+ *              totals still count them
+ *   workspace  pit_eval_metrics_workspace(batch, npts, nch) bytes, 8-byte aligned; its first word is the arrival ticket: zero
+ *              before the first call, left zero by every call (calls that share it must be stream-ordered)
+ * Every workgroup reads the cursor before it takes its ticket; the workgroup of the last ticket alone moves the cursor, after the
+ * finishing sums - so one launch per batch is all a captured graph needs.  A (sample, channel) series is split into 1, 2, 4, ...,
+ * PIT_EVAL_MAX_PARTS workgroups by a rule on (batch, npts, nch) alone (each part keeps >= 1024 points; no further split once 512
+ * workgroups exist); len and n_valid only switch work off.  Partial sums are fp64; the last arriver adds the parts in part order,
+ * the channels in channel order and the samples in index order: the same inputs and state give the same bits.  No host
+ * synchronisation, no allocation, capturable.
+ * PIT_ERR_NULL for a missing tru, pred, state or workspace, or one of pred_scale / pred_shift without the other; PIT_ERR_SIZE for
+ * batch <= 0, batch > 65535, npts <= 0, nch <= 0, p < 1, capacity < 0, an optional output with capacity == 0 or with a stride
+ * smaller than its row.  pit_eval_metrics_workspace returns PIT_ERR_SIZE for a non-positive size. */
+#define PIT_HAS_EVAL_METRICS 1
+#define PIT_EVAL_STATE_DOUBLES 8
+#define PIT_EVAL_MAX_PARTS 64
+#define PIT_EVAL_ADVANCE 1
+#define PIT_EVAL_STORE_TRUE 2
+long pit_eval_metrics_workspace(int batch, int npts, int nch);
+int pit_eval_metrics(const float* tru, const float* pred, const float* pred_scale, const float* pred_shift,
+                     const int* len, const int* n_valid, int batch, int npts, int nch, int p, double* state,
+                     float* per_sample, long ps_stride, float* pred_store, long store_stride, long capacity,
+                     int advance, void* workspace, void* stream);
+
 /* ---- The two slab forms of pit_block_fwd (additions to ABI 31; csrc/pit_block.hip) ------------------------------------------------
  * pit_block_fwd runs 16-row slabs, or - n_head = 2, n_pts = 256, the weights through LDS, and 8 * ceil(batch / 8) * n_pts / 8
  * workgroups no more than the device has CUs (batch <= 8 on MI355X) - 8-row slabs with the two heads stacked in the M dimension of

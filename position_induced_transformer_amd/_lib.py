@@ -184,6 +184,8 @@ SIGNATURES = {
     "pit_distlist_bwd_workspace": [_I, _I, _I, _I],
     "pit_distlist_bwd": _LIST + _BWD_DIST + [_P] + _SAVED_OUT + [_P] * 5 + _TAIL,            # ..., d_sqd, out ..., the transposed index, dv_workspace
     "pit_rel_max_norm": [_P, _P, _I, _I, _I, _P, _P, _P],
+    "pit_eval_metrics_workspace": [_I, _I, _I],
+    "pit_eval_metrics": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _L, _P, _L, _L, _I, _P, _P],
     "pit_instance_norm_fwd": [_P, _L, _L, _I, _I, _I, _F, _P, _P, _P],
     "pit_instance_norm_bwd": [_P, _P, _P, _I, _I, _I, _P, _P],
     "pit_adam_step": [_P, _P, _P, _P, _L, _P, _F, _F, _I, _F, _F, _F, _F, _I, _P, _P],
@@ -197,14 +199,18 @@ SIGNATURES = {
 }
 
 LONG_RETURN = {"pit_satt_tiles_elems", "pit_posatt_dmesh_workspace", "pit_mlp_bwd_params_ordered_workspace",
-               "pit_mlp_bwd_params_ordered_mfma_workspace", "pit_distmat_bwd_workspace", "pit_distlist_bwd_workspace"}
+               "pit_mlp_bwd_params_ordered_mfma_workspace", "pit_distmat_bwd_workspace", "pit_distlist_bwd_workspace",
+               "pit_eval_metrics_workspace"}
 # entries added to an ABI version after its first release (PIT_HAS_* in the header): a library of the same version built before
 # them lacks the symbols
 ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_workspace", "pit_distlist_bwd",
                "pit_rel_lp_loss_ragged_fwd_grad", "pit_rel_max_norm_ragged",       # PIT_HAS_DISTLIST, PIT_HAS_RAGGED_STEP
                "pit_block_fwd_set_form", "pit_block_fwd_last_rows",                # PIT_HAS_BLOCK_ROWS8
                "pit_block_bwd_last_riders",                                        # PIT_HAS_RIDER_TAIL
-               "pit_debug_att_counts"}                                             # PIT_HAS_ATT_COUNTS
+               "pit_debug_att_counts",                                             # PIT_HAS_ATT_COUNTS
+               "pit_eval_metrics_workspace", "pit_eval_metrics"}                   # PIT_HAS_EVAL_METRICS
+EVAL_STATE_DOUBLES = 8   # PIT_EVAL_STATE_DOUBLES
+EVAL_MAX_PARTS = 64      # PIT_EVAL_MAX_PARTS
 DISTLIST_CHUNK = 512   # PIT_DISTLIST_CHUNK
 
 

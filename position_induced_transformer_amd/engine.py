@@ -9,7 +9,7 @@ in one flat buffer (ddp.FlatGradients) so a data-parallel step is ONE all-reduce
 from __future__ import annotations
 
 import inspect
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
@@ -31,7 +31,104 @@ def early_gradient_parameters(model: torch.nn.Module):
     return params, mlps[mid - 1]
 
 
-class TrainStep:
+class _StaticBatch:
+    """What the captured steps of this module share: the static length tensors of a ragged batch, the copy of a new batch into
+    the static buffers, and the capture procedure.  Expects ``model``, ``mesh_in``, ``func_in``, ``mesh_out``, ``target``,
+    ``affine``, ``len_in``, ``len_out``, ``_len_loss`` and ``_len_kw`` on the object."""
+
+    def _init_lengths(self, len_in, len_out) -> None:
+        """The checks of a ragged step (before any launch) and its static length tensors."""
+        if self.affine is not None:
+            raise ValueError("pred_affine with lengths: a per-pixel affine has no meaning on ragged clouds")
+        if isinstance(self, (RolloutStep, RolloutEvalStep)):
+            raise ValueError("RolloutStep with lengths: the rollout runs on one fixed mesh")
+        params = inspect.signature(self.model.forward).parameters
+        any_kw = any(q.kind is inspect.Parameter.VAR_KEYWORD for q in params.values())
+        batch = self.func_in.shape[0]
+        for name, given in (("len_in", len_in), ("len_out", len_out)):
+            if given is None:
+                continue
+            if not any_kw and name not in params:
+                raise ValueError(f"{type(self.model).__name__}.forward does not accept the keyword {name}")
+            width = (self.mesh_in if name == "len_in" else self.mesh_out).shape[-2]
+            self._check_length_list(name, given, width)
+            t = ops.as_lengths(given, self.func_in.device, batch)      # (an int32 device tensor is used as it is)
+            setattr(self, name, t)
+            self._len_kw[name] = t
+        if self.len_out is not None:
+            self._len_loss = self.len_out
+        elif self.mesh_out is self.mesh_in or (self.mesh_out.data_ptr() == self.mesh_in.data_ptr()
+                                                and self.mesh_out.shape == self.mesh_in.shape):
+            self._len_loss = self.len_in
+
+    @staticmethod
+    def _check_length_list(name: str, lengths, width: int) -> None:
+        # a Python sequence is checked on the host; a tensor is taken as it is (a check would synchronise; the kernels clamp)
+        if not torch.is_tensor(lengths):
+            for n in lengths:
+                if not 1 <= int(n) <= width:
+                    raise ValueError(f"{name}: length {int(n)} outside [1, {width}]")
+
+    def _check_mesh_update(self, mesh_in, mesh_out) -> None:
+        if (mesh_in is not None or mesh_out is not None) and not getattr(self.model.down, "_batched", True):
+            raise ValueError("this model's meshes are batch-free (fixed): their selection plans were built once and "
+                             "are part of the captured step; only per-sample meshes can change between replays")
+
+    def _set_lengths(self, len_in, len_out) -> None:
+        for name, given in (("len_in", len_in), ("len_out", len_out)):
+            if given is None:
+                continue
+            static = getattr(self, name)
+            if static is None:
+                raise ValueError(f"set_batch({name}=...): this step was built without {name}")
+            self._check_length_list(name, given, (self.mesh_in if name == "len_in" else self.mesh_out).shape[-2])
+            static.copy_(ops.as_lengths(given, static.device, static.numel()))
+
+    def _capture_graph(self, warmup: int, collective: bool):
+        """Warm up (allocator, mesh-plan caches, the per-stream accumulators of ops) and capture ``self._step`` ON THE SAME
+        side stream: a workspace first requested during capture would be allocated - and zero-filled by a
+        captured memset on every replay - inside the graph.  Returns (graph, stream)."""
+        import position_induced_transformer_amd as _pkg
+        if not _pkg.GRAPH_PACKET_CAPTURE_OFF and getattr(getattr(self.model, "down", None), "_batched", False):
+            raise RuntimeError("this step builds per-sample selection plans inside the graph, which faults on replay with "
+                               "ROCm 7.2's hipGraph packet capture; DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 was not in effect "
+                               "when the HIP runtime started (import position_induced_transformer_amd, or export the "
+                               "variable, before the first .cuda() call) - run the step eagerly or restart")
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self._step()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        # A data-parallel step is captured in THREAD-LOCAL error mode, after the process group's watchdog has let go of
+        # the warm-up collectives.  That thread polls the events of every collective issued so far with hipEventQuery
+        # every 100 ms until it has seen them complete.  Under the default global mode HIP refuses the query while ANY
+        # stream captures ("operation not permitted when stream is capturing") and, in every mode, for an event whose
+        # stream has since JOINED a capture - as RCCL's internal stream does when the step's all-reduce is captured
+        # (tools/micro/capture_query_probe.py).  The watchdog rethrows and the process aborts: one capture in eight on
+        # MI355X, when a poll fell inside the capture window.  All work is complete after the synchronize above; a few
+        # poll periods later the watchdog's list is empty.  Launches from autograd's worker thread are still captured:
+        # the mode only decides whose unsafe calls are refused, not what the stream records.
+        mode = "global"
+        if collective:
+            mode = "thread_local"
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_backend() != "gloo":
+                # wait until the watchdog can have nothing left to poll: the last warm-up collective reports completion
+                # (bounded), then three of the watchdog's 100 ms periods for it to retire the entry
+                import time
+                work, t0 = getattr(self.flat, "last_work", None), time.monotonic()
+                while work is not None and not work.is_completed() and time.monotonic() - t0 < 5.0:
+                    time.sleep(0.005)
+                time.sleep(0.3)
+        with torch.cuda.graph(graph, stream=side, capture_error_mode=mode):
+            self._step()
+        return graph, side
+
+
+class TrainStep(_StaticBatch):
     def __init__(self, model: torch.nn.Module, batch: Sequence[torch.Tensor], out_dim: int, p: int,
                  pred_affine: Optional[Sequence[torch.Tensor]] = None, all_reduce: bool = False,
                  optimizer: Optional[torch.optim.Optimizer] = None, flat: Optional[FlatGradients] = None,
@@ -86,39 +183,6 @@ class TrainStep:
         self._seed = torch.ones((), device=self.func_in.device)      # d loss / d loss, allocated once
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._agree_early()                  # (a collective when the process group has more than one rank: every rank builds its step)
-
-    def _init_lengths(self, len_in, len_out) -> None:
-        """The checks of a ragged step (before any launch) and its static length tensors."""
-        if self.affine is not None:
-            raise ValueError("pred_affine with lengths: a per-pixel affine has no meaning on ragged clouds")
-        if isinstance(self, RolloutStep):
-            raise ValueError("RolloutStep with lengths: the rollout runs on one fixed mesh")
-        params = inspect.signature(self.model.forward).parameters
-        any_kw = any(q.kind is inspect.Parameter.VAR_KEYWORD for q in params.values())
-        batch = self.func_in.shape[0]
-        for name, given in (("len_in", len_in), ("len_out", len_out)):
-            if given is None:
-                continue
-            if not any_kw and name not in params:
-                raise ValueError(f"{type(self.model).__name__}.forward does not accept the keyword {name}")
-            width = (self.mesh_in if name == "len_in" else self.mesh_out).shape[-2]
-            self._check_length_list(name, given, width)
-            t = ops.as_lengths(given, self.func_in.device, batch)      # (an int32 device tensor is used as it is)
-            setattr(self, name, t)
-            self._len_kw[name] = t
-        if self.len_out is not None:
-            self._len_loss = self.len_out
-        elif self.mesh_out is self.mesh_in or (self.mesh_out.data_ptr() == self.mesh_in.data_ptr()
-                                                and self.mesh_out.shape == self.mesh_in.shape):
-            self._len_loss = self.len_in
-
-    @staticmethod
-    def _check_length_list(name: str, lengths, width: int) -> None:
-        # a Python sequence is checked on the host; a tensor is taken as it is (a check would synchronise; the kernels clamp)
-        if not torch.is_tensor(lengths):
-            for n in lengths:
-                if not 1 <= int(n) <= width:
-                    raise ValueError(f"{name}: length {int(n)} outside [1, {width}]")
 
     # two-bucket exchange: when the gradient of the marker module's output arrives, everything after it in the forward
     # has been back-propagated (launches enqueued) - fork the second stream there and reduce the early bucket on it
@@ -229,46 +293,8 @@ class TrainStep:
         self._step()
 
     def capture(self, warmup: int = 3) -> None:
-        """Warm up (allocator, mesh-plan caches, the per-stream accumulators of ops) and capture ON THE SAME
-        side stream: a workspace first requested during capture would be allocated - and zero-filled by a
-        captured memset on every replay - inside the graph."""
-        import position_induced_transformer_amd as _pkg
-        if not _pkg.GRAPH_PACKET_CAPTURE_OFF and getattr(getattr(self.model, "down", None), "_batched", False):
-            raise RuntimeError("this step builds per-sample selection plans inside the graph, which faults on replay with "
-                               "ROCm 7.2's hipGraph packet capture; DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 was not in effect "
-                               "when the HIP runtime started (import position_induced_transformer_amd, or export the "
-                               "variable, before the first .cuda() call) - run the step eagerly or restart")
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        # A data-parallel step is captured in THREAD-LOCAL error mode, after the process group's watchdog has let go of
-        # the warm-up collectives.  That thread polls the events of every collective issued so far with hipEventQuery
-        # every 100 ms until it has seen them complete.  Under the default global mode HIP refuses the query while ANY
-        # stream captures ("operation not permitted when stream is capturing") and, in every mode, for an event whose
-        # stream has since JOINED a capture - as RCCL's internal stream does when the step's all-reduce is captured
-        # (tools/micro/capture_query_probe.py).  The watchdog rethrows and the process aborts: one capture in eight on
-        # MI355X, when a poll fell inside the capture window.  All work is complete after the synchronize above; a few
-        # poll periods later the watchdog's list is empty.  Launches from autograd's worker thread are still captured:
-        # the mode only decides whose unsafe calls are refused, not what the stream records.
-        mode = "global"
-        if self.all_reduce:
-            mode = "thread_local"
-            import torch.distributed as dist
-            if dist.is_available() and dist.is_initialized() and dist.get_backend() != "gloo":
-                # wait until the watchdog can have nothing left to poll: the last warm-up collective reports completion
-                # (bounded), then three of the watchdog's 100 ms periods for it to retire the entry
-                import time
-                work, t0 = getattr(self.flat, "last_work", None), time.monotonic()
-                while work is not None and not work.is_completed() and time.monotonic() - t0 < 5.0:
-                    time.sleep(0.005)
-                time.sleep(0.3)
-        with torch.cuda.graph(graph, stream=side, capture_error_mode=mode):
-            self._step()
+        """Warm up and capture the step on one side stream (``_StaticBatch._capture_graph``)."""
+        graph, side = self._capture_graph(warmup, self.all_reduce)
         ops.assert_frozen_since_capture()     # route 'host': the graph must not update an lmda whose scale it baked in
         self.graph = graph
         self._capture_stream = side
@@ -287,17 +313,8 @@ class TrainStep:
         NACA, one copy serves both.)  ``len_in`` / ``len_out``: the new clouds' point counts, copied into the
         step's static length tensors; a list is range-checked here, a tensor is copied unchecked (a check would
         synchronise; the kernels clamp)."""
-        if (mesh_in is not None or mesh_out is not None) and not getattr(self.model.down, "_batched", True):
-            raise ValueError("this model's meshes are batch-free (fixed): their selection plans were built once and "
-                             "are part of the captured step; only per-sample meshes can change between replays")
-        for name, given in (("len_in", len_in), ("len_out", len_out)):
-            if given is None:
-                continue
-            static = getattr(self, name)
-            if static is None:
-                raise ValueError(f"set_batch({name}=...): this step was built without {name}")
-            self._check_length_list(name, given, (self.mesh_in if name == "len_in" else self.mesh_out).shape[-2])
-            static.copy_(ops.as_lengths(given, static.device, static.numel()))
+        self._check_mesh_update(mesh_in, mesh_out)
+        self._set_lengths(len_in, len_out)
         self.func_in.copy_(func_in)
         self.target.copy_(target)
         if mesh_in is not None and self.mesh_in.data_ptr() != self.func_in.data_ptr():
@@ -331,3 +348,202 @@ class RolloutStep(TrainStep):
             self.flat.all_reduce()
         if self.optimizer is not None:
             self.optimizer.step()
+
+
+# ---- the other half of the epoch: captured evaluation passes ----------------------------------------------------------------------
+class EvalResult(NamedTuple):
+    """What a pass reports: the SUMS of RelLpNorm / RelMaxNorm over the samples seen (the scripts divide by ntest,
+    train_darcy.py:144), the worst sample of each, and the number of samples."""
+    rel_lp: float
+    rel_max: float
+    worst_rel_lp: float
+    worst_rel_max: float
+    count: int
+
+
+def merge_eval_state(state: torch.Tensor, group=None) -> torch.Tensor:
+    """The evaluation state (ops.eval_metrics: 8 doubles) of every rank of ``group`` combined: the sums [0], [1], the cursor [4]
+    and the launch count [5] with SUM, the two worst values [2], [3] with MAX.  Returns a new tensor on ``state``'s device (which
+    must be one the group's backend reduces: CPU for gloo); without an initialised process group, a copy."""
+    import torch.distributed as dist
+    merged = state.detach().clone()
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return merged
+    worst = merged[2:4].clone()
+    dist.all_reduce(merged, op=dist.ReduceOp.SUM, group=group)
+    dist.all_reduce(worst, op=dist.ReduceOp.MAX, group=group)
+    merged[2:4] = worst
+    return merged
+
+
+class EvalStep(_StaticBatch):
+    """The evaluation loop of the reference scripts (train_darcy.py:136-144: model.eval(), no_grad, ``myloss(y, out).item()`` per
+    test batch) as ONE hipGraph per batch and ONE device->host copy per pass: forward, then one ops.eval_metrics launch that adds
+    RelLpNorm and RelMaxNorm of the batch to a state on the device, writes the per-sample errors and (``store_pred``) the
+    predictions at the pass's running row cursor.
+
+        step = EvalStep(model, (mesh_in, func_in, mesh_out, target), out_dim, p, capacity=ntest); step.capture()
+        step.reset()
+        for x, y in loader: step.set_batch(x, y, n_valid=len(x)); step.replay()
+        r = step.result()          # r.rel_lp / r.count: the script's test error
+
+    ``pred_is_true``: the model output goes into the metric's ``true`` slot (``myloss(out, y)``, train_vorticity.py:139).
+    ``len_in`` / ``len_out``: a ragged batch, as for TrainStep (the metric runs over the same lengths the loss would)."""
+
+    def __init__(self, model: torch.nn.Module, batch: Sequence[torch.Tensor], out_dim: int, p: int,
+                 pred_affine: Optional[Sequence[torch.Tensor]] = None, capacity: int = 0, store_pred: bool = False,
+                 pred_is_true: bool = False, len_in=None, len_out=None):
+        self.model = model
+        self.mesh_in, self.func_in, self.mesh_out, self.target = batch
+        self.out_dim, self.p = int(out_dim), int(p)
+        self.affine = pred_affine
+        self.pred_is_true = bool(pred_is_true)
+        if self.pred_is_true and pred_affine is not None:
+            raise ValueError("pred_affine with pred_is_true: the affine belongs to the metric's `pred` slot, which then holds the target")
+        self.capacity = int(capacity)
+        if self.capacity < 0:
+            raise ValueError("capacity must not be negative")
+        if store_pred and self.capacity == 0:
+            raise ValueError("store_pred needs a capacity (the rows of the result array)")
+        self.len_in = self.len_out = self._len_loss = None
+        self._len_kw = {}
+        if len_in is not None or len_out is not None:
+            self._init_lengths(len_in, len_out)
+        dev = self.func_in.device
+        self.batch = self.func_in.shape[0]
+        self.state = ops.new_eval_state(dev)
+        self.n_valid = torch.full((1,), self.batch, device=dev, dtype=torch.int32)
+        self._tables(store_pred)
+        self.out = None
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self._captured_params = None
+        self._captured_host_scales = None
+
+    def _npts(self) -> int:
+        return self.target.numel() // (self.batch * self.out_dim)
+
+    def _tables(self, store_pred: bool) -> None:
+        dev = self.func_in.device
+        self.per_sample = torch.zeros((self.capacity, 2), device=dev) if self.capacity else None
+        self.pred = torch.zeros((self.capacity, self._npts(), self.out_dim), device=dev) if store_pred else None
+
+    def _step(self) -> None:
+        with torch.no_grad():
+            out = self.model(self.mesh_in, self.func_in, self.mesh_out, **self._len_kw)
+            sc, sh = self.affine if self.affine is not None else (None, None)
+            true, pred = (out, self.target) if self.pred_is_true else (self.target, out)
+            ops.eval_metrics(true, pred, self.out_dim, self.p, self.state, sc, sh, lengths=self._len_loss, n_valid=self.n_valid,
+                             per_sample=self.per_sample, pred_store=self.pred, advance=True, store_true=self.pred_is_true)
+            self.out = out               # (the prediction of the last step / replay)
+
+    def run_eager(self) -> None:
+        self._step()
+
+    def capture(self, warmup: int = 3) -> None:
+        """``TrainStep.capture``'s procedure (``_StaticBatch._capture_graph``).  The warm-up passes move the state; ``reset()``
+        starts the pass.  What the graph depends on is recorded for ``reset()``: every parameter's address and - route 'host' -
+        the lmda versions whose host-evaluated scales were baked in."""
+        ops._STEP.cap_fresh = None        # the bf16 weight casts this graph needs are recorded in THIS graph
+        graph, side = self._capture_graph(warmup, False)
+        self._captured_host_scales = ([(lmda, version) for lmda, version in ops._HOSTC_CAPTURE["log"]], ops._PARAM_EPOCH[0])
+        ops.assert_frozen_since_capture()
+        self._captured_params = [(q, q.data_ptr()) for q in self.model.parameters()]
+        self.graph = graph
+        self._capture_stream = side
+        self._graph_out = self.out
+
+    def replay(self) -> None:
+        self.graph.replay()
+        self.out = self._graph_out        # (an eager run since the capture left its own tensor here)
+
+    def reset(self) -> None:
+        """Start a pass: zero the sums, the worst values and the cursor (no synchronisation; rows of ``per_sample`` / ``pred``
+        beyond a pass's count keep what earlier passes, the warm-up of ``capture`` among them, wrote).  Once per pass this is also the
+        check that the captured graph still evaluates the CURRENT model: it raises when a parameter no longer lives where the
+        graph reads it, and when the graph holds host-evaluated head scales (route 'host') of an lmda that changed since."""
+        if self.graph is not None:
+            for q, addr in self._captured_params:
+                if q.data_ptr() != addr:
+                    raise RuntimeError("EvalStep: a parameter was moved after the capture (a FlatGradients(flatten_params=True) built "
+                                       "later, .to(), a replaced .data): the graph still reads the old storage - capture again")
+            log, epoch = self._captured_host_scales
+            if log and (epoch != ops._PARAM_EPOCH[0] or any(lmda._version != version for lmda, version in log)):
+                raise RuntimeError("EvalStep: this graph was captured with head-scale route 'host' and holds the scales of the lmda "
+                                   "values of that moment; the parameters changed since (an optimizer step, a replayed training "
+                                   "graph, load_state_dict) - capture again, or capture with the 'device' route")
+        self.state.zero_()
+
+    def set_batch(self, func_in: torch.Tensor, target: torch.Tensor, mesh_in: Optional[torch.Tensor] = None,
+                  mesh_out: Optional[torch.Tensor] = None, len_in=None, len_out=None, n_valid: Optional[int] = None) -> None:
+        """``TrainStep.set_batch``, and ``n_valid``: how many samples of this batch count (an int in [0, batch], checked here;
+        it reaches the device as a fill of a static int32 scalar, no synchronisation; None = the whole batch).  The tensors of a
+        partly filled batch may have ``n_valid`` rows only: the other samples keep what they held and are never read by the
+        metric."""
+        n = self.batch if n_valid is None else int(n_valid)
+        if not 0 <= n <= self.batch:
+            raise ValueError(f"n_valid {n} outside [0, {self.batch}]")
+        self._check_mesh_update(mesh_in, mesh_out)
+        if len_in is not None and not torch.is_tensor(len_in) and len(len_in) == n < self.batch:
+            len_in = list(len_in) + [1] * (self.batch - n)
+        if len_out is not None and not torch.is_tensor(len_out) and len(len_out) == n < self.batch:
+            len_out = list(len_out) + [1] * (self.batch - n)
+        self._set_lengths(len_in, len_out)
+
+        def put(static, new):
+            if new.shape[0] == n < self.batch:
+                static[:n].copy_(new)
+            else:
+                static.copy_(new)
+        put(self.func_in, func_in)
+        put(self.target, target)
+        if mesh_in is not None and self.mesh_in.data_ptr() != self.func_in.data_ptr():
+            put(self.mesh_in, mesh_in)
+        if mesh_out is not None and self.mesh_out.data_ptr() != self.mesh_in.data_ptr():
+            put(self.mesh_out, mesh_out)
+        self.n_valid.fill_(n)
+
+    def result(self, all_reduce: bool = False) -> EvalResult:
+        """The pass so far: ONE device->host copy of the state (the only synchronisation of a pass).  ``all_reduce``: combined over
+        the ranks of the default process group (``merge_eval_state``)."""
+        state = self.state
+        if all_reduce:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                state = merge_eval_state(state.cpu() if dist.get_backend() == "gloo" else state)
+        host = state.cpu().tolist()
+        return EvalResult(host[0], host[1], host[2], host[3], int(round(host[4])))
+
+
+class RolloutEvalStep(EvalStep):
+    """The autoregressive evaluation loop of train_vorticity.py:133-141 as ONE hipGraph: ``steps`` forward passes under no_grad,
+    each prediction appended to the input history (tasks.rollout_loss), one ops.eval_metrics launch per step with the script's
+    argument order ``myloss(out, y_t)``; the last launch moves the cursor.  ``batch`` = (mesh, x, y) with x (b, .., memory) and
+    y (b, .., steps).  ``per_sample`` is (capacity, steps, 2), ``pred`` (capacity, steps, npts, out_dim); ``result()`` holds the
+    sums over steps and samples (the script divides by ntest * steps) and ``count`` the samples."""
+
+    def __init__(self, model, batch, steps: int, out_dim: int, p: int, capacity: int = 0, store_pred: bool = False):
+        mesh, x, y = batch
+        self.steps = int(steps)
+        if self.steps < 1:
+            raise ValueError("steps must be positive")
+        super().__init__(model, (mesh, x, mesh, y), out_dim, p, capacity=capacity, store_pred=store_pred, pred_is_true=True)
+
+    def _npts(self) -> int:
+        return self.target.numel() // (self.batch * self.out_dim * self.steps)
+
+    def _tables(self, store_pred: bool) -> None:
+        dev = self.func_in.device
+        self.per_sample = torch.zeros((self.capacity, self.steps, 2), device=dev) if self.capacity else None
+        self.pred = torch.zeros((self.capacity, self.steps, self._npts(), self.out_dim), device=dev) if store_pred else None
+
+    def _step(self) -> None:
+        with torch.no_grad():
+            x, y = self.func_in, self.target
+            for t in range(self.steps):
+                out = self.model(self.mesh_in, x, self.mesh_in)
+                ops.eval_metrics(out, y[..., t:t + 1], self.out_dim, self.p, self.state, n_valid=self.n_valid,
+                                 per_sample=self.per_sample[:, t] if self.per_sample is not None else None,
+                                 pred_store=self.pred[:, t] if self.pred is not None else None,
+                                 advance=(t == self.steps - 1), store_true=True)
+                x = torch.cat((x[..., 1:], out), dim=-1)
+            self.out = out

@@ -3339,6 +3339,92 @@ def rel_max_norm_ragged(true: torch.Tensor, pred: torch.Tensor, lengths, out_dim
     return out
 
 
+_EVAL_WS = {}              # (device index, stream) -> pit_eval_metrics' workspace (ticket word + slots; the ticket is zero between calls)
+EVAL_PARTS = (1, 2, 4, 8, 16, 32, 64)        # the dispatch instances of pit_eval_metrics: workgroups per (sample, channel) series
+
+
+def eval_parts(batch: int, npts: int, nch: int) -> int:
+    """The instance (one of EVAL_PARTS) pit_eval_metrics takes at this shape, read back from the library's workspace size."""
+    nbytes = _lib.lib().pit_eval_metrics_workspace(int(batch), int(npts), int(nch))
+    if nbytes < 0:
+        _lib.check(int(nbytes), "pit_eval_metrics_workspace")
+    return (nbytes - 16) // (32 * int(batch) * int(nch))
+
+
+def new_eval_state(device) -> torch.Tensor:
+    """The zeroed state of an evaluation pass (PIT_EVAL_STATE_DOUBLES doubles; see ``eval_metrics``)."""
+    return torch.zeros(_lib.EVAL_STATE_DOUBLES, device=device, dtype=torch.float64)
+
+
+@torch.compiler.disable
+def eval_metrics(true: torch.Tensor, pred: torch.Tensor, out_dim: int, p: int, state: torch.Tensor, pred_scale=None,
+                 pred_shift=None, lengths=None, n_valid=None, per_sample=None, pred_store=None, advance: bool = True,
+                 store_true: bool = False) -> None:
+    """One launch of pit_eval_metrics (include/pit_hip.h): RelLpNorm and RelMaxNorm (utils.py:59-98) of every valid sample over
+    its real points, added into ``state`` - 8 doubles on the device: [0] sum of RelLp, [1] sum of RelMax, [2] / [3] the worst of
+    each, [4] the cursor (samples consumed so far), [5] launches - with no host synchronisation.
+      lengths     per-sample point counts (``as_lengths``); padded points are never read
+      n_valid     an int32 device scalar: samples from there on are skipped (a partly filled last batch)
+      per_sample  (capacity, 2) fp32, last stride 1: row cursor + s receives {RelLp_s, RelMax_s}
+      pred_store  (capacity, npts, out_dim) fp32 with contiguous rows: row cursor + s receives pred' (zeros in padded points)
+      advance     this launch moves the cursor on by n_valid
+      store_true  ``pred_store`` receives ``true`` instead of pred' (callers that put the model output in the ``true`` slot)
+    Rows beyond the capacity are not written.  Forward only."""
+    _need_gpu(true, pred, pred_scale, pred_shift, per_sample, pred_store)
+    if torch.is_grad_enabled() and (true.requires_grad or pred.requires_grad):
+        raise NotImplementedError("eval_metrics is forward-only (the evaluation loops of the reference scripts run under "
+                                  "no_grad): call it under torch.no_grad() or on detached tensors")
+    if not state.is_cuda or state.dtype != torch.float64 or state.numel() != _lib.EVAL_STATE_DOUBLES or not state.is_contiguous():
+        raise RuntimeError(f"state must be {_lib.EVAL_STATE_DOUBLES} contiguous float64 values on the HIP device")
+    if (pred_scale is None) != (pred_shift is None):
+        raise ValueError("pred_scale and pred_shift go together")
+    b = true.size(0)
+    t = true.detach().reshape(b, -1, out_dim).contiguous()
+    q = pred.detach().reshape(b, -1, out_dim).contiguous()
+    if t.shape != q.shape:
+        raise RuntimeError(f"true {tuple(true.shape)} and pred {tuple(pred.shape)} do not match")
+    npts = t.shape[1]
+    sc = sh = None
+    if pred_scale is not None:
+        sc, sh = pred_scale.detach().contiguous(), pred_shift.detach().contiguous()
+        if sc.numel() != npts * out_dim or sh.numel() != npts * out_dim:
+            raise RuntimeError(f"pred_scale / pred_shift must hold (npts, out_dim) = ({npts}, {out_dim}) values")
+    if lengths is not None:
+        lengths = as_lengths(lengths, t.device, b)
+    if n_valid is not None and (not torch.is_tensor(n_valid) or not n_valid.is_cuda or n_valid.dtype != torch.int32
+                                or n_valid.numel() != 1):
+        raise RuntimeError("n_valid must be one int32 value on the HIP device")
+    capacity = 0
+    ps_stride = store_stride = 0
+    if per_sample is not None:
+        if per_sample.dim() != 2 or per_sample.shape[1] != 2 or per_sample.stride(1) != 1 or per_sample.shape[0] < 1:
+            raise RuntimeError("per_sample must be a (capacity, 2) tensor whose rows are contiguous")
+        capacity, ps_stride = per_sample.shape[0], per_sample.stride(0)
+    if pred_store is not None:
+        row = pred_store[0] if pred_store.dim() == 3 and pred_store.shape[0] > 0 else None
+        if row is None or tuple(row.shape) != (npts, out_dim) or not row.is_contiguous():
+            raise RuntimeError(f"pred_store must be a (capacity, {npts}, {out_dim}) tensor whose rows are contiguous")
+        if per_sample is not None and pred_store.shape[0] != capacity:
+            raise RuntimeError("per_sample and pred_store must have the same number of rows")
+        capacity, store_stride = pred_store.shape[0], pred_store.stride(0)
+    nbytes = _lib.lib().pit_eval_metrics_workspace(b, npts, out_dim)
+    if nbytes < 0:
+        _lib.check(int(nbytes), "pit_eval_metrics_workspace")
+    wkey = _ws_key(t.device)
+    ws = _EVAL_WS.get(wkey)
+    if ws is None or ws.numel() * 8 < nbytes:
+        # (a larger shape on this stream: a new zeroed buffer; the old one stays with whatever graph pinned it)
+        ws = _EVAL_WS[wkey] = torch.zeros((nbytes + 7) // 8, device=t.device, dtype=torch.float64)
+    if _capturing():
+        _pin(*[o for o in (ws, lengths, n_valid, sc, sh) if o is not None])
+    rc = _lib.lib().pit_eval_metrics(t.data_ptr(), q.data_ptr(), _lib.ptr(sc), _lib.ptr(sh), _lib.ptr(lengths), _lib.ptr(n_valid),
+                                     b, npts, out_dim, int(p), state.data_ptr(), _lib.ptr(per_sample), ps_stride,
+                                     _lib.ptr(pred_store), store_stride, capacity,
+                                     (1 if advance else 0) | (2 if store_true else 0), ws.data_ptr(),
+                                     _lib.stream_ptr())
+    _lib.check(rc, "pit_eval_metrics")
+
+
 class _InstanceNorm(torch.autograd.Function):
     """nn.InstanceNorm1d over the point axis on the (batch, points, channels) layout
     (train_vorticity.py:43,56,59), no permutes."""
