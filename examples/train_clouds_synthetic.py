@@ -3,7 +3,7 @@
 latent mesh shared by the batch) on synthetic ragged batches (tasks.ragged_clouds), engine.TrainStep with lengths and the fused
 Adam (ddp.FlatAdam(zero_grads=True)).
 
-    python examples/train_clouds_synthetic.py [--epochs 2] [--width 972]
+    python examples/train_clouds_synthetic.py [--epochs 2] [--width 972] [--feed]
 
 The step is captured once for the padded width; every batch then brings its own point counts through
 ``set_batch(..., len_in=...)`` - the lengths live in a static device tensor the kernels read, so no replay waits for the
@@ -11,7 +11,11 @@ host.  The evaluation metric is the reference's for clouds, RelMaxNorm (train_el
 
 After every epoch a held-out set of ragged batches is evaluated through one captured graph (engine.EvalStep with lengths): both
 metrics add up on the device, the last batch is only partly filled (``n_valid``), and ``result()`` is the pass's one
-synchronisation."""
+synchronisation.
+
+`--feed`: the clouds, their functions, targets and lengths stay on the device as one dataset, and the captured steps gather
+their own shuffled batches from it (engine.DeviceFeed: meshes, functions, targets and the int32 lengths in one launch at the head
+of the graph); an epoch is `steps_per_epoch` bare replays."""
 import argparse
 import os
 import sys
@@ -22,7 +26,7 @@ import torch  # noqa: E402
 
 from position_induced_transformer_amd import tasks  # noqa: E402
 from position_induced_transformer_amd.ddp import FlatAdam, FlatGradients  # noqa: E402
-from position_induced_transformer_amd.engine import EvalStep, TrainStep  # noqa: E402
+from position_induced_transformer_amd.engine import DeviceFeed, EvalStep, TrainStep  # noqa: E402
 from position_induced_transformer_amd.utils import RelMaxNorm, count_params  # noqa: E402
 
 
@@ -34,6 +38,14 @@ def batches(n_batches, batch, width, seed):
         yield tasks.ragged_clouds(lengths, width, seed=seed * 1000 + i, device="cuda") + (lengths,)
 
 
+def dataset(parts, last_rows=None):
+    """The batches of ``parts`` as one dataset on the device (the last one cut to ``last_rows`` clouds): the fields of a feed."""
+    parts = list(parts)
+    rows = [len(p[0]) for p in parts[:-1]] + [last_rows or len(parts[-1][0])]
+    cat = [torch.cat([p[k][:r] for p, r in zip(parts, rows)]).contiguous() for k in range(4)]
+    return {"mesh_in": cat[0], "func_in": cat[1], "target": cat[2], "len_in": cat[3]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--epochs", type=int, default=2)
@@ -41,6 +53,7 @@ def main():
     ap.add_argument("--batch", type=int, default=10)
     ap.add_argument("--width", type=int, default=972)
     ap.add_argument("--hid", type=int, default=64)
+    ap.add_argument("--feed", action="store_true", help="device-resident data feed inside the captured steps")
     args = ap.parse_args()
     torch.manual_seed(0)
     mesh_ltt = tasks.grid_mesh_2d(16, True, "cuda").reshape(-1, 2)
@@ -52,6 +65,8 @@ def main():
     # the static buffers of the captured step: the first batch, the query points are the clouds themselves
     mesh, func, target, lens, _ = next(batches(1, args.batch, args.width, seed=1))
     step = TrainStep(model, (mesh, func, mesh, target), 1, 2, optimizer=opt, flat=flat, len_in=lens)
+    if args.feed:
+        feed = DeviceFeed(step, dataset(batches(args.nbatches, args.batch, args.width, seed=2)), shuffle=True, seed=0)
     step.capture()
     metric = RelMaxNorm(1)
     # the held-out set: nbatches // 4 + 1 batches, the last of which holds batch // 2 clouds only
@@ -60,23 +75,35 @@ def main():
     n_test = (len(held_out) - 1) * args.batch + last_valid
     emesh = mesh.clone()                                             # (static buffers of its own; queries = the clouds themselves)
     evaluate = EvalStep(model, (emesh, func.clone(), emesh, target.clone()), 1, 2, capacity=n_test, len_in=lens.clone())
+    if args.feed:
+        test_feed = DeviceFeed(evaluate, dataset(held_out, last_valid), shuffle=False, drop_last=False)
     evaluate.capture()
     for ep in range(args.epochs):
         t1 = default_timer()
         train_l2 = torch.zeros((), device="cuda")
         train_max = torch.zeros((), device="cuda")
-        for m, f, t, _, lengths in batches(args.nbatches, args.batch, args.width, seed=2 + ep):
-            step.set_batch(f, t, mesh_in=m, len_in=lengths)          # new clouds, new sizes, the same graph
-            step.replay()
-            train_l2 += step.loss
-            train_max += metric(step.target, step.out, step.len_in)  # the prediction of the replay, real points only
+        if args.feed:
+            for _ in range(feed.steps_per_epoch):
+                step.replay()                                        # the feed's launch is the first of the graph
+                train_l2 += step.loss
+                train_max += metric(step.target, step.out, step.len_in)
+        else:
+            for m, f, t, _, lengths in batches(args.nbatches, args.batch, args.width, seed=2 + ep):
+                step.set_batch(f, t, mesh_in=m, len_in=lengths)      # new clouds, new sizes, the same graph
+                step.replay()
+                train_l2 += step.loss
+                train_max += metric(step.target, step.out, step.len_in)      # the prediction of the replay, real points only
         torch.cuda.synchronize()
         t2 = default_timer()
         n = args.nbatches * args.batch
-        evaluate.reset()
-        for i, (m, f, t, _, lengths) in enumerate(held_out):
-            evaluate.set_batch(f, t, mesh_in=m, len_in=lengths, n_valid=last_valid if i == len(held_out) - 1 else args.batch)
-            evaluate.replay()
+        evaluate.reset()                                             # (also sends an attached feed back to its first batch)
+        if args.feed:
+            for _ in range(test_feed.steps_per_epoch):               # (the feed writes n_valid for the last batch)
+                evaluate.replay()
+        else:
+            for i, (m, f, t, _, lengths) in enumerate(held_out):
+                evaluate.set_batch(f, t, mesh_in=m, len_in=lengths, n_valid=last_valid if i == len(held_out) - 1 else args.batch)
+                evaluate.replay()
         test = evaluate.result()                                     # the pass's only synchronisation
         print(ep, f"{t2 - t1:.3f}s", "rel-L2", float(train_l2) / n, "rel-max", float(train_max) / n,
               "| test rel-L2", test.rel_lp / test.count, "rel-max", test.rel_max / test.count, "samples", test.count)

@@ -3,14 +3,18 @@
 way the reference writes it - `from pit import *`, `class pit_darcy(pit_fixed)` with its own
 forward, Adam + CosineAnnealingLR, RelLpNorm - but importing the MI355X modules instead.
 
-    python examples/train_darcy_synthetic.py [--epochs 2] [--graph]
+    python examples/train_darcy_synthetic.py [--epochs 2] [--graph | --feed]
 
 `--graph` replaces the inner loop by the hipGraph-captured step (engine.TrainStep) with the
 fused Adam; without it the loop is literally the reference's eager loop.
 
 After every epoch a held-out synthetic set is evaluated as train_darcy.py:136-144 does, through one captured
 graph per batch (engine.EvalStep): the errors add up on the device, the last batch is only partly filled
-(``n_valid``), and ``result()`` is the one synchronisation of the pass."""
+(``n_valid``), and ``result()`` is the one synchronisation of the pass.
+
+`--feed` (implies `--graph`) also keeps both datasets on the device and lets the captured steps fetch their own batches
+(engine.DeviceFeed): an epoch is `steps_per_epoch` bare replays - no loader, no `.cuda()`, no `set_batch` - with the shuffle
+done by the feed's keyed permutation, and the evaluation pass gets its `n_valid` from the feed."""
 import argparse
 import os
 import sys
@@ -46,7 +50,9 @@ def main():
     ap.add_argument("--ntest", type=int, default=100)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--graph", action="store_true")
+    ap.add_argument("--feed", action="store_true", help="device-resident data feed inside the captured steps (implies --graph)")
     args = ap.parse_args()
+    args.graph = args.graph or args.feed
     torch.manual_seed(0)  # noqa: F405
     s = 43
     # synthetic "dataset": smooth random coefficient fields and a fixed smoothing of them as targets
@@ -77,6 +83,9 @@ def main():
         x0, y0 = next(iter(loader))
         step = TrainStep(model, (mesh, x0.cuda(), mesh, y0.cuda()), 1, 2, pred_affine=y_normalizer.affine(),
                          optimizer=opt, flat=flat)
+        if args.feed:
+            from position_induced_transformer_amd.engine import DeviceFeed
+            feed = DeviceFeed(step, {"func_in": x_train.cuda(), "target": y_train.cuda()}, shuffle=True, seed=0)
         step.capture()
     else:
         optimizer = torch.optim.Adam(model.parameters(), lr=1e-3)  # noqa: F405
@@ -86,35 +95,46 @@ def main():
     from position_induced_transformer_amd.engine import EvalStep
     evaluate = EvalStep(model, (mesh, x_test[:args.batch].clone(), mesh, y_test[:args.batch].clone()), 1, 2,
                         pred_affine=y_normalizer.affine(), capacity=args.ntest)
+    if args.feed:
+        test_feed = DeviceFeed(evaluate, {"func_in": x_test, "target": y_test}, shuffle=False, drop_last=False)
     evaluate.capture()
 
     for ep in range(args.epochs):
         model.train()
         t1 = default_timer()
         train_l2 = torch.zeros((), device="cuda")  # noqa: F405
-        for x, y in loader:
-            x, y = x.cuda(), y.cuda()
-            if args.graph:
-                step.set_batch(x, y)
-                step.replay()
+        if args.feed:
+            for _ in range(feed.steps_per_epoch):
+                step.replay()                                         # the feed's launch is the first of the graph
                 train_l2 += step.loss
-            else:
-                optimizer.zero_grad()
-                out = model(mesh, x, mesh)
-                out = y_normalizer.denormalize(out)
-                loss = myloss(y, out)
-                loss.backward()
-                optimizer.step()
-                scheduler.step()
-                train_l2 += loss.detach()
+        else:
+            for x, y in loader:
+                x, y = x.cuda(), y.cuda()
+                if args.graph:
+                    step.set_batch(x, y)
+                    step.replay()
+                    train_l2 += step.loss
+                else:
+                    optimizer.zero_grad()
+                    out = model(mesh, x, mesh)
+                    out = y_normalizer.denormalize(out)
+                    loss = myloss(y, out)
+                    loss.backward()
+                    optimizer.step()
+                    scheduler.step()
+                    train_l2 += loss.detach()
         torch.cuda.synchronize()  # noqa: F405
         t2 = default_timer()
         model.eval()
-        evaluate.reset()
-        for i in range(0, args.ntest, args.batch):
-            x, y = x_test[i:i + args.batch], y_test[i:i + args.batch]
-            evaluate.set_batch(x, y, n_valid=x.shape[0])              # (the last batch brings fewer rows)
-            evaluate.replay()
+        evaluate.reset()                                              # (also sends an attached feed back to its first batch)
+        if args.feed:
+            for _ in range(test_feed.steps_per_epoch):                # (the feed writes n_valid for the last batch)
+                evaluate.replay()
+        else:
+            for i in range(0, args.ntest, args.batch):
+                x, y = x_test[i:i + args.batch], y_test[i:i + args.batch]
+                evaluate.set_batch(x, y, n_valid=x.shape[0])          # (the last batch brings fewer rows)
+                evaluate.replay()
         test = evaluate.result()                                      # the pass's only synchronisation
         t3 = default_timer()
         print(ep, f"{t2 - t1:.3f}s", float(train_l2) / args.ntrain, "| test", f"{t3 - t2:.3f}s", test.rel_lp / test.count,

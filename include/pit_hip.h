@@ -1014,6 +1014,50 @@ int pit_eval_metrics(const float* tru, const float* pred, const float* pred_scal
                      float* per_sample, long ps_stride, float* pred_store, long store_stride, long capacity,
                      int advance, void* workspace, void* stream);
 
+/* ---- The data feed of a captured step (an addition to ABI 31; csrc/pit_feed.hip) -------------------------------------------------
+ * The reference loops take every batch from a host DataLoader - shuffle=True over a TensorDataset - and move it to the device per
+ * step (train_darcy.py:98,124-126).  pit_batch_feed is one launch for all of that when the dataset lives in device
+ * memory: it picks the step's samples, gathers their rows into the step's static buffers and moves a cursor that lives on the
+ * device, so a captured step that begins with it walks through epochs by replays alone.  A library built from this header defines
+ * PIT_HAS_BATCH_FEED; PIT_ABI_VERSION is unchanged (nothing that existed changed).
+ *
+ *   src, dst, row_bytes   HOST arrays of n_fields entries (1..PIT_FEED_MAX_FIELDS), read by the call and passed to the kernel by
+ *              value: field f of the dataset is n_samples contiguous rows of row_bytes[f] bytes at src[f] (device memory), dst[f]
+ *              the static buffer of `batch` such rows.  row_bytes[f] is a positive multiple of 4 and both pointers are 4-byte
+ *              aligned: rows are copied as raw words (any dtype; NaN payloads survive).  src and dst must not overlap.
+ *   state      two long long on the device: [0] the cursor (feeds so far; a negative value counts as 0), [1] the arrival ticket:
+ *              zero before the first call, left zero by every call (calls that share it must be stream-ordered)
+ *   order      optional n_samples int32 on the device: the caller's sampler (takes precedence over shuffle)
+ *   indices    optional `batch` int32 on the device: the sample index behind every slot
+ *   n_valid    optional int32 on the device
+ * With S steps per epoch - floor(n_samples / (batch*world)) with drop_last, the ceiling without - and c = state[0]: epoch
+ * e = c / S, step i = c % S; slot s holds global position g = (i*world + rank)*batch + s and the sample
+ *   order[g % n_samples] clamped into [0, n_samples)      (order given: every address stays in bounds whatever it holds)
+ *   g % n_samples                                         (shuffle == 0)
+ *   feistel(n_samples, seed, e)(g % n_samples)            (otherwise)
+ * *n_valid = clamp(n_samples - (i*world + rank)*batch, 0, batch); positions past the end wrap, so every slot holds a real sample.
+ * The keyed permutation (uint32 arithmetic; engine.feed_order restates it on the host, bit for bit):
+ *   fmix(h): h ^= h>>16; h *= 0x85EBCA6B; h ^= h>>13; h *= 0xC2B2AE35; h ^= h>>16
+ *   bits = max(2, bit_length(n-1)); bits += bits & 1; half = bits/2; mask = (1<<half)-1
+ *   key[j] = fmix(seed_lo ^ fmix(seed_hi + 0x9E3779B9*(e+1) + j)), j = 0..3        (e mod 2^32)
+ *   x = g; do { L = x>>half; R = x&mask; for j in 0..3: (L, R) = (R, L ^ (fmix(R + key[j]) & mask)); x = (L<<half)|R; } while (x >= n)
+ * - four Feistel rounds with cycle walking (the domain is < 4n): a bijection for every n, but no match for a Fisher-Yates shuffle
+ * in quality; callers that want a particular sampler pass `order`.
+ * Every workgroup reads the cursor before it takes its ticket; the workgroup of the last ticket alone writes cursor + 1 and clears
+ * the ticket.  No host synchronisation, no allocation, capturable.
+ * PIT_ERR_NULL for a missing src, dst, row_bytes or state, or a null entry of src or dst; PIT_ERR_SIZE for n_fields outside
+ * 1..PIT_FEED_MAX_FIELDS, n_samples <= 0, batch <= 0, batch > 65535, world <= 0, rank outside [0, world), a row_bytes[f] that is
+ * not a positive multiple of 4, a src[f] or dst[f] that is not 4-byte aligned, drop_last with n_samples < batch*world (no full
+ * step), drop_last or shuffle not 0 or 1; PIT_ERR_UNSUPPORTED for n_samples > 2^31 - 1 and for a row_bytes[f] beyond
+ * PIT_FEED_MAX_ROW_BYTES (1 GiB: a row is addressed with 32-bit byte offsets).  All before any launch. */
+#define PIT_HAS_BATCH_FEED 1
+#define PIT_FEED_MAX_FIELDS 8
+#define PIT_FEED_MAX_ROW_BYTES (1L << 30)
+int pit_batch_feed(const void* const* src, void* const* dst, const long* row_bytes, int n_fields,
+                   long n_samples, int batch, int rank, int world, int drop_last, int shuffle,
+                   const int* order, long long seed, long long* state, int* indices, int* n_valid,
+                   void* stream);
+
 /* ---- The two slab forms of pit_block_fwd (additions to ABI 31; csrc/pit_block.hip) ------------------------------------------------
  * pit_block_fwd runs 16-row slabs, or - n_head = 2, n_pts = 256, the weights through LDS, and 8 * ceil(batch / 8) * n_pts / 8
  * workgroups no more than the device has CUs (batch <= 8 on MI355X) - 8-row slabs with the two heads stacked in the M dimension of

@@ -17,6 +17,7 @@ _P = ctypes.c_void_p
 _I = ctypes.c_int
 _L = ctypes.c_long
 _F = ctypes.c_float
+_LL = ctypes.c_longlong
 
 class MlpParamsJob(ctypes.Structure):
     """pit_mlp_params_job of include/pit_hip.h (the argument list of pit_mlp_bwd_params)."""
@@ -186,6 +187,7 @@ SIGNATURES = {
     "pit_rel_max_norm": [_P, _P, _I, _I, _I, _P, _P, _P],
     "pit_eval_metrics_workspace": [_I, _I, _I],
     "pit_eval_metrics": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _L, _P, _L, _L, _I, _P, _P],
+    "pit_batch_feed": [_P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _P, _LL, _P, _P, _P, _P],
     "pit_instance_norm_fwd": [_P, _L, _L, _I, _I, _I, _F, _P, _P, _P],
     "pit_instance_norm_bwd": [_P, _P, _P, _I, _I, _I, _P, _P],
     "pit_adam_step": [_P, _P, _P, _P, _L, _P, _F, _F, _I, _F, _F, _F, _F, _I, _P, _P],
@@ -208,7 +210,10 @@ ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_
                "pit_block_fwd_set_form", "pit_block_fwd_last_rows",                # PIT_HAS_BLOCK_ROWS8
                "pit_block_bwd_last_riders",                                        # PIT_HAS_RIDER_TAIL
                "pit_debug_att_counts",                                             # PIT_HAS_ATT_COUNTS
-               "pit_eval_metrics_workspace", "pit_eval_metrics"}                   # PIT_HAS_EVAL_METRICS
+               "pit_eval_metrics_workspace", "pit_eval_metrics",                   # PIT_HAS_EVAL_METRICS
+               "pit_batch_feed"}                                                   # PIT_HAS_BATCH_FEED
+FEED_MAX_FIELDS = 8      # PIT_FEED_MAX_FIELDS
+FEED_MAX_ROW_BYTES = 1 << 30     # PIT_FEED_MAX_ROW_BYTES
 EVAL_STATE_DOUBLES = 8   # PIT_EVAL_STATE_DOUBLES
 EVAL_MAX_PARTS = 64      # PIT_EVAL_MAX_PARTS
 DISTLIST_CHUNK = 512   # PIT_DISTLIST_CHUNK

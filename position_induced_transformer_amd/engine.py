@@ -36,6 +36,13 @@ class _StaticBatch:
     the static buffers, and the capture procedure.  Expects ``model``, ``mesh_in``, ``func_in``, ``mesh_out``, ``target``,
     ``affine``, ``len_in``, ``len_out``, ``_len_loss`` and ``_len_kw`` on the object."""
 
+    _feed = None         # a DeviceFeed attached to the step: its launch is the first of ``_step``, and ``set_batch`` is refused
+
+    def _refuse_set_batch_with_feed(self) -> None:
+        if self._feed is not None:
+            raise RuntimeError("set_batch on a step with a DeviceFeed attached: the feed's launch fills the static buffers at the "
+                               "head of every step - two sources for the same buffers")
+
     def _init_lengths(self, len_in, len_out) -> None:
         """The checks of a ragged step (before any launch) and its static length tensors."""
         if self.affine is not None:
@@ -95,10 +102,14 @@ class _StaticBatch:
                                "when the HIP runtime started (import position_induced_transformer_amd, or export the "
                                "variable, before the first .cuda() call) - run the step eagerly or restart")
         side = torch.cuda.Stream()
+        # (a feed's cursor is put back where it was before the warm-up passes: a device copy on either side of them)
+        cursor = self._feed.state.clone() if self._feed is not None else None
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(warmup):
                 self._step()
+            if cursor is not None:
+                self._feed.state.copy_(cursor)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
@@ -257,6 +268,8 @@ class TrainStep(_StaticBatch):
             self._reduce_early_bucket(None)
 
     def _step(self) -> None:
+        if self._feed is not None:
+            self._feed.launch()                  # the step's FIRST launch: this step's samples into the static buffers
         self._early_pending = False
         early = self._decide_early()             # (False: ONE all-reduce after the pass)
         self._early_ok = early
@@ -313,6 +326,7 @@ class TrainStep(_StaticBatch):
         NACA, one copy serves both.)  ``len_in`` / ``len_out``: the new clouds' point counts, copied into the
         step's static length tensors; a list is range-checked here, a tensor is copied unchecked (a check would
         synchronise; the kernels clamp)."""
+        self._refuse_set_batch_with_feed()
         self._check_mesh_update(mesh_in, mesh_out)
         self._set_lengths(len_in, len_out)
         self.func_in.copy_(func_in)
@@ -337,6 +351,8 @@ class RolloutStep(TrainStep):
 
     def _step(self) -> None:
         from .tasks import rollout_loss
+        if self._feed is not None:
+            self._feed.launch()
         clear = None if getattr(self.optimizer, "zero_grads", False) else self.flat.flat
         if clear is not None:
             clear.zero_()
@@ -428,6 +444,8 @@ class EvalStep(_StaticBatch):
         self.pred = torch.zeros((self.capacity, self._npts(), self.out_dim), device=dev) if store_pred else None
 
     def _step(self) -> None:
+        if self._feed is not None:
+            self._feed.launch()                  # (also writes ``n_valid`` for the pass's last, partly filled batch)
         with torch.no_grad():
             out = self.model(self.mesh_in, self.func_in, self.mesh_out, **self._len_kw)
             sc, sh = self.affine if self.affine is not None else (None, None)
@@ -458,7 +476,8 @@ class EvalStep(_StaticBatch):
 
     def reset(self) -> None:
         """Start a pass: zero the sums, the worst values and the cursor (no synchronisation; rows of ``per_sample`` / ``pred``
-        beyond a pass's count keep what earlier passes, the warm-up of ``capture`` among them, wrote).  Once per pass this is also the
+        beyond a pass's count keep what earlier passes, the warm-up of ``capture`` among them, wrote; an attached DeviceFeed is sent
+        back to position 0).  Once per pass this is also the
         check that the captured graph still evaluates the CURRENT model: it raises when a parameter no longer lives where the
         graph reads it, and when the graph holds host-evaluated head scales (route 'host') of an lmda that changed since."""
         if self.graph is not None:
@@ -472,6 +491,8 @@ class EvalStep(_StaticBatch):
                                    "values of that moment; the parameters changed since (an optimizer step, a replayed training "
                                    "graph, load_state_dict) - capture again, or capture with the 'device' route")
         self.state.zero_()
+        if self._feed is not None:
+            self._feed.seek(0)                   # (a device fill: the pass starts at the head of the dataset)
 
     def set_batch(self, func_in: torch.Tensor, target: torch.Tensor, mesh_in: Optional[torch.Tensor] = None,
                   mesh_out: Optional[torch.Tensor] = None, len_in=None, len_out=None, n_valid: Optional[int] = None) -> None:
@@ -479,6 +500,7 @@ class EvalStep(_StaticBatch):
         it reaches the device as a fill of a static int32 scalar, no synchronisation; None = the whole batch).  The tensors of a
         partly filled batch may have ``n_valid`` rows only: the other samples keep what they held and are never read by the
         metric."""
+        self._refuse_set_batch_with_feed()
         n = self.batch if n_valid is None else int(n_valid)
         if not 0 <= n <= self.batch:
             raise ValueError(f"n_valid {n} outside [0, {self.batch}]")
@@ -537,6 +559,8 @@ class RolloutEvalStep(EvalStep):
         self.pred = torch.zeros((self.capacity, self.steps, self._npts(), self.out_dim), device=dev) if store_pred else None
 
     def _step(self) -> None:
+        if self._feed is not None:
+            self._feed.launch()
         with torch.no_grad():
             x, y = self.func_in, self.target
             for t in range(self.steps):
@@ -547,3 +571,181 @@ class RolloutEvalStep(EvalStep):
                                  advance=(t == self.steps - 1), store_true=True)
                 x = torch.cat((x[..., 1:], out), dim=-1)
             self.out = out
+
+
+# ---- the data feed: the dataset on the device, the batch gathered inside the captured step ------------------------------------------
+_M32 = 0xFFFFFFFF
+_FEED_ORDERS = {}          # (n, seed, epoch) -> the permutation (a few epochs are kept; expected_indices asks again and again)
+
+
+def _fmix(h):
+    """fmix of include/pit_hip.h on uint32 values held in a uint64 numpy array (or an int)."""
+    h = h ^ (h >> 16)
+    h = (h * 0x85EBCA6B) & _M32
+    h = h ^ (h >> 13)
+    h = (h * 0xC2B2AE35) & _M32
+    return h ^ (h >> 16)
+
+
+def feed_order(n: int, seed: int, epoch: int) -> torch.Tensor:
+    """The keyed permutation of ``range(n)`` that pit_batch_feed applies in epoch ``epoch`` (include/pit_hip.h), restated on the
+    host bit for bit: entry g is the sample at position g of the epoch.  A LongTensor on the CPU; needs no GPU.  Four Feistel
+    rounds with cycle walking: a bijection for every n, not a Fisher-Yates shuffle in quality (pass ``order`` to DeviceFeed for
+    a sampler of your own)."""
+    import numpy as np
+    n, seed, epoch = int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & _M32
+    if n < 1:
+        raise ValueError("feed_order: n must be positive")
+    hit = _FEED_ORDERS.get((n, seed, epoch))
+    if hit is not None:
+        return hit.clone()
+    bits = max(2, (n - 1).bit_length())
+    bits += bits & 1
+    half = bits // 2
+    mask = (1 << half) - 1
+    lo, hi = seed & _M32, seed >> 32
+    keys = [_fmix(lo ^ _fmix((hi + 0x9E3779B9 * (epoch + 1) + j) & _M32)) for j in range(4)]
+    x = np.arange(n, dtype=np.uint64)
+    todo = np.arange(n)
+    while todo.size:                                                   # cycle walking: the entries still outside [0, n)
+        v = x[todo]
+        left, right = v >> np.uint64(half), v & np.uint64(mask)
+        for key in keys:
+            left, right = right, left ^ (_fmix((right + np.uint64(key)) & np.uint64(_M32)) & np.uint64(mask))
+        v = (left << np.uint64(half)) | right
+        x[todo] = v
+        todo = todo[v >= n]
+    out = torch.from_numpy(x.astype(np.int64))
+    if len(_FEED_ORDERS) >= 8:
+        _FEED_ORDERS.pop(next(iter(_FEED_ORDERS)))
+    _FEED_ORDERS[(n, seed, epoch)] = out
+    return out.clone()
+
+
+class DeviceFeed:
+    """The data loader of a captured step, on the device: the dataset lives in device memory, and ONE launch at the head of the
+    step (ops.batch_feed) picks the step's samples - this rank's shard of a keyed permutation of the current epoch
+    (``feed_order``), of the identity (``shuffle=False``) or of the caller's ``order`` - gathers their rows into the step's
+    static buffers and moves a cursor that lives on the device.  An epoch, or a whole run, is then
+
+        feed = DeviceFeed(step, {"func_in": x_train, "target": y_train}, seed=0); step.capture()
+        for _ in range(epochs * feed.steps_per_epoch): step.replay()
+
+    with no host data traffic and no synchronisation (the loop of train_darcy.py:98,124-126 without loader, ``.cuda()`` and
+    ``set_batch``).  ``data`` maps names of the step's static buffers (``FIELDS``) to device tensors with a leading sample axis;
+    two names whose static buffers share storage are one field (NACA's mesh_in / func_in: the rule of ``set_batch``) and must
+    bring the same tensor.  With
+    ``drop_last=False`` (evaluation steps only: they have ``n_valid``) the last step of an epoch is partly filled: the launch
+    writes the step's ``n_valid`` and fills the remaining slots with samples from the head of the order, so the forward never
+    reads garbage.  Data-parallel: global position ``(i * world_size + rank) * batch + s`` for slot s of step i, so the ranks of
+    one step hold disjoint runs of the same order.  Attach the feed BEFORE ``capture()``."""
+
+    FIELDS = ("func_in", "target", "mesh_in", "mesh_out", "len_in", "len_out")
+
+    def __init__(self, step, data, shuffle: bool = True, seed: int = 0, drop_last: bool = True, rank: Optional[int] = None,
+                 world_size: Optional[int] = None, order=None):
+        if getattr(step, "graph", None) is not None:
+            raise ValueError("DeviceFeed: this step has already been captured (its graph holds no feed launch); attach the feed first")
+        if getattr(step, "_feed", None) is not None:
+            raise ValueError("DeviceFeed: this step already has a feed")
+        unknown = [name for name in data if name not in self.FIELDS]
+        if unknown or not data:
+            raise ValueError(f"DeviceFeed: unknown field name(s) {unknown}; the step's static buffers are {', '.join(self.FIELDS)}")
+        try:
+            step._check_mesh_update(data.get("mesh_in"), data.get("mesh_out"))
+        except ValueError as e:
+            raise ValueError(f"DeviceFeed: {e}") from None
+        for name in ("len_in", "len_out"):
+            if name in data and getattr(step, name) is None:
+                raise ValueError(f"DeviceFeed: field {name} on a step that was built without {name}")
+        self.n_valid = getattr(step, "n_valid", None)
+        if not drop_last and self.n_valid is None:
+            raise ValueError(f"DeviceFeed: drop_last=False on a {type(step).__name__}: it has no n_valid, the samples that fill a "
+                             "partly filled last batch would enter the loss")
+        self.src, self.dst, self.names = [], [], []
+        n = None
+        for name in self.FIELDS:
+            if name not in data:
+                continue
+            t, static = data[name], getattr(step, name)
+            if not torch.is_tensor(t) or t.dim() < 1 or t.shape[0] < 1:
+                raise ValueError(f"DeviceFeed: field {name} must be a tensor with a leading sample axis")
+            if not static.is_contiguous() or not t.is_contiguous():
+                raise ValueError(f"DeviceFeed: field {name} and its static buffer must be contiguous")
+            if t.dtype != static.dtype or t.shape[1:] != static.shape[1:] or t.device != static.device:
+                raise ValueError(f"DeviceFeed: field {name} has rows {tuple(t.shape[1:])} {t.dtype} on {t.device}, the step's static "
+                                 f"buffer {tuple(static.shape[1:])} {static.dtype} on {static.device}")
+            if (static[0].numel() * static.element_size()) % 4 or static[0].numel() == 0:
+                raise ValueError(f"DeviceFeed: field {name}: rows are copied as whole 4-byte words")
+            if n is not None and t.shape[0] != n:
+                raise ValueError(f"DeviceFeed: field {name} has {t.shape[0]} samples, the fields before it {n}")
+            n = t.shape[0]
+            shared = [k for k, d in enumerate(self.dst) if static.data_ptr() == d.data_ptr()]
+            if shared:                                                 # shares its static buffer with a field already taken
+                if t.data_ptr() != self.src[shared[0]].data_ptr():
+                    raise ValueError(f"DeviceFeed: {name} and {self.names[shared[0]]} share one static buffer of the step but "
+                                     "bring different data; pass the same tensor for both (or one of them)")
+                continue
+            self.src.append(t)
+            self.dst.append(static)
+            self.names.append(name)
+        if len(self.src) > 8:
+            raise ValueError("DeviceFeed: at most 8 fields")
+        if rank is None or world_size is None:
+            import torch.distributed as dist
+            up = dist.is_available() and dist.is_initialized()
+            rank = (dist.get_rank() if up else 0) if rank is None else rank
+            world_size = (dist.get_world_size() if up else 1) if world_size is None else world_size
+        self.rank, self.world_size = int(rank), int(world_size)
+        if self.world_size < 1 or not 0 <= self.rank < self.world_size:
+            raise ValueError(f"DeviceFeed: rank {self.rank} outside [0, {self.world_size})")
+        self.n_samples, self.batch = int(n), int(self.dst[0].shape[0])
+        self.shuffle, self.seed, self.drop_last = bool(shuffle), int(seed), bool(drop_last)
+        per_step = self.batch * self.world_size
+        if self.drop_last and self.n_samples < per_step:
+            raise ValueError(f"DeviceFeed: drop_last with {self.n_samples} samples and {per_step} per step leaves no full step")
+        self.steps_per_epoch = self.n_samples // per_step if self.drop_last else -(-self.n_samples // per_step)
+        dev = self.dst[0].device
+        self.order = None
+        if order is not None:
+            order = torch.as_tensor(order)
+            if order.dim() != 1 or order.numel() != self.n_samples or order.is_floating_point():
+                raise ValueError(f"DeviceFeed: order must hold {self.n_samples} integer sample indices")
+            lim = torch.iinfo(torch.int32)
+            self.order = order.detach().to(torch.int64).clamp(lim.min, lim.max).to(device=dev, dtype=torch.int32).contiguous()
+        self._host_order = None                                        # (a host copy of ``order``, made by expected_indices)
+        self.state = ops.new_feed_state(dev)                           # the cursor and the arrival ticket
+        self.cursor = self.state[0]
+        self.indices = torch.zeros(self.batch, device=dev, dtype=torch.int32)
+        self.step = step
+        step._feed = self
+
+    def seek(self, k: int) -> None:
+        """The next launch is feed number ``k`` (epoch k // steps_per_epoch, step k % steps_per_epoch): a device fill, no
+        synchronisation."""
+        if int(k) < 0:
+            raise ValueError("seek: a feed position is not negative")
+        self.cursor.fill_(int(k))
+
+    def launch(self) -> None:
+        """One feed, eagerly (the steps call this as the first launch of their ``_step``)."""
+        ops.batch_feed(self.src, self.dst, self.state, self.rank, self.world_size, self.drop_last, self.shuffle, self.order,
+                       self.seed, self.indices, self.n_valid)
+
+    def expected_indices(self, cursor: int):
+        """(the sample index behind every slot, n_valid) of the launch at ``cursor`` for this rank, restated on the host
+        (``feed_order``); reads ``order`` back once when the feed has one."""
+        n, c = self.n_samples, max(int(cursor), 0)
+        epoch, i = divmod(c, self.steps_per_epoch)
+        first = (i * self.world_size + self.rank) * self.batch
+        pos = [(first + s) % n for s in range(self.batch)]
+        if self.order is not None:
+            if self._host_order is None:
+                self._host_order = self.order.cpu().tolist()
+            idx = [min(max(self._host_order[g], 0), n - 1) for g in pos]
+        elif not self.shuffle:
+            idx = pos
+        else:
+            perm = feed_order(n, self.seed, epoch)
+            idx = [int(perm[g]) for g in pos]
+        return idx, min(max(n - first, 0), self.batch)

@@ -3425,6 +3425,70 @@ def eval_metrics(true: torch.Tensor, pred: torch.Tensor, out_dim: int, p: int, s
     _lib.check(rc, "pit_eval_metrics")
 
 
+def new_feed_state(device) -> torch.Tensor:
+    """The state of a data feed (``batch_feed``): two int64 on the device, [0] the cursor, [1] the arrival ticket (stays zero)."""
+    return torch.zeros(2, device=device, dtype=torch.int64)
+
+
+@torch.compiler.disable
+def batch_feed(src, dst, state: torch.Tensor, rank: int = 0, world: int = 1, drop_last: bool = True, shuffle: bool = True,
+               order=None, seed: int = 0, indices=None, n_valid=None) -> None:
+    """One launch of pit_batch_feed (include/pit_hip.h): gather this step's samples from the dataset on the device into the
+    step's static buffers and move the cursor on, with no host synchronisation.
+      src, dst    sequences of 1..8 contiguous device tensors: ``src[f]`` (n_samples, ...) the dataset's field f, ``dst[f]``
+                  (batch, ...) its static buffer - the same dtype and the same row; any dtype whose rows are whole 4-byte words
+      state       ``new_feed_state``: [0] is the cursor (the number of feeds so far)
+      rank, world this rank's shard of the global batch of ``batch * world`` positions
+      order       n_samples int32 on the device: the caller's sampler (entries are clamped into range where they are read)
+      indices     (batch) int32 on the device: receives the sample index behind every slot
+      n_valid     one int32 on the device: receives how many of the slots lie before the end of the epoch
+    The sample of a slot: see the header; ``engine.feed_order`` restates the keyed permutation on the host."""
+    src, dst = list(src), list(dst)
+    if len(src) != len(dst) or not 1 <= len(src) <= _lib.FEED_MAX_FIELDS:
+        raise ValueError(f"batch_feed takes 1..{_lib.FEED_MAX_FIELDS} fields, each with a source and a destination")
+    for t in src + dst + [state, order, indices, n_valid]:
+        if t is not None and (not torch.is_tensor(t) or not t.is_cuda):
+            raise RuntimeError("position_induced_transformer_amd: the data feed runs on the HIP device only; "
+                               "got a CPU tensor (move the dataset and the step's buffers to 'cuda')")
+    n, batch = src[0].shape[0], dst[0].shape[0]
+    rows = []
+    for a, b in zip(src, dst):
+        if not a.is_contiguous() or not b.is_contiguous():
+            raise RuntimeError("batch_feed: every field and every static buffer must be contiguous")
+        if a.dtype != b.dtype or a.shape[1:] != b.shape[1:] or a.shape[0] != n or b.shape[0] != batch or a.dim() < 1:
+            raise RuntimeError(f"batch_feed: a field {tuple(a.shape)} {a.dtype} does not fit its static buffer {tuple(b.shape)} "
+                               f"{b.dtype} (same row, same dtype, {n} samples, {batch} slots)")
+        row = (a.numel() // max(n, 1)) * a.element_size()
+        if row <= 0 or row % 4 or a.data_ptr() % 4 or b.data_ptr() % 4:
+            raise RuntimeError(f"batch_feed: rows are copied as aligned 4-byte words; got a row of {row} bytes")
+        if row > _lib.FEED_MAX_ROW_BYTES:
+            raise RuntimeError(f"batch_feed: a row of {row} bytes is beyond PIT_FEED_MAX_ROW_BYTES ({_lib.FEED_MAX_ROW_BYTES})")
+        rows.append(row)
+    if state.dtype != torch.int64 or state.numel() != 2 or not state.is_contiguous():
+        raise RuntimeError("state must be 2 contiguous int64 values on the HIP device (new_feed_state)")
+    if order is not None and (order.dtype != torch.int32 or order.numel() != n or not order.is_contiguous()):
+        raise RuntimeError(f"order must be {n} contiguous int32 values on the HIP device")
+    if indices is not None and (indices.dtype != torch.int32 or indices.numel() != batch or not indices.is_contiguous()):
+        raise RuntimeError(f"indices must be {batch} contiguous int32 values on the HIP device")
+    if n_valid is not None and (n_valid.dtype != torch.int32 or n_valid.numel() != 1):
+        raise RuntimeError("n_valid must be one int32 value on the HIP device")
+    if _capturing():
+        _pin(*[o for o in src + dst + [state, order, indices, n_valid] if o is not None])
+    k = len(src)
+    src_a = (ctypes.c_void_p * k)(*[t.data_ptr() for t in src])
+    dst_a = (ctypes.c_void_p * k)(*[t.data_ptr() for t in dst])
+    row_a = (ctypes.c_long * k)(*rows)
+    seed = int(seed)
+    if not -(1 << 63) <= seed < (1 << 64):
+        raise ValueError("seed must fit 64 bits")
+    seed = seed - (1 << 64) if seed >= (1 << 63) else seed
+    rc = _lib.lib().pit_batch_feed(ctypes.cast(src_a, ctypes.c_void_p), ctypes.cast(dst_a, ctypes.c_void_p),
+                                   ctypes.cast(row_a, ctypes.c_void_p), k, n, batch, int(rank), int(world),
+                                   1 if drop_last else 0, 1 if shuffle else 0, _lib.ptr(order), seed, state.data_ptr(),
+                                   _lib.ptr(indices), _lib.ptr(n_valid), _lib.stream_ptr())
+    _lib.check(rc, "pit_batch_feed")
+
+
 class _InstanceNorm(torch.autograd.Function):
     """nn.InstanceNorm1d over the point axis on the (batch, points, channels) layout
     (train_vorticity.py:43,56,59), no permutes."""
