@@ -3,7 +3,7 @@
 latent mesh shared by the batch) on synthetic ragged batches (tasks.ragged_clouds), engine.TrainStep with lengths and the fused
 Adam (ddp.FlatAdam(zero_grads=True)).
 
-    python examples/train_clouds_synthetic.py [--epochs 2] [--width 972] [--feed]
+    python examples/train_clouds_synthetic.py [--epochs 2] [--width 972] [--feed] [--clip NORM]
 
 The step is captured once for the padded width; every batch then brings its own point counts through
 ``set_batch(..., len_in=...)`` - the lengths live in a static device tensor the kernels read, so no replay waits for the
@@ -15,7 +15,10 @@ synchronisation.
 
 `--feed`: the clouds, their functions, targets and lengths stay on the device as one dataset, and the captured steps gather
 their own shuffled batches from it (engine.DeviceFeed: meshes, functions, targets and the int32 lengths in one launch at the head
-of the graph); an epoch is `steps_per_epoch` bare replays."""
+of the graph); an epoch is `steps_per_epoch` bare replays.
+
+`--clip NORM`: the guarded step (ddp.GuardedAdam) instead of FlatAdam - the gradient's global norm clipped at NORM, updates with
+a non-finite gradient skipped, and the epoch's `step.health()` line printed (one read of the device state per epoch)."""
 import argparse
 import os
 import sys
@@ -25,7 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from position_induced_transformer_amd import tasks  # noqa: E402
-from position_induced_transformer_amd.ddp import FlatAdam, FlatGradients  # noqa: E402
+from position_induced_transformer_amd.ddp import FlatAdam, FlatGradients, GuardedAdam  # noqa: E402
 from position_induced_transformer_amd.engine import DeviceFeed, EvalStep, TrainStep  # noqa: E402
 from position_induced_transformer_amd.utils import RelMaxNorm, count_params  # noqa: E402
 
@@ -54,6 +57,8 @@ def main():
     ap.add_argument("--width", type=int, default=972)
     ap.add_argument("--hid", type=int, default=64)
     ap.add_argument("--feed", action="store_true", help="device-resident data feed inside the captured steps")
+    ap.add_argument("--clip", type=float, default=None, metavar="NORM",
+                    help="clip the gradient's global norm and skip non-finite updates inside the captured step")
     args = ap.parse_args()
     torch.manual_seed(0)
     mesh_ltt = tasks.grid_mesh_2d(16, True, "cuda").reshape(-1, 2)
@@ -61,13 +66,18 @@ def main():
     print("parameters:", count_params(model))
     iterations = args.epochs * args.nbatches
     flat = FlatGradients(model.parameters(), flatten_params=True)
-    opt = FlatAdam(flat, lr=1e-3, cosine_t_max=iterations, zero_grads=True)
+    if args.clip is not None:
+        opt = GuardedAdam(flat, lr=1e-3, cosine_t_max=iterations, zero_grads=True, max_grad_norm=args.clip)
+    else:
+        opt = FlatAdam(flat, lr=1e-3, cosine_t_max=iterations, zero_grads=True)
     # the static buffers of the captured step: the first batch, the query points are the clouds themselves
     mesh, func, target, lens, _ = next(batches(1, args.batch, args.width, seed=1))
     step = TrainStep(model, (mesh, func, mesh, target), 1, 2, optimizer=opt, flat=flat, len_in=lens)
     if args.feed:
         feed = DeviceFeed(step, dataset(batches(args.nbatches, args.batch, args.width, seed=2)), shuffle=True, seed=0)
     step.capture()
+    if args.clip is not None:
+        step.health(reset=True)                                      # (the warm-up passes of the capture are not this epoch's)
     metric = RelMaxNorm(1)
     # the held-out set: nbatches // 4 + 1 batches, the last of which holds batch // 2 clouds only
     held_out = list(batches(args.nbatches // 4 + 1, args.batch, args.width, seed=99))
@@ -107,6 +117,11 @@ def main():
         test = evaluate.result()                                     # the pass's only synchronisation
         print(ep, f"{t2 - t1:.3f}s", "rel-L2", float(train_l2) / n, "rel-max", float(train_max) / n,
               "| test rel-L2", test.rel_lp / test.count, "rel-max", test.rel_max / test.count, "samples", test.count)
+        if args.clip is not None:
+            h = step.health(reset=True)
+            print(f"   guard: applied {h.applied} skipped {h.skipped} clipped {h.clipped} of {h.calls}; largest norm {h.max_norm:.4g}, "
+                  f"last {h.norm:.4g} (coef {h.coef:.4g}); train loss per sample {h.mean_loss / args.batch:.6g} "
+                  f"({h.nonfinite_loss} not finite)")
 
 
 if __name__ == "__main__":

@@ -3,7 +3,7 @@
 way the reference writes it - `from pit import *`, `class pit_darcy(pit_fixed)` with its own
 forward, Adam + CosineAnnealingLR, RelLpNorm - but importing the MI355X modules instead.
 
-    python examples/train_darcy_synthetic.py [--epochs 2] [--graph | --feed]
+    python examples/train_darcy_synthetic.py [--epochs 2] [--graph | --feed] [--clip NORM]
 
 `--graph` replaces the inner loop by the hipGraph-captured step (engine.TrainStep) with the
 fused Adam; without it the loop is literally the reference's eager loop.
@@ -14,7 +14,11 @@ graph per batch (engine.EvalStep): the errors add up on the device, the last bat
 
 `--feed` (implies `--graph`) also keeps both datasets on the device and lets the captured steps fetch their own batches
 (engine.DeviceFeed): an epoch is `steps_per_epoch` bare replays - no loader, no `.cuda()`, no `set_batch` - with the shuffle
-done by the feed's keyed permutation, and the evaluation pass gets its `n_valid` from the feed."""
+done by the feed's keyed permutation, and the evaluation pass gets its `n_valid` from the feed.
+
+`--clip NORM` (implies `--graph`) puts the guarded step in the graph (ddp.GuardedAdam): the gradient's global norm is clipped
+at NORM, an update whose gradient is not finite is skipped, and the epoch's line of `step.health()` - steps applied, skipped and
+clipped, the largest norm, the mean training loss from the device accumulator - is printed after each epoch."""
 import argparse
 import os
 import sys
@@ -51,8 +55,10 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--feed", action="store_true", help="device-resident data feed inside the captured steps (implies --graph)")
+    ap.add_argument("--clip", type=float, default=None, metavar="NORM",
+                    help="clip the gradient's global norm and skip non-finite updates inside the captured step (implies --graph)")
     args = ap.parse_args()
-    args.graph = args.graph or args.feed
+    args.graph = args.graph or args.feed or args.clip is not None
     torch.manual_seed(0)  # noqa: F405
     s = 43
     # synthetic "dataset": smooth random coefficient fields and a fixed smoothing of them as targets
@@ -76,10 +82,13 @@ def main():
     y_normalizer.cuda()
 
     if args.graph:
-        from position_induced_transformer_amd.ddp import FlatAdam, FlatGradients
+        from position_induced_transformer_amd.ddp import FlatAdam, FlatGradients, GuardedAdam
         from position_induced_transformer_amd.engine import TrainStep
         flat = FlatGradients(model.parameters(), flatten_params=True)
-        opt = FlatAdam(flat, lr=1e-3, cosine_t_max=iterations)
+        if args.clip is not None:
+            opt = GuardedAdam(flat, lr=1e-3, cosine_t_max=iterations, max_grad_norm=args.clip)
+        else:
+            opt = FlatAdam(flat, lr=1e-3, cosine_t_max=iterations)
         x0, y0 = next(iter(loader))
         step = TrainStep(model, (mesh, x0.cuda(), mesh, y0.cuda()), 1, 2, pred_affine=y_normalizer.affine(),
                          optimizer=opt, flat=flat)
@@ -87,6 +96,8 @@ def main():
             from position_induced_transformer_amd.engine import DeviceFeed
             feed = DeviceFeed(step, {"func_in": x_train.cuda(), "target": y_train.cuda()}, shuffle=True, seed=0)
         step.capture()
+        if args.clip is not None:
+            step.health(reset=True)                                   # (the warm-up passes of the capture are not this epoch's)
     else:
         optimizer = torch.optim.Adam(model.parameters(), lr=1e-3)  # noqa: F405
         scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=iterations)  # noqa: F405
@@ -139,6 +150,11 @@ def main():
         t3 = default_timer()
         print(ep, f"{t2 - t1:.3f}s", float(train_l2) / args.ntrain, "| test", f"{t3 - t2:.3f}s", test.rel_lp / test.count,
               "worst sample", test.worst_rel_lp)
+        if args.clip is not None:
+            h = step.health(reset=True)                               # one read of the device state per epoch
+            print(f"   guard: applied {h.applied} skipped {h.skipped} clipped {h.clipped} of {h.calls}; largest norm {h.max_norm:.4g}, "
+                  f"last {h.norm:.4g} (coef {h.coef:.4g}); train loss per sample {h.mean_loss / args.batch:.6g} "
+                  f"({h.nonfinite_loss} not finite)")
     torch.save({"model_state": model.state_dict()}, "/tmp/model.pth")  # noqa: F405
 
 

@@ -1058,6 +1058,64 @@ int pit_batch_feed(const void* const* src, void* const* dst, const long* row_byt
                    const int* order, long long seed, long long* state, int* indices, int* n_valid,
                    void* stream);
 
+/* ---- The guarded optimizer step (an addition to ABI 31; csrc/pit_optim.hip) ------------------------------------------------------
+ * The reference loops run Adam behind CosineAnnealingLR and read loss.item() every step (train_darcy.py:115-116,131-134): a
+ * diverging run is seen on the host the moment it happens.  A captured step has no such look, and pit_adam_step consumes whatever
+ * gradient it is given.  pit_adam_step_guarded is that step with the look built in, in two launches on the caller's stream and
+ * no host round trip.  Beyond the reference: global-norm clipping (torch.nn.utils.clip_grad_norm_), skipping an update whose
+ * gradient is not finite, decoupled weight decay (torch.optim.AdamW), a linear warm-up in front of the cosine schedule, and the
+ * sum of the steps' losses kept on the device (the scripts' train_l2 += loss.item()).  A library built from this header defines
+ * PIT_HAS_GUARDED_ADAM; PIT_ABI_VERSION is unchanged (nothing that existed changed; pit_adam_step is as it was).
+ *
+ * Launch 1 (grad_sumsq_kernel) writes the sum of squares of the n gradients as P = pit_adam_guard_parts(n) fp64 partials: partial
+ * b covers the run [b * R, min(n, (b + 1) * R)), R = 1024 * ceil(n / (1024 * PIT_GUARD_MAX_PARTS)); every value is widened to fp64
+ * before it is squared (exact, and no overflow: 3e19 in every element has a finite norm), and every addition inside a run has a
+ * fixed place, so the partials have the same bits on every call.  16-byte loads when grads is 16-byte aligned, dwords
+ * otherwise (the same bits either way); nothing beyond element n - 1 enters the sum.
+ * Launch 2 (adam_step_guarded_kernel): every workgroup adds the P partials in index order and forms norm = sqrt(sum) and
+ *   coef = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1      (fp64, then rounded to fp32; max_norm = 0: clipping off).
+ * norm not finite: the call is SKIPPED - params, exp_avg, exp_avg_sq and *step keep their bits; with zero_grads the gradients
+ * are still cleared.  Otherwise pit_adam_step's arithmetic runs on g * coef with bias corrections from *step + 1:
+ *   decoupled = 1:  p *= fl32(1 - lr_t * weight_decay) in front of the update (AdamW)
+ *   decoupled = 0:  g * coef + weight_decay * p (the coupled decay of pit_adam_step, after the clip: torch's order of
+ *                   clip_grad_norm_ and Adam.step)
+ * Gradients that are kept (zero_grads = 0) stay unclipped in memory; the coefficient is reported in state.
+ * Two counters on the device, both zero before the first call: *calls counts every call, skipped ones included, and positions
+ * the schedule (scheduler.step() runs every iteration in the scripts); *step counts the applied updates and feeds the bias
+ * corrections.  The rate of call k = *calls + 1:
+ *   k <= warmup_steps:  lr0 * (warmup_start + (1 - warmup_start) * (k - 1) / warmup_steps)
+ *   otherwise:          pit_adam_step's cosine closed form at k - 1 - warmup_steps (lr0 when cosine_t_max == 0)
+ * in fp64, once per workgroup; with warmup_steps == 0 and no skipped call it has pit_adam_step's bits.  Every workgroup reads
+ * both counters before it takes its ticket (scalars[3]); the workgroup of the last ticket writes them back.
+ *   partials   PIT_GUARD_MAX_PARTS doubles of device scratch
+ *   state      PIT_GUARD_STATE_DOUBLES doubles on the device (the PIT_GUARD_* slots below), zero before the first call; the caller
+ *              may zero them between calls (statistics only: the schedule rests on *calls and *step)
+ *   scalars    4 floats, zero before the first call: lr_t of the call, the bias corrections of the last APPLIED update, the ticket
+ *   loss       optional device scalar (may be null): added to PIT_GUARD_LOSS_SUM by the last workgroup when it is finite and
+ *              counted either way; the skip decision rests on the norm alone
+ * PIT_ERR_NULL for a missing pointer other than loss; PIT_ERR_SIZE for n <= 0 and for grads off a 4-byte boundary;
+ * PIT_ERR_UNSUPPORTED for a negative or NaN max_norm, warmup_steps < 0, warmup_start outside [0, 1] (or NaN).  All before any
+ * launch.  No host synchronisation, no allocation, capturable. */
+#define PIT_HAS_GUARDED_ADAM 1
+#define PIT_GUARD_MAX_PARTS 256
+#define PIT_GUARD_STATE_DOUBLES 10
+#define PIT_GUARD_CALLS 0            /* calls since the state was last zeroed */
+#define PIT_GUARD_APPLIED 1          /* ... that updated the parameters */
+#define PIT_GUARD_SKIPPED 2          /* ... that were skipped (norm not finite) */
+#define PIT_GUARD_CLIPPED 3          /* ... applied with coef < 1 */
+#define PIT_GUARD_LAST_NORM 4        /* the norm of the last call */
+#define PIT_GUARD_MAX_NORM 5         /* the largest finite norm seen */
+#define PIT_GUARD_LAST_COEF 6        /* the coefficient of the last call (1 when it was skipped) */
+#define PIT_GUARD_LOSS_SUM 7         /* sum of the finite losses */
+#define PIT_GUARD_LOSS_FINITE 8      /* how many there were */
+#define PIT_GUARD_LOSS_NONFINITE 9   /* and how many were not finite */
+int pit_adam_guard_parts(long n);    /* P for n elements (1..PIT_GUARD_MAX_PARTS); PIT_ERR_SIZE for n <= 0 */
+int pit_adam_step_guarded(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long n, long long* step,
+                          long long* calls, float lr0, float eta_min, int cosine_t_max, int warmup_steps,
+                          double warmup_start, float beta1, float beta2, float eps, float weight_decay, int decoupled,
+                          double max_norm, int zero_grads, const float* loss, double* partials, double* state,
+                          float* scalars, void* stream);
+
 /* ---- The two slab forms of pit_block_fwd (additions to ABI 31; csrc/pit_block.hip) ------------------------------------------------
  * pit_block_fwd runs 16-row slabs, or - n_head = 2, n_pts = 256, the weights through LDS, and 8 * ceil(batch / 8) * n_pts / 8
  * workgroups no more than the device has CUs (batch <= 8 on MI355X) - 8-row slabs with the two heads stacked in the M dimension of

@@ -18,6 +18,7 @@ _I = ctypes.c_int
 _L = ctypes.c_long
 _F = ctypes.c_float
 _LL = ctypes.c_longlong
+_D = ctypes.c_double
 
 class MlpParamsJob(ctypes.Structure):
     """pit_mlp_params_job of include/pit_hip.h (the argument list of pit_mlp_bwd_params)."""
@@ -191,6 +192,8 @@ SIGNATURES = {
     "pit_instance_norm_fwd": [_P, _L, _L, _I, _I, _I, _F, _P, _P, _P],
     "pit_instance_norm_bwd": [_P, _P, _P, _I, _I, _I, _P, _P],
     "pit_adam_step": [_P, _P, _P, _P, _L, _P, _F, _F, _I, _F, _F, _F, _F, _I, _P, _P],
+    "pit_adam_guard_parts": [_L],
+    "pit_adam_step_guarded": [_P, _P, _P, _P, _L, _P, _P, _F, _F, _I, _I, _D, _F, _F, _F, _F, _I, _D, _I, _P, _P, _P, _P, _P],
     "pit_debug_mfma_tile": [_P, _P, _P, _P],
     "pit_debug_rider_counts": [_P, _I, _I],
     "pit_debug_gemm_counts": [_P, _I, _I],
@@ -211,7 +214,10 @@ ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_
                "pit_block_bwd_last_riders",                                        # PIT_HAS_RIDER_TAIL
                "pit_debug_att_counts",                                             # PIT_HAS_ATT_COUNTS
                "pit_eval_metrics_workspace", "pit_eval_metrics",                   # PIT_HAS_EVAL_METRICS
-               "pit_batch_feed"}                                                   # PIT_HAS_BATCH_FEED
+               "pit_batch_feed",                                                   # PIT_HAS_BATCH_FEED
+               "pit_adam_guard_parts", "pit_adam_step_guarded"}                    # PIT_HAS_GUARDED_ADAM
+GUARD_MAX_PARTS = 256    # PIT_GUARD_MAX_PARTS
+GUARD_STATE_DOUBLES = 10         # PIT_GUARD_STATE_DOUBLES
 FEED_MAX_FIELDS = 8      # PIT_FEED_MAX_FIELDS
 FEED_MAX_ROW_BYTES = 1 << 30     # PIT_FEED_MAX_ROW_BYTES
 EVAL_STATE_DOUBLES = 8   # PIT_EVAL_STATE_DOUBLES

@@ -55,7 +55,179 @@ __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, f
     }
 }
 
+// ---- the guarded step (include/pit_hip.h, pit_adam_step_guarded): two launches --------------------------------------------------
+constexpr int GUARD_T = 256;            // threads of both kernels
+static_assert(GUARD_T >= PIT_GUARD_MAX_PARTS, "one thread stages one partial");
+constexpr long GUARD_UNIT = 1024;       // a run is a whole number of these: one 16-byte group per thread
+
+__host__ __device__ inline long guard_run(long n) {
+    return GUARD_UNIT * ((n + GUARD_UNIT * PIT_GUARD_MAX_PARTS - 1) / (GUARD_UNIT * PIT_GUARD_MAX_PARTS));
+}
+
+// Launch 1: partials[b] = sum of g[i]^2 over run b, in fp64 (a square of an fp32 value is exact there and cannot overflow).
+// Thread t owns the groups of four consecutive elements number t, t + 256, ... of its workgroup's run and adds them in that
+// order, element by element; the wave sums run over the DPP lanes and thread 0 adds the four waves in order: the partition
+// and every order of addition depend on n alone, so do the bits.  A group is one 16-byte load when the base is 16-byte
+// aligned (run starts are multiples of 1024 elements) and the group ends inside the buffer, four guarded dwords otherwise -
+// the same elements in the same places either way.
+__global__ __launch_bounds__(GUARD_T) void grad_sumsq_kernel(const float* __restrict__ g, long n, long run, int vec,
+                                                             double* __restrict__ partials) {
+    __shared__ double s_w[GUARD_T / PIT_WAVE];
+    const int tid = threadIdx.x;
+    const long a = (long)blockIdx.x * run, b = min(n, a + run);
+    double acc = 0.0;
+    for (long e = a + 4L * tid; e < b; e += 4L * GUARD_T) {
+        float x[4];
+        if (vec && e + 4 <= b) {
+            const float4 q = *reinterpret_cast<const float4*>(g + e);
+            x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) x[j] = e + j < b ? g[e + j] : 0.0f;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double d = (double)x[j];
+            acc += d * d;
+        }
+    }
+    const double w = wave_sum_d(acc);
+    if ((tid & (PIT_WAVE - 1)) == 0) s_w[tid / PIT_WAVE] = w;
+    __syncthreads();
+    if (tid == 0) partials[blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+}
+
+// Launch 2: every workgroup adds the partials in index order (identical bits everywhere), decides from the norm alone and
+// either runs adam_step_kernel's arithmetic on g * coef or leaves parameters and moments alone.  Both counters - calls
+// (the schedule's position) and step (the applied updates behind the bias corrections) - are read by every workgroup
+// before its ticket; the workgroup of the last ticket writes them back together with the statistics.
+__global__ __launch_bounds__(GUARD_T) void adam_step_guarded_kernel(
+        float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n, long long* step,
+        long long* calls, float lr0, float eta_min, int t_max, int warmup_steps, double warmup_start, float beta1, float beta2,
+        float eps, float weight_decay, int decoupled, double max_norm, int zero_grads, const float* loss,
+        const double* __restrict__ partials, int parts, double* state, float* scalars) {
+    __shared__ double s_part[PIT_GUARD_MAX_PARTS];
+    __shared__ double s_norm;
+    __shared__ float s_sc[5];
+    __shared__ int s_skip;
+    const int tid = threadIdx.x;
+    const long long t = __hip_atomic_load(step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;      // this update, if applied
+    const long long k = __hip_atomic_load(calls, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;     // this call
+    if (tid < parts) s_part[tid] = partials[tid];
+    __syncthreads();
+    if (tid == 0) {
+        double sum = 0.0;
+        // index order (reading by eights with the loads in flight gained nothing: DESIGN section 20)
+        for (int i = 0; i < parts; ++i) sum += s_part[i];
+        const double norm = sqrt(sum);
+        const bool finite = norm <= 1.79769313486231570815e308;        // false for NaN and +inf
+        float coef = 1.0f;
+        if (finite && max_norm > 0.0) coef = (float)fmin(1.0, max_norm / (norm + 1e-6));       // clip_grad_norm_
+        float lr_t = lr0;
+        if (k <= (long long)warmup_steps) {
+            lr_t = (float)((double)lr0 * (warmup_start + (1.0 - warmup_start) * (double)(k - 1) / (double)warmup_steps));
+        } else if (t_max > 0) {
+            // adam_step_kernel's expression on the calls after the warm-up (warmup_steps = 0: the same bits)
+            const double ph = 3.14159265358979323846 * (double)(k - 1 - warmup_steps) / (double)t_max;
+            lr_t = (float)((double)eta_min + 0.5 * ((double)lr0 - (double)eta_min) * (1.0 + cos(ph)));
+        }
+        s_sc[0] = lr_t;
+        s_sc[1] = (float)(1.0 - pow((double)beta1, (double)t));
+        s_sc[2] = (float)(1.0 - pow((double)beta2, (double)t));
+        s_sc[3] = coef;
+        s_sc[4] = (float)(1.0 - (double)lr_t * (double)weight_decay);  // AdamW: p *= 1 - lr_t * wd
+        s_norm = norm;
+        s_skip = finite ? 0 : 1;
+    }
+    __syncthreads();
+    const float lr = s_sc[0], bc1 = s_sc[1], bc2 = s_sc[2], coef = s_sc[3], shrink = s_sc[4];
+    const bool skip = s_skip != 0;
+    const float step_size = lr / bc1;
+    const float inv_sqrt_bc2 = 1.0f / sqrtf(bc2);
+    const float wd_coupled = decoupled ? 0.0f : weight_decay;
+    const bool shrinks = decoupled && weight_decay != 0.0f;
+    if (skip) {
+        if (zero_grads)                 // (the non-finite values would live on in the accumulator)
+            for (long i = (long)blockIdx.x * blockDim.x + tid; i < n; i += (long)gridDim.x * blockDim.x) g[i] = 0.0f;
+    } else {
+        for (long i = (long)blockIdx.x * blockDim.x + tid; i < n; i += (long)gridDim.x * blockDim.x) {
+            float gi = g[i];
+            if (zero_grads) g[i] = 0.0f;
+            gi *= coef;                 // (x * 1.0f is x: an inert guard has adam_step_kernel's bits; the build contracts nothing)
+            float pi = p[i];
+            if (shrinks) pi *= shrink;
+            if (wd_coupled != 0.0f) gi += wd_coupled * pi;
+            const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
+            const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
+            m[i] = mi;
+            v[i] = vi;
+            const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;       // torch: (sqrt(v)/sqrt(bc2)) + eps
+            pi -= step_size * (mi / denom);
+            p[i] = pi;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned* ticket = reinterpret_cast<unsigned*>(scalars + 3);
+        if (atomicAdd(ticket, 1u) == gridDim.x - 1u) {                // every workgroup has read both counters by now
+            const double norm = s_norm;
+            __hip_atomic_store(calls, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            scalars[0] = lr;
+            state[PIT_GUARD_CALLS] += 1.0;
+            state[PIT_GUARD_LAST_NORM] = norm;
+            state[PIT_GUARD_LAST_COEF] = (double)coef;
+            if (skip) {
+                state[PIT_GUARD_SKIPPED] += 1.0;
+            } else {
+                __hip_atomic_store(step, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                scalars[1] = bc1; scalars[2] = bc2;
+                state[PIT_GUARD_APPLIED] += 1.0;
+                if (coef < 1.0f) state[PIT_GUARD_CLIPPED] += 1.0;
+                if (norm > state[PIT_GUARD_MAX_NORM]) state[PIT_GUARD_MAX_NORM] = norm;
+            }
+            if (loss) {
+                const float l = *loss;
+                if (fabsf(l) <= 3.40282346638528859812e38f) {
+                    state[PIT_GUARD_LOSS_SUM] += (double)l;
+                    state[PIT_GUARD_LOSS_FINITE] += 1.0;
+                } else {
+                    state[PIT_GUARD_LOSS_NONFINITE] += 1.0;
+                }
+            }
+            atomicExch(ticket, 0u);
+        }
+    }
+}
+
 }  // namespace
+
+extern "C" int pit_adam_guard_parts(long n) {
+    if (n <= 0) return PIT_ERR_SIZE;
+    const long run = guard_run(n);
+    return (int)((n + run - 1) / run);
+}
+
+extern "C" int pit_adam_step_guarded(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long n, long long* step,
+                                     long long* calls, float lr0, float eta_min, int cosine_t_max, int warmup_steps,
+                                     double warmup_start, float beta1, float beta2, float eps, float weight_decay,
+                                     int decoupled, double max_norm, int zero_grads, const float* loss, double* partials,
+                                     double* state, float* scalars, void* stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !step || !calls || !partials || !state || !scalars) return PIT_ERR_NULL;
+    if (n <= 0) return PIT_ERR_SIZE;
+    if (!(max_norm >= 0.0) || warmup_steps < 0 || !(warmup_start >= 0.0 && warmup_start <= 1.0)) return PIT_ERR_UNSUPPORTED;
+    if ((uintptr_t)grads & 3u) return PIT_ERR_SIZE;
+    const long run = guard_run(n);
+    const int parts = (int)((n + run - 1) / run);
+    const int vec = ((uintptr_t)grads & 15u) == 0 ? 1 : 0;
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(parts), dim3(GUARD_T), 0, (hipStream_t)stream, grads, n, run, vec, partials);
+    PIT_CHECK_LAUNCH();
+    const int blocks = (int)std::min<long>((n + 255) / 256, 2048L);
+    hipLaunchKernelGGL(adam_step_guarded_kernel, dim3(blocks), dim3(GUARD_T), 0, (hipStream_t)stream, params, grads, exp_avg,
+                       exp_avg_sq, n, step, calls, lr0, eta_min, cosine_t_max, warmup_steps, warmup_start, beta1, beta2, eps,
+                       weight_decay, decoupled ? 1 : 0, max_norm, zero_grads, loss, partials, parts, state, scalars);
+    PIT_CHECK_LAUNCH();
+    return 0;
+}
 
 extern "C" int pit_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long n,
                              long long* step, float lr0, float eta_min, int cosine_t_max, float beta1, float beta2,

@@ -12,7 +12,7 @@ not DDP's mean (SURVEY section 8(e) loss-scaling note).
 """
 from __future__ import annotations
 
-from typing import Iterable, List
+from typing import Iterable, List, NamedTuple, Optional
 
 import torch
 import torch.distributed as dist
@@ -178,3 +178,124 @@ class FlatAdam:
                                       self.eps, self.weight_decay, 1 if self.zero_grads else 0,
                                       self.scalars.data_ptr(), _lib.stream_ptr())
         _lib.check(rc, "pit_adam_step")
+
+
+# ---- the guarded step: clip, skip, AdamW and warm-up inside the captured step ----------------------------------------------------
+def guard_run(n: int) -> int:
+    """Elements per partial of the guarded step's gradient norm (include/pit_hip.h, pit_adam_step_guarded)."""
+    from . import _lib
+    n = int(n)
+    if n <= 0:
+        raise ValueError(f"n must be positive, got {n}")
+    unit = 1024 * _lib.GUARD_MAX_PARTS
+    return 1024 * ((n + unit - 1) // unit)
+
+
+def guard_parts(n: int) -> int:
+    """pit_adam_guard_parts on the host: the number of fp64 partials for ``n`` gradients; partial ``b`` covers the elements
+    ``[b * guard_run(n), min(n, (b + 1) * guard_run(n)))``."""
+    run = guard_run(n)
+    return (int(n) + run - 1) // run
+
+
+def guarded_lr(k: int, lr: float, eta_min: float = 0.0, cosine_t_max: int = 0, warmup_steps: int = 0,
+               warmup_start: float = 0.0) -> float:
+    """The learning rate of call ``k`` (1-based, skipped calls included) of the guarded step, in fp64: a linear warm-up
+    from ``lr * warmup_start`` over the first ``warmup_steps`` calls, then CosineAnnealingLR's closed form counted from
+    the end of the warm-up (constant ``lr`` when ``cosine_t_max == 0``)."""
+    import math
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"calls are counted from 1, got {k}")
+    if k <= warmup_steps:
+        return lr * (warmup_start + (1.0 - warmup_start) * (k - 1) / warmup_steps)
+    if cosine_t_max > 0:
+        return eta_min + 0.5 * (lr - eta_min) * (1.0 + math.cos(math.pi * (k - 1 - warmup_steps) / cosine_t_max))
+    return lr
+
+
+class GuardHealth(NamedTuple):
+    """GuardedAdam.health(): the PIT_GUARD_* slots of include/pit_hip.h since the last reset, and the mean of the finite
+    losses (NaN when there was none)."""
+    calls: int
+    applied: int
+    skipped: int
+    clipped: int
+    norm: float
+    max_norm: float
+    coef: float
+    loss_sum: float
+    finite_loss: int
+    nonfinite_loss: int
+    mean_loss: float
+
+
+class GuardedAdam(FlatAdam):
+    """FlatAdam with the look at the gradient that a captured step has lost (pit_adam_step_guarded, two launches, no host
+    round trip): the global L2 norm of the flat gradient in fp64, ``torch.nn.utils.clip_grad_norm_``'s coefficient for
+    ``max_grad_norm`` (None or 0: no clipping), and NO update at all when the norm is not finite - parameters, moments and
+    ``step_count`` keep their bits, the gradients are still cleared with ``zero_grads``, and the skip is counted.
+    ``decoupled=True`` is torch.optim.AdamW's decay; ``warmup_steps`` / ``warmup_start`` put a linear warm-up in front of
+    the cosine schedule (``guarded_lr``).  The schedule counts every call (``calls``), the bias corrections the applied
+    updates (``step_count``).
+
+    In a data-parallel step the guard runs on the all-reduced buffer, so every rank sees the same bits and takes the same
+    decision: a NaN on one rank skips the step on all.  ``FlatGradients.all_reduce`` SUMS over the ranks (the loss sums
+    over the batch), so ``max_grad_norm`` bounds the norm of the SUMMED gradient - that of the global batch - not of a
+    rank's mean.
+
+    ``health()`` is the only call that synchronises."""
+
+    def __init__(self, flat: FlatGradients, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, cosine_t_max: int = 0, eta_min: float = 0.0, zero_grads: bool = False,
+                 max_grad_norm: Optional[float] = None, decoupled: bool = False, warmup_steps: int = 0,
+                 warmup_start: float = 0.0):
+        from . import _lib
+        max_norm = 0.0 if max_grad_norm is None else float(max_grad_norm)
+        if not max_norm >= 0.0:
+            raise ValueError(f"max_grad_norm must be None or a number >= 0, got {max_grad_norm!r}")
+        if int(warmup_steps) != warmup_steps or warmup_steps < 0:
+            raise ValueError(f"warmup_steps must be an integer >= 0, got {warmup_steps!r}")
+        if not 0.0 <= float(warmup_start) <= 1.0:
+            raise ValueError(f"warmup_start must lie in [0, 1], got {warmup_start!r}")
+        super().__init__(flat, lr, betas, eps, weight_decay, cosine_t_max, eta_min, zero_grads)
+        if flat.flat.dtype != torch.float32:
+            raise ValueError("GuardedAdam works on fp32 flat buffers")
+        self.max_grad_norm, self.decoupled = max_norm, bool(decoupled)
+        self.warmup_steps, self.warmup_start = int(warmup_steps), float(warmup_start)
+        dev = flat.flat.device
+        # everything the two launches touch exists before any capture
+        self.partials = torch.zeros(_lib.GUARD_MAX_PARTS, device=dev, dtype=torch.float64)
+        self.state = torch.zeros(_lib.GUARD_STATE_DOUBLES, device=dev, dtype=torch.float64)
+        self.calls = torch.zeros((), device=dev, dtype=torch.int64)
+        self._loss = None
+
+    def watch_loss(self, loss: Optional[torch.Tensor]) -> None:
+        """The device scalar whose value the next ``step()`` adds to the loss statistics (engine.TrainStep hands over the
+        step's loss just before ``step()``; None: no loss is recorded)."""
+        if loss is not None and (loss.dtype != torch.float32 or loss.numel() != 1 or loss.device != self.state.device):
+            raise ValueError("watch_loss takes one fp32 scalar on the optimizer's device")
+        self._loss = loss
+
+    def step(self) -> None:
+        from . import _lib, ops
+        f = self.flat
+        f.attach()
+        ops.parameters_changed()            # raw-pointer update: cached host-evaluated head scales are void
+        rc = _lib.lib().pit_adam_step_guarded(
+            f.flat_params.data_ptr(), f.flat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), f.flat.numel(),
+            self.step_count.data_ptr(), self.calls.data_ptr(), self.lr, self.eta_min, self.cosine_t_max, self.warmup_steps,
+            self.warmup_start, self.betas[0], self.betas[1], self.eps, self.weight_decay, 1 if self.decoupled else 0,
+            self.max_grad_norm, 1 if self.zero_grads else 0, _lib.ptr(self._loss), self.partials.data_ptr(),
+            self.state.data_ptr(), self.scalars.data_ptr(), _lib.stream_ptr())
+        _lib.check(rc, "pit_adam_step_guarded")
+
+    def health(self, reset: bool = False) -> GuardHealth:
+        """The statistics since the last reset, read from the device (this synchronises).  ``reset=True`` zeroes them
+        afterwards - the epoch's line; the schedule's position and the bias corrections are not touched."""
+        s = self.state.cpu().tolist()
+        if reset:
+            self.state.zero_()
+        n_loss = int(s[8])
+        return GuardHealth(int(s[0]), int(s[1]), int(s[2]), int(s[3]), s[4], s[5], s[6], s[7], n_loss, int(s[9]),
+                           s[7] / n_loss if n_loss else float("nan"))

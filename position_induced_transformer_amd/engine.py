@@ -299,8 +299,23 @@ class TrainStep(_StaticBatch):
         self.out = out.detach()              # (the prediction of the last step / replay: parity checks read it)
         if self.all_reduce:
             self._exchange_gradients()
+        self._optimizer_step()
+
+    def _optimizer_step(self) -> None:
         if self.optimizer is not None:
-            self.optimizer.step()          # torch optimizer (capturable) or ddp.FlatAdam (fused HIP step)
+            # ddp.GuardedAdam looks at the all-reduced gradient (every rank decides alike) and keeps the loss statistics
+            watch = getattr(self.optimizer, "watch_loss", None)
+            if watch is not None:
+                watch(self.loss)
+            self.optimizer.step()          # torch optimizer (capturable) or ddp.FlatAdam / GuardedAdam (fused HIP step)
+
+    def health(self, reset: bool = False):
+        """The optimizer's ``health(reset)`` (ddp.GuardedAdam: norm, clip and skip statistics and the epoch's mean loss, read
+        from the device - the one synchronising call of an epoch)."""
+        health = getattr(self.optimizer, "health", None)
+        if health is None:
+            raise RuntimeError("health() needs an optimizer that keeps statistics on the device (ddp.GuardedAdam)")
+        return health(reset)
 
     def run_eager(self) -> None:
         self._step()
@@ -362,8 +377,7 @@ class RolloutStep(TrainStep):
         self.loss = loss.detach()
         if self.all_reduce:
             self.flat.all_reduce()
-        if self.optimizer is not None:
-            self.optimizer.step()
+        self._optimizer_step()
 
 
 # ---- the other half of the epoch: captured evaluation passes ----------------------------------------------------------------------
