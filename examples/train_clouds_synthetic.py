@@ -3,7 +3,8 @@
 latent mesh shared by the batch) on synthetic ragged batches (tasks.ragged_clouds), engine.TrainStep with lengths and the fused
 Adam (ddp.FlatAdam(zero_grads=True)).
 
-    python examples/train_clouds_synthetic.py [--epochs 2] [--width 972] [--feed] [--clip NORM]
+    python examples/train_clouds_synthetic.py [--epochs 2] [--width 972] [--feed] [--clip NORM] [--ema DECAY]
+                                              [--save PATH] [--resume PATH]
 
 The step is captured once for the padded width; every batch then brings its own point counts through
 ``set_batch(..., len_in=...)`` - the lengths live in a static device tensor the kernels read, so no replay waits for the
@@ -18,7 +19,16 @@ their own shuffled batches from it (engine.DeviceFeed: meshes, functions, target
 of the graph); an epoch is `steps_per_epoch` bare replays.
 
 `--clip NORM`: the guarded step (ddp.GuardedAdam) instead of FlatAdam - the gradient's global norm clipped at NORM, updates with
-a non-finite gradient skipped, and the epoch's `step.health()` line printed (one read of the device state per epoch)."""
+a non-finite gradient skipped, and the epoch's `step.health()` line printed (one read of the device state per epoch).
+
+`--ema DECAY`: ddp.AveragedAdam - the guarded step also keeps an exponential average of the weights, in the same two launches.
+Every epoch is then evaluated twice through the SAME captured evaluation graph, on the live weights and, under
+`with opt.averaged():`, on the average (the two buffers change places; nothing is captured again), and both errors are printed.
+
+`--save PATH` writes `step.state_dict()` - model, optimizer (moments, counters, health slots, average) and the feed's position -
+at the end of every epoch; `--resume PATH` loads it AFTER the capture (whose warm-up passes move the optimizer) and goes on at
+the saved position (same `--epochs`: the schedule's length is part of the state, and `load_state_dict` refuses another).  PATH may
+contain `{epoch}` to keep every epoch's file.  The position of a run is its feed's cursor, so both imply `--feed`."""
 import argparse
 import os
 import sys
@@ -28,7 +38,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from position_induced_transformer_amd import tasks  # noqa: E402
-from position_induced_transformer_amd.ddp import FlatAdam, FlatGradients, GuardedAdam  # noqa: E402
+from position_induced_transformer_amd.ddp import AveragedAdam, FlatAdam, FlatGradients, GuardedAdam  # noqa: E402
 from position_induced_transformer_amd.engine import DeviceFeed, EvalStep, TrainStep  # noqa: E402
 from position_induced_transformer_amd.utils import RelMaxNorm, count_params  # noqa: E402
 
@@ -59,14 +69,23 @@ def main():
     ap.add_argument("--feed", action="store_true", help="device-resident data feed inside the captured steps")
     ap.add_argument("--clip", type=float, default=None, metavar="NORM",
                     help="clip the gradient's global norm and skip non-finite updates inside the captured step")
+    ap.add_argument("--ema", type=float, default=None, metavar="DECAY",
+                    help="keep an exponential average of the weights inside the guarded step and evaluate it too")
+    ap.add_argument("--save", default=None, metavar="PATH", help="write step.state_dict() after every epoch (implies --feed)")
+    ap.add_argument("--resume", default=None, metavar="PATH", help="load a saved state after the capture and go on (implies --feed)")
     args = ap.parse_args()
+    args.feed = args.feed or args.save is not None or args.resume is not None
     torch.manual_seed(0)
     mesh_ltt = tasks.grid_mesh_2d(16, True, "cuda").reshape(-1, 2)
     model = tasks.pit_cloud_latent(2, 1, 1, args.hid, 2, 4, mesh_ltt, 0.02, 0.02).cuda()
     print("parameters:", count_params(model))
     iterations = args.epochs * args.nbatches
     flat = FlatGradients(model.parameters(), flatten_params=True)
-    if args.clip is not None:
+    guarded = args.clip is not None or args.ema is not None
+    if args.ema is not None:
+        opt = AveragedAdam(flat, lr=1e-3, cosine_t_max=iterations, zero_grads=True, max_grad_norm=args.clip, average="ema",
+                           average_decay=args.ema)
+    elif guarded:
         opt = GuardedAdam(flat, lr=1e-3, cosine_t_max=iterations, zero_grads=True, max_grad_norm=args.clip)
     else:
         opt = FlatAdam(flat, lr=1e-3, cosine_t_max=iterations, zero_grads=True)
@@ -76,8 +95,13 @@ def main():
     if args.feed:
         feed = DeviceFeed(step, dataset(batches(args.nbatches, args.batch, args.width, seed=2)), shuffle=True, seed=0)
     step.capture()
-    if args.clip is not None:
+    if guarded:
         step.health(reset=True)                                      # (the warm-up passes of the capture are not this epoch's)
+    first_epoch = skip = 0
+    if args.resume is not None:                                      # build, capture, THEN load: the load overwrites the warm-up
+        step.load_state_dict(torch.load(args.resume, weights_only=True))
+        first_epoch, skip = divmod(int(feed.cursor), feed.steps_per_epoch)
+        print(f"resumed {args.resume} at step {int(feed.cursor)} (epoch {first_epoch})")
     metric = RelMaxNorm(1)
     # the held-out set: nbatches // 4 + 1 batches, the last of which holds batch // 2 clouds only
     held_out = list(batches(args.nbatches // 4 + 1, args.batch, args.width, seed=99))
@@ -88,12 +112,24 @@ def main():
     if args.feed:
         test_feed = DeviceFeed(evaluate, dataset(held_out, last_valid), shuffle=False, drop_last=False)
     evaluate.capture()
-    for ep in range(args.epochs):
+
+    def run_eval():
+        evaluate.reset()                                             # (also sends an attached feed back to its first batch)
+        if args.feed:
+            for _ in range(test_feed.steps_per_epoch):               # (the feed writes n_valid for the last batch)
+                evaluate.replay()
+        else:
+            for i, (m, f, t, _, lengths) in enumerate(held_out):
+                evaluate.set_batch(f, t, mesh_in=m, len_in=lengths, n_valid=last_valid if i == len(held_out) - 1 else args.batch)
+                evaluate.replay()
+        return evaluate.result()                                     # the pass's only synchronisation
+
+    for ep in range(first_epoch, args.epochs):
         t1 = default_timer()
         train_l2 = torch.zeros((), device="cuda")
         train_max = torch.zeros((), device="cuda")
         if args.feed:
-            for _ in range(feed.steps_per_epoch):
+            for _ in range(feed.steps_per_epoch - (skip if ep == first_epoch else 0)):
                 step.replay()                                        # the feed's launch is the first of the graph
                 train_l2 += step.loss
                 train_max += metric(step.target, step.out, step.len_in)
@@ -106,22 +142,21 @@ def main():
         torch.cuda.synchronize()
         t2 = default_timer()
         n = args.nbatches * args.batch
-        evaluate.reset()                                             # (also sends an attached feed back to its first batch)
-        if args.feed:
-            for _ in range(test_feed.steps_per_epoch):               # (the feed writes n_valid for the last batch)
-                evaluate.replay()
-        else:
-            for i, (m, f, t, _, lengths) in enumerate(held_out):
-                evaluate.set_batch(f, t, mesh_in=m, len_in=lengths, n_valid=last_valid if i == len(held_out) - 1 else args.batch)
-                evaluate.replay()
-        test = evaluate.result()                                     # the pass's only synchronisation
+        test = run_eval()
         print(ep, f"{t2 - t1:.3f}s", "rel-L2", float(train_l2) / n, "rel-max", float(train_max) / n,
               "| test rel-L2", test.rel_lp / test.count, "rel-max", test.rel_max / test.count, "samples", test.count)
-        if args.clip is not None:
+        if args.ema is not None:
+            with opt.averaged():                                     # the same graph reads the average where the weights live
+                avg = run_eval()
+            print("   averaged weights (%d updates): test rel-L2" % int(opt.n_averaged), avg.rel_lp / avg.count, "rel-max",
+                  avg.rel_max / avg.count)
+        if guarded:
             h = step.health(reset=True)
             print(f"   guard: applied {h.applied} skipped {h.skipped} clipped {h.clipped} of {h.calls}; largest norm {h.max_norm:.4g}, "
                   f"last {h.norm:.4g} (coef {h.coef:.4g}); train loss per sample {h.mean_loss / args.batch:.6g} "
                   f"({h.nonfinite_loss} not finite)")
+        if args.save is not None:
+            torch.save(step.state_dict(), args.save.format(epoch=ep))
 
 
 if __name__ == "__main__":

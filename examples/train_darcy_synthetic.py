@@ -3,7 +3,8 @@
 way the reference writes it - `from pit import *`, `class pit_darcy(pit_fixed)` with its own
 forward, Adam + CosineAnnealingLR, RelLpNorm - but importing the MI355X modules instead.
 
-    python examples/train_darcy_synthetic.py [--epochs 2] [--graph | --feed] [--clip NORM]
+    python examples/train_darcy_synthetic.py [--epochs 2] [--graph | --feed] [--clip NORM] [--ema DECAY]
+                                             [--save PATH] [--resume PATH]
 
 `--graph` replaces the inner loop by the hipGraph-captured step (engine.TrainStep) with the
 fused Adam; without it the loop is literally the reference's eager loop.
@@ -18,7 +19,17 @@ done by the feed's keyed permutation, and the evaluation pass gets its `n_valid`
 
 `--clip NORM` (implies `--graph`) puts the guarded step in the graph (ddp.GuardedAdam): the gradient's global norm is clipped
 at NORM, an update whose gradient is not finite is skipped, and the epoch's line of `step.health()` - steps applied, skipped and
-clipped, the largest norm, the mean training loss from the device accumulator - is printed after each epoch."""
+clipped, the largest norm, the mean training loss from the device accumulator - is printed after each epoch.
+
+`--ema DECAY` (implies `--graph`) uses ddp.AveragedAdam: the guarded step also keeps an exponential average of the weights, in the
+same two launches.  Each epoch is then evaluated twice through the SAME captured evaluation graph - on the live weights and, under
+`with opt.averaged():`, on the average (the two buffers change places in memory; nothing is captured again) - and both errors
+are printed.
+
+`--save PATH` writes `step.state_dict()` - model, optimizer (moments, counters, health slots, average) and the feed's position -
+at the end of every epoch; `--resume PATH` loads it AFTER the capture (whose warm-up passes move the optimizer) and continues at
+the saved position (same `--epochs`: the schedule's length is part of the state, and `load_state_dict` refuses another).  PATH may
+contain `{epoch}` to keep every epoch's file.  The position of a run is its feed's cursor, so both imply `--feed`."""
 import argparse
 import os
 import sys
@@ -57,8 +68,14 @@ def main():
     ap.add_argument("--feed", action="store_true", help="device-resident data feed inside the captured steps (implies --graph)")
     ap.add_argument("--clip", type=float, default=None, metavar="NORM",
                     help="clip the gradient's global norm and skip non-finite updates inside the captured step (implies --graph)")
+    ap.add_argument("--ema", type=float, default=None, metavar="DECAY",
+                    help="keep an exponential average of the weights inside the guarded step and evaluate it too (implies --graph)")
+    ap.add_argument("--save", default=None, metavar="PATH", help="write step.state_dict() after every epoch (implies --feed)")
+    ap.add_argument("--resume", default=None, metavar="PATH", help="load a saved state after the capture and go on (implies --feed)")
     args = ap.parse_args()
-    args.graph = args.graph or args.feed or args.clip is not None
+    args.feed = args.feed or args.save is not None or args.resume is not None
+    args.graph = args.graph or args.feed or args.clip is not None or args.ema is not None
+    guarded = args.clip is not None or args.ema is not None
     torch.manual_seed(0)  # noqa: F405
     s = 43
     # synthetic "dataset": smooth random coefficient fields and a fixed smoothing of them as targets
@@ -82,10 +99,12 @@ def main():
     y_normalizer.cuda()
 
     if args.graph:
-        from position_induced_transformer_amd.ddp import FlatAdam, FlatGradients, GuardedAdam
+        from position_induced_transformer_amd.ddp import AveragedAdam, FlatAdam, FlatGradients, GuardedAdam
         from position_induced_transformer_amd.engine import TrainStep
         flat = FlatGradients(model.parameters(), flatten_params=True)
-        if args.clip is not None:
+        if args.ema is not None:
+            opt = AveragedAdam(flat, lr=1e-3, cosine_t_max=iterations, max_grad_norm=args.clip, average="ema", average_decay=args.ema)
+        elif guarded:
             opt = GuardedAdam(flat, lr=1e-3, cosine_t_max=iterations, max_grad_norm=args.clip)
         else:
             opt = FlatAdam(flat, lr=1e-3, cosine_t_max=iterations)
@@ -96,7 +115,7 @@ def main():
             from position_induced_transformer_amd.engine import DeviceFeed
             feed = DeviceFeed(step, {"func_in": x_train.cuda(), "target": y_train.cuda()}, shuffle=True, seed=0)
         step.capture()
-        if args.clip is not None:
+        if guarded:
             step.health(reset=True)                                   # (the warm-up passes of the capture are not this epoch's)
     else:
         optimizer = torch.optim.Adam(model.parameters(), lr=1e-3)  # noqa: F405
@@ -110,12 +129,30 @@ def main():
         test_feed = DeviceFeed(evaluate, {"func_in": x_test, "target": y_test}, shuffle=False, drop_last=False)
     evaluate.capture()
 
-    for ep in range(args.epochs):
+    def run_eval():
+        evaluate.reset()                                              # (also sends an attached feed back to its first batch)
+        if args.feed:
+            for _ in range(test_feed.steps_per_epoch):                # (the feed writes n_valid for the last batch)
+                evaluate.replay()
+        else:
+            for i in range(0, args.ntest, args.batch):
+                x, y = x_test[i:i + args.batch], y_test[i:i + args.batch]
+                evaluate.set_batch(x, y, n_valid=x.shape[0])          # (the last batch brings fewer rows)
+                evaluate.replay()
+        return evaluate.result()                                      # the pass's only synchronisation
+
+    first_epoch = skip = 0
+    if args.resume is not None:                                       # build, capture, THEN load: the load overwrites the warm-up
+        step.load_state_dict(torch.load(args.resume, weights_only=True))  # noqa: F405
+        first_epoch, skip = divmod(int(feed.cursor), feed.steps_per_epoch)
+        print(f"resumed {args.resume} at step {int(feed.cursor)} (epoch {first_epoch})")
+
+    for ep in range(first_epoch, args.epochs):
         model.train()
         t1 = default_timer()
         train_l2 = torch.zeros((), device="cuda")  # noqa: F405
         if args.feed:
-            for _ in range(feed.steps_per_epoch):
+            for _ in range(feed.steps_per_epoch - (skip if ep == first_epoch else 0)):
                 step.replay()                                         # the feed's launch is the first of the graph
                 train_l2 += step.loss
         else:
@@ -137,24 +174,21 @@ def main():
         torch.cuda.synchronize()  # noqa: F405
         t2 = default_timer()
         model.eval()
-        evaluate.reset()                                              # (also sends an attached feed back to its first batch)
-        if args.feed:
-            for _ in range(test_feed.steps_per_epoch):                # (the feed writes n_valid for the last batch)
-                evaluate.replay()
-        else:
-            for i in range(0, args.ntest, args.batch):
-                x, y = x_test[i:i + args.batch], y_test[i:i + args.batch]
-                evaluate.set_batch(x, y, n_valid=x.shape[0])          # (the last batch brings fewer rows)
-                evaluate.replay()
-        test = evaluate.result()                                      # the pass's only synchronisation
+        test = run_eval()
         t3 = default_timer()
         print(ep, f"{t2 - t1:.3f}s", float(train_l2) / args.ntrain, "| test", f"{t3 - t2:.3f}s", test.rel_lp / test.count,
               "worst sample", test.worst_rel_lp)
-        if args.clip is not None:
+        if args.ema is not None:
+            with opt.averaged():                                      # the same graph reads the average where the weights live
+                avg = run_eval()
+            print("   averaged weights (%d updates): test" % int(opt.n_averaged), avg.rel_lp / avg.count, "worst sample", avg.worst_rel_lp)
+        if guarded:
             h = step.health(reset=True)                               # one read of the device state per epoch
             print(f"   guard: applied {h.applied} skipped {h.skipped} clipped {h.clipped} of {h.calls}; largest norm {h.max_norm:.4g}, "
                   f"last {h.norm:.4g} (coef {h.coef:.4g}); train loss per sample {h.mean_loss / args.batch:.6g} "
                   f"({h.nonfinite_loss} not finite)")
+        if args.save is not None:
+            torch.save(step.state_dict(), args.save.format(epoch=ep))  # noqa: F405
     torch.save({"model_state": model.state_dict()}, "/tmp/model.pth")  # noqa: F405
 
 

@@ -1116,6 +1116,45 @@ int pit_adam_step_guarded(float* params, float* grads, float* exp_avg, float* ex
                           double max_norm, int zero_grads, const float* loss, double* partials, double* state,
                           float* scalars, void* stream);
 
+/* ---- Averaged weights in the guarded step, and the exchange behind their evaluation (additions to ABI 31; csrc/pit_optim.hip) ----
+ * The reference saves {'model_state': ...} once, at the end (train_darcy.py:150): no optimizer state, no resume, and no averaged
+ * copy of the weights.  Beyond the reference: pit_adam_step_averaged is pit_adam_step_guarded with an exponential (EMA) or equal
+ * (SWA) average of the parameters kept in the SAME two launches, and pit_exchange_words swaps two buffers in place, so that a
+ * captured evaluation graph reads the average where it read the live weights.  A library built from this header defines
+ * PIT_HAS_AVERAGED_ADAM; PIT_ABI_VERSION is unchanged (nothing that existed changed; the guarded entry is as it was).
+ *
+ * The averaged step.  Its arguments are the guarded entry's up to `scalars`, then average, n_averaged, avg_mode, avg_decay,
+ * avg_ramp, avg_start, then stream.  Launch 1 is grad_sumsq_kernel; launch 2 (a second instance of
+ * adam_step_guarded_kernel) runs the guarded kernel's arithmetic expression for expression: params, both moments, *step, *calls, state and scalars come
+ * out with the guarded entry's bits, and the average never feeds back into the update.  On an APPLIED update, with t the new
+ * value of *step and p the parameter just written:
+ *   t <= avg_start:  average[i] = p; *n_averaged stays 0 (the average follows the weights until averaging starts)
+ *   t >  avg_start:  m = t - avg_start, the weight w once per workgroup in fp64, rounded to fp32:
+ *                      avg_mode 0 (EMA):    d = avg_ramp ? min(avg_decay, (1 + m) / (10 + m)) : avg_decay;  w = 1 - d
+ *                      avg_mode 1 (equal):  w = 1 / m
+ *                    a = average[i]; average[i] = (w == 1.0f) ? p : a + w * (p - a)     (three separately rounded fp32 operations)
+ *                    *n_averaged = m, written by the workgroup of the last ticket beside the other counters
+ * On a SKIPPED call (norm not finite) average and *n_averaged keep their bits.
+ *   average     n floats on the device, disjoint from params; the caller starts it as a copy of params
+ *   n_averaged  one long long on the device, zero before the first call
+ * Refusals, all before any launch, in the order pointers, sizes, values: the guarded entry's, and PIT_ERR_NULL for a missing
+ * average or n_averaged; PIT_ERR_UNSUPPORTED for avg_mode other than 0 or 1, for an EMA avg_decay outside [0, 1) (or NaN), for
+ * avg_start < 0, and for an average whose n floats overlap those of params.
+ *
+ * The exchange.  The n_words 4-byte words at a and at b change places, as raw bits (NaN payloads survive), in one launch of a
+ * grid-stride loop (at most 2048 workgroups): 16-byte loads and stores where a and b sit equally far from a 16-byte boundary
+ * (up to three head and three tail words go one by one), single words otherwise.  PIT_ERR_NULL for a null pointer; PIT_ERR_SIZE
+ * for n_words <= 0 and for a base that is not 4-byte aligned; PIT_ERR_UNSUPPORTED when the two ranges overlap.  All before any
+ * launch.  No host synchronisation, no allocation, capturable (both entries). */
+#define PIT_HAS_AVERAGED_ADAM 1
+int pit_adam_step_averaged(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long n, long long* step,
+                           long long* calls, float lr0, float eta_min, int cosine_t_max, int warmup_steps,
+                           double warmup_start, float beta1, float beta2, float eps, float weight_decay, int decoupled,
+                           double max_norm, int zero_grads, const float* loss, double* partials, double* state,
+                           float* scalars, float* average, long long* n_averaged, int avg_mode, double avg_decay,
+                           int avg_ramp, long long avg_start, void* stream);
+int pit_exchange_words(void* a, void* b, long n_words, void* stream);
+
 /* ---- The two slab forms of pit_block_fwd (additions to ABI 31; csrc/pit_block.hip) ------------------------------------------------
  * pit_block_fwd runs 16-row slabs, or - n_head = 2, n_pts = 256, the weights through LDS, and 8 * ceil(batch / 8) * n_pts / 8
  * workgroups no more than the device has CUs (batch <= 8 on MI355X) - 8-row slabs with the two heads stacked in the M dimension of

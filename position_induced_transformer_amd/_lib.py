@@ -194,6 +194,9 @@ SIGNATURES = {
     "pit_adam_step": [_P, _P, _P, _P, _L, _P, _F, _F, _I, _F, _F, _F, _F, _I, _P, _P],
     "pit_adam_guard_parts": [_L],
     "pit_adam_step_guarded": [_P, _P, _P, _P, _L, _P, _P, _F, _F, _I, _I, _D, _F, _F, _F, _F, _I, _D, _I, _P, _P, _P, _P, _P],
+    "pit_adam_step_averaged": [_P, _P, _P, _P, _L, _P, _P, _F, _F, _I, _I, _D, _F, _F, _F, _F, _I, _D, _I, _P, _P, _P, _P,
+                               _P, _P, _I, _D, _I, _LL, _P],
+    "pit_exchange_words": [_P, _P, _L, _P],
     "pit_debug_mfma_tile": [_P, _P, _P, _P],
     "pit_debug_rider_counts": [_P, _I, _I],
     "pit_debug_gemm_counts": [_P, _I, _I],
@@ -215,7 +218,8 @@ ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_
                "pit_debug_att_counts",                                             # PIT_HAS_ATT_COUNTS
                "pit_eval_metrics_workspace", "pit_eval_metrics",                   # PIT_HAS_EVAL_METRICS
                "pit_batch_feed",                                                   # PIT_HAS_BATCH_FEED
-               "pit_adam_guard_parts", "pit_adam_step_guarded"}                    # PIT_HAS_GUARDED_ADAM
+               "pit_adam_guard_parts", "pit_adam_step_guarded",                    # PIT_HAS_GUARDED_ADAM
+               "pit_adam_step_averaged", "pit_exchange_words"}                     # PIT_HAS_AVERAGED_ADAM
 GUARD_MAX_PARTS = 256    # PIT_GUARD_MAX_PARTS
 GUARD_STATE_DOUBLES = 10         # PIT_GUARD_STATE_DOUBLES
 FEED_MAX_FIELDS = 8      # PIT_FEED_MAX_FIELDS

@@ -101,14 +101,35 @@ __global__ __launch_bounds__(GUARD_T) void grad_sumsq_kernel(const float* __rest
 // either runs adam_step_kernel's arithmetic on g * coef or leaves parameters and moments alone.  Both counters - calls
 // (the schedule's position) and step (the applied updates behind the bias corrections) - are read by every workgroup
 // before its ticket; the workgroup of the last ticket writes them back together with the statistics.
+//
+// Two instances.  adam_step_guarded_kernel<> (no trailing argument) is the guarded step.  adam_step_guarded_kernel<avg_args>
+// (include/pit_hip.h, pit_adam_step_averaged) also keeps an average of the parameters: its weight is one more value thread 0
+// forms in fp64, the average one more buffer read and written per element from the parameter still in its register, and
+// *n_averaged one more counter of the last ticket.  Everything the trailing argument adds is compiled out of the first
+// instance, whose argument list and instructions are those of the kernel before the second existed.
+struct avg_args {
+    float* average;
+    long long* n_averaged;
+    int mode;
+    double decay;
+    int ramp;
+    long long start;
+};
+__device__ inline avg_args avg_of() { return avg_args{}; }
+__device__ inline avg_args avg_of(const avg_args& a) { return a; }
+
+template <typename... Avg>
 __global__ __launch_bounds__(GUARD_T) void adam_step_guarded_kernel(
         float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n, long long* step,
         long long* calls, float lr0, float eta_min, int t_max, int warmup_steps, double warmup_start, float beta1, float beta2,
         float eps, float weight_decay, int decoupled, double max_norm, int zero_grads, const float* loss,
-        const double* __restrict__ partials, int parts, double* state, float* scalars) {
+        const double* __restrict__ partials, int parts, double* state, float* scalars, Avg... avg_pack) {
+    constexpr bool AVG = sizeof...(Avg) == 1;
+    static_assert(sizeof...(Avg) <= 1, "no trailing argument, or one avg_args");
+    [[maybe_unused]] const avg_args avg = avg_of(avg_pack...);
     __shared__ double s_part[PIT_GUARD_MAX_PARTS];
     __shared__ double s_norm;
-    __shared__ float s_sc[5];
+    __shared__ float s_sc[AVG ? 6 : 5];
     __shared__ int s_skip;
     const int tid = threadIdx.x;
     const long long t = __hip_atomic_load(step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;      // this update, if applied
@@ -138,6 +159,19 @@ __global__ __launch_bounds__(GUARD_T) void adam_step_guarded_kernel(
         s_sc[4] = (float)(1.0 - (double)lr_t * (double)weight_decay);  // AdamW: p *= 1 - lr_t * wd
         s_norm = norm;
         s_skip = finite ? 0 : 1;
+        if constexpr (AVG) {
+            float w = 1.0f;             // t <= start: the average follows the weights
+            if (t > avg.start) {
+                const double mm = (double)(t - avg.start);
+                if (avg.mode == 0) {
+                    const double d = avg.ramp ? fmin(avg.decay, (1.0 + mm) / (10.0 + mm)) : avg.decay;
+                    w = (float)(1.0 - d);
+                } else {
+                    w = (float)(1.0 / mm);
+                }
+            }
+            s_sc[5] = w;
+        }
     }
     __syncthreads();
     const float lr = s_sc[0], bc1 = s_sc[1], bc2 = s_sc[2], coef = s_sc[3], shrink = s_sc[4];
@@ -146,6 +180,8 @@ __global__ __launch_bounds__(GUARD_T) void adam_step_guarded_kernel(
     const float inv_sqrt_bc2 = 1.0f / sqrtf(bc2);
     const float wd_coupled = decoupled ? 0.0f : weight_decay;
     const bool shrinks = decoupled && weight_decay != 0.0f;
+    float w_avg = 1.0f;
+    if constexpr (AVG) w_avg = s_sc[5];
     if (skip) {
         if (zero_grads)                 // (the non-finite values would live on in the accumulator)
             for (long i = (long)blockIdx.x * blockDim.x + tid; i < n; i += (long)gridDim.x * blockDim.x) g[i] = 0.0f;
@@ -164,6 +200,14 @@ __global__ __launch_bounds__(GUARD_T) void adam_step_guarded_kernel(
             const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;       // torch: (sqrt(v)/sqrt(bc2)) + eps
             pi -= step_size * (mi / denom);
             p[i] = pi;
+            if constexpr (AVG) {
+                if (w_avg == 1.0f) {
+                    avg.average[i] = pi;
+                } else {
+                    const float a = avg.average[i];
+                    avg.average[i] = a + w_avg * (pi - a);              // (three roundings: the build contracts nothing)
+                }
+            }
         }
     }
     __syncthreads();
@@ -184,6 +228,9 @@ __global__ __launch_bounds__(GUARD_T) void adam_step_guarded_kernel(
                 state[PIT_GUARD_APPLIED] += 1.0;
                 if (coef < 1.0f) state[PIT_GUARD_CLIPPED] += 1.0;
                 if (norm > state[PIT_GUARD_MAX_NORM]) state[PIT_GUARD_MAX_NORM] = norm;
+                if constexpr (AVG) {
+                    if (t > avg.start) *avg.n_averaged = t - avg.start;
+                }
             }
             if (loss) {
                 const float l = *loss;
@@ -197,6 +244,39 @@ __global__ __launch_bounds__(GUARD_T) void adam_step_guarded_kernel(
             atomicExch(ticket, 0u);
         }
     }
+}
+
+// ---- pit_exchange_words: two disjoint buffers change places, word for word ---------------------------------------------------------
+// Word w of either buffer belongs to one of three runs: `head` single words, `nvec` 16-byte groups, `tail` single words; the
+// host picks head so that both group bases are 16-byte aligned (equal distance from a boundary) or makes every word a head word.
+// Each word is read from both sides and written to both sides by ONE thread, so no thread sees another's store.
+__global__ __launch_bounds__(256) void exchange_words_kernel(unsigned* __restrict__ a, unsigned* __restrict__ b, long head,
+                                                             long nvec, long tail) {
+    const long first = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+    for (long i = first; i < head; i += stride) {
+        const unsigned x = a[i], y = b[i];
+        a[i] = y;
+        b[i] = x;
+    }
+    uint4* __restrict__ a4 = reinterpret_cast<uint4*>(a + head);
+    uint4* __restrict__ b4 = reinterpret_cast<uint4*>(b + head);
+    for (long i = first; i < nvec; i += stride) {
+        const uint4 x = a4[i], y = b4[i];
+        a4[i] = y;
+        b4[i] = x;
+    }
+    const long t0 = head + 4 * nvec;
+    for (long i = first; i < tail; i += stride) {
+        const unsigned x = a[t0 + i], y = b[t0 + i];
+        a[t0 + i] = y;
+        b[t0 + i] = x;
+    }
+}
+
+// [x, x + bytes) and [y, y + bytes) share a byte
+inline bool ranges_overlap(const void* x, const void* y, unsigned long long bytes) {
+    const uintptr_t p = (uintptr_t)x, q = (uintptr_t)y;
+    return p < q ? q - p < bytes : p - q < bytes;
 }
 
 }  // namespace
@@ -222,9 +302,57 @@ extern "C" int pit_adam_step_guarded(float* params, float* grads, float* exp_avg
     hipLaunchKernelGGL(grad_sumsq_kernel, dim3(parts), dim3(GUARD_T), 0, (hipStream_t)stream, grads, n, run, vec, partials);
     PIT_CHECK_LAUNCH();
     const int blocks = (int)std::min<long>((n + 255) / 256, 2048L);
-    hipLaunchKernelGGL(adam_step_guarded_kernel, dim3(blocks), dim3(GUARD_T), 0, (hipStream_t)stream, params, grads, exp_avg,
+    hipLaunchKernelGGL(adam_step_guarded_kernel<>, dim3(blocks), dim3(GUARD_T), 0, (hipStream_t)stream, params, grads, exp_avg,
                        exp_avg_sq, n, step, calls, lr0, eta_min, cosine_t_max, warmup_steps, warmup_start, beta1, beta2, eps,
                        weight_decay, decoupled ? 1 : 0, max_norm, zero_grads, loss, partials, parts, state, scalars);
+    PIT_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pit_adam_step_averaged(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long n, long long* step,
+                                      long long* calls, float lr0, float eta_min, int cosine_t_max, int warmup_steps,
+                                      double warmup_start, float beta1, float beta2, float eps, float weight_decay,
+                                      int decoupled, double max_norm, int zero_grads, const float* loss, double* partials,
+                                      double* state, float* scalars, float* average, long long* n_averaged, int avg_mode,
+                                      double avg_decay, int avg_ramp, long long avg_start, void* stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !step || !calls || !partials || !state || !scalars || !average ||
+        !n_averaged)
+        return PIT_ERR_NULL;
+    if (n <= 0) return PIT_ERR_SIZE;
+    if ((uintptr_t)grads & 3u) return PIT_ERR_SIZE;
+    if (!(max_norm >= 0.0) || warmup_steps < 0 || !(warmup_start >= 0.0 && warmup_start <= 1.0)) return PIT_ERR_UNSUPPORTED;
+    if (avg_mode != 0 && avg_mode != 1) return PIT_ERR_UNSUPPORTED;
+    if (avg_mode == 0 && !(avg_decay >= 0.0 && avg_decay < 1.0)) return PIT_ERR_UNSUPPORTED;
+    if (avg_start < 0) return PIT_ERR_UNSUPPORTED;
+    if (ranges_overlap(average, params, 4ull * (unsigned long long)n)) return PIT_ERR_UNSUPPORTED;
+    const long run = guard_run(n);
+    const int parts = (int)((n + run - 1) / run);
+    const int vec = ((uintptr_t)grads & 15u) == 0 ? 1 : 0;
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(parts), dim3(GUARD_T), 0, (hipStream_t)stream, grads, n, run, vec, partials);
+    PIT_CHECK_LAUNCH();
+    const int blocks = (int)std::min<long>((n + 255) / 256, 2048L);
+    const avg_args avg{average, n_averaged, avg_mode, avg_decay, avg_ramp ? 1 : 0, avg_start};
+    hipLaunchKernelGGL(adam_step_guarded_kernel<avg_args>, dim3(blocks), dim3(GUARD_T), 0, (hipStream_t)stream, params, grads, exp_avg,
+                       exp_avg_sq, n, step, calls, lr0, eta_min, cosine_t_max, warmup_steps, warmup_start, beta1, beta2, eps,
+                       weight_decay, decoupled ? 1 : 0, max_norm, zero_grads, loss, partials, parts, state, scalars, avg);
+    PIT_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pit_exchange_words(void* a, void* b, long n_words, void* stream) {
+    if (!a || !b) return PIT_ERR_NULL;
+    if (n_words <= 0 || ((uintptr_t)a & 3u) || ((uintptr_t)b & 3u)) return PIT_ERR_SIZE;
+    if (ranges_overlap(a, b, 4ull * (unsigned long long)n_words)) return PIT_ERR_UNSUPPORTED;
+    long head = n_words, nvec = 0, tail = 0;               // bases unequally far from a 16-byte boundary: single words throughout
+    if ((((uintptr_t)a ^ (uintptr_t)b) & 15u) == 0) {
+        head = std::min<long>(n_words, (long)(((16u - ((uintptr_t)a & 15u)) & 15u) / 4u));
+        nvec = (n_words - head) / 4;
+        tail = n_words - head - 4 * nvec;
+    }
+    const long items = std::max(std::max(head, tail), nvec);
+    const int blocks = (int)std::min<long>((items + 255) / 256, 2048L);
+    hipLaunchKernelGGL(exchange_words_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, static_cast<unsigned*>(a),
+                       static_cast<unsigned*>(b), head, nvec, tail);
     PIT_CHECK_LAUNCH();
     return 0;
 }

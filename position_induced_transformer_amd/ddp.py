@@ -12,6 +12,7 @@ not DDP's mean (SURVEY section 8(e) loss-scaling note).
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Iterable, List, NamedTuple, Optional
 
 import torch
@@ -179,6 +180,53 @@ class FlatAdam:
                                       self.scalars.data_ptr(), _lib.stream_ptr())
         _lib.check(rc, "pit_adam_step")
 
+    # -- state: what an interrupted run needs to go on with the same bits (engine.TrainStep.state_dict saves it with the model)
+    def _config(self) -> dict:
+        """The settings the saved tensors were produced under, as plain Python numbers."""
+        return {"class": type(self).__name__, "n": int(self.flat.flat.numel()), "lr": float(self.lr),
+                "beta1": float(self.betas[0]), "beta2": float(self.betas[1]), "eps": float(self.eps),
+                "weight_decay": float(self.weight_decay), "cosine_t_max": int(self.cosine_t_max), "eta_min": float(self.eta_min)}
+
+    def _state_tensors(self) -> dict:
+        """Every device tensor the step reads and carries from call to call.  Not among them: ``scalars`` (slots 0..2 are
+        rewritten by the next step, slot 3 is the arrival ticket and must stay 0) and the guarded step's ``partials`` (scratch)."""
+        return {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "step_count": self.step_count}
+
+    def state_dict(self) -> dict:
+        """CPU copies of the moments and the step counter (subclasses: of every tensor their step carries along), and
+        ``config``: the settings as plain numbers.  The parameters are the model's (``model.state_dict()``).  The dict passes
+        ``torch.save`` and ``torch.load(weights_only=True)``.  This synchronises."""
+        state = {name: t.detach().to("cpu", copy=True) for name, t in self._state_tensors().items()}
+        state["config"] = self._config()
+        return state
+
+    def load_state_dict(self, state: dict, strict: bool = True) -> None:
+        """Copy a ``state_dict()`` back IN PLACE (``copy_``: graphs captured on these tensors stay valid).  ``strict``: every
+        ``config`` entry must equal this optimizer's (ValueError naming the first that differs); ``strict=False`` takes the
+        tensors alone.  A state of another size is always refused."""
+        from . import ops
+        own = self._state_tensors()
+        missing = [name for name in own if name not in state]
+        if missing:
+            raise ValueError(f"{type(self).__name__}.load_state_dict: the state lacks {', '.join(missing)}")
+        config, mine = state.get("config") or {}, self._config()
+        if "n" in config and int(config["n"]) != mine["n"]:
+            raise ValueError(f"{type(self).__name__}.load_state_dict: the state was saved for n = {config['n']} elements, "
+                             f"this optimizer has n = {mine['n']}")
+        for name, t in own.items():
+            if not torch.is_tensor(state[name]) or tuple(state[name].shape) != tuple(t.shape):
+                raise ValueError(f"{type(self).__name__}.load_state_dict: {name} has shape "
+                                 f"{tuple(getattr(state[name], 'shape', ()))}, this optimizer's {tuple(t.shape)}")
+        if strict:
+            for name, value in mine.items():
+                if name not in config or config[name] != value:
+                    raise ValueError(f"{type(self).__name__}.load_state_dict: the state was saved with {name} = "
+                                     f"{config.get(name)!r}, this optimizer has {name} = {value!r} (strict=False takes the "
+                                     "tensors alone)")
+        for name, t in own.items():
+            t.copy_(state[name])
+        ops.parameters_changed()
+
 
 # ---- the guarded step: clip, skip, AdamW and warm-up inside the captured step ----------------------------------------------------
 def guard_run(n: int) -> int:
@@ -299,3 +347,147 @@ class GuardedAdam(FlatAdam):
         n_loss = int(s[8])
         return GuardHealth(int(s[0]), int(s[1]), int(s[2]), int(s[3]), s[4], s[5], s[6], s[7], n_loss, int(s[9]),
                            s[7] / n_loss if n_loss else float("nan"))
+
+    def _config(self) -> dict:
+        config = super()._config()
+        config.update(max_grad_norm=float(self.max_grad_norm), decoupled=bool(self.decoupled), warmup_steps=int(self.warmup_steps),
+                      warmup_start=float(self.warmup_start))
+        return config
+
+    def _state_tensors(self) -> dict:
+        tensors = super()._state_tensors()
+        tensors.update(calls=self.calls, state=self.state)            # the schedule's position and the health slots
+        return tensors
+
+
+# ---- averaged weights: an EMA or equal average of the parameters kept by the guarded step's own two launches ------------------------
+_AVERAGE_MODES = {"ema": 0, "equal": 1}
+
+
+def average_weight(m: int, mode: str = "ema", decay: float = 0.999, ramp: bool = False) -> float:
+    """The weight ``w`` of averaged update ``m`` (1-based: the m-th applied update after ``average_start``) in
+    ``average += w * (p - average)``, in fp64 as pit_adam_step_averaged forms it (include/pit_hip.h); the kernel's ``w`` is
+    ``numpy.float32`` of this.  "ema": ``1 - decay``, with ``ramp`` ``1 - min(decay, (1 + m) / (10 + m))`` (a short average at
+    the start of the run); "equal": ``1 / m``.  The counterpart of ``guarded_lr``."""
+    m = int(m)
+    if m < 1:
+        raise ValueError(f"averaged updates are counted from 1, got {m}")
+    if mode not in _AVERAGE_MODES:
+        raise ValueError(f"mode must be 'ema' or 'equal', got {mode!r}")
+    if mode == "equal":
+        return 1.0 / float(m)
+    d = min(float(decay), (1.0 + float(m)) / (10.0 + float(m))) if ramp else float(decay)
+    return 1.0 - d
+
+
+class AveragedAdam(GuardedAdam):
+    """GuardedAdam that also keeps an average of the parameters - what a user evaluates and ships - in the SAME two launches
+    (pit_adam_step_averaged): after every applied update, ``average += w * (p - average)`` with ``average_weight``'s ``w``
+    (``average="ema"``: exponential with ``average_decay``, ``average_ramp`` for the short average at the start; ``"equal"``:
+    the plain mean of the weights after each update, SWA).  Until ``average_start`` updates have been applied the average is a
+    copy of the weights.  A skipped call leaves ``average`` and ``n_averaged`` alone, and the average never feeds back into
+    the update: parameters, moments, counters and health have GuardedAdam's bits.
+
+    Evaluating it costs one launch each way and no capture: ``with opt.averaged():`` exchanges ``flat_params`` and ``average``
+    in place (pit_exchange_words), so every graph that reads the parameters where they live - an engine.EvalStep captured on
+    the same model under the 'device' head-scale route - evaluates the average; under the 'host' route such a graph holds the
+    scales of the lmda values of its capture and its ``reset()`` refuses, as after any other change of the parameters.  While
+    swapped, ``step()``, ``state_dict()`` and ``load_state_dict()`` raise: training would update the average, a checkpoint
+    would hold the two buffers crossed."""
+
+    def __init__(self, flat: FlatGradients, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, cosine_t_max: int = 0, eta_min: float = 0.0, zero_grads: bool = False,
+                 max_grad_norm: Optional[float] = None, decoupled: bool = False, warmup_steps: int = 0,
+                 warmup_start: float = 0.0, average: str = "ema", average_decay: float = 0.999, average_ramp: bool = False,
+                 average_start: int = 0):
+        if average not in _AVERAGE_MODES:
+            raise ValueError(f"average must be 'ema' or 'equal', got {average!r}")
+        if average == "ema" and not 0.0 <= float(average_decay) < 1.0:
+            raise ValueError(f"average_decay must lie in [0, 1), got {average_decay!r}")
+        if int(average_start) != average_start or average_start < 0:
+            raise ValueError(f"average_start must be an integer >= 0, got {average_start!r}")
+        super().__init__(flat, lr, betas, eps, weight_decay, cosine_t_max, eta_min, zero_grads, max_grad_norm, decoupled,
+                         warmup_steps, warmup_start)
+        self.average_mode, self.average_decay = average, float(average_decay)
+        self.average_ramp, self.average_start = bool(average_ramp), int(average_start)
+        # both exist before any capture; the average starts as the weights
+        self.average = flat.flat_params.clone()
+        self.n_averaged = torch.zeros((), device=flat.flat.device, dtype=torch.int64)
+        self.swapped = False
+
+    def _refuse_swapped(self, what: str) -> None:
+        if self.swapped:
+            raise RuntimeError(f"AveragedAdam.{what} while the average is swapped in (flat_params holds the average, `average` "
+                               "the live weights): swap back first (swap_average(), or leave the `with opt.averaged():` block)")
+
+    def step(self) -> None:
+        from . import _lib, ops
+        self._refuse_swapped("step()")
+        f = self.flat
+        f.attach()
+        ops.parameters_changed()            # raw-pointer update: cached host-evaluated head scales are void
+        rc = _lib.lib().pit_adam_step_averaged(
+            f.flat_params.data_ptr(), f.flat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), f.flat.numel(),
+            self.step_count.data_ptr(), self.calls.data_ptr(), self.lr, self.eta_min, self.cosine_t_max, self.warmup_steps,
+            self.warmup_start, self.betas[0], self.betas[1], self.eps, self.weight_decay, 1 if self.decoupled else 0,
+            self.max_grad_norm, 1 if self.zero_grads else 0, _lib.ptr(self._loss), self.partials.data_ptr(),
+            self.state.data_ptr(), self.scalars.data_ptr(), self.average.data_ptr(), self.n_averaged.data_ptr(),
+            _AVERAGE_MODES[self.average_mode], self.average_decay, 1 if self.average_ramp else 0, self.average_start,
+            _lib.stream_ptr())
+        _lib.check(rc, "pit_adam_step_averaged")
+
+    def swap_average(self) -> None:
+        """Exchange ``flat_params`` and ``average`` in place: one launch (pit_exchange_words), no allocation, addresses do not
+        move.  Toggles ``swapped``."""
+        from . import _lib, ops
+        f = self.flat
+        rc = _lib.lib().pit_exchange_words(f.flat_params.data_ptr(), self.average.data_ptr(), f.flat_params.numel(),
+                                           _lib.stream_ptr())
+        _lib.check(rc, "pit_exchange_words")
+        ops.parameters_changed()
+        self.swapped = not self.swapped
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """``with opt.averaged():`` - the model computes with the averaged weights inside the block and with its own after it
+        (also when the block raises)."""
+        self._refuse_swapped("averaged()")
+        self.swap_average()
+        try:
+            yield self
+        finally:
+            self.swap_average()
+
+    def averaged_model_state(self, model: torch.nn.Module) -> dict:
+        """``model.state_dict()`` with every parameter this optimizer updates replaced by (a copy of) its slice of the average;
+        parameters are matched by identity through ``flat.params``, buffers, frozen parameters and key names are untouched:
+        ``{'model_state': opt.averaged_model_state(model)}`` loads in the reference scripts and through
+        utils.load_reference_checkpoint."""
+        f = self.flat
+        source = f.flat_params if self.swapped else self.average
+        where = {id(p): (off, p.numel()) for p, off in zip(f.params, f.offsets)}
+        state = model.state_dict()
+        for name, p in model.named_parameters():
+            if id(p) in where and name in state:
+                off, n = where[id(p)]
+                state[name] = source[off:off + n].view_as(p).clone()
+        return state
+
+    def _config(self) -> dict:
+        config = super()._config()
+        config.update(average=self.average_mode, average_decay=float(self.average_decay), average_ramp=bool(self.average_ramp),
+                      average_start=int(self.average_start))
+        return config
+
+    def _state_tensors(self) -> dict:
+        tensors = super()._state_tensors()
+        tensors.update(average=self.average, n_averaged=self.n_averaged)
+        return tensors
+
+    def state_dict(self) -> dict:
+        self._refuse_swapped("state_dict()")
+        return super().state_dict()
+
+    def load_state_dict(self, state: dict, strict: bool = True) -> None:
+        self._refuse_swapped("load_state_dict()")
+        super().load_state_dict(state, strict)

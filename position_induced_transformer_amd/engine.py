@@ -321,7 +321,9 @@ class TrainStep(_StaticBatch):
         self._step()
 
     def capture(self, warmup: int = 3) -> None:
-        """Warm up and capture the step on one side stream (``_StaticBatch._capture_graph``)."""
+        """Warm up and capture the step on one side stream (``_StaticBatch._capture_graph``).  The warm-up passes are real
+        steps: they move the optimizer (a feed's cursor is put back).  To resume a saved run, therefore: build, ``capture()``,
+        THEN ``load_state_dict()`` - the load overwrites what the warm-up did, in place, and the graph stays valid."""
         graph, side = self._capture_graph(warmup, self.all_reduce)
         ops.assert_frozen_since_capture()     # route 'host': the graph must not update an lmda whose scale it baked in
         self.graph = graph
@@ -331,6 +333,41 @@ class TrainStep(_StaticBatch):
         self.graph.replay()
         if self.optimizer is not None:
             ops.parameters_changed()          # the replay rewrote the parameters behind autograd's back
+
+    def state_dict(self) -> dict:
+        """Everything a run needs to go on where it stopped, as CPU copies (this synchronises): ``{"format": 1, "model_state":
+        model.state_dict() (the reference's key names, train_darcy.py:150), "optimizer": the optimizer's state_dict()
+        (ddp.FlatAdam / GuardedAdam / AveragedAdam: moments, counters, health slots, average; a torch optimizer: its own; None
+        without one), "feed": the attached DeviceFeed's (None without one)}``.  Passes ``torch.save`` and, with the fused
+        optimizers, ``torch.load(weights_only=True)``.  Valid before or after ``capture()``."""
+        model_state = {k: v.detach().to("cpu", copy=True) for k, v in self.model.state_dict().items()}
+        return {"format": 1, "model_state": model_state,
+                "optimizer": self.optimizer.state_dict() if self.optimizer is not None else None,
+                "feed": self._feed.state_dict() if self._feed is not None else None}
+
+    def load_state_dict(self, state: dict, strict: bool = True) -> None:
+        """Put a ``state_dict()`` back: the model (in place - its parameters are views of ``flat_params``), the optimizer and the
+        feed, then ops.parameters_changed().  Valid before or after ``capture()``; because ``capture()``'s warm-up passes move the
+        optimizer, the order of a resume is build, capture, load.  The fused optimizers load in place (captured graphs stay
+        valid) and take ``strict`` (ddp.FlatAdam.load_state_dict); a torch optimizer's own ``load_state_dict`` replaces its
+        state tensors, so load it BEFORE the capture.  A state with an optimizer or a feed loaded into a step without one (or
+        the reverse) is refused."""
+        from .ddp import FlatAdam
+        if not isinstance(state, dict) or state.get("format") != 1:
+            raise ValueError("load_state_dict: not a TrainStep.state_dict() of format 1")
+        for name, mine in (("optimizer", self.optimizer), ("feed", self._feed)):
+            if (state.get(name) is None) != (mine is None):
+                raise ValueError(f"load_state_dict: the state has {'no' if state.get(name) is None else 'an'} {name} state, "
+                                 f"this step has {'no' if mine is None else 'an'} {name}")
+        self.model.load_state_dict(state["model_state"], strict=strict)
+        if self.optimizer is not None:
+            if isinstance(self.optimizer, FlatAdam):
+                self.optimizer.load_state_dict(state["optimizer"], strict=strict)
+            else:
+                self.optimizer.load_state_dict(state["optimizer"])
+        if self._feed is not None:
+            self._feed.load_state_dict(state["feed"])
+        ops.parameters_changed()
 
     def set_batch(self, func_in: torch.Tensor, target: torch.Tensor, mesh_in: Optional[torch.Tensor] = None,
                   mesh_out: Optional[torch.Tensor] = None, len_in=None, len_out=None) -> None:
@@ -740,6 +777,26 @@ class DeviceFeed:
         if int(k) < 0:
             raise ValueError("seek: a feed position is not negative")
         self.cursor.fill_(int(k))
+
+    _STATE_KEYS = ("n_samples", "batch", "world_size", "seed", "shuffle", "drop_last", "steps_per_epoch")
+
+    def state_dict(self) -> dict:
+        """The feed's position - ``cursor``, the number of feeds so far (one device->host read) - and what gives it its meaning:
+        n_samples, batch, world_size, seed, shuffle, drop_last and steps_per_epoch, as plain numbers.  A caller-supplied
+        ``order`` is NOT saved: a run that resumes with another ``order`` reads other samples at the same position."""
+        state = {"cursor": int(self.cursor)}
+        state.update({key: getattr(self, key) for key in self._STATE_KEYS})
+        return state
+
+    def load_state_dict(self, state: dict) -> None:
+        """``seek(state["cursor"])``, after checking that this feed is the one the position was saved from: a different
+        n_samples, batch, world_size, seed, shuffle, drop_last or steps_per_epoch raises ValueError (the position would mean
+        other samples)."""
+        for key in self._STATE_KEYS:
+            if key not in state or state[key] != getattr(self, key):
+                raise ValueError(f"DeviceFeed.load_state_dict: the state was saved with {key} = {state.get(key)!r}, this feed "
+                                 f"has {key} = {getattr(self, key)!r}: the position would mean other samples")
+        self.seek(state["cursor"])
 
     def launch(self) -> None:
         """One feed, eagerly (the steps call this as the first launch of their ``_step``)."""
