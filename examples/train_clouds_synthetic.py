@@ -3,8 +3,11 @@
 latent mesh shared by the batch) on synthetic ragged batches (tasks.ragged_clouds), engine.TrainStep with lengths and the fused
 Adam (ddp.FlatAdam(zero_grads=True)).
 
-    python examples/train_clouds_synthetic.py [--epochs 2] [--width 972] [--feed] [--clip NORM] [--ema DECAY]
-                                              [--save PATH] [--resume PATH]
+    python examples/train_clouds_synthetic.py [--epochs 2] [--width 972] [--latent shared|fps:M] [--feed] [--clip NORM]
+                                              [--ema DECAY] [--save PATH] [--resume PATH]
+
+`--latent fps:M`: tasks.pit_cloud_fps instead - every cloud gets a latent mesh of its own, M of its points chosen by
+farthest-point sampling (ops.farthest_point_sample: one launch inside the captured step, on the clouds the step was fed).
 
 The step is captured once for the padded width; every batch then brings its own point counts through
 ``set_batch(..., len_in=...)`` - the lengths live in a static device tensor the kernels read, so no replay waits for the
@@ -66,6 +69,8 @@ def main():
     ap.add_argument("--batch", type=int, default=10)
     ap.add_argument("--width", type=int, default=972)
     ap.add_argument("--hid", type=int, default=64)
+    ap.add_argument("--latent", default="shared", metavar="shared|fps:M",
+                    help="the latent mesh: one 16 x 16 grid shared by the batch, or M points of each cloud by farthest-point sampling")
     ap.add_argument("--feed", action="store_true", help="device-resident data feed inside the captured steps")
     ap.add_argument("--clip", type=float, default=None, metavar="NORM",
                     help="clip the gradient's global norm and skip non-finite updates inside the captured step")
@@ -76,8 +81,13 @@ def main():
     args = ap.parse_args()
     args.feed = args.feed or args.save is not None or args.resume is not None
     torch.manual_seed(0)
-    mesh_ltt = tasks.grid_mesh_2d(16, True, "cuda").reshape(-1, 2)
-    model = tasks.pit_cloud_latent(2, 1, 1, args.hid, 2, 4, mesh_ltt, 0.02, 0.02).cuda()
+    if args.latent == "shared":
+        mesh_ltt = tasks.grid_mesh_2d(16, True, "cuda").reshape(-1, 2)
+        model = tasks.pit_cloud_latent(2, 1, 1, args.hid, 2, 4, mesh_ltt, 0.02, 0.02).cuda()
+    elif args.latent.startswith("fps:") and args.latent[4:].isdigit() and 1 <= int(args.latent[4:]) <= args.width:
+        model = tasks.pit_cloud_fps(2, 1, 1, args.hid, 2, 4, int(args.latent[4:]), 0.02, 0.02).cuda()
+    else:
+        ap.error(f"--latent {args.latent}: 'shared' or 'fps:M' with 1 <= M <= --width")
     print("parameters:", count_params(model))
     iterations = args.epochs * args.nbatches
     flat = FlatGradients(model.parameters(), flatten_params=True)

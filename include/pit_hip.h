@@ -1155,6 +1155,36 @@ int pit_adam_step_averaged(float* params, float* grads, float* exp_avg, float* e
                            int avg_ramp, long long avg_start, void* stream);
 int pit_exchange_words(void* a, void* b, long n_words, void* stream);
 
+/* ---- Farthest-point sampling of per-sample clouds (an addition to ABI 31; csrc/pit_fps.hip) ----------------------------------------
+ * The reference's cloud model takes the cloud itself as its latent mesh (train_elasticity.py:46), so every processor block is a
+ * dense n x n attention per sample.  Beyond the reference: pit_fps picks m << n points of every cloud by farthest-point sampling,
+ * in ONE launch with one workgroup per sample, so that a captured step can sample the clouds it is fed.  A library built from
+ * this header defines PIT_HAS_FPS; PIT_ABI_VERSION is unchanged (nothing that existed changed).
+ *
+ *   mesh       fp32: sample s holds n rows of space_dim contiguous floats at mesh + s * mesh_bstride (mesh_bstride in elements,
+ *              >= n * space_dim)
+ *   lengths    optional `batch` int32 on the device: the real points of every sample, read on the device and clamped into [1, n];
+ *              NULL: n everywhere.  Rows at and beyond a sample's length are never read (they may hold NaN).
+ *   start      optional `batch` int32 on the device: the first pick of every sample; NULL: start_all.  Clamped into [0, length).
+ *   idx        (batch, m) int32; out_mesh (batch, m, space_dim) fp32; out_len optional `batch` int32
+ * Sample s with L real points p_0 .. p_{L-1}: dist_i = +inf, cur = start; for t = 0 .. min(m, L) - 1:
+ *   idx[t] = cur, out_mesh[t] = p_cur (the same bits);
+ *   d_i = ((p_i0 - p_cur0)^2 + (p_i1 - p_cur1)^2) + ... in fp32, coordinates in ascending order, every operation rounded;
+ *   dist_i = min(dist_i, d_i);  cur = the LOWEST index i < L with the largest dist_i.
+ * Points already chosen have dist 0 and take part like any other: a cloud with fewer than m distinct points repeats points.
+ * out_len[s] = min(m, L); slots t >= out_len[s] hold idx -1 and zero coordinates.  Precondition, not checked: the real
+ * coordinates are finite; whatever they hold, every index is clamped before use and nothing is addressed out of bounds.
+ * The points live in registers: space_dim 1..3 up to PIT_FPS_MAX_POINTS points, space_dim 4..8 up to PIT_FPS_MAX_POINTS_WIDE.
+ * No atomics (the same input gives the same bits), no host synchronisation, no allocation, capturable.
+ * PIT_ERR_NULL for a missing mesh, idx or out_mesh; PIT_ERR_SIZE for batch outside 1..65535, n < 1, m outside [1, n], space_dim
+ * outside 1..PIT_MAX_SPACE_DIM, mesh_bstride < n * space_dim; PIT_ERR_UNSUPPORTED for n beyond the limit of its space_dim.  All
+ * before any launch. */
+#define PIT_HAS_FPS 1
+#define PIT_FPS_MAX_POINTS 16384
+#define PIT_FPS_MAX_POINTS_WIDE 4096
+int pit_fps(const float* mesh, int batch, int n, int space_dim, long mesh_bstride, const int* lengths, const int* start,
+            int start_all, int m, int* idx, float* out_mesh, int* out_len, void* stream);
+
 /* ---- The two slab forms of pit_block_fwd (additions to ABI 31; csrc/pit_block.hip) ------------------------------------------------
  * pit_block_fwd runs 16-row slabs, or - n_head = 2, n_pts = 256, the weights through LDS, and 8 * ceil(batch / 8) * n_pts / 8
  * workgroups no more than the device has CUs (batch <= 8 on MI355X) - 8-row slabs with the two heads stacked in the M dimension of

@@ -189,6 +189,7 @@ SIGNATURES = {
     "pit_eval_metrics_workspace": [_I, _I, _I],
     "pit_eval_metrics": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _L, _P, _L, _L, _I, _P, _P],
     "pit_batch_feed": [_P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _P, _LL, _P, _P, _P, _P],
+    "pit_fps": [_P, _I, _I, _I, _L, _P, _P, _I, _I, _P, _P, _P, _P],
     "pit_instance_norm_fwd": [_P, _L, _L, _I, _I, _I, _F, _P, _P, _P],
     "pit_instance_norm_bwd": [_P, _P, _P, _I, _I, _I, _P, _P],
     "pit_adam_step": [_P, _P, _P, _P, _L, _P, _F, _F, _I, _F, _F, _F, _F, _I, _P, _P],
@@ -219,7 +220,10 @@ ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_
                "pit_eval_metrics_workspace", "pit_eval_metrics",                   # PIT_HAS_EVAL_METRICS
                "pit_batch_feed",                                                   # PIT_HAS_BATCH_FEED
                "pit_adam_guard_parts", "pit_adam_step_guarded",                    # PIT_HAS_GUARDED_ADAM
-               "pit_adam_step_averaged", "pit_exchange_words"}                     # PIT_HAS_AVERAGED_ADAM
+               "pit_adam_step_averaged", "pit_exchange_words",                     # PIT_HAS_AVERAGED_ADAM
+               "pit_fps"}                                                          # PIT_HAS_FPS
+FPS_MAX_POINTS = 16384   # PIT_FPS_MAX_POINTS
+FPS_MAX_POINTS_WIDE = 4096       # PIT_FPS_MAX_POINTS_WIDE (space_dim 4..8)
 GUARD_MAX_PARTS = 256    # PIT_GUARD_MAX_PARTS
 GUARD_STATE_DOUBLES = 10         # PIT_GUARD_STATE_DOUBLES
 FEED_MAX_FIELDS = 8      # PIT_FEED_MAX_FIELDS

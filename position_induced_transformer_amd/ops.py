@@ -7,6 +7,7 @@ CPU or eager-PyTorch path: tensors must live on the GPU and the shared library m
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import math
 import os
@@ -3487,6 +3488,92 @@ def batch_feed(src, dst, state: torch.Tensor, rank: int = 0, world: int = 1, dro
                                    1 if drop_last else 0, 1 if shuffle else 0, _lib.ptr(order), seed, state.data_ptr(),
                                    _lib.ptr(indices), _lib.ptr(n_valid), _lib.stream_ptr())
     _lib.check(rc, "pit_batch_feed")
+
+
+FpsResult = collections.namedtuple("FpsResult", ("idx", "mesh", "lengths"))
+FpsResult.__doc__ = """Result of ``farthest_point_sample``: ``idx`` (b, m) int32 - the picked points, -1 beyond a sample's picks;
+``mesh`` (b, m, space_dim) fp32 - their coordinates (the cloud's bits), zeros beyond; ``lengths`` (b,) int32 - picks per sample,
+min(m, length) - or None when the clouds had no lengths.  A batch-free (n, space_dim) cloud gives results without the batch axis."""
+
+
+def fps_max_points(space_dim: int) -> int:
+    """Largest cloud ``farthest_point_sample`` takes (the points live in registers): PIT_FPS_MAX_POINTS / _WIDE."""
+    return _lib.FPS_MAX_POINTS if int(space_dim) <= 3 else _lib.FPS_MAX_POINTS_WIDE
+
+
+def check_fps_shapes(mesh, n_samples, lengths=None, start=0) -> None:
+    """Shape, dtype and envelope refusals of ``farthest_point_sample``, raised before the device check and before anything is
+    launched."""
+    if not torch.is_tensor(mesh) or mesh.dim() not in (2, 3):
+        raise ValueError("mesh must be a (b, n, space_dim) or (n, space_dim) tensor of point clouds")
+    if mesh.dtype != torch.float32:
+        raise ValueError(f"mesh must be fp32, got {mesh.dtype}")
+    if 0 in mesh.shape:
+        raise ValueError(f"the mesh has an empty axis: {tuple(mesh.shape)}")
+    n, sdim = mesh.shape[-2], mesh.shape[-1]
+    batch = mesh.shape[0] if mesh.dim() == 3 else 1
+    if sdim > MAX_SPACE_DIM:
+        raise ValueError(f"space_dim {sdim} beyond {MAX_SPACE_DIM} coordinates")
+    if n > fps_max_points(sdim):
+        raise ValueError(f"a cloud of {n} points with {sdim} coordinates is beyond the sampler's {fps_max_points(sdim)} points "
+                         f"(space_dim 1..3: {_lib.FPS_MAX_POINTS}, 4..8: {_lib.FPS_MAX_POINTS_WIDE})")
+    if batch > 65535:
+        raise ValueError(f"a batch of {batch} clouds is beyond 65535")
+    if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or not 1 <= int(n_samples) <= n:
+        raise ValueError(f"n_samples must be an integer in [1, {n}] (the padded width), got {n_samples!r}")
+    for name, t in (("lengths", lengths), ("start", start)):
+        if torch.is_tensor(t):
+            if t.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"{name} must be an int32 or int64 tensor, got {t.dtype}")
+            if t.numel() != batch:
+                raise ValueError(f"{name} must hold one entry per sample: {t.numel()} entries for a batch of {batch}")
+        elif name == "lengths" and t is not None and len(t) != batch:
+            raise ValueError(f"lengths must hold one entry per sample: {len(t)} entries for a batch of {batch}")
+    if not torch.is_tensor(start) and (isinstance(start, bool) or not isinstance(start, (int, np.integer))):
+        raise ValueError(f"start must be an integer or a per-sample integer tensor, got {start!r}")
+
+
+@torch.compiler.disable
+def farthest_point_sample(mesh: torch.Tensor, n_samples: int, lengths=None, start=0) -> FpsResult:
+    """One launch of pit_fps (include/pit_hip.h): ``n_samples`` points of every cloud by farthest-point sampling - from
+    ``start``, repeatedly the point farthest (squared Euclidean distance, fp32) from everything picked so far, the lowest index
+    among equals.  No host synchronisation, capturable; the same input gives the same bits.
+      mesh       (b, n, space_dim) fp32 clouds, or (n, space_dim) for one cloud (results then drop the batch axis);
+                 space_dim 1..3 with n <= 16384, 4..8 with n <= 4096
+      lengths    real points per cloud (``as_lengths``: a device int32 tensor is used as it is, so a captured graph sees in-place
+                 updates); rows beyond are never read.  A cloud shorter than ``n_samples`` gives ``lengths[s]`` picks.
+      start      the first pick: an int, or a per-sample int tensor; clamped into the cloud
+    Nothing differentiates through the choice: the result carries no autograd graph (gather ``mesh`` by ``idx`` for that)."""
+    check_fps_shapes(mesh, n_samples, lengths, start)
+    if not mesh.is_cuda:
+        raise RuntimeError("position_induced_transformer_amd: the PiT hot path runs on the HIP device only; "
+                           "got a CPU tensor (move the model and its inputs to 'cuda')")
+    single = mesh.dim() == 2
+    src = (mesh.unsqueeze(0) if single else mesh).detach()
+    b, n, sdim = src.shape
+    m = int(n_samples)
+    if src.stride(2) != 1 or src.stride(1) != sdim or (b > 1 and src.stride(0) < n * sdim):
+        src = src.contiguous()
+    bstride = src.stride(0) if b > 1 else n * sdim
+    len_t = None if lengths is None else as_lengths(lengths, src.device, b)
+    start_t, start_all = None, 0
+    if torch.is_tensor(start):
+        start_t = start.detach().reshape(-1)
+        if start_t.dtype != torch.int32 or start_t.device != src.device or not start_t.is_contiguous():
+            start_t = start_t.to(device=src.device, dtype=torch.int32).contiguous()
+    else:
+        start_all = int(min(max(int(start), 0), n - 1))
+    idx = torch.empty((b, m), device=src.device, dtype=torch.int32)
+    out = torch.empty((b, m, sdim), device=src.device, dtype=torch.float32)
+    out_len = None if len_t is None else torch.empty((b,), device=src.device, dtype=torch.int32)
+    if _capturing():
+        _pin(*[o for o in (src, len_t, start_t) if o is not None])
+    rc = _lib.lib().pit_fps(src.data_ptr(), b, n, sdim, bstride, _lib.ptr(len_t), _lib.ptr(start_t), start_all, m,
+                            idx.data_ptr(), out.data_ptr(), _lib.ptr(out_len), _lib.stream_ptr())
+    _lib.check(rc, "pit_fps")
+    if single:
+        return FpsResult(idx[0], out[0], None if out_len is None else out_len[0])
+    return FpsResult(idx, out, out_len)
 
 
 class _InstanceNorm(torch.autograd.Function):

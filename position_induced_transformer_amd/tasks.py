@@ -152,6 +152,59 @@ class pit_cloud_latent(P.pit):
         return self.decoder(mesh_ltt, ltt, mesh_out, len_out=len_out).reshape(*size, self.out_dim)
 
 
+class pit_cloud_fps(P.pit):
+    """Per-sample clouds on a latent mesh chosen per cloud FROM the cloud: ``n_latent`` points by farthest-point sampling
+    (ops.farthest_point_sample - one launch inside the step, so a captured step samples the clouds it is fed).  What
+    ``pit_naca.ltt_mesh`` does with strides on a structured grid, for clouds that have no structure to stride over: the
+    processor's dense self-attention runs on n_latent x n_latent instead of n x n per sample.  ``func_in`` is fed to the
+    encoder as it is (``in_dim`` channels, coordinates included if wanted, as in train_elasticity.py:39)."""
+
+    def __init__(self, space_dim, in_dim, out_dim, hid_dim, n_head, n_blocks, n_latent, en_loc, de_loc, start=0):
+        super().__init__(space_dim, in_dim, out_dim, hid_dim, n_head, n_blocks, None, en_loc, de_loc)
+        if isinstance(n_latent, bool) or not isinstance(n_latent, (int, np.integer)) or n_latent < 1:
+            raise ValueError(f"n_latent must be a positive integer, got {n_latent!r}")
+        self.n_latent = int(n_latent)
+        self.start = start
+        self.last_latent = None
+        self.en_layer = P.kaiming_mlp(self.n_head * self.in_dim, self.hid_dim, self.hid_dim)
+
+    def forward(self, mesh_in, func_in, mesh_out, len_in=None, len_out=None):
+        """``mesh_in`` (b, n_in, space_dim) / ``mesh_out`` (b, n_out, space_dim): the clouds and the query points, padded;
+        ``len_in`` / ``len_out``: their point counts (None = full width; ``len_in`` alone serves both when ``mesh_out`` IS
+        ``mesh_in``).  The latent mesh is the sampling of ``mesh_in`` under ``len_in``: a cloud shorter than ``n_latent`` has
+        as many latent points as it has points.  Without lengths the plain per-sample path runs (any math mode; then
+        ``n_latent <= n_in``), and a mesh that requires grad receives its gradient through the chosen points (the choice
+        itself is a constant).  ``last_latent``: the ``ops.FpsResult`` of this call.  Padded rows of the result are finite
+        and meaningless: mask them, e.g. with ``RelLpNorm(...)(true, pred, lengths)``."""
+        if not torch.is_tensor(mesh_in) or mesh_in.dim() != 3:
+            raise ValueError("pit_cloud_fps needs per-sample (batch, n, space_dim) clouds")
+        if len_out is None and len_in is not None and mesh_out is mesh_in:
+            len_out = len_in
+        ragged = len_in is not None or len_out is not None
+        if ragged:
+            if len_in is None or len_out is None:
+                raise ValueError("pit_cloud_fps: a ragged batch needs len_in (and len_out, unless mesh_out is mesh_in)")
+            ops.check_ragged("euclid", mesh_out, mesh_in)              # (before anything is launched)
+            len_in = ops.as_lengths(len_in, mesh_in.device, mesh_in.shape[0])
+        else:
+            self._mesh_grad(mesh_in, mesh_out)
+        latent = ops.farthest_point_sample(mesh_in, self.n_latent, len_in, self.start)
+        self.last_latent = latent
+        size = mesh_out.shape[:-1]
+        if ragged:
+            ltt, len_ltt = latent.mesh, latent.lengths
+            f = self.encoder(mesh_in, func_in, ltt, len_in=len_in, len_ltt=len_ltt)
+            f = self.processor(f, ltt, len_ltt=len_ltt)
+            return self.decoder(ltt, f, mesh_out, len_ltt=len_ltt, len_out=len_out).reshape(*size, self.out_dim)
+        ltt = latent.mesh
+        if torch.is_grad_enabled() and mesh_in.requires_grad:
+            # the same bits as latent.mesh, as a differentiable function of mesh_in
+            ltt = torch.gather(mesh_in, 1, latent.idx.long().unsqueeze(-1).expand(-1, -1, mesh_in.shape[-1]))
+        f = self.encoder(mesh_in, func_in, ltt)
+        f = self.processor(f, ltt)
+        return self.decoder(ltt, f, mesh_out).reshape(*size, self.out_dim)
+
+
 class pit_naca(P.pit):
     """train_naca.py:17-65: latent mesh = strided sub-grid of the body-fitted output grid."""
 
