@@ -3,8 +3,8 @@
 latent mesh shared by the batch) on synthetic ragged batches (tasks.ragged_clouds), engine.TrainStep with lengths and the fused
 Adam (ddp.FlatAdam(zero_grads=True)).
 
-    python examples/train_clouds_synthetic.py [--epochs 2] [--width 972] [--latent shared|fps:M] [--feed] [--clip NORM]
-                                              [--ema DECAY] [--save PATH] [--resume PATH]
+    python examples/train_clouds_synthetic.py [--epochs 2] [--width 972] [--latent shared|fps:M] [--feed] [--points M]
+                                              [--clip NORM] [--ema DECAY] [--save PATH] [--resume PATH]
 
 `--latent fps:M`: tasks.pit_cloud_fps instead - every cloud gets a latent mesh of its own, M of its points chosen by
 farthest-point sampling (ops.farthest_point_sample: one launch inside the captured step, on the clouds the step was fed).
@@ -20,6 +20,12 @@ synchronisation.
 `--feed`: the clouds, their functions, targets and lengths stay on the device as one dataset, and the captured steps gather
 their own shuffled batches from it (engine.DeviceFeed: meshes, functions, targets and the int32 lengths in one launch at the head
 of the graph); an epoch is `steps_per_epoch` bare replays.
+
+`--points M` (implies `--feed`): every training step sees a random subset of M points of each cloud, drawn by the feed's launch
+(engine.DeviceFeed(subsample=True); a new subset per cloud in every epoch, the same one for mesh, function and target).  When M
+fits the shortest cloud of the dataset the step is built WITHOUT lengths - a rectangular batch on the dense per-sample kernels -
+otherwise with lengths, which then receive min(M, length).  The per-epoch evaluation runs on the full clouds, unchanged: the
+model does not depend on the discretisation, so the subset is an estimate of the same loss at a fraction of the cost.
 
 `--clip NORM`: the guarded step (ddp.GuardedAdam) instead of FlatAdam - the gradient's global norm clipped at NORM, updates with
 a non-finite gradient skipped, and the epoch's `step.health()` line printed (one read of the device state per epoch).
@@ -72,6 +78,8 @@ def main():
     ap.add_argument("--latent", default="shared", metavar="shared|fps:M",
                     help="the latent mesh: one 16 x 16 grid shared by the batch, or M points of each cloud by farthest-point sampling")
     ap.add_argument("--feed", action="store_true", help="device-resident data feed inside the captured steps")
+    ap.add_argument("--points", type=int, default=None, metavar="M",
+                    help="train on a random subset of M points of each cloud, drawn inside the captured step (implies --feed)")
     ap.add_argument("--clip", type=float, default=None, metavar="NORM",
                     help="clip the gradient's global norm and skip non-finite updates inside the captured step")
     ap.add_argument("--ema", type=float, default=None, metavar="DECAY",
@@ -79,7 +87,9 @@ def main():
     ap.add_argument("--save", default=None, metavar="PATH", help="write step.state_dict() after every epoch (implies --feed)")
     ap.add_argument("--resume", default=None, metavar="PATH", help="load a saved state after the capture and go on (implies --feed)")
     args = ap.parse_args()
-    args.feed = args.feed or args.save is not None or args.resume is not None
+    args.feed = args.feed or args.save is not None or args.resume is not None or args.points is not None
+    if args.points is not None and not 1 <= args.points <= args.width:
+        ap.error(f"--points {args.points}: 1 <= M <= --width")
     torch.manual_seed(0)
     if args.latent == "shared":
         mesh_ltt = tasks.grid_mesh_2d(16, True, "cuda").reshape(-1, 2)
@@ -101,9 +111,21 @@ def main():
         opt = FlatAdam(flat, lr=1e-3, cosine_t_max=iterations, zero_grads=True)
     # the static buffers of the captured step: the first batch, the query points are the clouds themselves
     mesh, func, target, lens, _ = next(batches(1, args.batch, args.width, seed=1))
-    step = TrainStep(model, (mesh, func, mesh, target), 1, 2, optimizer=opt, flat=flat, len_in=lens)
-    if args.feed:
-        feed = DeviceFeed(step, dataset(batches(args.nbatches, args.batch, args.width, seed=2)), shuffle=True, seed=0)
+    if args.points is None:
+        step = TrainStep(model, (mesh, func, mesh, target), 1, 2, optimizer=opt, flat=flat, len_in=lens)
+        if args.feed:
+            feed = DeviceFeed(step, dataset(batches(args.nbatches, args.batch, args.width, seed=2)), shuffle=True, seed=0)
+    else:
+        # static buffers of M points; the feed fills them with a subset of every cloud.  Lengths only if a cloud is shorter
+        data = dataset(batches(args.nbatches, args.batch, args.width, seed=2))
+        shortest = int(data["len_in"].min())
+        cut = mesh[:, :args.points].contiguous()
+        kw = {"len_in": [args.points] * args.batch} if shortest < args.points else {}
+        step = TrainStep(model, (cut, func[:, :args.points].contiguous(), cut, target[:, :args.points].contiguous()), 1, 2,
+                         optimizer=opt, flat=flat, **kw)
+        feed = DeviceFeed(step, data, shuffle=True, seed=0, subsample=True)
+        print(f"training on {args.points} of up to {args.width} points per cloud (shortest cloud {shortest}): a step "
+              f"{'with' if kw else 'without'} lengths")
     step.capture()
     if guarded:
         step.health(reset=True)                                      # (the warm-up passes of the capture are not this epoch's)

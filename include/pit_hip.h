@@ -1058,6 +1058,53 @@ int pit_batch_feed(const void* const* src, void* const* dst, const long* row_byt
                    const int* order, long long seed, long long* state, int* indices, int* n_valid,
                    void* stream);
 
+/* ---- A random subset of each cloud's points, drawn by the feed (an addition to ABI 31; csrc/pit_feed.hip) -------------------------
+ * The reference loops hand every step the whole cloud of each sample (train_elasticity.py:64,86-88: the loop over a shuffled
+ * DataLoader, x, ext, y = x.cuda(), ext.cuda(), y.cuda() and the forward on all of the cloud's points). pit_batch_feed_points is pit_batch_feed
+ * with one more thing done in the same launch: of every sample it delivers a random subset of the cloud's points, the same
+ * subset for every field of the cloud, a new one in every epoch - so a step trains on m points of clouds that hold n >= m, the
+ * batch is rectangular whatever the clouds' lengths are, and the subset is a function of (seed, epoch, sample, group) that
+ * engine.feed_points restates on the host.  pit_batch_feed and its kernel are untouched.  A library built from this header defines
+ * PIT_HAS_FEED_POINTS; PIT_ABI_VERSION is unchanged (nothing that existed changed).
+ *
+ *   src, dst, bytes, kind   HOST arrays of n_fields entries (1..PIT_FEED_MAX_FIELDS), passed to the kernel by value.  kind[f]:
+ *              PIT_FEED_WHOLE_ROW   pit_batch_feed's field: n_samples rows of bytes[f] bytes, copied whole
+ *              PIT_FEED_POINTS_G0/_G1   a point field of group g = 0 / 1: n_samples rows of n_g points of bytes[f] bytes at src[f],
+ *                                   `batch` rows of m_g points of bytes[f] bytes at dst[f]
+ *              bytes[f] is a positive multiple of 4 and the pointers are 4-byte aligned: raw words of any dtype (NaN payloads survive)
+ *   n0, m0, n1, m1   source and destination widths of the two groups, 1 <= m_g <= n_g (a group without fields: pass 0, 0)
+ *   len_src0/1 optional n_samples int32 on the device: the number of real points of every sample's cloud
+ *   len_dst0/1 optional `batch` int32 on the device: receives M of every slot (the static lengths of a ragged step)
+ *   points0/1  optional (batch, m_g) int32 on the device: the source point behind every destination point, -1 beyond M
+ *   everything from n_samples on: as in pit_batch_feed, with the same meaning, cursor and ticket rule.
+ * Slot s holds the sample idx that pit_batch_feed would choose with the same arguments and cursor (epoch e).  Then, per group g:
+ *   L = clamp(len_src_g[idx], 1, n_g) (n_g without len_src_g);  M = min(m_g, L)
+ *   key = seed XOR (((idx + 1) * 0x9E3779B97F4A7C15 + g * 0xD1B54A32D192ED03) mod 2^64)
+ *   destination point k < M of every field of the group = source point feistel(L, key, e)(k)      (the keyed permutation above,
+ *                                   with n = L and key in the place of seed)
+ *   destination points k >= M = zero words;  len_dst_g[s] = M;  points_g[s][k] = the source point, -1 for k >= M
+ * Source points >= L are never read (they may hold NaN): every source access goes through a buffer resource that spans exactly
+ * the sample's L points of that field.  L <= m_g: all of the cloud's points arrive, permuted.  Two groups of one sample, two
+ * samples and two epochs have different keys; a sample that `order` repeats within an epoch repeats its subset.  The subset
+ * arrives in permutation order, not sorted.
+ * Refusals, all before any launch and in this order: PIT_ERR_NULL for a missing src, dst, bytes, kind or state; PIT_ERR_SIZE for
+ * n_fields outside 1..PIT_FEED_MAX_FIELDS; PIT_ERR_NULL for a null entry of src or dst; PIT_ERR_SIZE for n_samples <= 0,
+ * batch <= 0, batch > 65535, world <= 0, rank outside [0, world), drop_last or shuffle not 0 or 1, a kind[f] outside 0..2, a
+ * bytes[f] that is not a positive multiple of 4, a src[f] or dst[f] that is not 4-byte aligned, a point field whose group has no
+ * widths (n_g < 1), a group with fields and m_g < 1 or m_g > n_g, a length or point-table pointer that is not 4-byte aligned or
+ * that belongs to a group without fields, drop_last with n_samples < batch*world; PIT_ERR_UNSUPPORTED for n_samples > 2^31 - 1
+ * and for a sample's field - bytes[f], n_g * bytes[f] for a point field - beyond PIT_FEED_MAX_ROW_BYTES. */
+#define PIT_HAS_FEED_POINTS 1
+#define PIT_FEED_WHOLE_ROW 0
+#define PIT_FEED_POINTS_G0 1
+#define PIT_FEED_POINTS_G1 2
+int pit_batch_feed_points(const void* const* src, void* const* dst, const long* bytes, const int* kind, int n_fields,
+                          int n0, int m0, int n1, int m1, const int* len_src0, const int* len_src1,
+                          int* len_dst0, int* len_dst1, int* points0, int* points1,
+                          long n_samples, int batch, int rank, int world, int drop_last, int shuffle,
+                          const int* order, long long seed, long long* state, int* indices, int* n_valid,
+                          void* stream);
+
 /* ---- The guarded optimizer step (an addition to ABI 31; csrc/pit_optim.hip) ------------------------------------------------------
  * The reference loops run Adam behind CosineAnnealingLR and read loss.item() every step (train_darcy.py:115-116,131-134): a
  * diverging run is seen on the host the moment it happens.  A captured step has no such look, and pit_adam_step consumes whatever

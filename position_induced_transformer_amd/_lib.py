@@ -189,6 +189,8 @@ SIGNATURES = {
     "pit_eval_metrics_workspace": [_I, _I, _I],
     "pit_eval_metrics": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _L, _P, _L, _L, _I, _P, _P],
     "pit_batch_feed": [_P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _P, _LL, _P, _P, _P, _P],
+    "pit_batch_feed_points": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P, _LL, _P, _P, _P,
+                              _P],
     "pit_fps": [_P, _I, _I, _I, _L, _P, _P, _I, _I, _P, _P, _P, _P],
     "pit_instance_norm_fwd": [_P, _L, _L, _I, _I, _I, _F, _P, _P, _P],
     "pit_instance_norm_bwd": [_P, _P, _P, _I, _I, _I, _P, _P],
@@ -221,13 +223,15 @@ ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_
                "pit_batch_feed",                                                   # PIT_HAS_BATCH_FEED
                "pit_adam_guard_parts", "pit_adam_step_guarded",                    # PIT_HAS_GUARDED_ADAM
                "pit_adam_step_averaged", "pit_exchange_words",                     # PIT_HAS_AVERAGED_ADAM
-               "pit_fps"}                                                          # PIT_HAS_FPS
+               "pit_fps",                                                          # PIT_HAS_FPS
+               "pit_batch_feed_points"}                                            # PIT_HAS_FEED_POINTS
 FPS_MAX_POINTS = 16384   # PIT_FPS_MAX_POINTS
 FPS_MAX_POINTS_WIDE = 4096       # PIT_FPS_MAX_POINTS_WIDE (space_dim 4..8)
 GUARD_MAX_PARTS = 256    # PIT_GUARD_MAX_PARTS
 GUARD_STATE_DOUBLES = 10         # PIT_GUARD_STATE_DOUBLES
 FEED_MAX_FIELDS = 8      # PIT_FEED_MAX_FIELDS
 FEED_MAX_ROW_BYTES = 1 << 30     # PIT_FEED_MAX_ROW_BYTES
+FEED_WHOLE_ROW, FEED_POINTS_G0, FEED_POINTS_G1 = 0, 1, 2         # PIT_FEED_WHOLE_ROW, PIT_FEED_POINTS_G0, PIT_FEED_POINTS_G1
 EVAL_STATE_DOUBLES = 8   # PIT_EVAL_STATE_DOUBLES
 EVAL_MAX_PARTS = 64      # PIT_EVAL_MAX_PARTS
 DISTLIST_CHUNK = 512   # PIT_DISTLIST_CHUNK

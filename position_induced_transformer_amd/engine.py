@@ -638,18 +638,9 @@ def _fmix(h):
     return h ^ (h >> 16)
 
 
-def feed_order(n: int, seed: int, epoch: int) -> torch.Tensor:
-    """The keyed permutation of ``range(n)`` that pit_batch_feed applies in epoch ``epoch`` (include/pit_hip.h), restated on the
-    host bit for bit: entry g is the sample at position g of the epoch.  A LongTensor on the CPU; needs no GPU.  Four Feistel
-    rounds with cycle walking: a bijection for every n, not a Fisher-Yates shuffle in quality (pass ``order`` to DeviceFeed for
-    a sampler of your own)."""
+def _keyed_permutation(n: int, seed: int, epoch: int):
+    """The arithmetic of ``feed_order`` (n >= 1, seed below 2^64, epoch below 2^32): a uint64 numpy array."""
     import numpy as np
-    n, seed, epoch = int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & _M32
-    if n < 1:
-        raise ValueError("feed_order: n must be positive")
-    hit = _FEED_ORDERS.get((n, seed, epoch))
-    if hit is not None:
-        return hit.clone()
     bits = max(2, (n - 1).bit_length())
     bits += bits & 1
     half = bits // 2
@@ -666,11 +657,43 @@ def feed_order(n: int, seed: int, epoch: int) -> torch.Tensor:
         v = (left << np.uint64(half)) | right
         x[todo] = v
         todo = todo[v >= n]
-    out = torch.from_numpy(x.astype(np.int64))
+    return x
+
+
+def feed_order(n: int, seed: int, epoch: int) -> torch.Tensor:
+    """The keyed permutation of ``range(n)`` that pit_batch_feed applies in epoch ``epoch`` (include/pit_hip.h), restated on the
+    host bit for bit: entry g is the sample at position g of the epoch.  A LongTensor on the CPU; needs no GPU.  Four Feistel
+    rounds with cycle walking: a bijection for every n, not a Fisher-Yates shuffle in quality (pass ``order`` to DeviceFeed for
+    a sampler of your own)."""
+    import numpy as np
+    n, seed, epoch = int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & _M32
+    if n < 1:
+        raise ValueError("feed_order: n must be positive")
+    hit = _FEED_ORDERS.get((n, seed, epoch))
+    if hit is not None:
+        return hit.clone()
+    out = torch.from_numpy(_keyed_permutation(n, seed, epoch).astype(np.int64))
     if len(_FEED_ORDERS) >= 8:
         _FEED_ORDERS.pop(next(iter(_FEED_ORDERS)))
     _FEED_ORDERS[(n, seed, epoch)] = out
     return out.clone()
+
+
+def feed_points(length: int, m: int, seed: int, epoch: int, sample: int, group: int = 0) -> torch.Tensor:
+    """The points of a cloud that pit_batch_feed_points delivers (include/pit_hip.h), restated on the host bit for bit: of
+    sample ``sample``'s cloud of ``length`` real points, in epoch ``epoch``, for point group ``group`` (0: mesh_in / func_in,
+    1: mesh_out / target), the ``min(m, length)`` source points in the order they arrive.  It is the head of
+    ``feed_order(length, key, epoch)`` with ``key = seed ^ ((sample + 1) * 0x9E3779B97F4A7C15 + group * 0xD1B54A32D192ED03)``
+    (mod 2^64): a function of (seed, epoch, sample, group) alone, so a resumed run draws the same subsets.  A LongTensor on
+    the CPU; needs no GPU.  (Not kept in ``feed_order``'s cache: every sample has a key of its own.)"""
+    length, m, sample, group = int(length), int(m), int(sample), int(group)
+    if length < 1 or m < 1:
+        raise ValueError("feed_points: length and m must be positive")
+    if sample < 0 or group not in (0, 1):
+        raise ValueError("feed_points: sample must not be negative and group is 0 or 1")
+    key = (int(seed) ^ ((sample + 1) * 0x9E3779B97F4A7C15 + group * 0xD1B54A32D192ED03)) & 0xFFFFFFFFFFFFFFFF
+    import numpy as np
+    return torch.from_numpy(_keyed_permutation(length, key, int(epoch) & _M32)[:min(m, length)].astype(np.int64))
 
 
 class DeviceFeed:
@@ -689,12 +712,24 @@ class DeviceFeed:
     ``drop_last=False`` (evaluation steps only: they have ``n_valid``) the last step of an epoch is partly filled: the launch
     writes the step's ``n_valid`` and fills the remaining slots with samples from the head of the order, so the forward never
     reads garbage.  Data-parallel: global position ``(i * world_size + rank) * batch + s`` for slot s of step i, so the ranks of
-    one step hold disjoint runs of the same order.  Attach the feed BEFORE ``capture()``."""
+    one step hold disjoint runs of the same order.  Attach the feed BEFORE ``capture()``.
+
+    ``subsample=True``: every step sees a random subset of each cloud's points (ops.batch_feed_points, still one launch).
+    ``mesh_in``, ``func_in``, ``mesh_out`` and ``target`` are then point fields: data ``(N, n, ...)`` against the step's static
+    ``(batch, m, ...)`` with ``m <= n``; mesh_in / func_in form group 0, mesh_out / target group 1 (one group, which ``target``
+    follows, when the step's mesh_out shares storage with its mesh_in), and every field of a group receives the same subset -
+    ``feed_points(length, m, seed, epoch, sample, group)``, new in every epoch, in permutation order (the layers do not depend
+    on the order of the points except in the order of their sums; ``pit_cloud_fps(start=0)`` then starts from a random point
+    of the cloud).  ``len_in`` / ``len_out`` in ``data`` are the SOURCE lengths: points beyond them are never read.  A step built
+    with lengths receives ``min(m, length)`` per slot (``m`` when the data has no lengths) and zero rows beyond; a step built
+    without needs ``m`` points in the shortest cloud, checked once here.  A sample that a caller's ``order`` repeats within an
+    epoch repeats its subset.  ``points_in`` / ``points_out``: (batch, m) int32, the source point behind every point of the
+    last launch (-1 beyond the length); ``expected_points`` restates them on the host."""
 
     FIELDS = ("func_in", "target", "mesh_in", "mesh_out", "len_in", "len_out")
 
     def __init__(self, step, data, shuffle: bool = True, seed: int = 0, drop_last: bool = True, rank: Optional[int] = None,
-                 world_size: Optional[int] = None, order=None):
+                 world_size: Optional[int] = None, order=None, subsample: bool = False):
         if getattr(step, "graph", None) is not None:
             raise ValueError("DeviceFeed: this step has already been captured (its graph holds no feed launch); attach the feed first")
         if getattr(step, "_feed", None) is not None:
@@ -706,8 +741,16 @@ class DeviceFeed:
             step._check_mesh_update(data.get("mesh_in"), data.get("mesh_out"))
         except ValueError as e:
             raise ValueError(f"DeviceFeed: {e}") from None
+        self.subsample = bool(subsample)
+        if self.subsample:
+            if getattr(step, "affine", None) is not None:
+                raise ValueError("DeviceFeed(subsample=True): a step with pred_affine - a per-pixel affine has no meaning on a "
+                                 "subset of the points")
+            if getattr(step, "pred", None) is not None:
+                raise ValueError("DeviceFeed(subsample=True): EvalStep(store_pred=True) would store the predictions of another "
+                                 "subset of the points in every pass")
         for name in ("len_in", "len_out"):
-            if name in data and getattr(step, name) is None:
+            if name in data and getattr(step, name) is None and not self.subsample:
                 raise ValueError(f"DeviceFeed: field {name} on a step that was built without {name}")
         self.n_valid = getattr(step, "n_valid", None)
         if not drop_last and self.n_valid is None:
@@ -715,15 +758,38 @@ class DeviceFeed:
                              "partly filled last batch would enter the loss")
         self.src, self.dst, self.names = [], [], []
         n = None
+        one_cloud = self.subsample and (step.mesh_out is step.mesh_in or (step.mesh_out.data_ptr() == step.mesh_in.data_ptr()
+                                                                           and step.mesh_out.shape == step.mesh_in.shape))
+        self.kinds, self._widths = [], [None, None]                    # (subsample) per field its kind; per group (n_g, m_g)
         for name in self.FIELDS:
-            if name not in data:
+            if name not in data or (self.subsample and name in ("len_in", "len_out")):
                 continue
             t, static = data[name], getattr(step, name)
             if not torch.is_tensor(t) or t.dim() < 1 or t.shape[0] < 1:
                 raise ValueError(f"DeviceFeed: field {name} must be a tensor with a leading sample axis")
             if not static.is_contiguous() or not t.is_contiguous():
                 raise ValueError(f"DeviceFeed: field {name} and its static buffer must be contiguous")
-            if t.dtype != static.dtype or t.shape[1:] != static.shape[1:] or t.device != static.device:
+            if self.subsample:
+                group = 0 if one_cloud or name in ("mesh_in", "func_in") else 1
+                mesh = ("mesh_in", "mesh_out") if one_cloud else (("mesh_in",), ("mesh_out",))[group]
+                if not any(k in data for k in mesh):
+                    raise ValueError(f"DeviceFeed(subsample=True): point field {name} without {mesh[0]} in data - the subset of "
+                                     "the function's points must be the subset of the mesh's")
+                if t.dim() < 2 or t.dim() != static.dim() or t.dtype != static.dtype or t.shape[2:] != static.shape[2:] \
+                        or t.device != static.device:
+                    raise ValueError(f"DeviceFeed: field {name} has points {tuple(t.shape[2:])} {t.dtype} on {t.device}, the "
+                                     f"step's static buffer {tuple(static.shape[2:])} {static.dtype} on {static.device}")
+                if t.shape[1] < static.shape[1]:
+                    raise ValueError(f"DeviceFeed(subsample=True): field {name} has {t.shape[1]} points, narrower than the step's "
+                                     f"{static.shape[1]}")
+                width = (int(t.shape[1]), int(static.shape[1]))
+                if self._widths[group] not in (None, width):
+                    raise ValueError(f"DeviceFeed(subsample=True): field {name} has {width[0]} points against the step's "
+                                     f"{width[1]}, the fields of its cloud before it {self._widths[group][0]} against "
+                                     f"{self._widths[group][1]}")
+                if (static[0, 0].numel() * static.element_size()) % 4 or static[0, 0].numel() == 0:
+                    raise ValueError(f"DeviceFeed: field {name}: points are copied as whole 4-byte words")
+            elif t.dtype != static.dtype or t.shape[1:] != static.shape[1:] or t.device != static.device:
                 raise ValueError(f"DeviceFeed: field {name} has rows {tuple(t.shape[1:])} {t.dtype} on {t.device}, the step's static "
                                  f"buffer {tuple(static.shape[1:])} {static.dtype} on {static.device}")
             if (static[0].numel() * static.element_size()) % 4 or static[0].numel() == 0:
@@ -740,8 +806,13 @@ class DeviceFeed:
             self.src.append(t)
             self.dst.append(static)
             self.names.append(name)
+            if self.subsample:
+                self.kinds.append(1 + group)
+                self._widths[group] = width
         if len(self.src) > 8:
             raise ValueError("DeviceFeed: at most 8 fields")
+        if self.subsample and not self.src:
+            raise ValueError("DeviceFeed(subsample=True): data holds lengths only")
         if rank is None or world_size is None:
             import torch.distributed as dist
             up = dist.is_available() and dist.is_initialized()
@@ -768,8 +839,45 @@ class DeviceFeed:
         self.state = ops.new_feed_state(dev)                           # the cursor and the arrival ticket
         self.cursor = self.state[0]
         self.indices = torch.zeros(self.batch, device=dev, dtype=torch.int32)
+        self.points_in = self.points_out = None
+        if self.subsample:
+            self._init_subsample(step, data, one_cloud, dev)
         self.step = step
         step._feed = self
+
+    def _init_subsample(self, step, data, one_cloud: bool, dev) -> None:
+        """The source lengths, the static lengths the launch writes and the index tables of a subsampling feed."""
+        self._len_src, self._len_dst, self._host_len = [None, None], [None, None], [None, None]
+        for g, name in enumerate(("len_in", "len_out")):
+            lengths, static = data.get(name), getattr(step, name)
+            if g == 1 and one_cloud and (lengths is not None or static is not None):
+                raise ValueError("DeviceFeed(subsample=True): len_out on a step whose mesh_out is its mesh_in - the one cloud has "
+                                 "one length, len_in")
+            if self._widths[g] is None:
+                if lengths is not None:
+                    raise ValueError(f"DeviceFeed(subsample=True): {name} without a point field of its cloud in data")
+                continue
+            n_g, m_g = self._widths[g]
+            if lengths is not None:
+                if not torch.is_tensor(lengths) or lengths.shape != (self.n_samples,) or lengths.is_floating_point() \
+                        or lengths.device != dev:
+                    raise ValueError(f"DeviceFeed: field {name} must hold {self.n_samples} integer lengths on {dev}")
+                if static is None:
+                    # a rectangular step: every cloud must fill it (one read of the lengths, here and never again)
+                    shortest = int(lengths.clamp(1, n_g).min())
+                    if shortest < m_g:
+                        raise ValueError(f"DeviceFeed(subsample=True): the shortest cloud of {name} has {shortest} points, the "
+                                         f"step takes {m_g}; build the step with {name}= (it then receives min({m_g}, length) "
+                                         "points per sample) or with fewer points")
+                self._len_src[g] = lengths.to(torch.int32).contiguous()
+            self._len_dst[g] = static
+            table = torch.full((self.batch, m_g), -1, device=dev, dtype=torch.int32)
+            if g == 0:
+                self.points_in = table
+            else:
+                self.points_out = table
+        self.n_in, self.m_in = self._widths[0] or (0, 0)
+        self.n_out, self.m_out = self._widths[1] or (0, 0)
 
     def seek(self, k: int) -> None:
         """The next launch is feed number ``k`` (epoch k // steps_per_epoch, step k % steps_per_epoch): a device fill, no
@@ -780,19 +888,31 @@ class DeviceFeed:
 
     _STATE_KEYS = ("n_samples", "batch", "world_size", "seed", "shuffle", "drop_last", "steps_per_epoch")
 
+    _SUBSAMPLE_KEYS = ("subsample", "n_in", "m_in", "n_out", "m_out")
+
+    def _state_keys(self):
+        return self._STATE_KEYS + (self._SUBSAMPLE_KEYS if self.subsample else ())
+
     def state_dict(self) -> dict:
         """The feed's position - ``cursor``, the number of feeds so far (one device->host read) - and what gives it its meaning:
         n_samples, batch, world_size, seed, shuffle, drop_last and steps_per_epoch, as plain numbers.  A caller-supplied
-        ``order`` is NOT saved: a run that resumes with another ``order`` reads other samples at the same position."""
+        ``order`` is NOT saved: a run that resumes with another ``order`` reads other samples at the same position.  A
+        subsampling feed adds ``subsample`` and the source and destination widths of its clouds (n_in, m_in, n_out, m_out; 0
+        for a cloud it does not feed): the subsets are a function of (seed, epoch, sample, group), so the position is all a
+        resumed run needs to draw the same ones."""
         state = {"cursor": int(self.cursor)}
-        state.update({key: getattr(self, key) for key in self._STATE_KEYS})
+        state.update({key: getattr(self, key) for key in self._state_keys()})
         return state
 
     def load_state_dict(self, state: dict) -> None:
         """``seek(state["cursor"])``, after checking that this feed is the one the position was saved from: a different
         n_samples, batch, world_size, seed, shuffle, drop_last or steps_per_epoch raises ValueError (the position would mean
-        other samples)."""
-        for key in self._STATE_KEYS:
+        other samples).  So does a state saved with ``subsample`` loaded into a feed without, or the reverse, or with other
+        widths."""
+        if bool(state.get("subsample", False)) != self.subsample:
+            raise ValueError(f"DeviceFeed.load_state_dict: the state was saved with subsample = {bool(state.get('subsample', False))!r}, "
+                             f"this feed has subsample = {self.subsample!r}: the position would mean other points")
+        for key in self._state_keys():
             if key not in state or state[key] != getattr(self, key):
                 raise ValueError(f"DeviceFeed.load_state_dict: the state was saved with {key} = {state.get(key)!r}, this feed "
                                  f"has {key} = {getattr(self, key)!r}: the position would mean other samples")
@@ -800,6 +920,11 @@ class DeviceFeed:
 
     def launch(self) -> None:
         """One feed, eagerly (the steps call this as the first launch of their ``_step``)."""
+        if self.subsample:
+            ops.batch_feed_points(self.src, self.dst, self.kinds, self.state, self.rank, self.world_size, self.drop_last,
+                                  self.shuffle, self.order, self.seed, self.indices, self.n_valid, self._len_src, self._len_dst,
+                                  (self.points_in, self.points_out))
+            return
         ops.batch_feed(self.src, self.dst, self.state, self.rank, self.world_size, self.drop_last, self.shuffle, self.order,
                        self.seed, self.indices, self.n_valid)
 
@@ -820,3 +945,25 @@ class DeviceFeed:
             perm = feed_order(n, self.seed, epoch)
             idx = [int(perm[g]) for g in pos]
         return idx, min(max(n - first, 0), self.batch)
+
+    def expected_points(self, cursor: int):
+        """``(points_in, points_out)`` of the launch at ``cursor`` for this rank, restated on the host: per group a list with,
+        for every slot, the LongTensor of source points that arrive (``feed_points`` for the slot's sample of
+        ``expected_indices``, with host copies of the source lengths, read back once); None for a group the feed does not
+        have.  Slot s of the launch holds ``src[idx][points]`` in its first ``len(points)`` rows and zeros beyond."""
+        if not self.subsample:
+            raise ValueError("expected_points: this feed was built without subsample")
+        idx, _ = self.expected_indices(cursor)
+        epoch = max(int(cursor), 0) // self.steps_per_epoch
+        out = []
+        for g in range(2):
+            if self._widths[g] is None:
+                out.append(None)
+                continue
+            n_g, m_g = self._widths[g]
+            if self._len_src[g] is not None and self._host_len[g] is None:
+                self._host_len[g] = self._len_src[g].cpu().tolist()
+            lens = self._host_len[g]
+            out.append([feed_points(min(max(lens[i], 1), n_g) if lens is not None else n_g, m_g, self.seed, epoch, i, g)
+                        for i in idx])
+        return tuple(out)

@@ -3490,6 +3490,99 @@ def batch_feed(src, dst, state: torch.Tensor, rank: int = 0, world: int = 1, dro
     _lib.check(rc, "pit_batch_feed")
 
 
+@torch.compiler.disable
+def batch_feed_points(src, dst, kinds, state: torch.Tensor, rank: int = 0, world: int = 1, drop_last: bool = True,
+                      shuffle: bool = True, order=None, seed: int = 0, indices=None, n_valid=None, len_src=(None, None),
+                      len_dst=(None, None), points=(None, None)) -> None:
+    """One launch of pit_batch_feed_points (include/pit_hip.h): ``batch_feed`` that delivers, of every sample, a random subset
+    of each cloud's points - the same subset for every field of a group, a function of (seed, epoch, sample, group) that
+    ``engine.feed_points`` restates on the host.
+      kinds       per field 0 (a whole row, as in ``batch_feed``), 1 or 2 (a point field of group 0 / 1): ``src[f]``
+                  (n_samples, n_g, ...) against ``dst[f]`` (batch, m_g, ...) with m_g <= n_g, the same trailing shape and dtype; a
+                  point is a whole number of 4-byte words
+      len_src     per group, optional (n_samples,) int32: the real points of every sample's cloud (the rest is never read)
+      len_dst     per group, optional (batch,) int32: receives min(m_g, length) per slot
+      points      per group, optional (batch, m_g) int32: receives the source point of every destination point, -1 beyond
+    Everything else as in ``batch_feed``."""
+    src, dst, kinds = list(src), list(dst), [int(k) for k in kinds]
+    if len(src) != len(dst) or len(src) != len(kinds) or not 1 <= len(src) <= _lib.FEED_MAX_FIELDS:
+        raise ValueError(f"batch_feed_points takes 1..{_lib.FEED_MAX_FIELDS} fields, each with a source, a destination and a kind")
+    len_src, len_dst, points = list(len_src), list(len_dst), list(points)
+    if not len(len_src) == len(len_dst) == len(points) == 2:
+        raise ValueError("batch_feed_points: len_src, len_dst and points hold one entry per group (two)")
+    extra = [state, order, indices, n_valid] + len_src + len_dst + points
+    for t in src + dst + extra:
+        if t is not None and (not torch.is_tensor(t) or not t.is_cuda):
+            raise RuntimeError("position_induced_transformer_amd: the data feed runs on the HIP device only; "
+                               "got a CPU tensor (move the dataset and the step's buffers to 'cuda')")
+    n, batch = src[0].shape[0], dst[0].shape[0]
+    sizes, widths = [], [[0, 0], [0, 0]]                               # per group [n_g, m_g]
+    for a, b, kind in zip(src, dst, kinds):
+        if kind not in (_lib.FEED_WHOLE_ROW, _lib.FEED_POINTS_G0, _lib.FEED_POINTS_G1):
+            raise ValueError(f"batch_feed_points: kind {kind} is none of 0 (whole row), 1, 2 (point field of group 0, 1)")
+        if not a.is_contiguous() or not b.is_contiguous():
+            raise RuntimeError("batch_feed_points: every field and every static buffer must be contiguous")
+        lead = 1 if kind == _lib.FEED_WHOLE_ROW else 2
+        if a.dtype != b.dtype or a.dim() < lead or b.dim() != a.dim() or a.shape[lead:] != b.shape[lead:] or a.shape[0] != n \
+                or b.shape[0] != batch:
+            raise RuntimeError(f"batch_feed_points: a field {tuple(a.shape)} {a.dtype} does not fit its static buffer "
+                               f"{tuple(b.shape)} {b.dtype} ({n} samples, {batch} slots)")
+        unit = a.element_size()
+        for d in a.shape[lead:]:
+            unit *= d
+        if unit <= 0 or unit % 4 or a.data_ptr() % 4 or b.data_ptr() % 4:
+            raise RuntimeError(f"batch_feed_points: rows and points are moved as aligned 4-byte words; got {unit} bytes")
+        row = unit
+        if lead == 2:
+            g = kind - _lib.FEED_POINTS_G0
+            if widths[g] != [0, 0] and widths[g] != [a.shape[1], b.shape[1]]:
+                raise RuntimeError(f"batch_feed_points: the fields of group {g} disagree on the number of points "
+                                   f"({widths[g]} and {[a.shape[1], b.shape[1]]})")
+            widths[g] = [a.shape[1], b.shape[1]]
+            if not 1 <= b.shape[1] <= a.shape[1]:
+                raise RuntimeError(f"batch_feed_points: {b.shape[1]} destination points of {a.shape[1]} source points")
+            row = unit * a.shape[1]
+        if row > _lib.FEED_MAX_ROW_BYTES:
+            raise RuntimeError(f"batch_feed_points: a sample's field of {row} bytes is beyond PIT_FEED_MAX_ROW_BYTES "
+                               f"({_lib.FEED_MAX_ROW_BYTES})")
+        sizes.append(unit)
+    if state.dtype != torch.int64 or state.numel() != 2 or not state.is_contiguous():
+        raise RuntimeError("state must be 2 contiguous int64 values on the HIP device (new_feed_state)")
+    if order is not None and (order.dtype != torch.int32 or order.numel() != n or not order.is_contiguous()):
+        raise RuntimeError(f"order must be {n} contiguous int32 values on the HIP device")
+    if indices is not None and (indices.dtype != torch.int32 or indices.numel() != batch or not indices.is_contiguous()):
+        raise RuntimeError(f"indices must be {batch} contiguous int32 values on the HIP device")
+    if n_valid is not None and (n_valid.dtype != torch.int32 or n_valid.numel() != 1):
+        raise RuntimeError("n_valid must be one int32 value on the HIP device")
+    for g in range(2):
+        for what, t, count in (("len_src", len_src[g], n), ("len_dst", len_dst[g], batch), ("points", points[g], batch * widths[g][1])):
+            if t is None:
+                continue
+            if widths[g] == [0, 0]:
+                raise RuntimeError(f"batch_feed_points: {what}[{g}] without a point field of group {g}")
+            if t.dtype != torch.int32 or t.numel() != count or not t.is_contiguous():
+                raise RuntimeError(f"{what}[{g}] must be {count} contiguous int32 values on the HIP device")
+    if _capturing():
+        _pin(*[o for o in src + dst + extra if o is not None])
+    k = len(src)
+    src_a = (ctypes.c_void_p * k)(*[t.data_ptr() for t in src])
+    dst_a = (ctypes.c_void_p * k)(*[t.data_ptr() for t in dst])
+    size_a = (ctypes.c_long * k)(*sizes)
+    kind_a = (ctypes.c_int * k)(*kinds)
+    seed = int(seed)
+    if not -(1 << 63) <= seed < (1 << 64):
+        raise ValueError("seed must fit 64 bits")
+    seed = seed - (1 << 64) if seed >= (1 << 63) else seed
+    rc = _lib.lib().pit_batch_feed_points(ctypes.cast(src_a, ctypes.c_void_p), ctypes.cast(dst_a, ctypes.c_void_p),
+                                          ctypes.cast(size_a, ctypes.c_void_p), ctypes.cast(kind_a, ctypes.c_void_p), k,
+                                          widths[0][0], widths[0][1], widths[1][0], widths[1][1],
+                                          _lib.ptr(len_src[0]), _lib.ptr(len_src[1]), _lib.ptr(len_dst[0]), _lib.ptr(len_dst[1]),
+                                          _lib.ptr(points[0]), _lib.ptr(points[1]), n, batch, int(rank), int(world),
+                                          1 if drop_last else 0, 1 if shuffle else 0, _lib.ptr(order), seed, state.data_ptr(),
+                                          _lib.ptr(indices), _lib.ptr(n_valid), _lib.stream_ptr())
+    _lib.check(rc, "pit_batch_feed_points")
+
+
 FpsResult = collections.namedtuple("FpsResult", ("idx", "mesh", "lengths"))
 FpsResult.__doc__ = """Result of ``farthest_point_sample``: ``idx`` (b, m) int32 - the picked points, -1 beyond a sample's picks;
 ``mesh`` (b, m, space_dim) fp32 - their coordinates (the cloud's bits), zeros beyond; ``lengths`` (b,) int32 - picks per sample,
