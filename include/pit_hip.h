@@ -1232,6 +1232,36 @@ int pit_exchange_words(void* a, void* b, long n_words, void* stream);
 int pit_fps(const float* mesh, int batch, int n, int space_dim, long mesh_bstride, const int* lengths, const int* start,
             int start_all, int m, int* idx, float* out_mesh, int* out_len, void* stream);
 
+/* ---- Farthest-point sampling of clouds of any size (an addition to ABI 31; csrc/pit_fps_large.hip) -------------------------------
+ * pit_fps keeps a cloud in one workgroup's registers and refuses clouds beyond PIT_FPS_MAX_POINTS.  pit_fps_large is a second
+ * sampler with the SAME semantics, bit for bit (the loop stated above: fp32 distances rounded operation by operation, the lowest
+ * index among equals, lengths and start clamped, -1 / zero slots beyond the picks), for clouds up to PIT_FPS_LARGE_MAX_POINTS points
+ * of 1..PIT_MAX_SPACE_DIM coordinates - one envelope for every space_dim.  The points stay in memory and the running distances in a
+ * workspace; a cloud is cut into slices of slice_points points, one workgroup each, and the hand-off between two picks is a kernel
+ * boundary: m dependent launches of one kernel on a grid of (slices, batch) workgroups, each of which reduces the previous launch's
+ * per-slice candidates itself.  A library built from this header defines PIT_HAS_FPS_LARGE; PIT_ABI_VERSION is unchanged (nothing
+ * that existed changed).
+ *
+ *   mesh .. out_len   as in pit_fps
+ *   slice_points      0: the library's choice (1024 points up to 262144 points, beyond that the multiple of 256 that gives 256
+ *                     slices: never more than 256 slices per cloud); otherwise a multiple of 256 in [256, 65536] - for tests that
+ *                     want several slices at small n, and for tuning.  The result does not depend on it.
+ *   workspace         pit_fps_large_workspace(batch, n, slice_points) bytes on the device, 8-byte aligned; needs no initial
+ *                     contents and holds nothing between calls.  Calls that share a workspace must run one after the other.
+ * The entry accepts small n too (there pit_fps is the single launch and the faster one).  No atomics (the same input gives the same
+ * bits), no grid barrier, no host synchronisation, no allocation, capturable (m kernel nodes).
+ * PIT_ERR_NULL for a missing mesh, idx, out_mesh or workspace; PIT_ERR_SIZE for batch outside 1..65535, n < 1, m outside [1, n],
+ * space_dim outside 1..PIT_MAX_SPACE_DIM, mesh_bstride < n * space_dim, a slice_points that is neither 0 nor a multiple of 256 in
+ * [256, 65536]; PIT_ERR_UNSUPPORTED for n > PIT_FPS_LARGE_MAX_POINTS or m > PIT_FPS_LARGE_MAX_SAMPLES.  In this order, all before
+ * any launch.  pit_fps_large_workspace returns 0 for sizes the entry refuses. */
+#define PIT_HAS_FPS_LARGE 1
+#define PIT_FPS_LARGE_MAX_POINTS 4194304
+#define PIT_FPS_LARGE_MAX_SAMPLES 16384
+long pit_fps_large_workspace(int batch, int n, int slice_points);      /* bytes; 0 for sizes the entry refuses */
+int  pit_fps_large(const float* mesh, int batch, int n, int space_dim, long mesh_bstride, const int* lengths,
+                   const int* start, int start_all, int m, int* idx, float* out_mesh, int* out_len,
+                   int slice_points, void* workspace, void* stream);
+
 /* ---- The two slab forms of pit_block_fwd (additions to ABI 31; csrc/pit_block.hip) ------------------------------------------------
  * pit_block_fwd runs 16-row slabs, or - n_head = 2, n_pts = 256, the weights through LDS, and 8 * ceil(batch / 8) * n_pts / 8
  * workgroups no more than the device has CUs (batch <= 8 on MI355X) - 8-row slabs with the two heads stacked in the M dimension of

@@ -192,6 +192,8 @@ SIGNATURES = {
     "pit_batch_feed_points": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P, _LL, _P, _P, _P,
                               _P],
     "pit_fps": [_P, _I, _I, _I, _L, _P, _P, _I, _I, _P, _P, _P, _P],
+    "pit_fps_large_workspace": [_I, _I, _I],
+    "pit_fps_large": [_P, _I, _I, _I, _L, _P, _P, _I, _I, _P, _P, _P, _I, _P, _P],
     "pit_instance_norm_fwd": [_P, _L, _L, _I, _I, _I, _F, _P, _P, _P],
     "pit_instance_norm_bwd": [_P, _P, _P, _I, _I, _I, _P, _P],
     "pit_adam_step": [_P, _P, _P, _P, _L, _P, _F, _F, _I, _F, _F, _F, _F, _I, _P, _P],
@@ -211,7 +213,7 @@ SIGNATURES = {
 
 LONG_RETURN = {"pit_satt_tiles_elems", "pit_posatt_dmesh_workspace", "pit_mlp_bwd_params_ordered_workspace",
                "pit_mlp_bwd_params_ordered_mfma_workspace", "pit_distmat_bwd_workspace", "pit_distlist_bwd_workspace",
-               "pit_eval_metrics_workspace"}
+               "pit_eval_metrics_workspace", "pit_fps_large_workspace"}
 # entries added to an ABI version after its first release (PIT_HAS_* in the header): a library of the same version built before
 # them lacks the symbols
 ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_workspace", "pit_distlist_bwd",
@@ -224,9 +226,12 @@ ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_
                "pit_adam_guard_parts", "pit_adam_step_guarded",                    # PIT_HAS_GUARDED_ADAM
                "pit_adam_step_averaged", "pit_exchange_words",                     # PIT_HAS_AVERAGED_ADAM
                "pit_fps",                                                          # PIT_HAS_FPS
-               "pit_batch_feed_points"}                                            # PIT_HAS_FEED_POINTS
+               "pit_batch_feed_points",                                            # PIT_HAS_FEED_POINTS
+               "pit_fps_large_workspace", "pit_fps_large"}                         # PIT_HAS_FPS_LARGE
 FPS_MAX_POINTS = 16384   # PIT_FPS_MAX_POINTS
 FPS_MAX_POINTS_WIDE = 4096       # PIT_FPS_MAX_POINTS_WIDE (space_dim 4..8)
+FPS_LARGE_MAX_POINTS = 4194304   # PIT_FPS_LARGE_MAX_POINTS (every space_dim)
+FPS_LARGE_MAX_SAMPLES = 16384    # PIT_FPS_LARGE_MAX_SAMPLES
 GUARD_MAX_PARTS = 256    # PIT_GUARD_MAX_PARTS
 GUARD_STATE_DOUBLES = 10         # PIT_GUARD_STATE_DOUBLES
 FEED_MAX_FIELDS = 8      # PIT_FEED_MAX_FIELDS

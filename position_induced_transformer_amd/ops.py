@@ -3597,6 +3597,18 @@ def fps_max_points(space_dim: int) -> int:
 def check_fps_shapes(mesh, n_samples, lengths=None, start=0) -> None:
     """Shape, dtype and envelope refusals of ``farthest_point_sample``, raised before the device check and before anything is
     launched."""
+    _check_fps_shapes(mesh, n_samples, lengths, start, False)
+
+
+def check_fps_large_shapes(mesh, n_samples, lengths=None, start=0, slice_points=0) -> None:
+    """The same refusals for ``farthest_point_sample_large``: its own envelope, and ``slice_points``."""
+    _check_fps_shapes(mesh, n_samples, lengths, start, True)
+    if isinstance(slice_points, bool) or not isinstance(slice_points, (int, np.integer)) or \
+            not (slice_points == 0 or (256 <= slice_points <= 65536 and slice_points % 256 == 0)):
+        raise ValueError(f"slice_points must be 0 (the library's choice) or a multiple of 256 in [256, 65536], got {slice_points!r}")
+
+
+def _check_fps_shapes(mesh, n_samples, lengths, start, large: bool) -> None:
     if not torch.is_tensor(mesh) or mesh.dim() not in (2, 3):
         raise ValueError("mesh must be a (b, n, space_dim) or (n, space_dim) tensor of point clouds")
     if mesh.dtype != torch.float32:
@@ -3607,13 +3619,17 @@ def check_fps_shapes(mesh, n_samples, lengths=None, start=0) -> None:
     batch = mesh.shape[0] if mesh.dim() == 3 else 1
     if sdim > MAX_SPACE_DIM:
         raise ValueError(f"space_dim {sdim} beyond {MAX_SPACE_DIM} coordinates")
-    if n > fps_max_points(sdim):
+    if large and n > _lib.FPS_LARGE_MAX_POINTS:
+        raise ValueError(f"a cloud of {n} points is beyond the large sampler's {_lib.FPS_LARGE_MAX_POINTS} points")
+    if not large and n > fps_max_points(sdim):
         raise ValueError(f"a cloud of {n} points with {sdim} coordinates is beyond the sampler's {fps_max_points(sdim)} points "
                          f"(space_dim 1..3: {_lib.FPS_MAX_POINTS}, 4..8: {_lib.FPS_MAX_POINTS_WIDE})")
     if batch > 65535:
         raise ValueError(f"a batch of {batch} clouds is beyond 65535")
     if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or not 1 <= int(n_samples) <= n:
         raise ValueError(f"n_samples must be an integer in [1, {n}] (the padded width), got {n_samples!r}")
+    if large and int(n_samples) > _lib.FPS_LARGE_MAX_SAMPLES:
+        raise ValueError(f"n_samples {n_samples} is beyond the large sampler's {_lib.FPS_LARGE_MAX_SAMPLES} picks")
     for name, t in (("lengths", lengths), ("start", start)):
         if torch.is_tensor(t):
             if t.dtype not in (torch.int32, torch.int64):
@@ -3638,6 +3654,25 @@ def farthest_point_sample(mesh: torch.Tensor, n_samples: int, lengths=None, star
       start      the first pick: an int, or a per-sample int tensor; clamped into the cloud
     Nothing differentiates through the choice: the result carries no autograd graph (gather ``mesh`` by ``idx`` for that)."""
     check_fps_shapes(mesh, n_samples, lengths, start)
+    return _fps_run(mesh, n_samples, lengths, start, None)
+
+
+@torch.compiler.disable
+def farthest_point_sample_large(mesh: torch.Tensor, n_samples: int, lengths=None, start=0, slice_points: int = 0) -> FpsResult:
+    """pit_fps_large (include/pit_hip.h): ``farthest_point_sample`` - the same arguments, the same result bit for bit - for
+    clouds up to 4194304 points of 1..8 coordinates and up to 16384 picks.  The points stay in memory; a cloud is cut into slices
+    of ``slice_points`` points, one workgroup each, and every pick is one launch (``n_samples`` dependent launches of one kernel),
+    so the whole chip works on one cloud.  No host synchronisation, capturable; no atomics: the same input gives the same bits.
+      slice_points   0: the library's choice (at most 256 slices per cloud); otherwise a multiple of 256 in [256, 65536].  The
+                     result does not depend on it.
+    The workspace (running distances and per-slice candidates) is allocated per call.  Small clouds are accepted too; there
+    ``farthest_point_sample`` is one launch and faster."""
+    check_fps_large_shapes(mesh, n_samples, lengths, start, slice_points)
+    return _fps_run(mesh, n_samples, lengths, start, int(slice_points))
+
+
+def _fps_run(mesh, n_samples, lengths, start, slice_points) -> FpsResult:
+    """The launch of pit_fps (``slice_points`` None) or pit_fps_large, after the shape checks."""
     if not mesh.is_cuda:
         raise RuntimeError("position_induced_transformer_amd: the PiT hot path runs on the HIP device only; "
                            "got a CPU tensor (move the model and its inputs to 'cuda')")
@@ -3659,11 +3694,20 @@ def farthest_point_sample(mesh: torch.Tensor, n_samples: int, lengths=None, star
     idx = torch.empty((b, m), device=src.device, dtype=torch.int32)
     out = torch.empty((b, m, sdim), device=src.device, dtype=torch.float32)
     out_len = None if len_t is None else torch.empty((b,), device=src.device, dtype=torch.int32)
+    work = None
+    if slice_points is not None:
+        work = torch.empty((_lib.lib().pit_fps_large_workspace(b, n, slice_points),), device=src.device, dtype=torch.uint8)
     if _capturing():
-        _pin(*[o for o in (src, len_t, start_t) if o is not None])
-    rc = _lib.lib().pit_fps(src.data_ptr(), b, n, sdim, bstride, _lib.ptr(len_t), _lib.ptr(start_t), start_all, m,
-                            idx.data_ptr(), out.data_ptr(), _lib.ptr(out_len), _lib.stream_ptr())
-    _lib.check(rc, "pit_fps")
+        _pin(*[o for o in (src, len_t, start_t, work) if o is not None])
+    if work is None:
+        rc = _lib.lib().pit_fps(src.data_ptr(), b, n, sdim, bstride, _lib.ptr(len_t), _lib.ptr(start_t), start_all, m,
+                                idx.data_ptr(), out.data_ptr(), _lib.ptr(out_len), _lib.stream_ptr())
+        _lib.check(rc, "pit_fps")
+    else:
+        rc = _lib.lib().pit_fps_large(src.data_ptr(), b, n, sdim, bstride, _lib.ptr(len_t), _lib.ptr(start_t), start_all, m,
+                                      idx.data_ptr(), out.data_ptr(), _lib.ptr(out_len), slice_points, work.data_ptr(),
+                                      _lib.stream_ptr())
+        _lib.check(rc, "pit_fps_large")
     if single:
         return FpsResult(idx[0], out[0], None if out_len is None else out_len[0])
     return FpsResult(idx, out, out_len)

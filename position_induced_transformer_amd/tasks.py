@@ -154,7 +154,8 @@ class pit_cloud_latent(P.pit):
 
 class pit_cloud_fps(P.pit):
     """Per-sample clouds on a latent mesh chosen per cloud FROM the cloud: ``n_latent`` points by farthest-point sampling
-    (ops.farthest_point_sample - one launch inside the step, so a captured step samples the clouds it is fed).  What
+    (ops.farthest_point_sample - one launch inside the step, so a captured step samples the clouds it is fed; clouds beyond that
+    sampler's envelope go through ops.farthest_point_sample_large, one launch per latent point, with the same picks).  What
     ``pit_naca.ltt_mesh`` does with strides on a structured grid, for clouds that have no structure to stride over: the
     processor's dense self-attention runs on n_latent x n_latent instead of n x n per sample.  ``func_in`` is fed to the
     encoder as it is (``in_dim`` channels, coordinates included if wanted, as in train_elasticity.py:39)."""
@@ -188,7 +189,10 @@ class pit_cloud_fps(P.pit):
             len_in = ops.as_lengths(len_in, mesh_in.device, mesh_in.shape[0])
         else:
             self._mesh_grad(mesh_in, mesh_out)
-        latent = ops.farthest_point_sample(mesh_in, self.n_latent, len_in, self.start)
+        if mesh_in.shape[1] <= ops.fps_max_points(mesh_in.shape[2]):
+            latent = ops.farthest_point_sample(mesh_in, self.n_latent, len_in, self.start)
+        else:                                                          # (the same picks, one launch per pick)
+            latent = ops.farthest_point_sample_large(mesh_in, self.n_latent, len_in, self.start)
         self.last_latent = latent
         size = mesh_out.shape[:-1]
         if ragged:

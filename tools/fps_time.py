@@ -2,6 +2,7 @@
 """What farthest-point sampling costs on the device (ops.farthest_point_sample / tasks.pit_cloud_fps), in ONE process.
 
     python tools/fps_time.py [--replays 200] [--repeats 9] [--lengths]
+    python tools/fps_time.py --large [--slices 0,512,2048] [--large-replays 50]
 
 1. The sampler alone: one pit_fps launch captured into a hipGraph, at b=10 n=972 m=256, b=8 n=4096 m=512 and b=4 n=16384
    m=1024 (uniform clouds in the unit square) - microseconds per launch and nanoseconds per picked point (the launch is m
@@ -10,6 +11,11 @@
    ddp.FlatAdam(zero_grads=True) in the graph: tasks.pit_elasticity, whose latent mesh is the cloud itself, and
    tasks.pit_cloud_fps with --latent (default 256) sampled points.  The two models are DIFFERENT functions: the comparison states
    what each costs per step, not a speed-up of one computation.  `--lengths`: both steps on the ragged path (full-width lengths).
+
+`--large`: the large sampler instead (ops.farthest_point_sample_large: one launch per pick, m kernel nodes in the graph), with m = 1024
+and every slice size of `--slices` (0: the library's choice): at b=4 n=16384 BOTH samplers, alternating in blocks of `--replays`;
+then the large sampler alone at n=65536 and n=262144, b=1 and b=4, in blocks of `--large-replays` (a sampling takes
+milliseconds there).  Microseconds per sampling and per pick.
 
 After a warm-up block the blocks of `--replays` bare replays alternate between the graphs, one synchronisation per block; every
 figure is the median block over `--repeats`, divided by the replays.  Prints one JSON line."""
@@ -56,13 +62,61 @@ def _capture(fn):
     return graph, keep
 
 
+LARGE_M = 1024
+LARGE_BOTH = (4, 16384)
+LARGE_ALONE = ((1, 65536), (4, 65536), (1, 262144), (4, 262144))
+
+
+def large(args) -> dict:
+    import torch
+    from position_induced_transformer_amd import ops
+    slices = [int(v) for v in args.slices.split(",")]
+    out = {"replays": args.replays, "large_replays": args.large_replays, "repeats": args.repeats, "m": LARGE_M, "both": [], "large": []}
+    g = torch.Generator().manual_seed(0)
+    keep = []
+
+    def rows(graphs, shapes, replays, dest):
+        for (kind, b, n, sp), (us, blocks) in zip(shapes, _median_us(graphs, replays, args.repeats).values()):
+            dest.append({"sampler": kind, "batch": b, "n": n, "slice_points": sp, "us_per_sampling": round(us, 1),
+                         "us_per_pick": round(us / LARGE_M, 3), "blocks_us": blocks})
+
+    b, n = LARGE_BOTH
+    mesh = torch.rand(b, n, 2, generator=g).cuda()
+    graph, res = _capture(lambda: ops.farthest_point_sample(mesh, LARGE_M))
+    keep.append((mesh, res))
+    graphs, shapes = {"small": graph.replay}, [("pit_fps", b, n, None)]
+    for sp in slices:
+        graph, res = _capture(lambda: ops.farthest_point_sample_large(mesh, LARGE_M, slice_points=sp))
+        keep.append(res)
+        assert torch.equal(res.idx, keep[0][1].idx)
+        graphs[f"large_{sp}"] = graph.replay
+        shapes.append(("pit_fps_large", b, n, sp))
+    rows(graphs, shapes, args.replays, out["both"])
+    graphs, shapes = {}, []
+    for b, n in LARGE_ALONE:
+        mesh = torch.rand(b, n, 2, generator=g).cuda()
+        for sp in slices:
+            graph, res = _capture(lambda: ops.farthest_point_sample_large(mesh, LARGE_M, slice_points=sp))
+            keep.append((mesh, res))
+            graphs[f"b{b}_n{n}_{sp}"] = graph.replay
+            shapes.append(("pit_fps_large", b, n, sp))
+    rows(graphs, shapes, args.large_replays, out["large"])
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--replays", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--latent", type=int, default=256)
     ap.add_argument("--lengths", action="store_true", help="both training steps on the ragged path (full-width lengths)")
+    ap.add_argument("--large", action="store_true", help="the large sampler (one launch per pick) instead")
+    ap.add_argument("--slices", default="0", help="--large: comma-separated slice_points to time (0: the library's choice)")
+    ap.add_argument("--large-replays", type=int, default=50, help="--large: replays per block at n = 65536 and 262144")
     args = ap.parse_args()
+    if args.large:
+        print(json.dumps(large(args)))
+        return
     import torch
     from position_induced_transformer_amd import ops, tasks
     from position_induced_transformer_amd.ddp import FlatAdam, FlatGradients
