@@ -1262,6 +1262,45 @@ int  pit_fps_large(const float* mesh, int batch, int n, int space_dim, long mesh
                    const int* start, int start_all, int m, int* idx, float* out_mesh, int* out_len,
                    int slice_points, void* workspace, void* stream);
 
+/* ---- The k nearest keys of every row, ascending (an addition to ABI 31; csrc/pit_knn.hip) -------------------------------------------
+ * The candidate lists of the any-metric layers (pit_distlist_fwd) built on the device without a library sort and - for a box
+ * metric - without the n_out x n_in matrix.  Two entries, one selection; a library built from this header defines PIT_HAS_KNN;
+ * PIT_ABI_VERSION is unchanged (nothing that existed changed).
+ *
+ * Row i of sample s has the fp32 distances d_0 .. d_(J-1), J = n_in, to the keys.  Order the pairs (d_j, j) by the distance and then
+ * by the key index (what a stable ascending sort of the row gives: the LOWEST index among equals, as in pit_fps):
+ *   for t = 0 .. k-1:  idx[s][i][t] = the key of pair t,  dist[s][i][t] = its distance (the kernel's own value);
+ *   next[s][i] = the distance of pair k (the (k+1)-th), or +inf when k == J.
+ * pit_knn_box - the distances come from coordinates; no matrix is formed.  Per axis a < space_dim, every operation rounded to fp32:
+ *     t = |x_a - y_a|;  u_a = min(t, p_a - t) where periods[a] = p_a > 0, u_a = t otherwise (periods NULL: no axis wraps);
+ *     d = ((u_0*u_0 + u_1*u_1) + u_2*u_2) + ...   coordinates in ascending order
+ *   mesh_out / mesh_in: (n_out, space_dim) / (n_in, space_dim) fp32 per sample; out_stride / in_stride: POINTS between two samples'
+ *   meshes, 0 = one mesh shared by every sample and read in place, otherwise >= n_out / n_in (the *_strided convention above).
+ *   periods: a HOST array of space_dim floats, read during the call, or NULL.  1 <= space_dim <= PIT_MAX_SPACE_DIM.
+ * pit_knn_rows - the distances are rows of a matrix the caller formed: sample s, row i at m + s * m_bstride + i * ld_m, n_in floats
+ *   (ld_m >= n_in; m_bstride 0 = one matrix for every sample, otherwise >= (n_out-1)*ld_m + n_in: pit_distmat_select_fwd's
+ *   convention).  Precondition, not checked: the entries are finite and >= 0; -0.0 counts as 0 and comes out as +0.0.  Whatever the
+ *   entries hold, every emitted index lies in [0, n_in), the indices of a row are distinct and nothing is addressed out of bounds;
+ *   columns at or beyond n_in and rows at or beyond n_out are never read.
+ * Outputs of both: idx (batch, n_out, k) int32, dist (batch, n_out, k) fp32, next (batch, n_out) fp32, contiguous.
+ * One launch, a workgroup per row (any batch * n_out).  A row of up to PIT_KNN_REG_MAX_KEYS keys keeps its distances in registers
+ * (form 1); a longer row is streamed and its distances are recomputed in every pass of the search (form 2).  No global atomics (the
+ * same input gives the same bits), no workspace, no allocation, no host synchronisation, capturable.
+ * 1 <= k <= min(n_in, PIT_KNN_MAX_K); batch * n_out * k < 2^31.  Refusals, all before any launch and in this order: PIT_ERR_NULL for
+ * a missing mesh_out, mesh_in / m, idx, dist or next; PIT_ERR_SIZE for batch, n_out or n_in < 1, space_dim outside
+ * 1..PIT_MAX_SPACE_DIM, a stride the conventions above refuse, k outside [1, n_in], batch * n_out * k >= 2^31;
+ * PIT_ERR_UNSUPPORTED for k > PIT_KNN_MAX_K.
+ * pit_knn_last_form - host-side and process-global: the form (1 or 2) of this process's latest pit_knn_box / pit_knn_rows launch,
+ *   0 before the first. */
+#define PIT_HAS_KNN 1
+#define PIT_KNN_MAX_K 2048            /* the width the list layers accept (PIT_DISTLIST_MAX_CAP) */
+#define PIT_KNN_REG_MAX_KEYS 1024     /* rows up to this many keys take form 1 */
+int pit_knn_box(const float* mesh_out, const float* mesh_in, int batch, int n_out, int n_in, int space_dim, long out_stride,
+                long in_stride, const float* periods, int k, int* idx, float* dist, float* next, void* stream);
+int pit_knn_rows(const float* m, long ld_m, long m_bstride, int batch, int n_out, int n_in, int k, int* idx, float* dist,
+                 float* next, void* stream);
+int pit_knn_last_form(void);
+
 /* ---- The two slab forms of pit_block_fwd (additions to ABI 31; csrc/pit_block.hip) ------------------------------------------------
  * pit_block_fwd runs 16-row slabs, or - n_head = 2, n_pts = 256, the weights through LDS, and 8 * ceil(batch / 8) * n_pts / 8
  * workgroups no more than the device has CUs (batch <= 8 on MI355X) - 8-row slabs with the two heads stacked in the M dimension of

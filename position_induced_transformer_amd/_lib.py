@@ -194,6 +194,9 @@ SIGNATURES = {
     "pit_fps": [_P, _I, _I, _I, _L, _P, _P, _I, _I, _P, _P, _P, _P],
     "pit_fps_large_workspace": [_I, _I, _I],
     "pit_fps_large": [_P, _I, _I, _I, _L, _P, _P, _I, _I, _P, _P, _P, _I, _P, _P],
+    "pit_knn_box": [_P, _P, _I, _I, _I, _I, _L, _L, _P, _I, _P, _P, _P, _P],
+    "pit_knn_rows": [_P, _L, _L, _I, _I, _I, _I, _P, _P, _P, _P],
+    "pit_knn_last_form": [],
     "pit_instance_norm_fwd": [_P, _L, _L, _I, _I, _I, _F, _P, _P, _P],
     "pit_instance_norm_bwd": [_P, _P, _P, _I, _I, _I, _P, _P],
     "pit_adam_step": [_P, _P, _P, _P, _L, _P, _F, _F, _I, _F, _F, _F, _F, _I, _P, _P],
@@ -227,11 +230,14 @@ ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_
                "pit_adam_step_averaged", "pit_exchange_words",                     # PIT_HAS_AVERAGED_ADAM
                "pit_fps",                                                          # PIT_HAS_FPS
                "pit_batch_feed_points",                                            # PIT_HAS_FEED_POINTS
-               "pit_fps_large_workspace", "pit_fps_large"}                         # PIT_HAS_FPS_LARGE
+               "pit_fps_large_workspace", "pit_fps_large",                         # PIT_HAS_FPS_LARGE
+               "pit_knn_box", "pit_knn_rows", "pit_knn_last_form"}                 # PIT_HAS_KNN
 FPS_MAX_POINTS = 16384   # PIT_FPS_MAX_POINTS
 FPS_MAX_POINTS_WIDE = 4096       # PIT_FPS_MAX_POINTS_WIDE (space_dim 4..8)
 FPS_LARGE_MAX_POINTS = 4194304   # PIT_FPS_LARGE_MAX_POINTS (every space_dim)
 FPS_LARGE_MAX_SAMPLES = 16384    # PIT_FPS_LARGE_MAX_SAMPLES
+KNN_MAX_K = 2048         # PIT_KNN_MAX_K
+KNN_REG_MAX_KEYS = 1024  # PIT_KNN_REG_MAX_KEYS
 GUARD_MAX_PARTS = 256    # PIT_GUARD_MAX_PARTS
 GUARD_STATE_DOUBLES = 10         # PIT_GUARD_STATE_DOUBLES
 FEED_MAX_FIELDS = 8      # PIT_FEED_MAX_FIELDS

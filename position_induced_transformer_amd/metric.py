@@ -27,6 +27,11 @@ so a mesh may require grad; ``pit_metric(..., neighbors="auto")`` runs its down 
     lists = knn_lists(sq, mesh_out, mesh_in, k=None, locality=0.02)     # NeighborLists(idx, sqd, cut_rows)
     out = layer.forward_list(lists.idx, lists.sqd, inputs)
 
+``builder="hip"`` (layers and ``pit_metric``) builds the lists with the project's own kernels instead of dense blocks and
+``torch.topk``: for ``sqdist_euclid`` and ``sqdist_periodic_box`` with float periods from the coordinates in one launch
+(``knn_lists_box``, no N x J block at all), for any other metric by ``knn_lists(..., select="hip")``; among equal distances the
+lowest key index is listed.  The default, "torch", is unchanged.
+
 Not part of ``pit.py``, whose star-exports are the reference's.
 """
 from __future__ import annotations
@@ -40,13 +45,16 @@ from . import ops
 from . import pit as _pit
 
 __all__ = ["sqdist_euclid", "sqdist_periodic_box", "posatt_metric", "posatt_cross_metric", "pit_metric", "list_capacity",
-           "NeighborLists", "knn_lists"]
+           "NeighborLists", "knn_lists", "knn_lists_box"]
 
 
 def sqdist_euclid(mesh_out: torch.Tensor, mesh_in: torch.Tensor) -> torch.Tensor:
     """sum((mesh_out[:, None] - mesh_in[None]) ** 2, -1), the op sequence of pit.py:47 / :134; batched or batch-free meshes."""
     diff = mesh_out.unsqueeze(-2) - mesh_in.unsqueeze(-3)
     return torch.sum(diff ** 2, dim=-1)
+
+
+sqdist_euclid.box_periods = None       # a box metric without a wrapped axis: builder="hip" builds its lists from coordinates
 
 
 def sqdist_periodic_box(periods):
@@ -70,6 +78,7 @@ def sqdist_periodic_box(periods):
                 cols.append(dk if p is None else torch.minimum(dk, p - dk))
             d = torch.stack(cols, dim=-1)
         return torch.sum(d ** 2, dim=-1)
+    sqdist.box_periods = periods       # (what builder="hip" hands to knn_lists_box when every period is a float or None)
     return sqdist
 
 
@@ -89,40 +98,11 @@ def default_neighbors(locality: float, n_in: int) -> int:
 NeighborLists = namedtuple("NeighborLists", ["idx", "sqd", "cut_rows"])
 
 
-def knn_lists(sqdist, mesh_out, mesh_in, k=None, chunk: int = 4096, locality: float = 1.0) -> NeighborLists:
-    """The ``k`` nearest keys of every row under ``sqdist``: ``idx`` (int64) and ``sqd`` of shape (N, k), or (b, N, k) when a
-    mesh is batched.  The keys come from dense distances of ``chunk`` rows at a time under no_grad (peak memory chunk x J) and
-    ``torch.topk``; ``sqd`` is then recomputed for the chosen pairs only, by calling ``sqdist`` with the rows as its batch axis -
-    sqdist((R, 1, s), (R, k, s)) -> (R, 1, k) - so autograd holds O(N k) and a mesh may require grad.  ``k`` None: list_capacity
-    of ``locality`` plus room for ties (default_neighbors).  ``cut_rows``: a 0-d tensor on the meshes' device, computed without
-    a synchronisation: the number of rows whose list may hold other keys than the dense layer of ``locality`` keeps - rows
-    whose (k+1)-th nearest value is <= their m_(rank+1), i.e. a tie shell at the threshold reaches beyond the list; without a
-    mask (locality 1.0) every row, unless the lists hold all J keys."""
-    n_in = int(mesh_in.shape[-2])
-    if k is None:
-        k = default_neighbors(locality, n_in)
-    k = int(k)
-    need = list_capacity(locality, n_in)
-    if not (need <= k <= n_in):
-        raise ValueError(f"k = {k}: a layer of locality {locality} over {n_in} keys needs between {need} and {n_in} neighbours")
-    batched = mesh_out.dim() == 3 or mesh_in.dim() == 3
-    n_out = int(mesh_out.shape[-2])
-    rank = ops.quantile_rank(float(locality), n_in)[0]
-    with torch.no_grad():
-        mo, mi = mesh_out.detach(), mesh_in.detach()
-        parts, cut = [], None
-        for r0 in range(0, n_out, int(chunk)):
-            m = sqdist(mo[..., r0:r0 + int(chunk), :], mi)
-            vals, ind = torch.topk(m, min(k + 1, n_in), dim=-1, largest=False, sorted=True)
-            parts.append(ind[..., :k])
-            if k < n_in:
-                hit = (vals[..., k] <= vals[..., rank + 1]) if float(locality) < 1.0 else torch.ones_like(vals[..., k], dtype=torch.bool)
-                cut = hit.sum() if cut is None else cut + hit.sum()
-        idx = torch.cat(parts, dim=-2)
-        if cut is None:
-            cut = torch.zeros((), dtype=torch.int64, device=idx.device)
-    s = mesh_out.shape[-1]
-    if batched:
+def _listed_sqdist(sqdist, mesh_out, mesh_in, idx):
+    """``sqdist`` of the listed pairs only, the rows as its batch axis - sqdist((R, 1, s), (R, k, s)) -> (R, 1, k) - in the shape
+    of ``idx``: O(N k) and differentiable."""
+    n_out, k, s = int(mesh_out.shape[-2]), int(idx.shape[-1]), mesh_out.shape[-1]
+    if mesh_out.dim() == 3 or mesh_in.dim() == 3:
         b = idx.shape[0]
         rows = (mesh_out if mesh_out.dim() == 3 else mesh_out.unsqueeze(0).expand(b, -1, -1)).reshape(b * n_out, 1, s)
         if mesh_in.dim() == 3:
@@ -132,8 +112,90 @@ def knn_lists(sqdist, mesh_out, mesh_in, k=None, chunk: int = 4096, locality: fl
         keys = keys.reshape(b * n_out, k, s)
     else:
         rows, keys = mesh_out.unsqueeze(1), mesh_in[idx]
-    sqd = sqdist(rows, keys).reshape(idx.shape)
-    return NeighborLists(idx, sqd, cut)
+    return sqdist(rows, keys).reshape(idx.shape)
+
+
+def _check_neighbors(k, locality: float, n_in: int) -> int:
+    if k is None:
+        k = default_neighbors(locality, n_in)
+    k = int(k)
+    need = list_capacity(locality, n_in)
+    if not (need <= k <= n_in):
+        raise ValueError(f"k = {k}: a layer of locality {locality} over {n_in} keys needs between {need} and {n_in} neighbours")
+    return k
+
+
+def _cut_rows(dist, nxt, k: int, n_in: int, locality: float):
+    """knn_lists's count of rows whose list may be cut inside a tie shell, from a kernel's own (dist, next); no synchronisation."""
+    if k >= n_in:
+        return torch.zeros((), dtype=torch.int64, device=dist.device)
+    if float(locality) >= 1.0:
+        return torch.full((), nxt.numel(), dtype=torch.int64, device=dist.device)
+    return (nxt <= dist[..., ops.quantile_rank(float(locality), n_in)[0] + 1]).sum()
+
+
+def knn_lists_box(mesh_out, mesh_in, k=None, periods=None, locality: float = 1.0) -> NeighborLists:
+    """``knn_lists`` for a box metric - Euclidean, or periodic in the axes whose ``periods[a]`` is a float (None: the axis does
+    not wrap) - with the keys from ONE launch of ops.knn_box: no N x J block is formed, no library sort runs, and among equal
+    distances the lowest key index is taken.  ``idx`` (int64) lists a row's keys ascending by (distance, index); ``sqd`` is
+    recomputed for the listed pairs by sqdist_euclid / sqdist_periodic_box(periods) as knn_lists does, so a mesh may require grad;
+    ``cut_rows`` follows knn_lists's rule on the kernel's own distances, without a synchronisation.  ``k`` None:
+    default_neighbors; at most 2048 (ops.KNN_MAX_K).  Every refusal is a ValueError raised before a launch."""
+    for name, t in (("mesh_out", mesh_out), ("mesh_in", mesh_in)):
+        if not torch.is_tensor(t) or t.dim() not in (2, 3) or 0 in t.shape:
+            raise ValueError(f"{name} must be a non-empty (n, space_dim) or (b, n, space_dim) tensor")
+    n_in = int(mesh_in.shape[-2])
+    k = _check_neighbors(k, locality, n_in)
+    if k > ops.KNN_MAX_K:
+        raise ValueError(f"k = {k}: at most {ops.KNN_MAX_K} neighbours are supported (the width the list layers accept)")
+    per = ops.check_knn_box_shapes(mesh_out, mesh_in, k, periods)[5]
+    with torch.no_grad():
+        got = ops.knn_box(mesh_out, mesh_in, k, periods)
+        cut = _cut_rows(got.dist, got.next, k, n_in, locality)
+        idx = got.idx.long()
+    sqdist = sqdist_euclid if per is None else sqdist_periodic_box(tuple(p if p > 0.0 else None for p in per))
+    return NeighborLists(idx, _listed_sqdist(sqdist, mesh_out, mesh_in, idx), cut)
+
+
+def knn_lists(sqdist, mesh_out, mesh_in, k=None, chunk: int = 4096, locality: float = 1.0, select: str = "torch") -> NeighborLists:
+    """The ``k`` nearest keys of every row under ``sqdist``: ``idx`` (int64) and ``sqd`` of shape (N, k), or (b, N, k) when a
+    mesh is batched.  The keys come from dense distances of ``chunk`` rows at a time under no_grad (peak memory chunk x J) and
+    ``torch.topk``; ``sqd`` is then recomputed for the chosen pairs only, by calling ``sqdist`` with the rows as its batch axis -
+    sqdist((R, 1, s), (R, k, s)) -> (R, 1, k) - so autograd holds O(N k) and a mesh may require grad.  ``k`` None: list_capacity
+    of ``locality`` plus room for ties (default_neighbors).  ``cut_rows``: a 0-d tensor on the meshes' device, computed without
+    a synchronisation: the number of rows whose list may hold other keys than the dense layer of ``locality`` keeps - rows
+    whose (k+1)-th nearest value is <= their m_(rank+1), i.e. a tie shell at the threshold reaches beyond the list; without a
+    mask (locality 1.0) every row, unless the lists hold all J keys.  ``select``: "torch" - torch.topk, whose choice among equal
+    distances is unspecified - or "hip": ops.knn_rows on the same chunks (k <= 2048), the lowest key index among equals and the
+    lists ascending by (distance, index)."""
+    if select not in ("torch", "hip"):
+        raise ValueError(f"select must be 'torch' or 'hip', got {select!r}")
+    n_in = int(mesh_in.shape[-2])
+    k = _check_neighbors(k, locality, n_in)
+    if select == "hip" and k > ops.KNN_MAX_K:
+        raise ValueError(f"k = {k}: select='hip' supports at most {ops.KNN_MAX_K} neighbours")
+    n_out = int(mesh_out.shape[-2])
+    rank = ops.quantile_rank(float(locality), n_in)[0]
+    with torch.no_grad():
+        mo, mi = mesh_out.detach(), mesh_in.detach()
+        parts, cut = [], None
+        for r0 in range(0, n_out, int(chunk)):
+            m = sqdist(mo[..., r0:r0 + int(chunk), :], mi)
+            if select == "hip":
+                got = ops.knn_rows(m, k)
+                parts.append(got.idx)
+                hit = _cut_rows(got.dist, got.next, k, n_in, locality)
+                cut = hit if cut is None else cut + hit
+                continue
+            vals, ind = torch.topk(m, min(k + 1, n_in), dim=-1, largest=False, sorted=True)
+            parts.append(ind[..., :k])
+            if k < n_in:
+                hit = (vals[..., k] <= vals[..., rank + 1]) if float(locality) < 1.0 else torch.ones_like(vals[..., k], dtype=torch.bool)
+                cut = hit.sum() if cut is None else cut + hit.sum()
+        idx = torch.cat(parts, dim=-2).long()
+        if cut is None:
+            cut = torch.zeros((), dtype=torch.int64, device=idx.device)
+    return NeighborLists(idx, _listed_sqdist(sqdist, mesh_out, mesh_in, idx), cut)
 
 
 class posatt_metric(nn.Module):
@@ -143,10 +205,13 @@ class posatt_metric(nn.Module):
     _PLAN_CACHE = 8
     _self_attn = True
 
-    def __init__(self, n_head, in_dim, locality, sqdist=sqdist_euclid, neighbors=None):
+    def __init__(self, n_head, in_dim, locality, sqdist=sqdist_euclid, neighbors=None, builder: str = "torch"):
         super().__init__()
         if not (neighbors is None or neighbors == "auto" or (isinstance(neighbors, int) and neighbors > 0)):
             raise ValueError(f"neighbors must be None, 'auto' or a positive int, got {neighbors!r}")
+        if builder not in ("torch", "hip"):
+            raise ValueError(f"builder must be 'torch' or 'hip', got {builder!r}")
+        self.builder = builder                # who builds the kNN lists: "torch" (dense chunks + topk) or "hip" (ops.knn_box / knn_rows)
         self.neighbors = neighbors            # None: dense distances; otherwise forward() builds kNN lists of that width
         self.last_lists = None                # the NeighborLists of the latest forward() on lists (cut_rows is read from here)
         self.locality = locality
@@ -208,11 +273,22 @@ class posatt_metric(nn.Module):
         plan = self._list_plan(idx, sqd, inputs.shape[1])
         return ops.posatt_list_apply(inputs, self.lmda, plan, self.n_head, concat=self._self_attn, sqd=sqd)
 
+    def _build_lists(self, mesh_out, mesh_in, k):
+        """builder "torch": knn_lists as ever.  "hip": a ``sqdist`` that says it is a box metric (``box_periods``: None, or per
+        axis a float or None) gets its lists from coordinates (knn_lists_box); any other metric from ops.knn_rows on its chunks."""
+        if self.builder == "torch":
+            return knn_lists(self.sqdist, mesh_out, mesh_in, k, locality=self.locality)
+        if hasattr(self.sqdist, "box_periods"):
+            per = self.sqdist.box_periods
+            if per is None or all(p is None or (isinstance(p, (int, float)) and not isinstance(p, bool)) for p in per):
+                return knn_lists_box(mesh_out, mesh_in, k, periods=per, locality=self.locality)
+        return knn_lists(self.sqdist, mesh_out, mesh_in, k, locality=self.locality, select="hip")
+
     def _on_meshes(self, mesh_out, mesh_in, inputs):
         # distances formed for this call - kNN lists (pit_metric(..., neighbors=...)) or the whole matrix: their plan is built
         # for this call too, like every per-sample mesh plan (the cache of forward_dist / forward_list is for what the caller keeps)
         if self.neighbors is not None:
-            lists = knn_lists(self.sqdist, mesh_out, mesh_in, None if self.neighbors == "auto" else self.neighbors, locality=self.locality)
+            lists = self._build_lists(mesh_out, mesh_in, None if self.neighbors == "auto" else self.neighbors)
             self.last_lists = lists
             ops.check_list_shapes(lists.idx, lists.sqd, inputs, self._self_attn)
             plan = ops.ListPlan(lists.idx, lists.sqd, inputs.shape[1], self.locality)
@@ -255,14 +331,16 @@ class pit_metric(_pit.pit):
     fixed-mesh task forward: the coordinates of ``mesh_in`` are prepended to ``func_in`` (train_darcy.py:51-55).
     ``learn_latent``: the latent mesh becomes a parameter.  ``neighbors``: an int, or "auto" for default_neighbors - down and up
     then build kNN lists under ``sqdist`` (knn_lists) and run on them (forward_list), O(N k) instead of O(N J); conv stays dense
-    on the latent mesh.  None: dense distances everywhere."""
+    on the latent mesh.  None: dense distances everywhere.  ``builder``: "torch" (dense chunks and torch.topk) or "hip" - the lists come
+    from the project's own kernels: from coordinates for sqdist_euclid / sqdist_periodic_box with float periods (no N x J block),
+    from ops.knn_rows on the chunks for any other metric."""
 
     def __init__(self, space_dim, in_dim, out_dim, hid_dim, n_head, n_blocks, mesh_ltt, en_loc, de_loc, sqdist=sqdist_euclid,
-                 learn_latent: bool = False, neighbors=None):
+                 learn_latent: bool = False, neighbors=None, builder: str = "torch"):
         super().__init__(space_dim, in_dim, out_dim, hid_dim, n_head, n_blocks, mesh_ltt, en_loc, de_loc)
-        self.down = posatt_cross_metric(self.n_head, self.in_dim, self.en_local, sqdist, neighbors)
+        self.down = posatt_cross_metric(self.n_head, self.in_dim, self.en_local, sqdist, neighbors, builder)
         self.conv = nn.ModuleList([posatt_metric(self.n_head, self.hid_dim, 1.0, sqdist) for _ in range(self.n_blocks)])
-        self.up = posatt_cross_metric(self.n_head, self.hid_dim, self.de_local, sqdist, neighbors)
+        self.up = posatt_cross_metric(self.n_head, self.hid_dim, self.de_local, sqdist, neighbors, builder)
         if learn_latent:
             self.mesh_ltt = nn.Parameter(self.mesh_ltt.detach().clone())
 

@@ -3713,6 +3713,201 @@ def _fps_run(mesh, n_samples, lengths, start, slice_points) -> FpsResult:
     return FpsResult(idx, out, out_len)
 
 
+KNN_MAX_K = _lib.KNN_MAX_K                  # PIT_KNN_MAX_K: the width the list layers accept (LIST_MAX_CAP)
+KNN_REG_MAX_KEYS = _lib.KNN_REG_MAX_KEYS    # PIT_KNN_REG_MAX_KEYS: longer rows are streamed (form 2)
+
+KnnResult = collections.namedtuple("KnnResult", ("idx", "dist", "next"))
+KnnResult.__doc__ = """Result of ``knn_box`` / ``knn_rows``: ``idx`` (.., N, k) int32 - the k nearest keys of every row, ascending
+by (distance, key index); ``dist`` (.., N, k) fp32 - their distances, the kernel's own values; ``next`` (.., N) fp32 - the distance
+of pair k + 1, +inf when k == J."""
+
+
+def _check_knn_k(k, n_out: int, n_in: int, batch: int) -> int:
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= n_in:
+        raise ValueError(f"k must be an integer in [1, {n_in}] (the keys of a row), got {k!r}")
+    if int(k) > KNN_MAX_K:
+        raise ValueError(f"k = {k}: at most {KNN_MAX_K} neighbours are supported (the width the list layers accept)")
+    if batch * n_out * int(k) >= 2 ** 31:
+        raise ValueError(f"batch * N * k = {batch * n_out * int(k)} does not fit 31 bits")
+    return int(k)
+
+
+def _knn_periods(periods, sdim: int):
+    """``periods`` as ``sdim`` Python floats, 0.0 for an axis that does not wrap; None when no axis wraps."""
+    if periods is None:
+        return None
+    if torch.is_tensor(periods) or isinstance(periods, (str, bytes)) or not hasattr(periods, "__len__"):
+        raise ValueError(f"periods must be None or a sequence of {sdim} entries, each a float or None, got {periods!r}")
+    if len(periods) != sdim:
+        raise ValueError(f"periods has {len(periods)} entries for meshes with {sdim} coordinates")
+    out = []
+    for p in periods:
+        if p is None:
+            out.append(0.0)
+        elif isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)):
+            raise ValueError(f"a period must be a float or None (a tensor period is not supported by the box kernel), got {p!r}")
+        elif not math.isfinite(float(p)):
+            raise ValueError(f"a period must be finite, got {p!r}")
+        else:
+            out.append(float(p) if float(p) > 0.0 else 0.0)
+    return out if any(p > 0.0 for p in out) else None
+
+
+def check_knn_box_shapes(mesh_out, mesh_in, k, periods=None):
+    """Shape, dtype and envelope refusals of ``knn_box``, raised before the device check and before anything is launched.
+    Returns (batch, n_out, n_in, space_dim, k, periods as floats or None)."""
+    for name, t in (("mesh_out", mesh_out), ("mesh_in", mesh_in)):
+        if not torch.is_tensor(t) or t.dim() not in (2, 3):
+            raise ValueError(f"{name} must be a (n, space_dim) or (b, n, space_dim) tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be fp32, got {t.dtype}")
+        if 0 in t.shape:
+            raise ValueError(f"{name} has an empty axis: {tuple(t.shape)}")
+    sdim = int(mesh_out.shape[-1])
+    if int(mesh_in.shape[-1]) != sdim:
+        raise ValueError(f"the meshes have {sdim} and {int(mesh_in.shape[-1])} coordinates")
+    if sdim > MAX_SPACE_DIM:
+        raise ValueError(f"space_dim {sdim} beyond {MAX_SPACE_DIM} coordinates")
+    if mesh_out.dim() == 3 and mesh_in.dim() == 3 and mesh_out.shape[0] != mesh_in.shape[0]:
+        raise ValueError(f"mesh_out holds {mesh_out.shape[0]} samples, mesh_in {mesh_in.shape[0]}")
+    batch = int(mesh_out.shape[0]) if mesh_out.dim() == 3 else (int(mesh_in.shape[0]) if mesh_in.dim() == 3 else 1)
+    n_out, n_in = int(mesh_out.shape[-2]), int(mesh_in.shape[-2])
+    k = _check_knn_k(k, n_out, n_in, batch)
+    return batch, n_out, n_in, sdim, k, _knn_periods(periods, sdim)
+
+
+def check_knn_rows_shapes(m, k):
+    """The same for ``knn_rows``.  Returns (batch, n_out, n_in, k)."""
+    if not torch.is_tensor(m) or m.dim() not in (2, 3):
+        raise ValueError("m must be a (N, J) or (b, N, J) tensor of distances")
+    if m.dtype != torch.float32:
+        raise ValueError(f"m must be fp32, got {m.dtype}")
+    if 0 in m.shape:
+        raise ValueError(f"m has an empty axis: {tuple(m.shape)}")
+    batch = int(m.shape[0]) if m.dim() == 3 else 1
+    n_out, n_in = int(m.shape[-2]), int(m.shape[-1])
+    return batch, n_out, n_in, _check_knn_k(k, n_out, n_in, batch)
+
+
+def _knn_need_gpu(*tensors) -> None:
+    _need_gpu(*tensors)
+    if len({t.device for t in tensors}) > 1:
+        raise ValueError(f"the tensors live on different devices: {[str(t.device) for t in tensors]}")
+
+
+def _knn_mesh(mesh, batch: int):
+    """A mesh as the kernel reads it: (tensor to keep alive, sample stride in points).  A batch-free mesh, an expanded one and a
+    batch of one are read in place with stride 0."""
+    t = mesh.detach()
+    n, sdim = int(t.shape[-2]), int(t.shape[-1])
+    if t.dim() == 2 or batch == 1 or t.stride(0) == 0:
+        rows = t if t.dim() == 2 else t[0]
+        if rows.stride(1) != 1 or (n > 1 and rows.stride(0) != sdim):
+            rows = rows.contiguous()
+        return rows, 0
+    if t.stride(2) != 1 or (n > 1 and t.stride(1) != sdim) or t.stride(0) % sdim or t.stride(0) < n * sdim:
+        t = t.contiguous()
+    return t, t.stride(0) // sdim
+
+
+@torch.compiler.disable
+def knn_box(mesh_out: torch.Tensor, mesh_in: torch.Tensor, k: int, periods=None) -> KnnResult:
+    """One launch of pit_knn_box (include/pit_hip.h): for every point of ``mesh_out`` its ``k`` nearest points of ``mesh_in``
+    under the squared distance of a box - Euclidean, or with ``periods[a]`` (a float; None: no wrap) the period of axis a, the op
+    sequence of metric.sqdist_euclid / sqdist_periodic_box - ascending by (distance, key index), the lowest index among equals.
+    The N x J matrix is never formed; no workspace, no host synchronisation, capturable; the same input gives the same bits.
+      mesh_out   (N, s) or (b, N, s) fp32; mesh_in (J, s) or (b, J, s) fp32; a batch-free mesh is shared by the batch and read in place
+      k          1 .. min(J, 2048)
+    Results are (N, k) / (N,) when both meshes are batch-free, (b, N, k) / (b, N) otherwise.  Nothing differentiates through the
+    choice (recompute the listed distances for that: metric.knn_lists_box)."""
+    batch, n_out, n_in, sdim, k, per = check_knn_box_shapes(mesh_out, mesh_in, k, periods)
+    _knn_need_gpu(mesh_out, mesh_in)
+    mo, so = _knn_mesh(mesh_out, batch)
+    mi, si = _knn_mesh(mesh_in, batch)
+    dev = mo.device
+    idx = torch.empty((batch, n_out, k), device=dev, dtype=torch.int32)
+    dist = torch.empty((batch, n_out, k), device=dev, dtype=torch.float32)
+    nxt = torch.empty((batch, n_out), device=dev, dtype=torch.float32)
+    per_c = None if per is None else (ctypes.c_float * sdim)(*per)
+    if _capturing():
+        _pin(mo, mi)
+    rc = _lib.lib().pit_knn_box(mo.data_ptr(), mi.data_ptr(), batch, n_out, n_in, sdim, so, si,
+                                None if per_c is None else ctypes.cast(per_c, ctypes.c_void_p), k, idx.data_ptr(),
+                                dist.data_ptr(), nxt.data_ptr(), _lib.stream_ptr())
+    _lib.check(rc, "pit_knn_box")
+    if mesh_out.dim() == 2 and mesh_in.dim() == 2:
+        return KnnResult(idx[0], dist[0], nxt[0])
+    return KnnResult(idx, dist, nxt)
+
+
+@torch.compiler.disable
+def knn_rows(m: torch.Tensor, k: int) -> KnnResult:
+    """One launch of pit_knn_rows: the ``k`` smallest entries of every row of ``m`` - (N, J) or (b, N, J) fp32 distances under ANY
+    metric, finite and >= 0 (not checked) - ascending by (value, column), the lowest column among equals: torch.sort(stable=True)
+    cut at k.  A view with a leading dimension beyond J is read in place (its guard columns are never read)."""
+    batch, n_out, n_in, k = check_knn_rows_shapes(m, k)
+    _knn_need_gpu(m)
+    src = m.detach()
+    if src.stride(-1) != 1 or (n_out > 1 and src.stride(-2) < n_in):
+        src = src.contiguous()
+    ld = src.stride(-2) if n_out > 1 else n_in
+    bstride = 0
+    if src.dim() == 3 and batch > 1 and src.stride(0) != 0:
+        if src.stride(0) < (n_out - 1) * ld + n_in:
+            src = src.contiguous()
+            ld = n_in
+        bstride = src.stride(0)
+    idx = torch.empty((batch, n_out, k), device=src.device, dtype=torch.int32)
+    dist = torch.empty((batch, n_out, k), device=src.device, dtype=torch.float32)
+    nxt = torch.empty((batch, n_out), device=src.device, dtype=torch.float32)
+    if _capturing():
+        _pin(src)
+    rc = _lib.lib().pit_knn_rows(src.data_ptr(), ld, bstride, batch, n_out, n_in, k, idx.data_ptr(), dist.data_ptr(),
+                                 nxt.data_ptr(), _lib.stream_ptr())
+    _lib.check(rc, "pit_knn_rows")
+    if m.dim() == 2:
+        return KnnResult(idx[0], dist[0], nxt[0])
+    return KnnResult(idx, dist, nxt)
+
+
+def knn_last_form() -> int:
+    """pit_knn_last_form: 1 (the row's distances in registers) or 2 (streamed) for this process's latest knn launch, 0 before."""
+    return int(_lib.lib().pit_knn_last_form())
+
+
+def knn_box_restated(mesh_out, mesh_in, k: int, periods=None, row_chunk: int = 512) -> KnnResult:
+    """``knn_box`` restated on the host in numpy fp32, operation by operation (the loop of include/pit_hip.h): t = |x - y|,
+    u = minimum(t, p - t) on a wrapped axis, d = ((u0*u0 + u1*u1) + u2*u2) + ..., a stable ascending sort of every row, cut at
+    ``k``.  CPU tensors in, CPU tensors out, the shapes and dtypes of ``knn_box``; for tests."""
+    batch, n_out, n_in, sdim, k, per = check_knn_box_shapes(mesh_out, mesh_in, k, periods)
+    mo = mesh_out.detach().cpu().numpy().astype(np.float32, copy=False)
+    mi = mesh_in.detach().cpu().numpy().astype(np.float32, copy=False)
+    idx = np.empty((batch, n_out, k), np.int32)
+    dist = np.empty((batch, n_out, k), np.float32)
+    nxt = np.empty((batch, n_out), np.float32)
+    for s in range(batch):
+        x_all, y = (mo[s] if mo.ndim == 3 else mo), (mi[s] if mi.ndim == 3 else mi)
+        for r0 in range(0, n_out, int(row_chunk)):
+            x = x_all[r0:r0 + int(row_chunk)]
+            d = None
+            for a in range(sdim):
+                t = np.abs(x[:, None, a] - y[None, :, a])
+                if per is not None and per[a] > 0.0:
+                    t = np.minimum(t, np.float32(per[a]) - t)
+                q = t * t
+                d = q if d is None else d + q
+            assert d.dtype == np.float32
+            order = np.argsort(d, axis=-1, kind="stable")
+            srt = np.take_along_axis(d, order, axis=-1)
+            idx[s, r0:r0 + len(x)] = order[:, :k]
+            dist[s, r0:r0 + len(x)] = srt[:, :k]
+            nxt[s, r0:r0 + len(x)] = srt[:, k] if k < n_in else np.float32(np.inf)
+    out = KnnResult(torch.from_numpy(idx), torch.from_numpy(dist), torch.from_numpy(nxt))
+    if mesh_out.dim() == 2 and mesh_in.dim() == 2:
+        return KnnResult(out.idx[0], out.dist[0], out.next[0])
+    return out
+
+
 class _InstanceNorm(torch.autograd.Function):
     """nn.InstanceNorm1d over the point axis on the (batch, points, channels) layout
     (train_vorticity.py:43,56,59), no permutes."""
