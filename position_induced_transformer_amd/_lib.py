@@ -1,222 +1,176 @@
-"""ctypes binding of csrc/libpit_hip.so (C ABI declared in include/pit_hip.h).
+"""ctypes binding of csrc/libpit_hip.so, derived from the C ABI's own declaration, include/pit_hip.h.
+
+The header is parsed once, at import: prototypes -> PROTOTYPES / SIGNATURES / LONG_RETURN, structs -> the _fields_ of the
+ctypes.Structure classes, object-like integer #defines -> DEFINES.  Nothing of it is restated here, so an ABI addition touches
+the header (and ADDED_LATER, when it joins a released version) and nothing else on the Python side.
 
 There is no fallback: if the library is missing or a symbol is absent this raises, and
 every op in this package goes through it.  torch is imported first so that the HIP
 runtime already loaded by PyTorch-ROCm is the one the library binds to."""
 from __future__ import annotations
 
+import collections
 import ctypes
+import operator
 import os
+import re
+import types
 
 import torch  # noqa: F401  (must precede the CDLL load)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PIT_LIB_PATH") or os.path.join(_HERE, "csrc", "libpit_hip.so")   # (override: diagnostic builds, tools/)
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "pit_hip.h"))
 
-_P = ctypes.c_void_p
-_I = ctypes.c_int
-_L = ctypes.c_long
-_F = ctypes.c_float
-_LL = ctypes.c_longlong
-_D = ctypes.c_double
+# ---- the header's text -> prototypes, structs, constants ------------------------------------------------------------------------
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong, "float": ctypes.c_float,
+            "double": ctypes.c_double}
+_RETURNS = {"int": ctypes.c_int, "long": ctypes.c_long, "const char*": ctypes.c_char_p}
+_BINARY = {"|": (1, operator.or_), "&": (2, operator.and_), "<<": (3, operator.lshift), ">>": (3, operator.rshift),
+           "+": (4, operator.add), "-": (4, operator.sub), "*": (5, operator.mul)}          # C's precedence
+_TOKEN = re.compile(r"0[xX][0-9a-fA-F]+[uUlL]*|\d+[uUlL]*|PIT_\w+|<<|>>|[-+*|&()]")
+
+Prototype = collections.namedtuple("Prototype", "restype argtypes argnames")
+Header = collections.namedtuple("Header", "prototypes structs defines")
+
+
+def _ctype(c_type: str, where: str):
+    """The ctypes type of a parameter or field: any pointer is c_void_p, a scalar must be in the map (never a default)."""
+    if "*" in c_type:
+        return ctypes.c_void_p
+    c_type = " ".join(w for w in c_type.split() if w not in ("const", "struct"))
+    if c_type not in _SCALARS:
+        raise ValueError(f"{where}: no ctypes type for the C type {c_type!r}")
+    return _SCALARS[c_type]
+
+
+def _declarators(text: str, where: str) -> list:
+    """[(name, ctypes type), ...] of one C declaration: `const float* x`, `double* const* p`, `int a, b`, `float *e, *q`."""
+    out, base = [], None
+    for piece in text.split(","):
+        m = re.fullmatch(r"\s*(.*?)(\w+)\s*", piece, flags=re.S)
+        if not m:
+            raise ValueError(f"{where}: cannot parse the declaration {' '.join(text.split())!r}")
+        spec, name = m.groups()
+        if base is None:                      # the first declarator names the base type; the `*`s belong to each declarator
+            base, star, rest = spec.partition("*")
+            spec = star + rest
+        elif spec.replace("*", " ").replace("const", " ").strip():
+            raise ValueError(f"{where}: cannot parse the declaration {' '.join(text.split())!r}")
+        out.append((name, _ctype(base + spec, f"{where}, {name}")))
+    return out
+
+
+def _evaluate(expr: str, known: dict, name: str) -> int:
+    """An integer #define's value: digits (L / U suffixes dropped), + - * << >> | & ( ) and earlier PIT_ names - nothing else."""
+    toks = _TOKEN.findall(expr)
+    if "".join(toks) != "".join(expr.split()) or not toks:
+        raise ValueError(f"#define {name}: {expr.strip()!r} is not an integer expression this binding evaluates")
+    pos = 0
+
+    def take():
+        nonlocal pos
+        if pos >= len(toks):
+            raise ValueError(f"#define {name}: {expr.strip()!r} ends early")
+        pos += 1
+        return toks[pos - 1]
+
+    def atom() -> int:
+        t = take()
+        if t == "(":
+            v = binary(1)
+            if take() != ")":
+                raise ValueError(f"#define {name}: unbalanced parentheses in {expr.strip()!r}")
+            return v
+        if t in "+-":
+            return atom() if t == "+" else -atom()
+        if t.startswith("PIT_"):
+            if t not in known:
+                raise ValueError(f"#define {name}: refers to {t}, which no earlier #define gives a value")
+            return known[t]
+        if t[0].isdigit():
+            return int(t.rstrip("uUlL"), 0)
+        raise ValueError(f"#define {name}: unexpected {t!r} in {expr.strip()!r}")
+
+    def binary(min_prec: int) -> int:
+        v = atom()
+        while pos < len(toks) and toks[pos] in _BINARY and _BINARY[toks[pos]][0] >= min_prec:
+            prec, fn = _BINARY[take()]
+            v = fn(v, binary(prec + 1))
+        return v
+
+    value = binary(1)
+    if pos != len(toks):
+        raise ValueError(f"#define {name}: unexpected {toks[pos]!r} in {expr.strip()!r}")
+    return value
+
+
+def parse_header(text: str) -> Header:
+    """Prototypes of the pit_* entries, struct layouts and object-like integer PIT_* #defines of a C header's text.  Anything
+    else in it (beside comments, other preprocessor lines, forward declarations and the extern "C" braces) raises."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text.replace("\\\n", " "), flags=re.S)
+    defines = {}
+    for name, paren, body in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(PIT_\w+)(\(?)([^\n]*)$", text, flags=re.M):
+        if not paren and body.strip():        # (function-like macros and the empty include guard are not values)
+            defines[name] = _evaluate(body, defines, name)
+    text = re.sub(r"^[ \t]*#[^\n]*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{', " ", text)
+    structs = {}
+
+    def struct(m) -> str:
+        where = f"struct {m.group(1)}"
+        structs[m.group(1)] = [f for decl in m.group(2).split(";") if decl.strip() for f in _declarators(decl, where)]
+        return " "
+    text = re.sub(r"(?:typedef\s+)?struct\s+(\w+)\s*\{(.*?)\}\s*\w*\s*;", struct, text, flags=re.S)
+    prototypes = {}
+    for stmt in text.split(";"):
+        stmt = stmt.strip().lstrip("}").strip()               # (the extern "C" block's closing brace)
+        if not stmt or re.fullmatch(r"struct\s+\w+", stmt):
+            continue
+        m = re.fullmatch(r"([\w\s*]+?)\s*\b(pit_\w+)\s*\(([^()]*)\)", stmt, flags=re.S)
+        if not m:
+            raise ValueError(f"cannot parse the declaration {' '.join(stmt.split())[:80]!r}")
+        ret, name, params = m.groups()
+        ret = re.sub(r"\s*\*", "*", " ".join(ret.split()))
+        if ret not in _RETURNS:
+            raise ValueError(f"{name}: no ctypes type for the return type {ret!r}")
+        args = [] if params.strip() == "void" else [a for p in params.split(",") for a in _declarators(p, name)]
+        prototypes[name] = Prototype(_RETURNS[ret], [t for _, t in args], [n for n, _ in args])
+    return Header(prototypes, structs, defines)
+
+
+try:
+    with open(HEADER_PATH) as _f:
+        _HEADER = parse_header(_f.read())
+except OSError as _e:
+    raise RuntimeError(f"{HEADER_PATH} not found: the binding is derived from it ({_e})") from None
+
+PROTOTYPES = _HEADER.prototypes                                           # name -> (restype, argtypes, argnames)
+SIGNATURES = {name: p.argtypes for name, p in PROTOTYPES.items()}         # name -> argtypes
+LONG_RETURN = {name for name, p in PROTOTYPES.items() if p.restype is ctypes.c_long}
+DEFINES = types.MappingProxyType(_HEADER.defines)                         # the header's own names -> values, read-only
+
 
 class MlpParamsJob(ctypes.Structure):
     """pit_mlp_params_job of include/pit_hip.h (the argument list of pit_mlp_bwd_params)."""
-    _fields_ = [("x", _P), ("ldx", _L), ("rows", _I), ("n0", _I), ("n1", _I), ("n2", _I), ("h", _P), ("out_gelu", _I),
-                ("d_y", _P), ("ld_dy", _L), ("d_w1", _P), ("d_b1", _P), ("d_w2", _P), ("d_b2", _P),
-                ("accumulate", _I), ("scratch", _P), ("math_mode", _I)]
+    _fields_ = _HEADER.structs["pit_mlp_params_job"]
 
 
 class BlockWeightsJob(ctypes.Structure):
     """pit_block_weights_job of include/pit_hip.h (the argument list of pit_block_weights)."""
-    _fields_ = [("mesh", _P), ("n_pts", _I), ("space_dim", _I), ("metric", _I), ("period", _F),
-                ("n_layers", _I), ("heads", _P), ("head_is_scale", _I), ("n_head", _I),
-                ("e", _P), ("q", _P), ("inv", _P), ("rowstat", _P), ("scale_out", _P)]
+    _fields_ = _HEADER.structs["pit_block_weights_job"]
 
 
 class SlabPlan(ctypes.Structure):
     """pit_slab_plan of include/pit_hip.h (the static per-slab plan of a masked cross-attention layer on a fixed mesh pair)."""
-    _fields_ = [("n_out", _I), ("n_in", _I), ("cap", _I), ("n_slabs", _I), ("umax", _I), ("stats", _P), ("rank_w", _F),
-                ("idx", _P), ("cnt", _P), ("m", _P), ("slot", _P), ("keys", _P), ("nkeys", _P), ("rows", _I),
-                ("grid_w", _I), ("grid_h", _I), ("patch_w", _I), ("patch_h", _I)]       # (all 0: consecutive rows)
+    _fields_ = _HEADER.structs["pit_slab_plan"]
 
 
 class DecoderWeightsJob(ctypes.Structure):
     """pit_decoder_weights_job of include/pit_hip.h (the argument list of pit_decoder_weights)."""
-    _fields_ = [("plan", _P), ("head", _P), ("head_is_scale", _I), ("n_head", _I), ("max_union", _I), ("max_count", _I),
-                ("pw", _P), ("qw", _P), ("scale_out", _P), ("w1", _P), ("w1f", _P), ("dim", _I)]
+    _fields_ = _HEADER.structs["pit_decoder_weights_job"]
 
 
-# The argument groups that recur in the layer entries beside the main mesh path (ragged, distance matrix, candidate lists), in
-# the header's order: their types here, their values in the *_args builders below SIGNATURES.
-_VALUES = [_P, _I, _L, _L]                 # values, dim, ld_values, values_bstride
-_VALUES_B = [_P, _I, _I, _L, _L]           # values, batch, dim, ld_values, values_bstride
-_HEAD = [_P, _I, _I]                       # head, n_head, head_is_scale
-_HEAD_BWD = _HEAD + [_P]                   # ..., scale
-_STATS = [_P, _F, _I]                      # stats, rank_w, masked
-_STATS_RAGGED = [_P, _P, _I]               # (rank_w per sample, on the device)
-_STATS_BWD = [_P, _I]                      # rowstat, masked
-_OUT = [_P, _L, _L, _I, _I, _P, _P]        # out, ld_out, out_bstride, out_col0, copy_inputs, rowstat, scale_out
-_DOUT = [_P, _L, _L, _I]                   # d_out, ld_dout, dout_bstride, out_col0
-_DVALUES = [_P, _L, _L, _I]                # d_values, ld_dvalues, dvalues_bstride, add_residual
-_DHEAD = [_P, _I, _P]                      # d_head, accumulate_head, workspace
-_SAVED_OUT = [_P, _L, _L]                  # out, ld_out, out_bstride (the forward's result, read by d(m) / d(sqd))
-_TAIL = [_I, _P]                           # math_mode, stream
-_RAGGED = [_P, _P, _I, _I, _I, _I, _P, _P]                  # mesh_out, mesh_in, mesh_batch, n_out, n_in, space_dim, len_out, len_in
-_RAGGED_STRIDED = _RAGGED[:6] + [_L, _L] + _RAGGED[6:]      # ..., out_stride, in_stride, len_out, len_in
-_RAGGED_LISTS = [_P, _P, _I]                                # nbr_idx, nbr_cnt, nbr_cap
-_MAT = [_P, _L, _L, _I, _I]                                 # m, ld_m, m_bstride, n_out, n_in
-_LIST = [_P, _P, _L, _L, _I, _I, _I]                        # idx, sqd, ld, bstride, cap, n_out, n_in
-_FWD_RAGGED = _VALUES + _HEAD + _STATS_RAGGED + _OUT + _RAGGED_LISTS + _TAIL
-_BWD_RAGGED = _VALUES + _HEAD_BWD + _STATS_BWD + _DOUT + _DVALUES + _DHEAD + _RAGGED_LISTS + [_P, _P] + _TAIL      # ..., rev_ptr, rev_row
-_FWD_DIST = _VALUES_B + _HEAD + _STATS + _OUT + _TAIL
-_BWD_DIST = _VALUES_B + _HEAD_BWD + _STATS_BWD + _DOUT + _DVALUES + _DHEAD
-
-# name -> argtypes, mirrors include/pit_hip.h one to one
-SIGNATURES = {
-    "pit_version": [],
-    "pit_error_string": [_I],
-    "pit_head_scale": [_P, _I, _P, _P],
-    "pit_select_fwd": [_P, _P, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P],
-    "pit_select_wide_fwd": [_P, _P, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P],
-    "pit_plan_fwd": [_P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P],
-    "pit_lists_transpose": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
-    "pit_neighbors_fwd": [_P, _P, _I, _I, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _P, _P],
-    "pit_posatt_fwd": [_P, _P, _I, _I, _I, _I, _I, _F,
-                       _P, _I, _I, _L, _L,
-                       _P, _I, _I,
-                       _P, _F, _I, _I,
-                       _P, _L, _L, _I, _I,
-                       _P, _P, _P, _P, _I, _I, _I, _P],
-    "pit_posatt_fwd_job": [_P, _P, _I, _I, _I, _I, _I, _F,
-                           _P, _I, _I, _L, _L,
-                           _P, _I, _I,
-                           _P, _F, _I, _I,
-                           _P, _L, _L, _I, _I,
-                           _P, _P, _P, _P, _I, _I, _I, _P, _P],
-    "pit_posatt_bwd": [_P, _P, _I, _I, _I, _I, _I, _F,
-                       _P, _I, _I, _L, _L,
-                       _P, _I, _I, _P,
-                       _P, _I,
-                       _P, _L, _L, _I,
-                       _P, _L, _L, _I,
-                       _P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _P],
-    "pit_posatt_dmesh": [_P, _P, _I, _I, _I, _I, _I, _F,
-                         _P, _I, _I, _L, _L,
-                         _P, _I, _I, _P,
-                         _P, _I,
-                         _P, _L, _L, _I,
-                         _P, _P, _I, _I, _P, _P,
-                         _P, _P, _I, _P, _P],
-    "pit_posatt_dmesh_workspace": [_I, _I, _I, _I, _I, _I],
-    "pit_posatt_dhead_finish": [_I, _P, _P, _P, _P, _P, _P, _P, _P],
-    "pit_block_supported": [_I, _I, _I, _I],
-    "pit_block_weights": [_P, _I, _I, _I, _F, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P],
-    "pit_block_fwd": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _L, _I, _P],
-    "pit_slab_plan_build": [_P, _P, _I, _I, _I, _I, _F, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
-    "pit_decoder_union_slots": [_P, _I],
-    "pit_slab_plan_build_patch": [_P, _P, _I, _I, _I, _I, _F, _P, _P, _I, _I, _I, _I, _I, _P, _F, _P, _P, _P, _P, _P, _P],
-    "pit_fold_supported": [_I, _I, _I, _I, _I],
-    "pit_fold_weights": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
-    "pit_fold_att_fwd": [_P, _P, _L, _L, _I, _I, _I, _P, _P, _L, _L, _I, _I, _P],
-    "pit_fold_att_bwd": [_P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _L, _L, _P, _L, _L, _P, _P, _P, _P, _I, _I, _P],
-    "pit_thin_tail_scratch_floats": [],
-    "pit_thin_tail_fwd": [_P, _L, _I, _I, _I, _P, _P, _P, _P, _L, _I, _P],
-    "pit_thin_tail_bwd": [_P, _L, _I, _I, _I, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _I, _P],
-    "pit_satt_supported": [_I, _I, _I, _I, _I],
-    "pit_satt_fwd": [_P, _I, _I, _I, _I, _F, _P, _L, _L, _I, _I, _P, _I, _I, _P, _P, _L, _L, _I, _I, _P, _P, _P, _I, _P],
-    "pit_satt_bwd": [_P, _I, _I, _I, _I, _F, _I, _I, _P, _I, _P, _P, _P, _P, _L, _L, _I, _P, _L, _L, _I, _P, _P, _I, _P, _P],
-    "pit_satt_tiles_elems": [_I],
-    "pit_mlp_chain_supported": [_I, _I, _I, _I],
-    "pit_mlp_chain_fwd": [_P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _P],
-    "pit_mlp_chain_bwd": [_I, _I, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _I, _I, _P],
-    "pit_cast_bf16_multi": [_I, _P, _P, _P, _P],
-    "pit_linear_fwd": [_P, _L, _I, _I, _I, _P, _P, _P, _L, _I, _P],
-    "pit_linear_bwd": [_P, _L, _I, _I, _I, _P, _P, _L, _P, _L, _P, _I, _I, _P],
-    "pit_edge_supported": [_I, _I, _I, _I],
-    "pit_decoder_weights": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
-    "pit_decoder_fwd": [_P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L,
-                        _P, _P, _P, _I, _P, _I, _P],
-    "pit_decoder_bwd": [_P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _L, _P, _P, _L, _P,
-                        _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P],
-    "pit_union_att_supported": [_I, _I, _I, _I],
-    "pit_union_att_fwd": [_P, _P, _L, _L, _I, _I, _I, _P, _P, _L, _L, _I, _I, _P],
-    "pit_union_att_bwd": [_P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _L, _L, _I, _P, _L, _L, _P, _I, _P],
-    "pit_encoder_fwd": [_P, _P, _I, _I, _P, _L, _L, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P,
-                        _P, _P, _P, _P, _P, _L, _P, _P, _P, _L, _P, _P, _P],
-    "pit_encoder_bwd": [_P, _P, _I, _I, _P, _L, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P],
-    "pit_posatt_pre_supported": [_I, _I, _I, _I],
-    "pit_posatt_pre_fwd": [_P, _P, _I, _I, _I, _I, _P, _L, _L, _P, _L, _L, _I, _I, _I, _P],
-    "pit_posatt_pre_bwd": [_P, _P, _P, _I, _I, _I, _I, _P, _L, _L, _P, _L, _L, _I, _P, _L, _L, _I, _P, _I, _P],
-    "pit_block_bwd": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _L, _P, _P, _L, _P, _P, _I, _P],
-    "pit_mlp_bf16_io_supported": [_I, _I, _I, _I, _I],
-    "pit_mlp_fwd": [_P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _L, _I, _P],
-    "pit_mlp_bwd": [_P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _L,
-                    _P, _L, _P, _P, _P, _P, _I, _P, _I, _P],
-    "pit_mlp_bwd_data": [_I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _L, _P, _L, _P, _I, _P],
-    "pit_mlp_bwd_params": [_P, _L, _I, _I, _I, _I, _P, _I, _P, _L, _P, _P, _P, _P, _I, _P, _I, _P],
-    "pit_mlp_bwd_params_ordered": [_P, _L, _I, _I, _I, _I, _P, _I, _P, _L, _P, _P, _P, _P, _I, _P, _P, _P],
-    "pit_mlp_bwd_params_ordered_workspace": [_I, _I, _I, _I],
-    "pit_mlp_bwd_params_ordered_mfma": [_P, _L, _I, _I, _I, _I, _P, _I, _P, _L, _P, _P, _P, _P, _I, _P, _P, _P],
-    "pit_mlp_bwd_params_ordered_mfma_workspace": [_I, _I, _I, _I],
-    "pit_lists_sort_ranges": [_P, _P, _I, _I, _L, _P, _P],
-    "pit_posatt_overflow_dv_ordered": [_P, _P, _I, _I, _I, _I, _I, _F, _I, _I, _P, _I, _I, _P, _P,
-                                       _P, _L, _L, _I, _P, _L, _L, _P, _I, _I, _P],
-    "pit_mlp_bwd_params_deferrable": [_I, _I, _I, _I, _I, _L],
-    "pit_rel_lp_loss_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
-    "pit_rel_lp_loss_fwd_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P],
-    "pit_rel_lp_loss_fwd_grad_ordered": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P],
-    "pit_rel_lp_loss_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "pit_plan_ragged_fwd": [_P, _P, _I, _I, _I, _I, _P, _P, _F, _I, _P, _P, _I, _P, _P, _P],
-    "pit_posatt_ragged_fwd": _RAGGED + _FWD_RAGGED,
-    "pit_posatt_ragged_bwd": _RAGGED + _BWD_RAGGED,
-    "pit_plan_ragged_strided_fwd": [_P, _P, _I, _I, _I, _I, _L, _L, _P, _P, _F, _I, _P, _P, _I, _P, _P, _P],
-    "pit_posatt_ragged_strided_fwd": _RAGGED_STRIDED + _FWD_RAGGED,
-    "pit_posatt_ragged_strided_bwd": _RAGGED_STRIDED + _BWD_RAGGED,
-    "pit_rel_lp_loss_ragged_fwd": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
-    "pit_rel_lp_loss_ragged_bwd": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
-    "pit_rel_lp_loss_ragged_fwd_grad": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P],
-    "pit_rel_max_norm_ragged": [_P, _P, _P, _I, _I, _I, _P, _P],
-    "pit_distmat_select_fwd": [_P, _L, _L, _I, _I, _I, _I, _I, _P, _P],
-    "pit_distmat_fwd": _MAT + _FWD_DIST,
-    "pit_distmat_bwd_workspace": [_I, _I, _I],
-    "pit_distmat_bwd": _MAT + _BWD_DIST + [_P] + _SAVED_OUT + [_P] + _TAIL,                 # ..., d_m, out ..., a_workspace
-    "pit_distlist_select_fwd": [_P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _P, _P],
-    "pit_distlist_fwd": _LIST + _FWD_DIST,
-    "pit_distlist_bwd_workspace": [_I, _I, _I, _I],
-    "pit_distlist_bwd": _LIST + _BWD_DIST + [_P] + _SAVED_OUT + [_P] * 5 + _TAIL,            # ..., d_sqd, out ..., the transposed index, dv_workspace
-    "pit_rel_max_norm": [_P, _P, _I, _I, _I, _P, _P, _P],
-    "pit_eval_metrics_workspace": [_I, _I, _I],
-    "pit_eval_metrics": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _L, _P, _L, _L, _I, _P, _P],
-    "pit_batch_feed": [_P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _P, _LL, _P, _P, _P, _P],
-    "pit_batch_feed_points": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P, _LL, _P, _P, _P,
-                              _P],
-    "pit_fps": [_P, _I, _I, _I, _L, _P, _P, _I, _I, _P, _P, _P, _P],
-    "pit_fps_large_workspace": [_I, _I, _I],
-    "pit_fps_large": [_P, _I, _I, _I, _L, _P, _P, _I, _I, _P, _P, _P, _I, _P, _P],
-    "pit_knn_box": [_P, _P, _I, _I, _I, _I, _L, _L, _P, _I, _P, _P, _P, _P],
-    "pit_knn_rows": [_P, _L, _L, _I, _I, _I, _I, _P, _P, _P, _P],
-    "pit_knn_last_form": [],
-    "pit_instance_norm_fwd": [_P, _L, _L, _I, _I, _I, _F, _P, _P, _P],
-    "pit_instance_norm_bwd": [_P, _P, _P, _I, _I, _I, _P, _P],
-    "pit_adam_step": [_P, _P, _P, _P, _L, _P, _F, _F, _I, _F, _F, _F, _F, _I, _P, _P],
-    "pit_adam_guard_parts": [_L],
-    "pit_adam_step_guarded": [_P, _P, _P, _P, _L, _P, _P, _F, _F, _I, _I, _D, _F, _F, _F, _F, _I, _D, _I, _P, _P, _P, _P, _P],
-    "pit_adam_step_averaged": [_P, _P, _P, _P, _L, _P, _P, _F, _F, _I, _I, _D, _F, _F, _F, _F, _I, _D, _I, _P, _P, _P, _P,
-                               _P, _P, _I, _D, _I, _LL, _P],
-    "pit_exchange_words": [_P, _P, _L, _P],
-    "pit_debug_mfma_tile": [_P, _P, _P, _P],
-    "pit_debug_rider_counts": [_P, _I, _I],
-    "pit_debug_gemm_counts": [_P, _I, _I],
-    "pit_debug_att_counts": [_P, _I, _I],
-    "pit_block_fwd_set_form": [_I],
-    "pit_block_fwd_last_rows": [],
-    "pit_block_bwd_last_riders": [_P, _I],
-}
-
-LONG_RETURN = {"pit_satt_tiles_elems", "pit_posatt_dmesh_workspace", "pit_mlp_bwd_params_ordered_workspace",
-               "pit_mlp_bwd_params_ordered_mfma_workspace", "pit_distmat_bwd_workspace", "pit_distlist_bwd_workspace",
-               "pit_eval_metrics_workspace", "pit_fps_large_workspace"}
 # entries added to an ABI version after its first release (PIT_HAS_* in the header): a library of the same version built before
 # them lacks the symbols
 ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_workspace", "pit_distlist_bwd",
@@ -232,26 +186,30 @@ ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_
                "pit_batch_feed_points",                                            # PIT_HAS_FEED_POINTS
                "pit_fps_large_workspace", "pit_fps_large",                         # PIT_HAS_FPS_LARGE
                "pit_knn_box", "pit_knn_rows", "pit_knn_last_form"}                 # PIT_HAS_KNN
-FPS_MAX_POINTS = 16384   # PIT_FPS_MAX_POINTS
-FPS_MAX_POINTS_WIDE = 4096       # PIT_FPS_MAX_POINTS_WIDE (space_dim 4..8)
-FPS_LARGE_MAX_POINTS = 4194304   # PIT_FPS_LARGE_MAX_POINTS (every space_dim)
-FPS_LARGE_MAX_SAMPLES = 16384    # PIT_FPS_LARGE_MAX_SAMPLES
-KNN_MAX_K = 2048         # PIT_KNN_MAX_K
-KNN_REG_MAX_KEYS = 1024  # PIT_KNN_REG_MAX_KEYS
-GUARD_MAX_PARTS = 256    # PIT_GUARD_MAX_PARTS
-GUARD_STATE_DOUBLES = 10         # PIT_GUARD_STATE_DOUBLES
-FEED_MAX_FIELDS = 8      # PIT_FEED_MAX_FIELDS
-FEED_MAX_ROW_BYTES = 1 << 30     # PIT_FEED_MAX_ROW_BYTES
-FEED_WHOLE_ROW, FEED_POINTS_G0, FEED_POINTS_G1 = 0, 1, 2         # PIT_FEED_WHOLE_ROW, PIT_FEED_POINTS_G0, PIT_FEED_POINTS_G1
-EVAL_STATE_DOUBLES = 8   # PIT_EVAL_STATE_DOUBLES
-EVAL_MAX_PARTS = 64      # PIT_EVAL_MAX_PARTS
-DISTLIST_CHUNK = 512   # PIT_DISTLIST_CHUNK
+ABI_VERSION = DEFINES["PIT_ABI_VERSION"]      # of the header this checkout carries; lib() holds the loaded library to it
+FPS_MAX_POINTS = DEFINES["PIT_FPS_MAX_POINTS"]
+FPS_MAX_POINTS_WIDE = DEFINES["PIT_FPS_MAX_POINTS_WIDE"]          # (space_dim 4..8)
+FPS_LARGE_MAX_POINTS = DEFINES["PIT_FPS_LARGE_MAX_POINTS"]        # (every space_dim)
+FPS_LARGE_MAX_SAMPLES = DEFINES["PIT_FPS_LARGE_MAX_SAMPLES"]
+KNN_MAX_K = DEFINES["PIT_KNN_MAX_K"]
+KNN_REG_MAX_KEYS = DEFINES["PIT_KNN_REG_MAX_KEYS"]
+GUARD_MAX_PARTS = DEFINES["PIT_GUARD_MAX_PARTS"]
+GUARD_STATE_DOUBLES = DEFINES["PIT_GUARD_STATE_DOUBLES"]
+FEED_MAX_FIELDS = DEFINES["PIT_FEED_MAX_FIELDS"]
+FEED_MAX_ROW_BYTES = DEFINES["PIT_FEED_MAX_ROW_BYTES"]
+FEED_WHOLE_ROW = DEFINES["PIT_FEED_WHOLE_ROW"]
+FEED_POINTS_G0 = DEFINES["PIT_FEED_POINTS_G0"]
+FEED_POINTS_G1 = DEFINES["PIT_FEED_POINTS_G1"]
+EVAL_STATE_DOUBLES = DEFINES["PIT_EVAL_STATE_DOUBLES"]
+EVAL_MAX_PARTS = DEFINES["PIT_EVAL_MAX_PARTS"]
+DISTLIST_CHUNK = DEFINES["PIT_DISTLIST_CHUNK"]
 
 
 def distlist_chunk_slots(n_out: int, cap: int) -> int:
-    """PIT_DISTLIST_CHUNK_SLOTS of include/pit_hip.h."""
+    """PIT_DISTLIST_CHUNK_SLOTS of include/pit_hip.h (a function-like macro: written out here, checked against a compiler by the
+    tests)."""
     return int(n_out) * int(cap) // (DISTLIST_CHUNK // 2) + 1
-ABI_VERSION = 31       # PIT_ABI_VERSION of include/pit_hip.h this binding was written against
+
 
 _lib = None
 
@@ -264,7 +222,7 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} not found: build it with `python -m position_induced_transformer_amd.build` "
                 "(hipcc --offload-arch=gfx950). There is no CPU or PyTorch fallback for the PiT hot path.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
+        for name, proto in PROTOTYPES.items():
             try:
                 fn = getattr(handle, name)   # AttributeError if the ABI lost a symbol
             except AttributeError:
@@ -272,8 +230,8 @@ def lib() -> ctypes.CDLL:
                     raise
                 raise RuntimeError(f"{LIB_PATH} was built before {name} joined PIT_ABI_VERSION {ABI_VERSION}: "
                                    "rebuild it (python -m position_induced_transformer_amd.build)") from None
-            fn.argtypes = argtypes
-            fn.restype = ctypes.c_char_p if name == "pit_error_string" else (_L if name in LONG_RETURN else _I)
+            fn.argtypes = proto.argtypes
+            fn.restype = proto.restype
         got = handle.pit_version()           # the default library and a PIT_LIB_PATH override alike
         if got != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH} implements PIT_ABI_VERSION {got}, this package binds version {ABI_VERSION}: "
@@ -296,32 +254,39 @@ def ptr(t) -> int:
     return 0 if t is None else t.data_ptr()
 
 
-# ---- the values of the argument groups above (t: a (batch, points, channels) tensor whose rows are contiguous) --------------------
+# ---- argument groups that recur in the layer entries beside the main mesh path (ragged, distance matrix, candidate lists), in the
+# header's parameter order (t: a (batch, points, channels) tensor whose rows are contiguous) ---------------------------------------
 def values_args(t, with_batch: bool) -> tuple:
+    """values, [batch,] dim, ld_values, values_bstride"""
     b, _, d = t.shape
     return (t.data_ptr(),) + ((b, d) if with_batch else (d,)) + (t.stride(1), t.stride(0))
 
 
 def head_args(head, n_head: int, is_scale: bool, *scale) -> tuple:
-    """_HEAD; with the forward's scale_out as ``scale``: _HEAD_BWD."""
+    """head, n_head, head_is_scale; with the forward's scale_out as ``scale``: ..., scale"""
     return (head.data_ptr(), n_head, 1 if is_scale else 0) + tuple(c.data_ptr() for c in scale)
 
 
 def out_args(out, d: int, concat: bool, rowstat, scale_out) -> tuple:
+    """out, ld_out, out_bstride, out_col0, copy_inputs, rowstat, scale_out"""
     return (out.data_ptr(), out.stride(1), out.stride(0), d if concat else 0, 1 if concat else 0, rowstat.data_ptr(), scale_out.data_ptr())
 
 
 def dout_args(d_out, d: int, concat: bool) -> tuple:
+    """d_out, ld_dout, dout_bstride, out_col0"""
     return (d_out.data_ptr(), d_out.stride(1), d_out.stride(0), d if concat else 0)
 
 
 def dvalues_args(d_values, j: int, d: int, concat: bool) -> tuple:
+    """d_values, ld_dvalues, dvalues_bstride, add_residual"""
     return (ptr(d_values), d, j * d, 1 if concat else 0)
 
 
 def dhead_args(d_head, workspace) -> tuple:
+    """d_head, accumulate_head, workspace"""
     return (ptr(d_head), 0, ptr(workspace))
 
 
 def saved_out_args(out) -> tuple:
+    """out, ld_out, out_bstride (the forward's result, read by d(m) / d(sqd))"""
     return (None, 0, 0) if out is None else (out.data_ptr(), out.stride(1), out.stride(0))

@@ -21,8 +21,24 @@ import torch
 
 from . import _lib
 
-METRIC_ID = {"euclid": 0, "periodic1d": 1, "periodic2d": 2}
-MAX_SPACE_DIM = 8                  # PIT_MAX_SPACE_DIM of include/pit_hip.h: coordinates per mesh point
+# The header's values this module uses, bound once at import (include/pit_hip.h through _lib.DEFINES): no launch path looks one up
+_H = _lib.DEFINES
+METRIC_ID = {"euclid": _H["PIT_METRIC_EUCLID"], "periodic1d": _H["PIT_METRIC_PERIODIC1D"], "periodic2d": _H["PIT_METRIC_PERIODIC2D"]}
+MAX_SPACE_DIM = _H["PIT_MAX_SPACE_DIM"]                # coordinates per mesh point
+MATH_MODES = {"fp32": _H["PIT_MATH_FP32"], "bf16": _H["PIT_MATH_BF16"]}
+# bf16 STORAGE flags of the `math_mode` argument
+IO_X_BF16, IO_SAVE_BF16, IO_DX_BF16 = _H["PIT_IO_X_BF16"], _H["PIT_IO_SAVE_BF16"], _H["PIT_IO_DX_BF16"]
+IO_OUT_BF16, IO_DOUT_BF16 = _H["PIT_IO_OUT_BF16"], _H["PIT_IO_DOUT_BF16"]
+ATT_UNION = _H["PIT_ATT_UNION"]
+SLAB_UNION_MAX = _H["PIT_SLAB_UNION_MAX"]
+LIST_MAX_CAP = _H["PIT_DISTLIST_MAX_CAP"]              # slots of a row the selection holds in registers
+KNN_MAX_K = _lib.KNN_MAX_K                             # the width the list layers accept (LIST_MAX_CAP)
+KNN_REG_MAX_KEYS = _lib.KNN_REG_MAX_KEYS               # longer rows are streamed (form 2)
+_DSCALE_SLOTS = _H["PIT_DSCALE_SLOTS"]                 # fp64 accumulators per head of a d(scale) workspace
+_HEAD_ACCUMULATE, _HEAD_DEFER, _HEAD_IS_SCALE = _H["PIT_HEAD_ACCUMULATE"], _H["PIT_HEAD_DEFER"], _H["PIT_HEAD_IS_SCALE"]
+_EVAL_ADVANCE, _EVAL_STORE_TRUE = _H["PIT_EVAL_ADVANCE"], _H["PIT_EVAL_STORE_TRUE"]
+_ERR_UNSUPPORTED = _H["PIT_ERR_UNSUPPORTED"]
+del _H
 
 # In-place gradient accumulation is OPT-IN per parameter: ddp.FlatGradients marks the parameters whose
 # ``.grad`` it owns (``mark_inplace_grad``), and only for those - while the ``.grad`` is still the
@@ -73,8 +89,8 @@ def _dscale_workspace(device, n_head: int) -> torch.Tensor:
     zeroed buffer per device serves every layer (launches are stream-ordered)."""
     key = _ws_key(device)                     # per (device, stream): concurrent streams never share accumulators
     ws = _DSCALE_WS.get(key)
-    if ws is None or ws.numel() < n_head * 1024 + 8:
-        ws = torch.zeros(max(8, n_head) * 1024 + 8, device=device, dtype=torch.float64)   # slots + counter
+    if ws is None or ws.numel() < n_head * _DSCALE_SLOTS + 8:
+        ws = torch.zeros(max(8, n_head) * _DSCALE_SLOTS + 8, device=device, dtype=torch.float64)   # slots + counter
         _DSCALE_WS[key] = ws
     if _capturing():
         _pin(ws)
@@ -101,7 +117,7 @@ def _layer_workspace(slot: torch.Tensor, n_head: int) -> torch.Tensor:
     if ws is None:
         while len(_LAYER_WS) >= 1024:         # gradient buffers were re-created many times: drop the oldest
             _LAYER_WS.pop(next(iter(_LAYER_WS)))
-        ws = _LAYER_WS[key] = torch.zeros(n_head * 1024, device=slot.device, dtype=torch.float64)
+        ws = _LAYER_WS[key] = torch.zeros(n_head * _DSCALE_SLOTS, device=slot.device, dtype=torch.float64)
     if _capturing():
         _pin(ws)
     return ws
@@ -135,8 +151,8 @@ def _flush_head_finishes(task: int) -> None:
 
 def _launch_head_finishes(entries, rider=None) -> None:
     """ONE pit_posatt_dhead_finish launch on the current device and stream: d(lmda) of every layer in ``entries`` =
-    [(work, d_head, head, scale, n_head, flags), ...] from its accumulators ``work`` (flags: 1 = add into d_head in place,
-    4 = the head is the scale itself), with the postponed weight-gradient job ``rider`` (_PENDING_DW's form) riding along."""
+    [(work, d_head, head, scale, n_head, flags), ...] from its accumulators ``work`` (flags: PIT_HEAD_ACCUMULATE = add into d_head in
+    place, PIT_HEAD_IS_SCALE = the head is the scale itself), with the postponed weight-gradient job ``rider`` (_PENDING_DW's form) riding along."""
     n = len(entries)
     ws, dh, hd, sc = ((ctypes.c_void_p * n)(*[_lib.ptr(e[i]) for e in entries]) for i in range(4))
     nh = (ctypes.c_int * n)(*[e[4] for e in entries])
@@ -191,13 +207,13 @@ class _HeadGrad:
                            which exists whether or not lmda needs a gradient (_PosAtt); otherwise a fresh torch.zeros buffer;
       always_accumulators  accumulators although ``need`` is false: the launch reduces d(scale) unconditionally (_Encoder);
       kernel_finishes      the launch itself forms d(lmda) unless deferred (_PosAtt's candidate-list / dense launch): it is handed
-                           ``d_head`` and ``acc`` (bit 1: add in place, bit 2: PIT_HEAD_DEFER) and ``finish`` only queues."""
+                           ``d_head`` and ``acc`` (PIT_HEAD_ACCUMULATE: add in place, PIT_HEAD_DEFER) and ``finish`` only queues."""
     __slots__ = ("need", "n_head", "scale_bit", "kernel_finishes", "slot", "defer", "work", "d_head")
 
     def __init__(self, head_param, need: bool, n_head: int, device, head_is_scale: bool, *, shared_workspace: bool = False,
                  always_accumulators: bool = False, kernel_finishes: bool = False):
         self.need, self.n_head, self.kernel_finishes = bool(need), n_head, kernel_finishes
-        self.scale_bit = 4 if head_is_scale else 0
+        self.scale_bit = _HEAD_IS_SCALE if head_is_scale else 0
         self.slot = _grad_slot(head_param) if need else None
         self.defer = bool(DEFER_HEAD_FINISH and self.slot is not None)
         if self.defer:
@@ -206,7 +222,7 @@ class _HeadGrad:
         elif shared_workspace:
             self.work = _dscale_workspace(device, n_head)
         elif need or always_accumulators:
-            self.work = torch.zeros(n_head * 1024, device=device, dtype=torch.float64)
+            self.work = torch.zeros(n_head * _DSCALE_SLOTS, device=device, dtype=torch.float64)
         else:
             self.work = None
         if self.slot is not None:
@@ -216,7 +232,7 @@ class _HeadGrad:
 
     @property
     def acc(self) -> int:
-        return (1 if self.slot is not None else 0) | (2 if self.defer else 0)
+        return (_HEAD_ACCUMULATE if self.slot is not None else 0) | (_HEAD_DEFER if self.defer else 0)
 
     def finish(self, head, scale):
         """After the launch: what the backward returns to autograd for lmda (None: not wanted, or it went in place)."""
@@ -227,7 +243,7 @@ class _HeadGrad:
         """``finish`` for [(_HeadGrad, head, scale), ...] of one node: the deferred layers are queued, all others share ONE launch."""
         now = []
         for g, head, scale in layers:
-            entry = (g.work, g.d_head, head, scale, g.n_head, (1 if g.slot is not None else 0) | g.scale_bit)
+            entry = (g.work, g.d_head, head, scale, g.n_head, (_HEAD_ACCUMULATE if g.slot is not None else 0) | g.scale_bit)
             if g.defer:
                 _defer_head_finish(*entry)
             elif g.need and not g.kernel_finishes:
@@ -432,8 +448,6 @@ def _dw_deliver(job, inplace: bool, device):
     return (None,) * 4 if inplace else tuple(keep[4:])
 
 
-# bf16 STORAGE flags of the `math_mode` argument (include/pit_hip.h, PIT_IO_*)
-IO_X_BF16, IO_SAVE_BF16, IO_DX_BF16, IO_OUT_BF16, IO_DOUT_BF16 = 0x100, 0x200, 0x400, 0x800, 0x1000
 # bf16 mode: the decoder tail (up-projection output, the decoder MLP's saved activations, their gradients) is kept in
 # memory as bf16 when the shapes take the kernels that implement it (pit.decoder asks); PIT_BF16_STORAGE=0: fp32 tensors
 BF16_STORAGE = os.environ.get("PIT_BF16_STORAGE", "1") != "0"
@@ -481,7 +495,6 @@ def mesh_period(metric: str, mesh_in: torch.Tensor) -> float:
     return 0.0
 
 
-SLAB_UNION_MAX = 64                                          # PIT_SLAB_UNION_MAX
 FOLD_SLAB_ROWS = (256, 128, 64)                              # slab heights MeshPlan.fold_plan tries, tallest first
 # The fused decoder's slabs as 4 x 4 patches of a row-major output grid instead of 16 consecutive rows (pit_hip.h: pit_slab_plan,
 # patch geometry): the rows of a patch list neighbouring keys, so a slab's key union - what its gather, tile copies and atomic adds scale
@@ -517,7 +530,6 @@ PLAN_FLAGS = 0                                               # pit_plan_fwd's `f
 UNION_TILES = os.environ.get("PIT_UNION_TILES", "auto")      # "auto" (probe per kind of plan), "0", "1"
 UNION_DV = os.environ.get("PIT_UNION_DV", "auto")            # d(values) of union-tile layers: "auto", "lists" (transposed lists)
 _UNION_DECISIONS = {}
-ATT_UNION = 0x2000                                           # PIT_ATT_UNION
 
 
 def as_lengths(lengths, device, batch: int) -> torch.Tensor:
@@ -780,7 +792,7 @@ class MeshPlan:
         rc = _lib.lib().pit_lists_transpose(self.nbr_idx.data_ptr(), self.nbr_cnt.data_ptr(), self.mesh_batch, self.n_out,
                                             self.n_in, self.nbr_cap, rev_ptr.data_ptr(), rev_row.data_ptr(), work.data_ptr(),
                                             _lib.stream_ptr())
-        if rc == -4:                                    # PIT_ERR_UNSUPPORTED (rows longer than 4096 keys): the whole plan again
+        if rc == _ERR_UNSUPPORTED:                      # (rows longer than 4096 keys): the whole plan again
             self._build_lists(self.nbr_cap, True)
             return
         _lib.check(rc, "pit_lists_transpose")
@@ -1753,9 +1765,6 @@ def posatt_dist_apply(values: torch.Tensor, lmda: torch.Tensor, plan: DistPlan, 
 
 
 # ---- the same layer on candidate lists of caller-supplied squared distances (csrc/pit_distlist.hip; metric.py) -------------------
-LIST_MAX_CAP = 2048         # PIT_DISTLIST_MAX_CAP: slots of a row the selection holds in registers
-
-
 def list_capacity(locality: float, n_in: int) -> int:
     """Least width of the candidate lists of a layer of ``locality`` over ``n_in`` keys: k + 2 slots (the selection needs
     m_(k) and m_(k+1) and the row's tie at m_(k+1)), 1 without a mask."""
@@ -3421,7 +3430,7 @@ def eval_metrics(true: torch.Tensor, pred: torch.Tensor, out_dim: int, p: int, s
     rc = _lib.lib().pit_eval_metrics(t.data_ptr(), q.data_ptr(), _lib.ptr(sc), _lib.ptr(sh), _lib.ptr(lengths), _lib.ptr(n_valid),
                                      b, npts, out_dim, int(p), state.data_ptr(), _lib.ptr(per_sample), ps_stride,
                                      _lib.ptr(pred_store), store_stride, capacity,
-                                     (1 if advance else 0) | (2 if store_true else 0), ws.data_ptr(),
+                                     (_EVAL_ADVANCE if advance else 0) | (_EVAL_STORE_TRUE if store_true else 0), ws.data_ptr(),
                                      _lib.stream_ptr())
     _lib.check(rc, "pit_eval_metrics")
 
@@ -3713,9 +3722,6 @@ def _fps_run(mesh, n_samples, lengths, start, slice_points) -> FpsResult:
     return FpsResult(idx, out, out_len)
 
 
-KNN_MAX_K = _lib.KNN_MAX_K                  # PIT_KNN_MAX_K: the width the list layers accept (LIST_MAX_CAP)
-KNN_REG_MAX_KEYS = _lib.KNN_REG_MAX_KEYS    # PIT_KNN_REG_MAX_KEYS: longer rows are streamed (form 2)
-
 KnnResult = collections.namedtuple("KnnResult", ("idx", "dist", "next"))
 KnnResult.__doc__ = """Result of ``knn_box`` / ``knn_rows``: ``idx`` (.., N, k) int32 - the k nearest keys of every row, ascending
 by (distance, key index); ``dist`` (.., N, k) fp32 - their distances, the kernel's own values; ``next`` (.., N) fp32 - the distance
@@ -3943,7 +3949,6 @@ def instance_norm_points(x: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
     return _InstanceNorm.apply(x, eps)
 
 
-MATH_MODES = {"fp32": 0, "bf16": 1}      # PIT_MATH_* of include/pit_hip.h
 _MATH = threading.local()
 
 
