@@ -934,6 +934,53 @@ int pit_distlist_bwd(const int* idx, const float* sqd, long ld, long bstride, in
                      const int* rev_ptr, const int* rev_pos, const int* chunk_ptr, const int* chunk_key, float* dv_workspace,
                      int math_mode, void* stream);
 
+/* ---- Ragged batches on candidate lists (additions to ABI 31; csrc/pit_distlist.hip) ------------------------------------------------
+ * The three list entries above for a padded batch whose sample s has len_out[s] rows and len_in[s] keys: int32 DEVICE arrays of
+ * `batch` entries, read by the kernels and clamped into [1, n_out] / [1, n_in]; either may be NULL = the full width.  No host
+ * synchronisation: one captured graph serves every mix of sizes.  Per-sample lists only (bstride != 0, or a batch of one:
+ * PIT_ERR_SIZE otherwise).  A library built from this header defines PIT_HAS_DISTLIST_RAGGED; PIT_ABI_VERSION is unchanged
+ * (nothing that existed changed: the entries above run the code and give the bits they did).
+ * The result for sample s is what the entries above compute for that cloud alone - lists idx[s][0:len_out[s]], values
+ * [0:len_in[s]], n_in = len_in[s]:
+ *   - a slot is valid iff its key lies in [0, len_in[s]); keys in [len_in[s], n_in) are padding like any key outside [0, n_in):
+ *     compared, never dereferenced, their sqd may hold anything;
+ *   - the rank (k_s, w_s) comes from len_in[s] and `locality` on the device with the fp32 operations of ops.quantile_rank (the
+ *     rule of pit_plan_ragged_fwd); pit_distlist_select_ragged_fwd writes w_s to rank_w[s] (mesh_batch floats), which
+ *     pit_distlist_ragged_fwd reads.  The width check (rank_k <= cap - 1) uses the rank of the padded n_in, which bounds k_s;
+ *   - a row i >= len_out[s]: stats 0, every head column of out 0 (copy_inputs: the input columns copied as they are), rowstat 0,
+ *     d_sqd 0, no contribution to d_values or d_head; its list, its sqd and its d_out row are never read;
+ *   - d_values of a key j >= len_in[s] is written as zero; value rows j >= len_in[s] are never read (they may hold NaN).
+ * Precondition, not checked: a real row lists at least min(k_s + 2, len_in[s]) valid slots and no key twice.
+ * The transposed index is the one of pit_distlist_bwd, built from the keys alone against the padded n_in - it does not depend on
+ * the lengths, which filter where the slots are read (an entry whose row is >= len_out[s] weighs 0).  Order of d_values: a
+ * key's entries ascend in row * cap + slot, so the entries of padded rows stand behind the real ones; the real entries take the
+ * places of the same 64-entry groups and PIT_DISTLIST_CHUNK-entry chunks as in the cloud-alone run and skipped entries add +0:
+ * for a key whose whole range fits one chunk the bits are the cloud-alone run's.  A longer range is summed chunk by chunk by
+ * separate waves and added in chunk order; it is specified to a tolerance only.  Every other sum is per row and has the
+ * cloud-alone order; d(scale) goes through the fp64 slots as above. */
+#define PIT_HAS_DISTLIST_RAGGED 1
+int pit_distlist_select_ragged_fwd(const int* idx, const float* sqd, long ld, long bstride, int cap, int mesh_batch, int n_out, int n_in,
+                                   float locality, int need_kth, const int* len_out, const int* len_in, float* stats, float* rank_w,
+                                   void* stream);
+int pit_distlist_ragged_fwd(const int* idx, const float* sqd, long ld, long bstride, int cap, int n_out, int n_in,
+                            const float* values, int batch, int dim, long ld_values, long values_bstride,
+                            const float* head, int n_head, int head_is_scale,
+                            const float* stats, const float* rank_w, int masked,
+                            const int* len_out, const int* len_in,
+                            float* out, long ld_out, long out_bstride, int out_col0, int copy_inputs,
+                            float* rowstat, float* scale_out, int math_mode, void* stream);
+int pit_distlist_ragged_bwd(const int* idx, const float* sqd, long ld, long bstride, int cap, int n_out, int n_in,
+                            const float* values, int batch, int dim, long ld_values, long values_bstride,
+                            const float* head, int n_head, int head_is_scale, const float* scale,
+                            const float* rowstat, int masked,
+                            const int* len_out, const int* len_in,
+                            const float* d_out, long ld_dout, long dout_bstride, int out_col0,
+                            float* d_values, long ld_dvalues, long dvalues_bstride, int add_residual,
+                            float* d_head, int accumulate_head, double* workspace,
+                            float* d_sqd, const float* out, long ld_out, long out_bstride,
+                            const int* rev_ptr, const int* rev_pos, const int* chunk_ptr, const int* chunk_key, float* dv_workspace,
+                            int math_mode, void* stream);
+
 /* ---- A training step and the evaluation metric on ragged batches (additions to ABI 31; csrc/pit_ragged_step.hip) -----------------
  * utils.py:59-98 (RelMaxNorm, RelLpNorm) on every sample TRUNCATED to its first len[s] points, as engine.TrainStep and
  * utils.RelMaxNorm use them with lengths.  A library built from this header defines PIT_HAS_RAGGED_STEP; PIT_ABI_VERSION is
@@ -1300,6 +1347,19 @@ int pit_knn_box(const float* mesh_out, const float* mesh_in, int batch, int n_ou
 int pit_knn_rows(const float* m, long ld_m, long m_bstride, int batch, int n_out, int n_in, int k, int* idx, float* dist,
                  float* next, void* stream);
 int pit_knn_last_form(void);
+
+/* ---- pit_knn_box on ragged batches (an addition to ABI 31; csrc/pit_knn.hip) --------------------------------------------------------
+ * pit_knn_box_ragged - pit_knn_box plus len_out / len_in: int32 DEVICE arrays of `batch` entries, clamped into [1, n_out] /
+ * [1, n_in] by the kernel, either NULL = the full width; no host synchronisation, capturable.  Sample s searches its first
+ * L = len_in[s] keys only: keys beyond are never read (they may hold NaN).  A real row i < len_out[s] emits k' = min(k, L) pairs -
+ * idx, dist and next equal pit_knn_box on the trimmed sample (n_out = len_out[s], n_in = L, k') bit for bit; its slots t >= k' hold
+ * key -1 and distance 0, and next is the distance of pair k or +inf when k >= L.  A row i >= len_out[s] holds -1 / 0 / +inf and reads
+ * nothing.  The form (pit_knn_last_form) is chosen from the padded n_in on the host; the refusals are pit_knn_box's, in its order,
+ * with the padded sizes.  A library built from this header defines PIT_HAS_KNN_RAGGED; PIT_ABI_VERSION is unchanged. */
+#define PIT_HAS_KNN_RAGGED 1
+int pit_knn_box_ragged(const float* mesh_out, const float* mesh_in, int batch, int n_out, int n_in, int space_dim, long out_stride,
+                       long in_stride, const float* periods, int k, const int* len_out, const int* len_in, int* idx, float* dist,
+                       float* next, void* stream);
 
 /* ---- The two slab forms of pit_block_fwd (additions to ABI 31; csrc/pit_block.hip) ------------------------------------------------
  * pit_block_fwd runs 16-row slabs, or - n_head = 2, n_pts = 256, the weights through LDS, and 8 * ceil(batch / 8) * n_pts / 8

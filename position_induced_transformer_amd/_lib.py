@@ -185,7 +185,9 @@ ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_
                "pit_fps",                                                          # PIT_HAS_FPS
                "pit_batch_feed_points",                                            # PIT_HAS_FEED_POINTS
                "pit_fps_large_workspace", "pit_fps_large",                         # PIT_HAS_FPS_LARGE
-               "pit_knn_box", "pit_knn_rows", "pit_knn_last_form"}                 # PIT_HAS_KNN
+               "pit_knn_box", "pit_knn_rows", "pit_knn_last_form",                 # PIT_HAS_KNN
+               "pit_distlist_select_ragged_fwd", "pit_distlist_ragged_fwd", "pit_distlist_ragged_bwd",      # PIT_HAS_DISTLIST_RAGGED
+               "pit_knn_box_ragged"}                                               # PIT_HAS_KNN_RAGGED
 ABI_VERSION = DEFINES["PIT_ABI_VERSION"]      # of the header this checkout carries; lib() holds the loaded library to it
 FPS_MAX_POINTS = DEFINES["PIT_FPS_MAX_POINTS"]
 FPS_MAX_POINTS_WIDE = DEFINES["PIT_FPS_MAX_POINTS_WIDE"]          # (space_dim 4..8)

@@ -20,6 +20,19 @@
 // Rows of values, d_out and out are read through sized buffer descriptors (one per sample, wave-uniform): an offset beyond the
 // tensor reads 0, which is also how the tail of a group of four slots is fed.  VEC: 16-byte pieces (lane holds 4 consecutive
 // columns), otherwise 4-byte pieces (lane holds columns lane, lane + 64, ...).
+//
+// RAGGED BATCHES (the *_ragged_* entries; RAG = true instances of the same kernels, the RAG = false instances are the code they
+// were): sample s has lo = len_out[s] rows and li = len_in[s] keys, read on the device and clamped into [1, width]; per-sample
+// lists only.  A slot is valid iff its key lies in [0, li); the rank (k_s, w_s) of the sample comes from li (sample_rank,
+// pit_layer.h) - the selection writes w_s, the forward reads it.  A row >= lo writes zero statistics, zero head columns, zero
+// rowstat and zero d_sqd and reads neither its list nor d_out; a key >= li gets a zero d_values row and its value row is never read.
+// d(values) runs over the SAME transposed index as ever, built from the keys alone against the padded n_in; the lengths filter
+// where the slots are read: an entry whose row is >= lo weighs 0 (its d_out row is not loaded).  Order of that sum: a key's
+// entries ascend in row * cap + slot, so the entries of rows >= lo stand BEHIND those of the real rows; the real entries
+// therefore fill the same places of the same 64-entry groups and PIT_DISTLIST_CHUNK-entry chunks as in a run of the trimmed cloud
+// alone, and the skipped ones add +0 after them: for a key whose range - padded rows' entries included - fits one chunk the sum
+// is the cloud-alone sum bit for bit.  A hub key's chunks are summed by separate waves and added in chunk order; chunks that
+// hold skipped entries only add zeros.  The tests hold a hub key to a tolerance only, not to bits.
 #include "pit_layer.h"
 
 namespace {
@@ -31,6 +44,7 @@ struct ListArgs : LayerIO {
     const int* idx; const float* sqd; long ld, bstride; int cap;     // bstride 0: one list set shared by the batch
     int batch, n_out, n_in;
     float rank_w;
+    const int* len_out; const int* len_in; const float* rank_w_s;    // ragged instances only: NULL length = full width; w per sample
     float* d_sqd;
     const int* rev_ptr; const int* rev_pos; const int* chunk_ptr; const int* chunk_key; float* dv_ws;
     int chunk_slots;
@@ -74,15 +88,27 @@ __device__ __forceinline__ void store_cols(float* row, int cg, int lane, int dim
 
 // ---- selection --------------------------------------------------------------------------------------------------------
 // Padding holds the pattern 0xFFFFFFFF, above every candidate of the search (valid values are finite and >= 0).
-template <int NPL>
+// RAG: k is formed here from the sample's key count and q = fl32(locality); w goes to rank_w[s]; a row >= len_out[s] gets 0, 0, 0
+template <int NPL, bool RAG>
 __global__ __launch_bounds__(256) void distlist_select_kernel(const int* __restrict__ idx, const float* __restrict__ sqd, long ld, long bstride,
                                                               int cap, int n_out, int n_in, int k, int need_kth, long rows,
-                                                              float* __restrict__ stats) {
+                                                              float* __restrict__ stats, const int* __restrict__ len_out,
+                                                              const int* __restrict__ len_in, float q, float* __restrict__ rank_w) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long row = (long)blockIdx.x * 4 + wave;
     if (row >= rows) return;                              // (wave-uniform; no barriers below)
     const int s = (int)(row / n_out), i = (int)(row - (long)s * n_out);
     const long base = (long)s * bstride + (long)i * ld;
+    if constexpr (RAG) {
+        n_in = clamp_len(len_in, s, n_in);                // the keys of THIS sample: the rest of the kernel is the dense one
+        float w;
+        k = min(sample_rank(q, n_in, w), cap - 1);
+        if (i == 0 && lane == 0) rank_w[s] = w;
+        if (i >= clamp_len(len_out, s, n_out)) {          // padded row: defined statistics, nothing is read
+            if (lane == 0) { stats[row] = 0.0f; stats[rows + row] = 0.0f; stats[2 * rows + row] = 0.0f; }
+            return;
+        }
+    }
     uint32_t key[NPL];
     uint32_t kmin = 0xFFFFFFFFu;
 #pragma unroll
@@ -128,12 +154,12 @@ __global__ __launch_bounds__(256) void distlist_select_kernel(const int* __restr
 
 // ---- the weights of 64 slots --------------------------------------------------------------------------------------------
 // lane = slot t0 + lane of the row at `base`: its key (0 for padding and beyond the list), its distance (0 there) and validity
-__device__ __forceinline__ bool load_slot(const ListArgs& a, long base, int t0, int lane, int& j, float& m) {
+__device__ __forceinline__ bool load_slot(const ListArgs& a, int n_in, long base, int t0, int lane, int& j, float& m) {
     const int t = t0 + lane;
     const bool in = t < a.cap;
     const long at = base + (in ? t : 0);
     const int jj = a.idx[at];
-    const bool valid = in && key_ok(jj, a.n_in);
+    const bool valid = in && key_ok(jj, n_in);
     const float mm = a.sqd[at];
     j = valid ? jj : 0;
     m = valid ? mm : 0.0f;
@@ -142,7 +168,7 @@ __device__ __forceinline__ bool load_slot(const ListArgs& a, long base, int t0, 
 
 // ---- forward --------------------------------------------------------------------------------------------------------------
 // grid (rows / 4, head groups of NH, colgroups)
-template <int NH, bool VEC>
+template <int NH, bool VEC, bool RAG>
 __global__ __launch_bounds__(256) void distlist_fwd_kernel(ListArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long rows_all = (long)a.batch * a.n_out;
@@ -162,13 +188,30 @@ __global__ __launch_bounds__(256) void distlist_fwd_kernel(ListArgs a) {
         load_cols<VEC>(rv, a.values_bytes, true, (unsigned)((long)n * a.ld_values * 4), cg, lane, a.dim, v);
         store_cols<VEC>(orow, cg, lane, a.dim, v);
     }
+    int li = a.n_in;
+    float rank_w = a.rank_w;
+    if constexpr (RAG) {
+        li = clamp_len(a.len_in, s, a.n_in);
+        rank_w = a.rank_w_s[mb];
+        if (n >= clamp_len(a.len_out, s, a.n_out)) {      // padded row (wave-uniform): zeros, its list is not read
+            const float z[LQ] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int q = 0; q < NH; ++q) {
+                if (h0 + q >= a.n_head) continue;
+                store_cols<VEC>(orow + a.out_col0 + (long)(h0 + q) * a.dim, cg, lane, a.dim, z);
+                if (cg == 0 && lane == 0)
+                    *reinterpret_cast<float4*>(a.rowstat + (((long)mb * a.n_head + h0 + q) * a.n_out + n) * 4) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            }
+            return;
+        }
+    }
     float c[NH], T[NH], smin[NH], rsum[NH], qsum[NH], acc[NH][LQ];
     bool hv[NH];
 #pragma unroll
     for (int q = 0; q < NH; ++q) {
         hv[q] = h0 + q < a.n_head;
         c[q] = head_c(a, hv[q] ? h0 + q : 0);
-        T[q] = a.masked ? quantile_lerp(__fmul_rn(c[q], a.stats[srow]), __fmul_rn(c[q], a.stats[rows_total + srow]), a.rank_w) : __builtin_inff();
+        T[q] = a.masked ? quantile_lerp(__fmul_rn(c[q], a.stats[srow]), __fmul_rn(c[q], a.stats[rows_total + srow]), rank_w) : __builtin_inff();
         smin[q] = __fmul_rn(c[q], a.stats[2 * rows_total + srow]);
         rsum[q] = 0.0f; qsum[q] = 0.0f;
 #pragma unroll
@@ -177,7 +220,7 @@ __global__ __launch_bounds__(256) void distlist_fwd_kernel(ListArgs a) {
     }
     for (int t0 = 0; t0 < a.cap; t0 += 64) {
         int j; float m;
-        const bool valid = load_slot(a, base, t0, lane, j, m);
+        const bool valid = load_slot(a, li, base, t0, lane, j, m);
         float p[NH];
         bool any = false;
 #pragma unroll
@@ -225,9 +268,10 @@ __global__ __launch_bounds__(256) void distlist_fwd_kernel(ListArgs a) {
 // ---- d(values) --------------------------------------------------------------------------------------------------------------
 // acc += sum over the entries e0 .. e1 - 1 of rev_pos (list set mb), ascending, and over the heads, of P g: 64 entries at a time
 // (lane = entry), per head the entries with a weight are broadcast in order, four at a time.
-template <bool VEC>
-__device__ __forceinline__ void dv_range(const ListArgs& a, int mb, __amdgpu_buffer_rsrc_t rg, const int* rev_pos, int e0, int e1, int cg, int lane,
-                                         float (&acc)[LQ]) {
+// RAG: `li` keys count and the entries of rows >= `lo` weigh 0 (the dense instances pass n_in and do not look at `lo`).
+template <bool VEC, bool RAG>
+__device__ __forceinline__ void dv_range(const ListArgs& a, int mb, int li, int lo, __amdgpu_buffer_rsrc_t rg, const int* rev_pos, int e0, int e1,
+                                         int cg, int lane, float (&acc)[LQ]) {
     const long slots = (long)a.n_out * a.cap;
     for (int eb = e0; eb < e1; eb += 64) {
         const int e = eb + lane;
@@ -236,7 +280,7 @@ __device__ __forceinline__ void dv_range(const ListArgs& a, int mb, __amdgpu_buf
         pos = pos < 0 ? 0 : (pos > slots - 1 ? slots - 1 : pos);
         const int row = (int)(pos / a.cap), slot = (int)(pos - (long)row * a.cap);
         const long at = (long)mb * a.bstride + (long)row * a.ld + slot;
-        const bool valid = ev && key_ok(a.idx[at], a.n_in);
+        const bool valid = ev && key_ok(a.idx[at], li) && (!RAG || row < lo);
         const float mm = a.sqd[at];
         const float m = valid ? mm : 0.0f;
         for (int h = 0; h < a.n_head; ++h) {
@@ -269,7 +313,7 @@ __device__ __forceinline__ void dv_range(const ListArgs& a, int mb, __amdgpu_buf
 //              chunk order; + the residual; writes d_values.  grid (keys / 4, batch, colgroups)
 // HUB = true:  one wave per (sample, chunk slot): the slot's CHUNK entries of its key into the workspace.
 //              grid (chunk slots / 4, batch, colgroups)
-template <bool HUB, bool VEC>
+template <bool HUB, bool VEC, bool RAG>
 __global__ __launch_bounds__(256) void distlist_dv_kernel(ListArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int item = blockIdx.x * 4 + wave, s = blockIdx.y, cg = blockIdx.z;
@@ -287,18 +331,27 @@ __global__ __launch_bounds__(256) void distlist_dv_kernel(ListArgs a) {
         key = a.chunk_key[(long)mb * a.chunk_slots + item];
         if (!key_ok(key, a.n_in)) return;                 // a free slot
     }
+    int li = a.n_in, lo = a.n_out;
+    if constexpr (RAG) {
+        li = clamp_len(a.len_in, s, a.n_in);
+        lo = clamp_len(a.len_out, s, a.n_out);
+        if (key >= li) {                                  // a padding key (wave-uniform): a zero row; its chunks are never read
+            if (!HUB) store_cols<VEC>(a.d_values + (long)s * a.dvalues_bstride + (long)key * a.ld_dvalues, cg, lane, a.dim, acc);
+            return;
+        }
+    }
     const int r0 = min(max(rev_ptr[key], 0), entries), r1 = min(max(rev_ptr[key + 1], r0), entries);
     if (HUB) {
         const int ch = item - chunk_ptr[key];
         const int e0 = (ch >= 0 && ch < (r1 - r0 + CHUNK - 1) / CHUNK) ? r0 + ch * CHUNK : r1;
-        dv_range<VEC>(a, mb, rg, rev_pos, e0, min(e0 + CHUNK, r1), cg, lane, acc);
+        dv_range<VEC, RAG>(a, mb, li, lo, rg, rev_pos, e0, min(e0 + CHUNK, r1), cg, lane, acc);
         float* w = a.dv_ws + ((long)s * a.chunk_slots + item) * wcols + (long)cg * 64 * LQ;
 #pragma unroll
         for (int u = 0; u < LQ; ++u) w[VEC ? lane * LQ + u : u * 64 + lane] = acc[u];
         return;
     }
     if (r1 - r0 <= CHUNK) {
-        dv_range<VEC>(a, mb, rg, rev_pos, r0, r1, cg, lane, acc);
+        dv_range<VEC, RAG>(a, mb, li, lo, rg, rev_pos, r0, r1, cg, lane, acc);
     } else {
         const int c0 = min(max(chunk_ptr[key], 0), a.chunk_slots), c1 = min(max(chunk_ptr[key + 1], c0), a.chunk_slots);
         for (int ch = c0; ch < c1; ++ch) {
@@ -307,7 +360,7 @@ __global__ __launch_bounds__(256) void distlist_dv_kernel(ListArgs a) {
             for (int u = 0; u < LQ; ++u) acc[u] += w[VEC ? lane * LQ + u : u * 64 + lane];
         }
     }
-    if (a.add_residual) {                                 // self attention: n_out == n_in
+    if (a.add_residual && (!RAG || key < lo)) {           // self attention: n_out == n_in (ragged: the d_out of a padded row is never read)
         float r[LQ];
         load_cols<VEC>(rg, a.dout_bytes, true, (unsigned)((long)key * a.ld_dout * 4), cg, lane, a.dim, r);
 #pragma unroll
@@ -319,7 +372,7 @@ __global__ __launch_bounds__(256) void distlist_dv_kernel(ListArgs a) {
 // ---- d(scale) and d(sqd) ------------------------------------------------------------------------------------------------------
 // One wave per row of a list set; 64 slots at a time (lane = slot), inside them the samples that use the list set, ascending, then the
 // heads in groups of NH.  The value row of a kept slot is gathered once per head group.  grid (list rows / 4)
-template <int NH, bool VEC>
+template <int NH, bool VEC, bool RAG>
 __global__ __launch_bounds__(256) void distlist_rows_bwd_kernel(ListArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long rows_total = (long)(a.bstride ? a.batch : 1) * a.n_out;
@@ -329,9 +382,18 @@ __global__ __launch_bounds__(256) void distlist_rows_bwd_kernel(ListArgs a) {
     const int s_beg = a.bstride ? mb : 0, s_end = a.bstride ? mb + 1 : a.batch;
     const long base = (long)mb * a.bstride + (long)n * a.ld;
     const bool need_a = a.d_sqd != nullptr;
+    int li = a.n_in;
+    if constexpr (RAG) {                                  // (per-sample lists: mb is the sample)
+        li = clamp_len(a.len_in, s_beg, a.n_in);
+        if (n >= clamp_len(a.len_out, s_beg, a.n_out)) {  // padded row (wave-uniform): no d(scale), a zero d_sqd row
+            if (a.d_sqd)
+                for (int t = lane; t < a.cap; t += 64) a.d_sqd[srow * a.cap + t] = 0.0f;
+            return;
+        }
+    }
     for (int t0 = 0; t0 < a.cap; t0 += 64) {
         int j; float m;
-        const bool valid = load_slot(a, base, t0, lane, j, m);
+        const bool valid = load_slot(a, li, base, t0, lane, j, m);
         float dsq = 0.0f;
         for (int s = s_beg; s < s_end; ++s) {
             const __amdgpu_buffer_rsrc_t rv = make_rsrc(a.values + (long)s * a.values_bstride, a.values_bytes);
@@ -439,18 +501,25 @@ int list_check(ListArgs& a, int need_dout) {
     return need_dout ? layer_check_dout(a, std::max(a.n_out, a.add_residual ? a.n_in : 0)) : 0;
 }
 
+// what the ragged entries add to the dense ones' operands (rag = false: the dense entry, the rest is unused)
+struct RagLens { bool rag; const int* len_out; const int* len_in; };
+
 template <int NPL>
 void launch_select(const int* idx, const float* sqd, long ld, long bstride, int cap, int n_out, int n_in, int k, int need_kth, long rows,
-                   float* stats, hipStream_t st) {
-    hipLaunchKernelGGL(distlist_select_kernel<NPL>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, idx, sqd, ld, bstride, cap, n_out, n_in,
-                       k, need_kth, rows, stats);
+                   float* stats, const RagLens& r, float q, float* rank_w, hipStream_t st) {
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (r.rag)
+        hipLaunchKernelGGL((distlist_select_kernel<NPL, true>), grid, dim3(256), 0, st, idx, sqd, ld, bstride, cap, n_out, n_in, k, need_kth, rows,
+                           stats, r.len_out, r.len_in, q, rank_w);
+    else
+        hipLaunchKernelGGL((distlist_select_kernel<NPL, false>), grid, dim3(256), 0, st, idx, sqd, ld, bstride, cap, n_out, n_in, k, need_kth, rows,
+                           stats, nullptr, nullptr, 0.0f, nullptr);
 }
 
-}  // namespace
-
-extern "C" int pit_distlist_select_fwd(const int* idx, const float* sqd, long ld, long bstride, int cap, int mesh_batch, int n_out, int n_in,
-                                       int rank_k, int need_kth, float* stats, void* stream) {
-    if (!idx || !sqd || !stats) return PIT_ERR_NULL;
+// rag: rank_k is the rank of the padded width (the largest a sample can have) - what the width of the lists is checked against
+int list_select(const int* idx, const float* sqd, long ld, long bstride, int cap, int mesh_batch, int n_out, int n_in, int rank_k, int need_kth,
+                float* stats, const RagLens& r, float q, float* rank_w, void* stream) {
+    if (!idx || !sqd || !stats || (r.rag && !rank_w)) return PIT_ERR_NULL;
     if (mesh_batch <= 0 || n_out <= 0 || n_in <= 0 || cap <= 0 || ld < cap || bstride < 0) return PIT_ERR_SIZE;
     if (mesh_batch > 1 && bstride < (long)(n_out - 1) * ld + cap) return PIT_ERR_SIZE;
     if (need_kth && (rank_k < 0 || rank_k > cap - 1)) return PIT_ERR_SIZE;
@@ -460,27 +529,32 @@ extern "C" int pit_distlist_select_fwd(const int* idx, const float* sqd, long ld
     const long bs = mesh_batch > 1 ? bstride : 0L;
     hipStream_t st = (hipStream_t)stream;
     const int npl = (cap + 63) / 64;
-    if (npl <= 1) launch_select<1>(idx, sqd, ld, bs, cap, n_out, n_in, rank_k, need_kth, rows, stats, st);
-    else if (npl <= 2) launch_select<2>(idx, sqd, ld, bs, cap, n_out, n_in, rank_k, need_kth, rows, stats, st);
-    else if (npl <= 4) launch_select<4>(idx, sqd, ld, bs, cap, n_out, n_in, rank_k, need_kth, rows, stats, st);
-    else if (npl <= 8) launch_select<8>(idx, sqd, ld, bs, cap, n_out, n_in, rank_k, need_kth, rows, stats, st);
-    else if (npl <= 16) launch_select<16>(idx, sqd, ld, bs, cap, n_out, n_in, rank_k, need_kth, rows, stats, st);
-    else launch_select<32>(idx, sqd, ld, bs, cap, n_out, n_in, rank_k, need_kth, rows, stats, st);
+    if (npl <= 1) launch_select<1>(idx, sqd, ld, bs, cap, n_out, n_in, rank_k, need_kth, rows, stats, r, q, rank_w, st);
+    else if (npl <= 2) launch_select<2>(idx, sqd, ld, bs, cap, n_out, n_in, rank_k, need_kth, rows, stats, r, q, rank_w, st);
+    else if (npl <= 4) launch_select<4>(idx, sqd, ld, bs, cap, n_out, n_in, rank_k, need_kth, rows, stats, r, q, rank_w, st);
+    else if (npl <= 8) launch_select<8>(idx, sqd, ld, bs, cap, n_out, n_in, rank_k, need_kth, rows, stats, r, q, rank_w, st);
+    else if (npl <= 16) launch_select<16>(idx, sqd, ld, bs, cap, n_out, n_in, rank_k, need_kth, rows, stats, r, q, rank_w, st);
+    else launch_select<32>(idx, sqd, ld, bs, cap, n_out, n_in, rank_k, need_kth, rows, stats, r, q, rank_w, st);
     PIT_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int pit_distlist_fwd(const int* idx, const float* sqd, long ld, long bstride, int cap, int n_out, int n_in,
-                                const float* values, int batch, int dim, long ld_values, long values_bstride,
-                                const float* head, int n_head, int head_is_scale,
-                                const float* stats, float rank_w, int masked,
-                                float* out, long ld_out, long out_bstride, int out_col0, int copy_inputs,
-                                float* rowstat, float* scale_out, int math_mode, void* stream) {
-    if (!idx || !sqd || !values || !head || !stats || !out || !rowstat) return PIT_ERR_NULL;
+// ragged batches run on per-sample lists only (a batch of one has one list set whatever its stride says)
+bool rag_lists_ok(long bstride, int batch) { return bstride != 0 || batch == 1; }
+
+int list_fwd(const int* idx, const float* sqd, long ld, long bstride, int cap, int n_out, int n_in,
+             const float* values, int batch, int dim, long ld_values, long values_bstride,
+             const float* head, int n_head, int head_is_scale,
+             const float* stats, float rank_w, const float* rank_w_s, const RagLens& r, int masked,
+             float* out, long ld_out, long out_bstride, int out_col0, int copy_inputs,
+             float* rowstat, float* scale_out, int math_mode, void* stream) {
+    if (!idx || !sqd || !values || !head || !stats || !out || !rowstat || (r.rag && !rank_w_s)) return PIT_ERR_NULL;
     if (math_mode != PIT_MATH_FP32) return PIT_ERR_UNSUPPORTED;
+    if (r.rag && !rag_lists_ok(bstride, batch)) return PIT_ERR_SIZE;
     ListArgs a = ListArgs();
     a.idx = idx; a.sqd = sqd; a.ld = ld; a.bstride = bstride; a.cap = cap; a.batch = batch; a.n_out = n_out; a.n_in = n_in;
     a.rank_w = rank_w;
+    a.len_out = r.len_out; a.len_in = r.len_in; a.rank_w_s = rank_w_s;
     layer_set_fwd(a, values, dim, ld_values, values_bstride, head, n_head, head_is_scale, stats, masked, out, ld_out, out_bstride, out_col0,
                   copy_inputs, rowstat, scale_out);
     if (int rc = list_check(a, 0)) return rc;
@@ -491,12 +565,55 @@ extern "C" int pit_distlist_fwd(const int* idx, const float* sqd, long ld, long 
     const int nh = n_head == 1 ? 1 : n_head == 2 ? 2 : 4;
     const dim3 grid((unsigned)(((long)batch * n_out + 3) / 4), (unsigned)((n_head + nh - 1) / nh), (unsigned)a.colgroups);
     hipStream_t st = (hipStream_t)stream;
-#define PIT_LIST_FWD(NH_) do { if (vec) hipLaunchKernelGGL((distlist_fwd_kernel<NH_, true>), grid, dim3(256), 0, st, a); \
-                               else hipLaunchKernelGGL((distlist_fwd_kernel<NH_, false>), grid, dim3(256), 0, st, a); } while (0)
+#define PIT_LIST_FWD2(NH_, RAG_) do { if (vec) hipLaunchKernelGGL((distlist_fwd_kernel<NH_, true, RAG_>), grid, dim3(256), 0, st, a); \
+                                      else hipLaunchKernelGGL((distlist_fwd_kernel<NH_, false, RAG_>), grid, dim3(256), 0, st, a); } while (0)
+#define PIT_LIST_FWD(NH_) do { if (r.rag) PIT_LIST_FWD2(NH_, true); else PIT_LIST_FWD2(NH_, false); } while (0)
     if (nh == 1) PIT_LIST_FWD(1); else if (nh == 2) PIT_LIST_FWD(2); else PIT_LIST_FWD(4);
 #undef PIT_LIST_FWD
+#undef PIT_LIST_FWD2
     PIT_CHECK_LAUNCH();
     return 0;
+}
+
+}  // namespace
+
+extern "C" int pit_distlist_select_fwd(const int* idx, const float* sqd, long ld, long bstride, int cap, int mesh_batch, int n_out, int n_in,
+                                       int rank_k, int need_kth, float* stats, void* stream) {
+    return list_select(idx, sqd, ld, bstride, cap, mesh_batch, n_out, n_in, rank_k, need_kth, stats, RagLens{false, nullptr, nullptr}, 0.0f,
+                       nullptr, stream);
+}
+
+extern "C" int pit_distlist_select_ragged_fwd(const int* idx, const float* sqd, long ld, long bstride, int cap, int mesh_batch, int n_out,
+                                              int n_in, float locality, int need_kth, const int* len_out, const int* len_in, float* stats,
+                                              float* rank_w, void* stream) {
+    if (!(locality >= 0.0f && locality <= 1.0f)) return PIT_ERR_SIZE;
+    // the rank of the padded width bounds every sample's (ops.quantile_rank's arithmetic, here on the host)
+    const int k_max = n_in > 0 ? (int)floorf(locality * (float)(n_in - 1)) : 0;
+    return list_select(idx, sqd, ld, bstride, cap, mesh_batch, n_out, n_in, k_max, need_kth, stats, RagLens{true, len_out, len_in}, locality,
+                       rank_w, stream);
+}
+
+extern "C" int pit_distlist_fwd(const int* idx, const float* sqd, long ld, long bstride, int cap, int n_out, int n_in,
+                                const float* values, int batch, int dim, long ld_values, long values_bstride,
+                                const float* head, int n_head, int head_is_scale,
+                                const float* stats, float rank_w, int masked,
+                                float* out, long ld_out, long out_bstride, int out_col0, int copy_inputs,
+                                float* rowstat, float* scale_out, int math_mode, void* stream) {
+    return list_fwd(idx, sqd, ld, bstride, cap, n_out, n_in, values, batch, dim, ld_values, values_bstride, head, n_head, head_is_scale, stats,
+                    rank_w, nullptr, RagLens{false, nullptr, nullptr}, masked, out, ld_out, out_bstride, out_col0, copy_inputs, rowstat,
+                    scale_out, math_mode, stream);
+}
+
+extern "C" int pit_distlist_ragged_fwd(const int* idx, const float* sqd, long ld, long bstride, int cap, int n_out, int n_in,
+                                       const float* values, int batch, int dim, long ld_values, long values_bstride,
+                                       const float* head, int n_head, int head_is_scale,
+                                       const float* stats, const float* rank_w, int masked,
+                                       const int* len_out, const int* len_in,
+                                       float* out, long ld_out, long out_bstride, int out_col0, int copy_inputs,
+                                       float* rowstat, float* scale_out, int math_mode, void* stream) {
+    return list_fwd(idx, sqd, ld, bstride, cap, n_out, n_in, values, batch, dim, ld_values, values_bstride, head, n_head, head_is_scale, stats,
+                    0.0f, rank_w, RagLens{true, len_out, len_in}, masked, out, ld_out, out_bstride, out_col0, copy_inputs, rowstat, scale_out,
+                    math_mode, stream);
 }
 
 extern "C" long pit_distlist_bwd_workspace(int batch, int n_out, int cap, int dim) {
@@ -505,22 +622,26 @@ extern "C" long pit_distlist_bwd_workspace(int batch, int n_out, int cap, int di
     return (long)batch * PIT_DISTLIST_CHUNK_SLOTS(n_out, cap) * colgroups * 64 * LQ * (long)sizeof(float);
 }
 
-extern "C" int pit_distlist_bwd(const int* idx, const float* sqd, long ld, long bstride, int cap, int n_out, int n_in,
-                                const float* values, int batch, int dim, long ld_values, long values_bstride,
-                                const float* head, int n_head, int head_is_scale, const float* scale,
-                                const float* rowstat, int masked,
-                                const float* d_out, long ld_dout, long dout_bstride, int out_col0,
-                                float* d_values, long ld_dvalues, long dvalues_bstride, int add_residual,
-                                float* d_head, int accumulate_head, double* workspace,
-                                float* d_sqd, const float* out, long ld_out, long out_bstride,
-                                const int* rev_ptr, const int* rev_pos, const int* chunk_ptr, const int* chunk_key, float* dv_workspace,
-                                int math_mode, void* stream) {
+namespace {
+
+int list_bwd(const int* idx, const float* sqd, long ld, long bstride, int cap, int n_out, int n_in,
+             const float* values, int batch, int dim, long ld_values, long values_bstride,
+             const float* head, int n_head, int head_is_scale, const float* scale,
+             const float* rowstat, int masked, const RagLens& r,
+             const float* d_out, long ld_dout, long dout_bstride, int out_col0,
+             float* d_values, long ld_dvalues, long dvalues_bstride, int add_residual,
+             float* d_head, int accumulate_head, double* workspace,
+             float* d_sqd, const float* out, long ld_out, long out_bstride,
+             const int* rev_ptr, const int* rev_pos, const int* chunk_ptr, const int* chunk_key, float* dv_workspace,
+             int math_mode, void* stream) {
     if (!idx || !sqd || !values || !head || !rowstat || !d_out) return PIT_ERR_NULL;
     if ((d_head && !workspace) || (d_sqd && !out)) return PIT_ERR_NULL;
     if (d_values && (!rev_ptr || !rev_pos || !chunk_ptr || !chunk_key || !dv_workspace)) return PIT_ERR_NULL;
     if (math_mode != PIT_MATH_FP32) return PIT_ERR_UNSUPPORTED;
+    if (r.rag && !rag_lists_ok(bstride, batch)) return PIT_ERR_SIZE;
     ListArgs a = ListArgs();
     a.idx = idx; a.sqd = sqd; a.ld = ld; a.bstride = bstride; a.cap = cap; a.batch = batch; a.n_out = n_out; a.n_in = n_in;
+    a.len_out = r.len_out; a.len_in = r.len_in;
     layer_set_bwd(a, values, dim, ld_values, values_bstride, head, n_head, head_is_scale, scale, rowstat, masked, d_out, ld_dout, dout_bstride,
                   out_col0, d_values, ld_dvalues, dvalues_bstride, add_residual, d_head, workspace);
     if (add_residual && (n_out != n_in || out_col0 < dim)) return PIT_ERR_SIZE;
@@ -543,24 +664,59 @@ extern "C" int pit_distlist_bwd(const int* idx, const float* sqd, long ld, long 
     if (d_values) {
         const dim3 hub((unsigned)((slots + 3) / 4), (unsigned)batch, (unsigned)a.colgroups);
         const dim3 grid((unsigned)((n_in + 3) / 4), (unsigned)batch, (unsigned)a.colgroups);
-        if (vec) {
-            hipLaunchKernelGGL((distlist_dv_kernel<true, true>), hub, dim3(256), 0, st, a);
-            hipLaunchKernelGGL((distlist_dv_kernel<false, true>), grid, dim3(256), 0, st, a);
-        } else {
-            hipLaunchKernelGGL((distlist_dv_kernel<true, false>), hub, dim3(256), 0, st, a);
-            hipLaunchKernelGGL((distlist_dv_kernel<false, false>), grid, dim3(256), 0, st, a);
-        }
+#define PIT_LIST_DV(VEC_, RAG_) do { hipLaunchKernelGGL((distlist_dv_kernel<true, VEC_, RAG_>), hub, dim3(256), 0, st, a); \
+                                     hipLaunchKernelGGL((distlist_dv_kernel<false, VEC_, RAG_>), grid, dim3(256), 0, st, a); } while (0)
+        if (r.rag) { if (vec) PIT_LIST_DV(true, true); else PIT_LIST_DV(false, true); }
+        else       { if (vec) PIT_LIST_DV(true, false); else PIT_LIST_DV(false, false); }
+#undef PIT_LIST_DV
         PIT_CHECK_LAUNCH();
     }
     if (d_head || d_sqd) {
         const long rows = (long)(bstride ? batch : 1) * n_out;
         const dim3 grid((unsigned)((rows + 3) / 4));
         const int nh = n_head == 1 ? 1 : n_head == 2 ? 2 : 4;
-#define PIT_LIST_ROWS(NH_) do { if (vec) hipLaunchKernelGGL((distlist_rows_bwd_kernel<NH_, true>), grid, dim3(256), 0, st, a); \
-                                else hipLaunchKernelGGL((distlist_rows_bwd_kernel<NH_, false>), grid, dim3(256), 0, st, a); } while (0)
+#define PIT_LIST_ROWS2(NH_, RAG_) do { if (vec) hipLaunchKernelGGL((distlist_rows_bwd_kernel<NH_, true, RAG_>), grid, dim3(256), 0, st, a); \
+                                       else hipLaunchKernelGGL((distlist_rows_bwd_kernel<NH_, false, RAG_>), grid, dim3(256), 0, st, a); } while (0)
+#define PIT_LIST_ROWS(NH_) do { if (r.rag) PIT_LIST_ROWS2(NH_, true); else PIT_LIST_ROWS2(NH_, false); } while (0)
         if (nh == 1) PIT_LIST_ROWS(1); else if (nh == 2) PIT_LIST_ROWS(2); else PIT_LIST_ROWS(4);
 #undef PIT_LIST_ROWS
+#undef PIT_LIST_ROWS2
         PIT_CHECK_LAUNCH();
     }
     return layer_finish_head(head, scale, d_head, workspace, n_head, accumulate_head, head_is_scale, stream);
+}
+
+}  // namespace
+
+extern "C" int pit_distlist_bwd(const int* idx, const float* sqd, long ld, long bstride, int cap, int n_out, int n_in,
+                                const float* values, int batch, int dim, long ld_values, long values_bstride,
+                                const float* head, int n_head, int head_is_scale, const float* scale,
+                                const float* rowstat, int masked,
+                                const float* d_out, long ld_dout, long dout_bstride, int out_col0,
+                                float* d_values, long ld_dvalues, long dvalues_bstride, int add_residual,
+                                float* d_head, int accumulate_head, double* workspace,
+                                float* d_sqd, const float* out, long ld_out, long out_bstride,
+                                const int* rev_ptr, const int* rev_pos, const int* chunk_ptr, const int* chunk_key, float* dv_workspace,
+                                int math_mode, void* stream) {
+    return list_bwd(idx, sqd, ld, bstride, cap, n_out, n_in, values, batch, dim, ld_values, values_bstride, head, n_head, head_is_scale, scale,
+                    rowstat, masked, RagLens{false, nullptr, nullptr}, d_out, ld_dout, dout_bstride, out_col0, d_values, ld_dvalues,
+                    dvalues_bstride, add_residual, d_head, accumulate_head, workspace, d_sqd, out, ld_out, out_bstride, rev_ptr, rev_pos,
+                    chunk_ptr, chunk_key, dv_workspace, math_mode, stream);
+}
+
+extern "C" int pit_distlist_ragged_bwd(const int* idx, const float* sqd, long ld, long bstride, int cap, int n_out, int n_in,
+                                       const float* values, int batch, int dim, long ld_values, long values_bstride,
+                                       const float* head, int n_head, int head_is_scale, const float* scale,
+                                       const float* rowstat, int masked,
+                                       const int* len_out, const int* len_in,
+                                       const float* d_out, long ld_dout, long dout_bstride, int out_col0,
+                                       float* d_values, long ld_dvalues, long dvalues_bstride, int add_residual,
+                                       float* d_head, int accumulate_head, double* workspace,
+                                       float* d_sqd, const float* out, long ld_out, long out_bstride,
+                                       const int* rev_ptr, const int* rev_pos, const int* chunk_ptr, const int* chunk_key,
+                                       float* dv_workspace, int math_mode, void* stream) {
+    return list_bwd(idx, sqd, ld, bstride, cap, n_out, n_in, values, batch, dim, ld_values, values_bstride, head, n_head, head_is_scale, scale,
+                    rowstat, masked, RagLens{true, len_out, len_in}, d_out, ld_dout, dout_bstride, out_col0, d_values, ld_dvalues,
+                    dvalues_bstride, add_residual, d_head, accumulate_head, workspace, d_sqd, out, ld_out, out_bstride, rev_ptr, rev_pos,
+                    chunk_ptr, chunk_key, dv_workspace, math_mode, stream);
 }

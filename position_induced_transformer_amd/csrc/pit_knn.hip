@@ -16,6 +16,10 @@
 // into 4 registers per thread (form 1); a longer row recomputes them in every pass, four independent keys per thread in flight
 // (form 2), because no memory holds a row (the matrix never exists).  Counters of one wave that hit the same bin - the first pass
 // sees the exponent bits, which are nearly equal for a whole row - are added once per wave for the two most frequent leaders.
+//
+// pit_knn_box_ragged (RAG = true instances of the box kernel): sample s searches its first L = len_in[s] keys - the selection core
+// takes the key count and k at run time, so the row runs it with (L, min(k, L)) and then fills the slots it did not reach with
+// key -1 / distance 0; a row >= len_out[s] is filled whole and reads nothing.  The form is the host's choice from the padded n_in.
 #include "pit_common.h"
 
 namespace {
@@ -196,20 +200,38 @@ __device__ __forceinline__ void knn_row(const Loader& ld, unsigned J, int k, int
     }
 }
 
-template <int SDIM, bool WRAP, bool CACHED>
+template <int SDIM, bool WRAP, bool CACHED, bool RAG>
 __global__ __launch_bounds__(KNN_THREADS) void knn_box_kernel(const float* __restrict__ mesh_out, const float* __restrict__ mesh_in,
                                                               int n_out, int n_in, long out_stride, long in_stride,
                                                               knn_periods per, int k, int* __restrict__ idx,
-                                                              float* __restrict__ dist, float* __restrict__ next) {
+                                                              float* __restrict__ dist, float* __restrict__ next,
+                                                              const int* __restrict__ len_out, const int* __restrict__ len_in) {
     const long row = blockIdx.x;                         // sample * n_out + i
     const long sample = row / n_out, i = row - sample * n_out;
+    int k_row = k;                                       // the pairs this row emits (ragged: min(k, the sample's keys))
+    if constexpr (RAG) {                                 // lengths clamped into [1, width]; NULL: the full width
+        const int lo = len_out ? max(1, min(len_out[sample], n_out)) : n_out;
+        const int li = len_in ? max(1, min(len_in[sample], n_in)) : n_in;
+        const int kk = min(k, li);
+        // the slots the search does not reach: all of a padded row's, those beyond the sample's keys otherwise (block-uniform)
+        for (int t = (i >= lo ? 0 : kk) + (int)threadIdx.x; t < k; t += KNN_THREADS) {
+            idx[row * k + t] = -1;
+            dist[row * k + t] = 0.0f;
+        }
+        if (i >= lo) {
+            if (threadIdx.x == 0) next[row] = __builtin_inff();
+            return;
+        }
+        n_in = li;                                       // (the selection writes +inf to `next` when it took every key)
+        k_row = kk;
+    }
     box_loader<SDIM, WRAP> ld;
     ld.keys = mesh_in + sample * in_stride * SDIM;
     const float* x = mesh_out + (sample * out_stride + i) * SDIM;
 #pragma unroll
     for (int a = 0; a < SDIM; ++a) ld.x[a] = x[a];
     ld.per = per;
-    knn_row<box_loader<SDIM, WRAP>, CACHED>(ld, (unsigned)n_in, k, idx + row * k, dist + row * k, next + row);
+    knn_row<box_loader<SDIM, WRAP>, CACHED>(ld, (unsigned)n_in, k_row, idx + row * k, dist + row * k, next + row);
 }
 
 template <bool CACHED>
@@ -223,11 +245,12 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_rows_kernel(const float* __re
     knn_row<rows_loader, CACHED>(ld, (unsigned)n_in, k, idx + row * k, dist + row * k, next + row);
 }
 
-template <int SDIM>
+template <int SDIM, bool RAG>
 void knn_box_launch(bool wrap, bool cached, unsigned rows, hipStream_t st, const float* mesh_out, const float* mesh_in, int n_out,
-                    int n_in, long out_stride, long in_stride, const knn_periods& per, int k, int* idx, float* dist, float* next) {
-#define PIT_KNN_BOX(W_, C_) hipLaunchKernelGGL((knn_box_kernel<SDIM, W_, C_>), dim3(rows), dim3(KNN_THREADS), 0, st, mesh_out, \
-                                               mesh_in, n_out, n_in, out_stride, in_stride, per, k, idx, dist, next)
+                    int n_in, long out_stride, long in_stride, const knn_periods& per, int k, int* idx, float* dist, float* next,
+                    const int* len_out, const int* len_in) {
+#define PIT_KNN_BOX(W_, C_) hipLaunchKernelGGL((knn_box_kernel<SDIM, W_, C_, RAG>), dim3(rows), dim3(KNN_THREADS), 0, st, mesh_out, \
+                                               mesh_in, n_out, n_in, out_stride, in_stride, per, k, idx, dist, next, len_out, len_in)
     if (wrap) { if (cached) PIT_KNN_BOX(true, true); else PIT_KNN_BOX(true, false); }
     else      { if (cached) PIT_KNN_BOX(false, true); else PIT_KNN_BOX(false, false); }
 #undef PIT_KNN_BOX
@@ -244,11 +267,10 @@ int knn_refuse(bool pointers_ok, bool sizes_ok, int batch, int n_out, int n_in, 
     return 0;
 }
 
-}  // namespace
-
-extern "C" int pit_knn_box(const float* mesh_out, const float* mesh_in, int batch, int n_out, int n_in, int space_dim,
-                           long out_stride, long in_stride, const float* periods, int k, int* idx, float* dist, float* next,
-                           void* stream) {
+template <bool RAG>
+int knn_box_entry(const float* mesh_out, const float* mesh_in, int batch, int n_out, int n_in, int space_dim, long out_stride,
+                  long in_stride, const float* periods, int k, const int* len_out, const int* len_in, int* idx, float* dist,
+                  float* next, void* stream) {
     const bool sizes_ok = space_dim >= 1 && space_dim <= PIT_MAX_SPACE_DIM && (out_stride == 0 || out_stride >= n_out) &&
                           (in_stride == 0 || in_stride >= n_in);
     const int rc = knn_refuse(mesh_out && mesh_in && idx && dist && next, sizes_ok, batch, n_out, n_in, k);
@@ -262,8 +284,8 @@ extern "C" int pit_knn_box(const float* mesh_out, const float* mesh_in, int batc
     const bool cached = n_in <= PIT_KNN_REG_MAX_KEYS;
     const unsigned rows = (unsigned)((long)batch * n_out);
     hipStream_t st = (hipStream_t)stream;
-#define PIT_KNN_SDIM(S_) case S_: knn_box_launch<S_>(wrap, cached, rows, st, mesh_out, mesh_in, n_out, n_in, out_stride, in_stride, \
-                                                     per, k, idx, dist, next); break
+#define PIT_KNN_SDIM(S_) case S_: knn_box_launch<S_, RAG>(wrap, cached, rows, st, mesh_out, mesh_in, n_out, n_in, out_stride, in_stride, \
+                                                          per, k, idx, dist, next, len_out, len_in); break
     switch (space_dim) {
         PIT_KNN_SDIM(1); PIT_KNN_SDIM(2); PIT_KNN_SDIM(3); PIT_KNN_SDIM(4);
         PIT_KNN_SDIM(5); PIT_KNN_SDIM(6); PIT_KNN_SDIM(7); PIT_KNN_SDIM(8);
@@ -272,6 +294,22 @@ extern "C" int pit_knn_box(const float* mesh_out, const float* mesh_in, int batc
     PIT_CHECK_LAUNCH();
     g_last_form = cached ? 1 : 2;
     return 0;
+}
+
+}  // namespace
+
+extern "C" int pit_knn_box(const float* mesh_out, const float* mesh_in, int batch, int n_out, int n_in, int space_dim,
+                           long out_stride, long in_stride, const float* periods, int k, int* idx, float* dist, float* next,
+                           void* stream) {
+    return knn_box_entry<false>(mesh_out, mesh_in, batch, n_out, n_in, space_dim, out_stride, in_stride, periods, k, nullptr, nullptr,
+                                idx, dist, next, stream);
+}
+
+extern "C" int pit_knn_box_ragged(const float* mesh_out, const float* mesh_in, int batch, int n_out, int n_in, int space_dim,
+                                  long out_stride, long in_stride, const float* periods, int k, const int* len_out,
+                                  const int* len_in, int* idx, float* dist, float* next, void* stream) {
+    return knn_box_entry<true>(mesh_out, mesh_in, batch, n_out, n_in, space_dim, out_stride, in_stride, periods, k, len_out, len_in,
+                               idx, dist, next, stream);
 }
 
 extern "C" int pit_knn_rows(const float* m, long ld_m, long m_bstride, int batch, int n_out, int n_in, int k, int* idx,

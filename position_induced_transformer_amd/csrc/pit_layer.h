@@ -42,6 +42,20 @@ __device__ __forceinline__ float weight_raw(float m, float c, float T, float smi
     return keep ? __expf(smin - sv) : 0.0f;
 }
 
+// A sample's point count on one side of a ragged batch, clamped into [1, n].  len == NULL: a side without lengths - every sample
+// has the full width (the shared mesh of a mixed pair, or a cloud side given without lengths); a wave-uniform branch on a
+// kernel argument
+__device__ __forceinline__ int clamp_len(const int* len, int s, int n) { return len ? max(1, min(len[s], n)) : n; }
+
+// torch.quantile's rank in ATen's fp32 arithmetic for a sample of `li` keys (ops.quantile_rank: fp32 product, floor, fp32
+// difference); q = fl32(locality).  Returns k, w in `w`.
+__device__ __forceinline__ int sample_rank(float q, int li, float& w) {
+    const float rank = __fmul_rn(q, (float)(li - 1));
+    const int k = (int)floorf(rank);
+    w = __fsub_rn(rank, (float)k);
+    return k;
+}
+
 // lane src's v, in every lane (src wave-uniform)
 __device__ __forceinline__ float lane_f(float v, int src) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src)); }
 

@@ -28,10 +28,6 @@ namespace {
 constexpr int RT = 16;     // owner items per workgroup
 constexpr int KT = 64;     // contracted items per tile
 
-// len == NULL: a side without lengths - every sample has the full width (the shared mesh of a mixed pair, or a cloud side given
-// without lengths); a wave-uniform branch on a kernel argument
-__device__ __forceinline__ int clamp_len(const int* len, int s, int n) { return len ? max(1, min(len[s], n)) : n; }
-
 __device__ __forceinline__ float4 load_pt3(const float* p, int sdim) {
     float4 v;
     v.x = p[0];
@@ -65,9 +61,9 @@ __global__ __launch_bounds__(256) void ragged_select_kernel(RagSelectArgs a) {
     const int s = (int)(row / a.n_out), i = (int)(row - (long)s * a.n_out);
     const int lo = clamp_len(a.len_out, s, a.n_out), li = clamp_len(a.len_in, s, a.n_in);
     // torch.quantile's rank in ATen's fp32 arithmetic, for THIS sample's key count (ops.quantile_rank)
-    const float rank = __fmul_rn(a.q, (float)(li - 1));
-    const int k = (int)floorf(rank);
-    if (i == 0 && threadIdx.x == 0) a.rank_w[s] = __fsub_rn(rank, (float)k);
+    float w;
+    const int k = sample_rank(a.q, li, w);               // (pit_layer.h)
+    if (i == 0 && threadIdx.x == 0) a.rank_w[s] = w;
     if (i >= lo) {                                        // padded row: defined statistics, nothing is read
         if (threadIdx.x == 0) { a.stats[row] = 0.0f; a.stats[rows + row] = 0.0f; a.stats[2 * rows + row] = 0.0f; }
         return;

@@ -14,7 +14,8 @@ d loss / d m, so autograd differentiates through the metric, tie rules included:
     out.square().sum().backward()                      # model.mesh_ltt.grad: through min(|dx|, l - |dx|) by autograd
 
 Precomputed matrices (geodesic distances on a surface or a graph) go to ``forward_dist(m_dist, inputs)``.  The entries of a
-matrix must be finite and >= 0; that is not checked (a check would synchronise).  fp32 math mode only; no ragged batches.
+matrix must be finite and >= 0; that is not checked (a check would synchronise).  fp32 math mode only; ragged batches on
+candidate lists only (below).
 
 Where the (N, J) matrix cannot be formed - a decoder of 11 271 x 728 points per sample, geodesics on 50 000 vertices - the layers
 run on CANDIDATE LISTS instead: ``forward_list(idx, sqd, inputs)`` takes, per row, K slots (key, squared distance), (N, K) shared
@@ -31,6 +32,15 @@ so a mesh may require grad; ``pit_metric(..., neighbors="auto")`` runs its down 
 ``torch.topk``: for ``sqdist_euclid`` and ``sqdist_periodic_box`` with float periods from the coordinates in one launch
 (``knn_lists_box``, no N x J block at all), for any other metric by ``knn_lists(..., select="hip")``; among equal distances the
 lowest key index is listed.  The default, "torch", is unchanged.
+
+RAGGED BATCHES - per-sample clouds of different point counts, padded to one width - run on the candidate lists:
+``forward_list(idx, sqd, inputs, lengths=)`` (or ``len_out=`` / ``len_in=``) on per-sample (b, N, K) lists,
+``knn_lists_box(..., len_out=, len_in=)``, the layers' ``forward(..., lengths=)`` / ``forward(..., len_out=, len_in=)`` with
+``neighbors`` set, ``builder="hip"`` and a box metric, and ``pit_metric.forward(mesh_in, func_in, mesh_out, len_in=, len_out=)``.
+The lengths are int32 device tensors (``ops.as_lengths``) the kernels read: no synchronisation, one captured graph for every mix
+of sizes.  Sample s comes out as the list layer computes that cloud alone; padded rows give zeros, padded points take no part and
+receive zero gradients, and the padding may hold anything, NaN included.  Dense matrices (``forward_dist``), ``builder="torch"``,
+metrics that are no box metric, per-sample latent meshes in ``pit_metric`` and the bf16 math mode do not take lengths.
 
 Not part of ``pit.py``, whose star-exports are the reference's.
 """
@@ -98,10 +108,26 @@ def default_neighbors(locality: float, n_in: int) -> int:
 NeighborLists = namedtuple("NeighborLists", ["idx", "sqd", "cut_rows"])
 
 
-def _listed_sqdist(sqdist, mesh_out, mesh_in, idx):
+def _listed_sqdist(sqdist, mesh_out, mesh_in, idx, len_out=None, len_in=None):
     """``sqdist`` of the listed pairs only, the rows as its batch axis - sqdist((R, 1, s), (R, k, s)) -> (R, 1, k) - in the shape
-    of ``idx``: O(N k) and differentiable."""
+    of ``idx``: O(N k) and differentiable.  With lengths (a ragged batch; ``idx`` holds -1 at padding) the metric sees real
+    points only: a padding key is replaced by key 0 of its sample and a padded row by row 0 before the gather, through
+    torch.where - so whatever the padded points hold (NaN included) neither reaches ``sqdist`` nor, as 0 * NaN, a gradient; the
+    layer's d(sqd) is 0 at those pairs, so the stand-ins receive nothing either."""
     n_out, k, s = int(mesh_out.shape[-2]), int(idx.shape[-1]), mesh_out.shape[-1]
+    if len_out is not None or len_in is not None:
+        b, dev = idx.shape[0], idx.device
+        ok = idx >= 0
+        if len_in is not None:
+            ok = ok & (idx < len_in.view(b, 1, 1))
+        if len_out is not None:
+            row_ok = torch.arange(n_out, device=dev).view(1, n_out) < len_out.view(b, 1)
+            ok = ok & row_ok.unsqueeze(-1)
+            mesh_out = torch.where(row_ok.unsqueeze(-1), mesh_out, mesh_out[:, :1])
+        idx = torch.where(ok, idx, torch.zeros_like(idx))
+        if len_in is not None:                               # (rows beyond the length are never gathered; keep NaN out of the backward's scatter)
+            key_ok = torch.arange(mesh_in.shape[-2], device=dev).view(1, -1) < len_in.view(b, 1)
+            mesh_in = torch.where(key_ok.unsqueeze(-1), mesh_in, mesh_in[:, :1])
     if mesh_out.dim() == 3 or mesh_in.dim() == 3:
         b = idx.shape[0]
         rows = (mesh_out if mesh_out.dim() == 3 else mesh_out.unsqueeze(0).expand(b, -1, -1)).reshape(b * n_out, 1, s)
@@ -134,13 +160,41 @@ def _cut_rows(dist, nxt, k: int, n_in: int, locality: float):
     return (nxt <= dist[..., ops.quantile_rank(float(locality), n_in)[0] + 1]).sum()
 
 
-def knn_lists_box(mesh_out, mesh_in, k=None, periods=None, locality: float = 1.0) -> NeighborLists:
+def _sample_lengths(mesh_out, mesh_in, len_out, len_in):
+    """The lengths of a ragged batch as (len_out, len_in) device tensors (None where not given); a length for a side whose mesh is
+    shared by the batch is a ValueError (the rule of ops.check_mixed), raised before the device check."""
+    if len_out is None and len_in is None:
+        return None, None
+    ops.check_knn_lengths(mesh_out, mesh_in, len_out, len_in)
+    cloud = mesh_out if mesh_out.dim() == 3 else mesh_in
+    return tuple(None if v is None else ops.as_lengths(v, cloud.device, cloud.shape[0]) for v in (len_out, len_in))
+
+
+def _cut_rows_ragged(dist, nxt, k: int, n_out: int, n_in: int, locality: float, len_out, len_in):
+    """``_cut_rows`` for a ragged batch: real rows only, each against the rank of ITS sample (ops.quantile_rank's fp32 arithmetic
+    as torch ops on the device lengths - no synchronisation); a sample with no more than k keys lists them all: no cut rows."""
+    b, dev = dist.shape[0], dist.device
+    li = torch.full((b,), n_in, device=dev, dtype=torch.int64) if len_in is None else len_in.long().clamp(1, n_in)
+    lo = torch.full((b,), n_out, device=dev, dtype=torch.int64) if len_out is None else len_out.long().clamp(1, n_out)
+    real = (torch.arange(n_out, device=dev).view(1, n_out) < lo.view(b, 1)) & (li > k).view(b, 1)
+    if float(locality) >= 1.0:
+        return real.sum()
+    # fl32(q) * fl32(li - 1), floor: an fp32 tensor times a Python scalar multiplies in fp32 (no host-to-device copy: capturable)
+    rank = torch.floor(torch.mul((li - 1).to(torch.float32), float(locality))).long()
+    at = (rank + 1).clamp(max=k - 1).view(b, 1, 1).expand(b, n_out, 1)
+    return ((nxt <= dist.gather(-1, at).squeeze(-1)) & real).sum()
+
+
+def knn_lists_box(mesh_out, mesh_in, k=None, periods=None, locality: float = 1.0, len_out=None, len_in=None) -> NeighborLists:
     """``knn_lists`` for a box metric - Euclidean, or periodic in the axes whose ``periods[a]`` is a float (None: the axis does
     not wrap) - with the keys from ONE launch of ops.knn_box: no N x J block is formed, no library sort runs, and among equal
     distances the lowest key index is taken.  ``idx`` (int64) lists a row's keys ascending by (distance, index); ``sqd`` is
     recomputed for the listed pairs by sqdist_euclid / sqdist_periodic_box(periods) as knn_lists does, so a mesh may require grad;
     ``cut_rows`` follows knn_lists's rule on the kernel's own distances, without a synchronisation.  ``k`` None:
-    default_neighbors; at most 2048 (ops.KNN_MAX_K).  Every refusal is a ValueError raised before a launch."""
+    default_neighbors; at most 2048 (ops.KNN_MAX_K).  Every refusal is a ValueError raised before a launch.
+    ``len_out`` / ``len_in``: a ragged batch (ops.knn_box with lengths) - ``k`` and its default come from the PADDED width;
+    sample s lists min(k, len_in[s]) of its own keys, every other slot holds key -1 (padding to the list layers) and a finite
+    ``sqd`` the layers never use; ``cut_rows`` counts real rows only, each against its sample's own rank."""
     for name, t in (("mesh_out", mesh_out), ("mesh_in", mesh_in)):
         if not torch.is_tensor(t) or t.dim() not in (2, 3) or 0 in t.shape:
             raise ValueError(f"{name} must be a non-empty (n, space_dim) or (b, n, space_dim) tensor")
@@ -149,12 +203,16 @@ def knn_lists_box(mesh_out, mesh_in, k=None, periods=None, locality: float = 1.0
     if k > ops.KNN_MAX_K:
         raise ValueError(f"k = {k}: at most {ops.KNN_MAX_K} neighbours are supported (the width the list layers accept)")
     per = ops.check_knn_box_shapes(mesh_out, mesh_in, k, periods)[5]
+    len_out, len_in = _sample_lengths(mesh_out, mesh_in, len_out, len_in)
     with torch.no_grad():
-        got = ops.knn_box(mesh_out, mesh_in, k, periods)
-        cut = _cut_rows(got.dist, got.next, k, n_in, locality)
+        got = ops.knn_box(mesh_out, mesh_in, k, periods, len_out=len_out, len_in=len_in)
+        if len_out is None and len_in is None:
+            cut = _cut_rows(got.dist, got.next, k, n_in, locality)
+        else:
+            cut = _cut_rows_ragged(got.dist, got.next, k, int(mesh_out.shape[-2]), n_in, locality, len_out, len_in)
         idx = got.idx.long()
     sqdist = sqdist_euclid if per is None else sqdist_periodic_box(tuple(p if p > 0.0 else None for p in per))
-    return NeighborLists(idx, _listed_sqdist(sqdist, mesh_out, mesh_in, idx), cut)
+    return NeighborLists(idx, _listed_sqdist(sqdist, mesh_out, mesh_in, idx, len_out, len_in), cut)
 
 
 def knn_lists(sqdist, mesh_out, mesh_in, k=None, chunk: int = 4096, locality: float = 1.0, select: str = "torch") -> NeighborLists:
@@ -263,14 +321,26 @@ class posatt_metric(nn.Module):
                                            tuple(sqd.stride()), idx._version, sqd._version, int(n_in), float(self.locality), sqd.device.index)
         return self._cached_plan(key, lambda: ops.ListPlan(idx, sqd, n_in, self.locality))
 
-    def forward_list(self, idx, sqd, inputs, lengths=None):
+    def forward_list(self, idx, sqd, inputs, lengths=None, len_out=None, len_in=None):
         """The layer on candidate lists: ``idx`` (int32 / int64) and ``sqd`` (fp32), (N, K) or (b, N, K); slot (i, t) says that
         key idx[i, t] lies at squared distance sqd[i, t] from row i; a key outside [0, J) marks padding.  K >= list_capacity(
-        locality, J).  The self form (this class) needs N == J and prepends the inputs."""
-        self._refuse_lengths(lengths)
+        locality, J).  The self form (this class) needs N == J and prepends the inputs.
+        ``len_out`` / ``len_in`` (``lengths``: both, the self form): a ragged batch on per-sample (b, N, K) lists - sample s has
+        len_out[s] rows and len_in[s] keys and comes out as ``forward_list(idx[s, :len_out[s]], sqd[s, :len_out[s]],
+        inputs[s:s+1, :len_in[s]])`` gives it; rows beyond are zero in every head column (the self form copies their inputs),
+        keys >= len_in[s] are padding, and whatever the padding holds (NaN included) is never used.  K is checked against the
+        padded J.  Such a plan follows its length tensors and is not kept in the cache."""
+        if lengths is not None:
+            if len_out is not None or len_in is not None:
+                raise ValueError("give either lengths (both sides) or len_out / len_in")
+            len_out = len_in = lengths
         ops._check_dist_mode()
         ops.check_list_shapes(idx, sqd, inputs, self._self_attn)
-        plan = self._list_plan(idx, sqd, inputs.shape[1])
+        if len_out is not None or len_in is not None:
+            ops.check_list_lengths(idx, len_out, len_in)
+            plan = ops.ListPlan(idx, sqd, inputs.shape[1], self.locality, len_out=len_out, len_in=len_in)
+        else:
+            plan = self._list_plan(idx, sqd, inputs.shape[1])
         return ops.posatt_list_apply(inputs, self.lmda, plan, self.n_head, concat=self._self_attn, sqd=sqd)
 
     def _build_lists(self, mesh_out, mesh_in, k):
@@ -278,11 +348,42 @@ class posatt_metric(nn.Module):
         axis a float or None) gets its lists from coordinates (knn_lists_box); any other metric from ops.knn_rows on its chunks."""
         if self.builder == "torch":
             return knn_lists(self.sqdist, mesh_out, mesh_in, k, locality=self.locality)
+        box, per = self._box_periods()
+        if box:
+            return knn_lists_box(mesh_out, mesh_in, k, periods=per, locality=self.locality)
+        return knn_lists(self.sqdist, mesh_out, mesh_in, k, locality=self.locality, select="hip")
+
+    RAGGED_SUPPORT = ("lengths (ragged batches) on the metric layers run on candidate lists built by the project's own kernels "
+                      "for a box metric: neighbors set, builder='hip' and sqdist_euclid or sqdist_periodic_box with float periods "
+                      "(or forward_list with lengths on lists of the caller's); ")
+
+    def _box_periods(self):
+        """(True, periods) when ``sqdist`` says it is a box metric whose periods the box kernel takes, else (False, None)."""
         if hasattr(self.sqdist, "box_periods"):
             per = self.sqdist.box_periods
             if per is None or all(p is None or (isinstance(p, (int, float)) and not isinstance(p, bool)) for p in per):
-                return knn_lists_box(mesh_out, mesh_in, k, periods=per, locality=self.locality)
-        return knn_lists(self.sqdist, mesh_out, mesh_in, k, locality=self.locality, select="hip")
+                return True, per
+        return False, None
+
+    def _on_meshes_ragged(self, mesh_out, mesh_in, inputs, len_out, len_in):
+        """The layer on lists built for a ragged batch; every refusal before a launch."""
+        if self.neighbors is None:
+            raise NotImplementedError(self.RAGGED_SUPPORT + "dense distance matrices (neighbors=None) do not take lengths")
+        if self.builder != "hip":
+            raise NotImplementedError(self.RAGGED_SUPPORT + "builder='torch' does not take lengths")
+        box, per = self._box_periods()
+        if not box:
+            raise NotImplementedError(self.RAGGED_SUPPORT + "this metric carries no box_periods with float periods")
+        for name, t in (("mesh_out", mesh_out), ("mesh_in", mesh_in)):
+            if not torch.is_tensor(t) or t.dim() not in (2, 3):
+                raise ValueError(f"{name} must be a (n, space_dim) or (b, n, space_dim) tensor")
+        len_out, len_in = _sample_lengths(mesh_out, mesh_in, len_out, len_in)
+        lists = knn_lists_box(mesh_out, mesh_in, None if self.neighbors == "auto" else self.neighbors, periods=per,
+                              locality=self.locality, len_out=len_out, len_in=len_in)
+        self.last_lists = lists
+        ops.check_list_shapes(lists.idx, lists.sqd, inputs, self._self_attn)
+        plan = ops.ListPlan(lists.idx, lists.sqd, inputs.shape[1], self.locality, len_out=len_out, len_in=len_in)
+        return ops.posatt_list_apply(inputs, self.lmda, plan, self.n_head, concat=self._self_attn, sqd=lists.sqd)
 
     def _on_meshes(self, mesh_out, mesh_in, inputs):
         # distances formed for this call - kNN lists (pit_metric(..., neighbors=...)) or the whole matrix: their plan is built
@@ -299,8 +400,10 @@ class posatt_metric(nn.Module):
         return ops.posatt_dist_apply(inputs, self.lmda, plan, self.n_head, concat=self._self_attn, m_dist=m_dist)
 
     def forward(self, mesh, inputs, lengths=None):
-        self._refuse_lengths(lengths)
+        """``lengths``: a ragged batch of per-sample clouds (b, n, space_dim) - see ``_on_meshes_ragged`` for what takes them."""
         ops._check_dist_mode()
+        if lengths is not None:
+            return self._on_meshes_ragged(mesh, mesh, inputs, lengths, lengths)
         return self._on_meshes(mesh, mesh, inputs)
 
     def dist2att(self, m_dist, scale, locality):
@@ -320,8 +423,11 @@ class posatt_cross_metric(posatt_metric):
     _self_attn = False
 
     def forward(self, mesh_out, mesh_in, inputs, out_bf16: bool = False, len_out=None, len_in=None):
-        self._refuse_lengths(len_out if len_out is not None else len_in)
+        """``len_out`` / ``len_in``: the point counts of the per-sample sides of a ragged batch; either mesh may be the 2-d one
+        shared by the batch, which takes no length."""
         ops._check_dist_mode()
+        if len_out is not None or len_in is not None:
+            return self._on_meshes_ragged(mesh_out, mesh_in, inputs, len_out, len_in)
         return self._on_meshes(mesh_out, mesh_in, inputs)
 
 
@@ -333,7 +439,11 @@ class pit_metric(_pit.pit):
     then build kNN lists under ``sqdist`` (knn_lists) and run on them (forward_list), O(N k) instead of O(N J); conv stays dense
     on the latent mesh.  None: dense distances everywhere.  ``builder``: "torch" (dense chunks and torch.topk) or "hip" - the lists come
     from the project's own kernels: from coordinates for sqdist_euclid / sqdist_periodic_box with float periods (no N x J block),
-    from ops.knn_rows on the chunks for any other metric."""
+    from ops.knn_rows on the chunks for any other metric.
+
+    Ragged batches: ``forward(mesh_in, func_in, mesh_out, len_in=, len_out=)`` with per-sample clouds (b, n, space_dim) against
+    the latent mesh, which is shared by the batch and has no length - with ``neighbors`` set, ``builder="hip"`` and a box metric
+    (posatt_metric.RAGGED_SUPPORT).  The processor is the dense one on the latent mesh, unchanged; ``learn_latent`` works."""
 
     def __init__(self, space_dim, in_dim, out_dim, hid_dim, n_head, n_blocks, mesh_ltt, en_loc, de_loc, sqdist=sqdist_euclid,
                  learn_latent: bool = False, neighbors=None, builder: str = "torch"):
@@ -344,10 +454,31 @@ class pit_metric(_pit.pit):
         if learn_latent:
             self.mesh_ltt = nn.Parameter(self.mesh_ltt.detach().clone())
 
-    def forward(self, mesh_in, func_in, mesh_out):
+    # pit.encoder / decoder send a shared mesh against clouds with lengths through ops.check_mixed, whose refusals (space_dim > 3,
+    # non-Euclidean metrics, mesh gradients) belong to the Euclidean ragged kernels: the metric layers take the lengths themselves
+    def encoder(self, mesh_in, func_in, mesh_ltt, len_in=None, len_ltt=None):
+        if len_in is None and len_ltt is None:
+            return super().encoder(mesh_in, func_in, mesh_ltt)
+        if len_ltt is not None:
+            raise ValueError("a length for the latent mesh: pit_metric's latent mesh is shared by the batch and has no length")
+        return self._mlp_gelu(self.en_layer, self.down(mesh_ltt, mesh_in, func_in, len_in=len_in))
+
+    def decoder(self, mesh_ltt, func_ltt, mesh_out, len_ltt=None, len_out=None):
+        if len_ltt is None and len_out is None:
+            return super().decoder(mesh_ltt, func_ltt, mesh_out)
+        if len_ltt is not None:
+            raise ValueError("a length for the latent mesh: pit_metric's latent mesh is shared by the batch and has no length")
+        return self.de(self.up(mesh_out, mesh_ltt, func_ltt, len_out=len_out))
+
+    def forward(self, mesh_in, func_in, mesh_out, len_in=None, len_out=None):
+        """``len_in`` / ``len_out``: the point counts of the clouds ``mesh_in`` / ``mesh_out`` (b, n, space_dim) of a ragged batch
+        (None = full width; ``len_in`` alone serves both when ``mesh_out`` IS ``mesh_in``).  Padded rows of the result are
+        finite (the decoder MLP's bias path) and meaningless: mask them, e.g. with ``RelLpNorm(...)(true, pred, lengths)``."""
+        if len_out is None and len_in is not None and mesh_out is mesh_in:
+            len_out = len_in
         mesh_ltt = self.mesh_ltt.to(func_in.device) if self.mesh_ltt.device != func_in.device else self.mesh_ltt
         coords = mesh_in if mesh_in.dim() == 3 else mesh_in.unsqueeze(0).expand(func_in.shape[0], -1, -1)
         func = torch.cat((coords, func_in), dim=-1)
-        func = self.encoder(mesh_in, func, mesh_ltt)
+        func = self.encoder(mesh_in, func, mesh_ltt, len_in=len_in)
         func = self.processor(func, mesh_ltt)
-        return self.decoder(mesh_ltt, func, mesh_out)
+        return self.decoder(mesh_ltt, func, mesh_out, len_out=len_out)

@@ -1795,17 +1795,46 @@ def check_list_shapes(idx, sqd, values, concat: bool) -> None:
         raise ValueError(f"the self-attention form needs one list per input point (N == J): {idx.shape[-2]} lists, {values.shape[1]} points")
 
 
+class SharedListLengthsError(ValueError, NotImplementedError):
+    """Lengths with (N, K) lists shared by the batch: a ValueError - the combination has no meaning, one list set cannot follow
+    per-sample key counts - that callers written against the earlier blanket refusal of lengths (NotImplementedError) still catch."""
+
+
+def check_list_lengths(idx, len_out, len_in) -> None:
+    """What lengths on candidate lists do not cover, refused before the device check and before anything is launched."""
+    if len_out is None and len_in is None:
+        return
+    if idx.dim() != 3:
+        raise SharedListLengthsError("lengths need per-sample (b, N, K) lists: lists shared by the batch have no per-sample length")
+    for name, given in (("len_out", len_out), ("len_in", len_in)):
+        if given is None:
+            continue
+        if torch.is_tensor(given) and given.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"{name} must be an int32 or int64 tensor, got {given.dtype}")
+        count = given.numel() if torch.is_tensor(given) else len(given)
+        if count != idx.shape[0]:
+            raise ValueError(f"{name} must hold one entry per sample: {count} entries for a batch of {idx.shape[0]}")
+
+
 class ListPlan:
     """Candidate lists ``(idx, sqd)`` - (N, K), shared by the whole batch, or (b, N, K) - of a layer of ``locality`` over
     ``n_in`` keys: an int32 copy of the keys, a detached view of the distances, the selection statistics over the valid slots
     (pit_distlist_select_fwd; the rank comes from ``n_in``, not from K) and - built when a backward first asks for it - the
     transposed index that d(values) runs over.  A slot whose key is outside [0, n_in) is padding.  Preconditions, not checked
     (a check would synchronise): valid distances finite and >= 0, no key twice in a row, at least k + 2 valid slots per row of a
-    masked layer."""
+    masked layer.
 
-    def __init__(self, idx: torch.Tensor, sqd: torch.Tensor, n_in: int, locality: float):
+    ``len_out`` / ``len_in`` (either; ``as_lengths`` forms): a RAGGED batch on per-sample (b, N, K) lists - sample s has len_out[s]
+    rows and len_in[s] keys; the plan keeps the two int32 device tensors (a captured step overwrites them in place) and a device
+    array ``rank_w`` the selection fills per sample, and runs the pit_distlist_*_ragged_* entries.  ``n_in`` stays the padded
+    width: the list width is checked against its rank, which bounds every sample's, and the transposed index is built against
+    it from the keys alone, so it outlives any change of the lengths."""
+
+    def __init__(self, idx: torch.Tensor, sqd: torch.Tensor, n_in: int, locality: float, len_out=None, len_in=None):
         _check_dist_mode()
         check_list_shapes(idx, sqd, None, False)
+        self.ragged = len_out is not None or len_in is not None
+        check_list_lengths(idx, len_out, len_in)
         if not (0.0 <= float(locality) <= 1.0):
             raise ValueError(f"locality must lie in [0, 1], got {locality}")
         n_in = int(n_in)
@@ -1823,6 +1852,8 @@ class ListPlan:
         _need_gpu(sqd)
         if idx.device != sqd.device:
             raise RuntimeError(f"idx lives on {idx.device}, sqd on {sqd.device}")
+        self.len_out = None if len_out is None else as_lengths(len_out, sqd.device, int(idx.shape[0]))
+        self.len_in = None if len_in is None else as_lengths(len_in, sqd.device, int(idx.shape[0]))
         self.source_idx, self.source = idx, sqd.detach()    # (keep the caller's storages - and with them their addresses - alive)
         i3 = idx.detach() if idx.dim() == 3 else idx.detach().unsqueeze(0)
         if i3.dtype != torch.int32:
@@ -1837,6 +1868,7 @@ class ListPlan:
         self.masked = self.locality < 1.0
         self.rank_k, self.rank_w = quantile_rank(self.locality, n_in)
         self.stats = torch.empty((3, self.mesh_batch * n), device=sqd.device, dtype=torch.float32)
+        self.rank_w_dev = torch.empty((self.mesh_batch,), device=sqd.device, dtype=torch.float32) if self.ragged else None
         self._rev = None
         self.refresh()
 
@@ -1846,6 +1878,15 @@ class ListPlan:
         src = self.source if self.source.dim() == 3 else self.source.unsqueeze(0)
         if self.sqd.data_ptr() != src.data_ptr():
             self.sqd.copy_(src)                             # (the caller's tensor was not contiguous: the plan works on a copy)
+        if self.ragged:                                     # (the rank of every sample is formed on the device from its length)
+            rc = _lib.lib().pit_distlist_select_ragged_fwd(self.idx.data_ptr(), self.sqd.data_ptr(), self.ld, self.bstride, self.cap,
+                                                           self.mesh_batch, self.n_out, self.n_in, self.locality, 1 if self.masked else 0,
+                                                           _lib.ptr(self.len_out), _lib.ptr(self.len_in), self.stats.data_ptr(),
+                                                           self.rank_w_dev.data_ptr(), _lib.stream_ptr())
+            _lib.check(rc, "pit_distlist_select_ragged_fwd")
+            if _capturing():
+                _pin(self)
+            return
         rc = _lib.lib().pit_distlist_select_fwd(self.idx.data_ptr(), self.sqd.data_ptr(), self.ld, self.bstride, self.cap, self.mesh_batch,
                                                 self.n_out, self.n_in, self.rank_k if self.masked else 0, 1 if self.masked else 0,
                                                 self.stats.data_ptr(), _lib.stream_ptr())
@@ -1886,6 +1927,11 @@ class ListPlan:
         return (self.idx.data_ptr(), self.sqd.data_ptr(), self.ld, self.bstride, self.cap, self.n_out, self.n_in)
 
     def launch_fwd(self, io) -> None:
+        if self.ragged:
+            rc = _lib.lib().pit_distlist_ragged_fwd(*self._geometry(), *io.values, *io.head, self.stats.data_ptr(), self.rank_w_dev.data_ptr(),
+                                                    1 if self.masked else 0, _lib.ptr(self.len_out), _lib.ptr(self.len_in), *io.out, *io.tail)
+            _lib.check(rc, "pit_distlist_ragged_fwd")
+            return
         rc = _lib.lib().pit_distlist_fwd(*self._geometry(), *io.values, *io.head, self.stats.data_ptr(), self.rank_w, 1 if self.masked else 0,
                                          *io.out, *io.tail)
         _lib.check(rc, "pit_distlist_fwd")
@@ -1898,6 +1944,12 @@ class ListPlan:
             rev = self.transposed()
             dv_ws = torch.empty(((L.pit_distlist_bwd_workspace(io.batch, self.n_out, self.cap, io.dim) + 3) // 4,), device=self.idx.device,
                                 dtype=torch.float32)
+        if self.ragged:
+            rc = L.pit_distlist_ragged_bwd(*self._geometry(), *io.values, *io.head, io.rowstat, 1 if self.masked else 0, _lib.ptr(self.len_out),
+                                           _lib.ptr(self.len_in), *io.d_out, *io.d_values, *io.d_head, _lib.ptr(grads.d_source),
+                                           *_lib.saved_out_args(grads.out), *(_lib.ptr(t) for t in rev), _lib.ptr(dv_ws), *io.tail)
+            _lib.check(rc, "pit_distlist_ragged_bwd")
+            return
         rc = L.pit_distlist_bwd(*self._geometry(), *io.values, *io.head, io.rowstat, 1 if self.masked else 0, *io.d_out, *io.d_values, *io.d_head,
                                 _lib.ptr(grads.d_source), *_lib.saved_out_args(grads.out), *(_lib.ptr(t) for t in rev), _lib.ptr(dv_ws), *io.tail)
         _lib.check(rc, "pit_distlist_bwd")
@@ -3782,6 +3834,23 @@ def check_knn_box_shapes(mesh_out, mesh_in, k, periods=None):
     return batch, n_out, n_in, sdim, k, _knn_periods(periods, sdim)
 
 
+def check_knn_lengths(mesh_out, mesh_in, len_out, len_in) -> None:
+    """What lengths on ``knn_box`` do not cover, refused before the device check: a length belongs to a per-sample (b, n, s) side
+    (the rule of ``check_mixed``), one entry per sample."""
+    batch = int(mesh_out.shape[0]) if mesh_out.dim() == 3 else (int(mesh_in.shape[0]) if mesh_in.dim() == 3 else 1)
+    for name, given, mesh in (("len_out", len_out, mesh_out), ("len_in", len_in, mesh_in)):
+        if given is None:
+            continue
+        if mesh.dim() != 3:
+            raise ValueError(f"{name} for a mesh shared by the batch: every one of its points is real for every sample - lengths "
+                             "belong to the per-sample side only")
+        if torch.is_tensor(given) and given.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"{name} must be an int32 or int64 tensor, got {given.dtype}")
+        count = given.numel() if torch.is_tensor(given) else len(given)
+        if count != batch:
+            raise ValueError(f"{name} must hold one entry per sample: {count} entries for a batch of {batch}")
+
+
 def check_knn_rows_shapes(m, k):
     """The same for ``knn_rows``.  Returns (batch, n_out, n_in, k)."""
     if not torch.is_tensor(m) or m.dim() not in (2, 3):
@@ -3817,7 +3886,7 @@ def _knn_mesh(mesh, batch: int):
 
 
 @torch.compiler.disable
-def knn_box(mesh_out: torch.Tensor, mesh_in: torch.Tensor, k: int, periods=None) -> KnnResult:
+def knn_box(mesh_out: torch.Tensor, mesh_in: torch.Tensor, k: int, periods=None, len_out=None, len_in=None) -> KnnResult:
     """One launch of pit_knn_box (include/pit_hip.h): for every point of ``mesh_out`` its ``k`` nearest points of ``mesh_in``
     under the squared distance of a box - Euclidean, or with ``periods[a]`` (a float; None: no wrap) the period of axis a, the op
     sequence of metric.sqdist_euclid / sqdist_periodic_box - ascending by (distance, key index), the lowest index among equals.
@@ -3825,8 +3894,15 @@ def knn_box(mesh_out: torch.Tensor, mesh_in: torch.Tensor, k: int, periods=None)
       mesh_out   (N, s) or (b, N, s) fp32; mesh_in (J, s) or (b, J, s) fp32; a batch-free mesh is shared by the batch and read in place
       k          1 .. min(J, 2048)
     Results are (N, k) / (N,) when both meshes are batch-free, (b, N, k) / (b, N) otherwise.  Nothing differentiates through the
-    choice (recompute the listed distances for that: metric.knn_lists_box)."""
+    choice (recompute the listed distances for that: metric.knn_lists_box).
+      len_out / len_in   a RAGGED batch (pit_knn_box_ragged): the point counts of the per-sample sides (``as_lengths`` forms; a
+                 shared mesh takes none), read on the device - no synchronisation, so a captured launch follows lengths
+                 overwritten in place.  Sample s searches its first L = len_in[s] keys only (the rest may hold NaN) and a real
+                 row equals ``knn_box`` on the trimmed sample with min(k, L) neighbours bit for bit; its further slots hold key
+                 -1 / distance 0 and ``next`` is +inf when k >= L; rows >= len_out[s] hold -1 / 0 / +inf.  ``k`` is checked
+                 against the padded width."""
     batch, n_out, n_in, sdim, k, per = check_knn_box_shapes(mesh_out, mesh_in, k, periods)
+    check_knn_lengths(mesh_out, mesh_in, len_out, len_in)
     _knn_need_gpu(mesh_out, mesh_in)
     mo, so = _knn_mesh(mesh_out, batch)
     mi, si = _knn_mesh(mesh_in, batch)
@@ -3835,10 +3911,19 @@ def knn_box(mesh_out: torch.Tensor, mesh_in: torch.Tensor, k: int, periods=None)
     dist = torch.empty((batch, n_out, k), device=dev, dtype=torch.float32)
     nxt = torch.empty((batch, n_out), device=dev, dtype=torch.float32)
     per_c = None if per is None else (ctypes.c_float * sdim)(*per)
+    per_p = None if per_c is None else ctypes.cast(per_c, ctypes.c_void_p)
+    if len_out is not None or len_in is not None:
+        lo = None if len_out is None else as_lengths(len_out, dev, batch)
+        li = None if len_in is None else as_lengths(len_in, dev, batch)
+        if _capturing():
+            _pin(mo, mi, lo, li)
+        rc = _lib.lib().pit_knn_box_ragged(mo.data_ptr(), mi.data_ptr(), batch, n_out, n_in, sdim, so, si, per_p, k, _lib.ptr(lo),
+                                           _lib.ptr(li), idx.data_ptr(), dist.data_ptr(), nxt.data_ptr(), _lib.stream_ptr())
+        _lib.check(rc, "pit_knn_box_ragged")
+        return KnnResult(idx, dist, nxt)
     if _capturing():
         _pin(mo, mi)
-    rc = _lib.lib().pit_knn_box(mo.data_ptr(), mi.data_ptr(), batch, n_out, n_in, sdim, so, si,
-                                None if per_c is None else ctypes.cast(per_c, ctypes.c_void_p), k, idx.data_ptr(),
+    rc = _lib.lib().pit_knn_box(mo.data_ptr(), mi.data_ptr(), batch, n_out, n_in, sdim, so, si, per_p, k, idx.data_ptr(),
                                 dist.data_ptr(), nxt.data_ptr(), _lib.stream_ptr())
     _lib.check(rc, "pit_knn_box")
     if mesh_out.dim() == 2 and mesh_in.dim() == 2:
@@ -3881,19 +3966,28 @@ def knn_last_form() -> int:
     return int(_lib.lib().pit_knn_last_form())
 
 
-def knn_box_restated(mesh_out, mesh_in, k: int, periods=None, row_chunk: int = 512) -> KnnResult:
+def knn_box_restated(mesh_out, mesh_in, k: int, periods=None, row_chunk: int = 512, len_out=None, len_in=None) -> KnnResult:
     """``knn_box`` restated on the host in numpy fp32, operation by operation (the loop of include/pit_hip.h): t = |x - y|,
     u = minimum(t, p - t) on a wrapped axis, d = ((u0*u0 + u1*u1) + u2*u2) + ..., a stable ascending sort of every row, cut at
-    ``k``.  CPU tensors in, CPU tensors out, the shapes and dtypes of ``knn_box``; for tests."""
+    ``k``.  CPU tensors in, CPU tensors out, the shapes and dtypes of ``knn_box``; for tests.  ``len_out`` / ``len_in``: the
+    ragged form of ``knn_box`` - every sample restated on its first len_in[s] keys and len_out[s] rows, the rest filled with
+    -1 / 0 / +inf."""
     batch, n_out, n_in, sdim, k, per = check_knn_box_shapes(mesh_out, mesh_in, k, periods)
+    check_knn_lengths(mesh_out, mesh_in, len_out, len_in)
+    ragged = len_out is not None or len_in is not None
+    lens = [None if v is None else [max(1, min(int(x), w)) for x in (v.tolist() if torch.is_tensor(v) else v)]
+            for v, w in ((len_out, n_out), (len_in, n_in))]
     mo = mesh_out.detach().cpu().numpy().astype(np.float32, copy=False)
     mi = mesh_in.detach().cpu().numpy().astype(np.float32, copy=False)
-    idx = np.empty((batch, n_out, k), np.int32)
-    dist = np.empty((batch, n_out, k), np.float32)
-    nxt = np.empty((batch, n_out), np.float32)
+    idx = np.full((batch, n_out, k), -1, np.int32)
+    dist = np.zeros((batch, n_out, k), np.float32)
+    nxt = np.full((batch, n_out), np.inf, np.float32)
+    k_all = k
     for s in range(batch):
         x_all, y = (mo[s] if mo.ndim == 3 else mo), (mi[s] if mi.ndim == 3 else mi)
-        for r0 in range(0, n_out, int(row_chunk)):
+        lo, n_in = (n_out if lens[0] is None else lens[0][s]), (int(mesh_in.shape[-2]) if lens[1] is None else lens[1][s])
+        x_all, y, k = x_all[:lo], y[:n_in], min(k_all, n_in)
+        for r0 in range(0, lo, int(row_chunk)):
             x = x_all[r0:r0 + int(row_chunk)]
             d = None
             for a in range(sdim):
@@ -3905,11 +3999,11 @@ def knn_box_restated(mesh_out, mesh_in, k: int, periods=None, row_chunk: int = 5
             assert d.dtype == np.float32
             order = np.argsort(d, axis=-1, kind="stable")
             srt = np.take_along_axis(d, order, axis=-1)
-            idx[s, r0:r0 + len(x)] = order[:, :k]
-            dist[s, r0:r0 + len(x)] = srt[:, :k]
+            idx[s, r0:r0 + len(x), :k] = order[:, :k]
+            dist[s, r0:r0 + len(x), :k] = srt[:, :k]
             nxt[s, r0:r0 + len(x)] = srt[:, k] if k < n_in else np.float32(np.inf)
     out = KnnResult(torch.from_numpy(idx), torch.from_numpy(dist), torch.from_numpy(nxt))
-    if mesh_out.dim() == 2 and mesh_in.dim() == 2:
+    if mesh_out.dim() == 2 and mesh_in.dim() == 2 and not ragged:
         return KnnResult(out.idx[0], out.dist[0], out.next[0])
     return out
 
