@@ -1400,6 +1400,37 @@ int pit_block_fwd_last_rows(void);
 #define PIT_BLOCK_RIDER_SLOTS 5
 int pit_block_bwd_last_riders(int* out, int n);
 
+/* The finishing launch carrying several postponed jobs (csrc/pit_posatt.hip: posatt_dhead_finish_tail).  A rider tile of
+ * pit_block_bwd is latency - two cold round trips, 1.7 us of fp32 MFMA, the atomics' acknowledgement - and a launch pays for it
+ * once however many run side by side; pit_posatt_dhead_finish pays that price already for its `rider` and leaves most compute
+ * units idle.  So a caller may hand the jobs of its LAST block launches (which then pass rider = rider2 = NULL and shrink to
+ * their chain) to the finishing launch.  A library built from this header defines PIT_HAS_FINISH_TAIL; PIT_ABI_VERSION is
+ * unchanged (nothing that existed changed: a finish call with nothing staged makes the launches it always made).
+ *
+ * pit_posatt_dhead_finish_stage - host-only, no device work: COPIES the n job structs jobs[0..n) (the caller's may die at once)
+ *   into a list of the calling thread; several calls append.  The thread's NEXT pit_posatt_dhead_finish consumes the list,
+ *   whatever else it does: up to 8 staged jobs in the fp32 math mode that accumulate and have at most 2^28 MACs run inside its
+ *   launch beside `rider` - as 64 x 64 LDS-staged tiles, the thin dW2 | db2 row reduction or register-direct tiles, 512 threads and
+ *   64 KiB of LDS per workgroup; beyond two workgroups per compute unit the job with the most tiles takes more rows per tile.
+ *   Every other staged job - and every staged job when n_layers <= 0 or the call's arguments are refused - runs as the
+ *   pit_mlp_bwd_params launches of its own on `stream`, after the finishing launch.  d_head is what it is without staged jobs,
+ *   bit for bit.  The staging call notes each job in pit_debug_rider_counts, under PIT_RIDER_DHEAD_FINISH when the finish call
+ *   will carry it and PIT_RIDER_OWN otherwise; the finish call notes its `rider` only.  Returns 0, PIT_ERR_NULL (jobs or one of
+ *   its entries NULL: nothing staged) or PIT_ERR_SIZE (n < 0).
+ * pit_finish_last_tail - what the most recent pit_posatt_dhead_finish of this process did with staged jobs: copies
+ *   min(n, PIT_FINISH_TAIL_SLOTS) values to out (host array), returns PIT_FINISH_TAIL_SLOTS.  All zero after a call that found
+ *   nothing staged.  Host-side and process-global, no device work, nothing read by a kernel. */
+#define PIT_HAS_FINISH_TAIL 1
+#define PIT_FINISH_TAIL_STAGED  0   /* jobs the call found staged                                           */
+#define PIT_FINISH_TAIL_CARRIED 1   /* ... of those, performed inside the finishing launch                  */
+#define PIT_FINISH_TAIL_RD      2   /* their workgroups: register-direct reductions (gemm_rd_body)          */
+#define PIT_FINISH_TAIL_TILE    3   /* gemm_rr_tile tiles                                                   */
+#define PIT_FINISH_TAIL_THIN    4   /* thin_rider workgroups                                                */
+#define PIT_FINISH_TAIL_OWN     5   /* staged jobs performed as launches of their own                       */
+#define PIT_FINISH_TAIL_SLOTS   6
+int pit_posatt_dhead_finish_stage(const pit_mlp_params_job* const* jobs, int n);
+int pit_finish_last_tail(int* out, int n);
+
 /* Layout probe used by the tests: D = A(32x8) * B(8x32) through the same
  * v_mfma_f32_32x32x2_f32 fragment maps the kernels use. */
 int pit_debug_mfma_tile(const float* a, const float* b, float* d, void* stream);

@@ -177,6 +177,7 @@ ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_
                "pit_rel_lp_loss_ragged_fwd_grad", "pit_rel_max_norm_ragged",       # PIT_HAS_DISTLIST, PIT_HAS_RAGGED_STEP
                "pit_block_fwd_set_form", "pit_block_fwd_last_rows",                # PIT_HAS_BLOCK_ROWS8
                "pit_block_bwd_last_riders",                                        # PIT_HAS_RIDER_TAIL
+               "pit_posatt_dhead_finish_stage", "pit_finish_last_tail",            # PIT_HAS_FINISH_TAIL
                "pit_debug_att_counts",                                             # PIT_HAS_ATT_COUNTS
                "pit_eval_metrics_workspace", "pit_eval_metrics",                   # PIT_HAS_EVAL_METRICS
                "pit_batch_feed",                                                   # PIT_HAS_BATCH_FEED

@@ -23,11 +23,13 @@ namespace {
 thread_local int t_rider_counts[PIT_RIDER_KINDS];
 thread_local int t_gemm_counts[PIT_GEMM_KINDS];
 thread_local int t_att_counts[PIT_ATT_KINDS];
+thread_local int t_rider_mute = 0;
 }  // namespace
 
 void pit_rider_note(int kind) {
-    if (kind >= 0 && kind < PIT_RIDER_KINDS) ++t_rider_counts[kind];
+    if (!t_rider_mute && kind >= 0 && kind < PIT_RIDER_KINDS) ++t_rider_counts[kind];
 }
+void pit_rider_mute(int on) { t_rider_mute = on; }
 
 extern "C" int pit_debug_rider_counts(int* out, int n, int reset) {
     for (int k = 0; out && k < n && k < PIT_RIDER_KINDS; ++k) out[k] = t_rider_counts[k];

@@ -35,6 +35,9 @@ extern thread_local int t_call_math;
                                    t_call_math = ((mode_) & 0xff); } while (0)
 // include/pit_hip.h, pit_debug_rider_counts: a host that accepts a postponed weight-gradient job notes it (kind = PIT_RIDER_*)
 void pit_rider_note(int kind);
+// pit_rider_mute(1) .. (0): notes of the calling thread are dropped in between (pit_posatt_dhead_finish performs a staged job that
+// its staging call has already noted)
+void pit_rider_mute(int on);
 // include/pit_hip.h, pit_debug_gemm_counts: every launch site of pit_mlp.hip / pit_mlp_slab.hip notes its kernel (kind = a
 // PIT_GEMM_* counter); pit_gemm_note_last stores a value in a PIT_GEMM_LAST_* slot
 void pit_gemm_note(int kind);

@@ -61,7 +61,33 @@ constexpr int THIN_RIDER_ROWS = 4, THIN_RIDER_WGS = 16;
 // launch)
 // `allow_rr`: 1 = the caller's kernel runs rr1 / rr2 reductions through gemm_rr_tile (>= 64 KiB of LDS, >= 4 waves); 2 = and a thin
 // dW2 | db2 through thin_rider (dw_pair_body<true>, 8 waves)
-bool plan_dw_pair(const pit_mlp_params_job& job, int waves, DwPair* out, int target_wgs = 768, int allow_rr = 0);
+// `chunks_per_tile`: RR_BK-row chunks one tile workgroup reduces (0 = the default, 2): more chunks, fewer workgroups - for a
+// carrying launch that wants every workgroup resident at once (pit_posatt_dhead_finish with staged jobs)
+bool plan_dw_pair(const pit_mlp_params_job& job, int waves, DwPair* out, int target_wgs = 768, int allow_rr = 0, int chunks_per_tile = 0);
+
+// A DwPair of plain fp32 weight-gradient reductions (make_dw2 / make_dw1: A read down its columns, B along its rows, the ones
+// column last, nothing but the atomic epilogue) in 208 bytes instead of 536, so that a kernel's arguments hold several of them
+// (pit_posatt.hip: posatt_dhead_finish_tail).  pack_tail refuses anything a TailGemm cannot say; tail_pair_body expands the one
+// reduction its workgroup runs.
+struct TailGemm { const float* A; const float* B; float* C; float* C2; int a_cs, b_rs, ldc, M, N, K; unsigned a_bytes, b_bytes; int k_slab, vec; };
+struct TailPair { TailGemm g1, g2; int n1, n2, gx1, gy1, gx2, gy2; int rr1, rr2, tx1, tiles1, slabs1, tx2, tiles2, slabs2, nchunks, pad_; };
+inline bool pack_tail(const GemmArgs& g, TailGemm* c) {
+    if (g.a_rs != 1 || g.b_cs != 1 || g.a_cs <= 0 || g.a_cs > 0x7fffffffL || g.b_rs <= 0 || g.b_rs > 0x7fffffffL || g.ldc <= 0 ||
+        g.ldc > 0x7fffffffL) return false;
+    if (g.a_gz || g.a_out || g.bias || g.Z || g.G || g.bf16 || !g.atomic || g.ones_col != g.N - 1 || !g.C || !g.C2) return false;
+    if (g.a16 || g.b16 || g.c16 || g.z16 || g.g16 || g.remap_gx || g.remap_gy) return false;
+    c->A = g.A; c->B = g.B; c->C = g.C; c->C2 = g.C2;
+    c->a_cs = (int)g.a_cs; c->b_rs = (int)g.b_rs; c->ldc = (int)g.ldc; c->M = g.M; c->N = g.N; c->K = g.K;
+    c->a_bytes = g.a_bytes; c->b_bytes = g.b_bytes; c->k_slab = g.k_slab; c->vec = (g.a_vec ? 1 : 0) | (g.b_vec ? 2 : 0);
+    return true;
+}
+inline bool pack_tail(const DwPair& w, TailPair* t) {
+    if (w.xcd_spb || !pack_tail(w.g1, &t->g1) || !pack_tail(w.g2, &t->g2)) return false;
+    t->n1 = w.n1; t->n2 = w.n2; t->gx1 = w.gx1; t->gy1 = w.gy1; t->gx2 = w.gx2; t->gy2 = w.gy2;
+    t->rr1 = w.rr1; t->rr2 = w.rr2; t->tx1 = w.tx1; t->tiles1 = w.tiles1; t->slabs1 = w.slabs1;
+    t->tx2 = w.tx2; t->tiles2 = w.tiles2; t->slabs2 = w.slabs2; t->nchunks = w.nchunks; t->pad_ = 0;
+    return true;
+}
 // both reductions as gemm_rr_tile tiles (fp32 or - bf16 math mode - bf16 MFMA operands) for a carrying launch that has 64 KiB of LDS
 // and at least four waves (pit_satt.hip's backward launch): any size, `budget_wgs` workgroups in all
 bool plan_rr_rider(const pit_mlp_params_job& job, DwPair* out, int budget_wgs);
@@ -547,6 +573,34 @@ __device__ __forceinline__ void dw_pair_body(const pit_detail::DwPair& w, int id
     const int rr = second ? w.rr2 : w.rr1, tx = second ? w.tx2 : w.tx1;
     const int slabs = second ? w.slabs2 : w.slabs1, gx = second ? w.gx2 : w.gx1, gy = second ? w.gy2 : w.gy1;
     if (TAIL && rr == 2) {
+        if (g.M == 1) thin_rider<1, 4>(g, id, slabs, smem);
+        else thin_rider<pit_detail::THIN_RIDER_ROWS, 2>(g, id, slabs, smem);
+    }
+    else if (rr) rr_rider(g, slab, tile, tx, slabs, w.nchunks, smem);
+    else gemm_rd_body<1, EPI_ATOMIC>(g, id % gx, (id / gx) % gy, id / (gx * gy));
+}
+
+// dw_pair_body<true> for a pair in its compact form (pit_detail::TailPair; 8 waves, 64 KiB of LDS): the workgroup's reduction is
+// selected first and only that one expanded into the GemmArgs the bodies read
+__device__ __forceinline__ void tail_pair_body(const pit_detail::TailPair& w, int id, float* smem) {
+    const bool second = id >= w.n1;
+    if (second) id -= w.n1;
+    const int tiles = second ? w.tiles2 : w.tiles1;
+    int slab = 0, tile = 0;
+    if (tiles) { slab = id / tiles; tile = id % tiles; }
+    const pit_detail::TailGemm& c = second ? w.g2 : w.g1;
+    GemmArgs g = GemmArgs();
+    g.A = c.A; g.a_rs = 1; g.a_cs = c.a_cs;
+    g.B = c.B; g.b_rs = c.b_rs; g.b_cs = 1;
+    g.M = c.M; g.N = c.N; g.K = c.K;
+    g.a_bytes = c.a_bytes; g.b_bytes = c.b_bytes;
+    g.a_vec = c.vec & 1; g.b_vec = (c.vec >> 1) & 1;
+    g.k_slab = c.k_slab;
+    g.C = c.C; g.ldc = c.ldc; g.C2 = c.C2;
+    g.epi = EPI_ATOMIC; g.atomic = 1; g.ones_col = c.N - 1;
+    const int rr = second ? w.rr2 : w.rr1, tx = second ? w.tx2 : w.tx1;
+    const int slabs = second ? w.slabs2 : w.slabs1, gx = second ? w.gx2 : w.gx1, gy = second ? w.gy2 : w.gy1;
+    if (rr == 2) {
         if (g.M == 1) thin_rider<1, 4>(g, id, slabs, smem);
         else thin_rider<pit_detail::THIN_RIDER_ROWS, 2>(g, id, slabs, smem);
     }

@@ -1688,7 +1688,7 @@ int launch_dz1(int rows, int n1, int n2, const float* w2, const float* z1, const
 
 // the reductions of a postponed pit_mlp_bwd_params, laid out for a launch that carries them along
 // (pit_posatt.hip: posatt_bwd_pair_dw_kernel); same tiling as launch_gemm_pair_atomic
-bool pit_detail::plan_dw_pair(const pit_mlp_params_job& j, int waves, DwPair* out, int target_wgs, int allow_rr) {
+bool pit_detail::plan_dw_pair(const pit_mlp_params_job& j, int waves, DwPair* out, int target_wgs, int allow_rr, int chunks_per_tile) {
     static const bool off = exp_env("PIT_NO_DW_RIDER") != nullptr;
     if (off || !j.accumulate) return false;
     if (!j.x || !j.h || !j.d_y || !j.d_w1 || !j.d_b1 || !j.d_w2 || !j.d_b2 || !j.scratch) return false;
@@ -1714,7 +1714,8 @@ bool pit_detail::plan_dw_pair(const pit_mlp_params_job& j, int waves, DwPair* ou
     // coalesced, a few chunks per workgroup - the register-direct form of the same reduction keeps 6-12x as many
     // workgroups busy for the same MACs and lengthens the launch it rides in
     static const bool no_rr = exp_env("PIT_NO_RR_RIDER") != nullptr;
-    static const int per_wg = exp_env("PIT_RR_RIDER_CHUNKS") ? std::max(1, atoi(exp_env("PIT_RR_RIDER_CHUNKS"))) : 2;
+    static const int per_wg_default = exp_env("PIT_RR_RIDER_CHUNKS") ? std::max(1, atoi(exp_env("PIT_RR_RIDER_CHUNKS"))) : 2;
+    const int per_wg = chunks_per_tile > 0 ? chunks_per_tile : per_wg_default;
     if (allow_rr && !no_rr && (j.math_mode & 0xff) == 0) {
         auto as_rr = [&](const GemmArgs& g, int& rr, int& tx, int& tiles, int& slabs, int& n) {
             const int n_real = g.ones_col >= 0 ? g.N - 1 : g.N;

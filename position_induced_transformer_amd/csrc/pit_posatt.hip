@@ -23,9 +23,11 @@
 #include "pit_common.h"
 #include "pit_block_dev.h"      // block_weights_body: the processor's weights as a rider of the down-projection launch
 #include "pit_gemm_rd.h"
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
+#include <vector>
 
 namespace {
 
@@ -86,10 +88,14 @@ __device__ __forceinline__ void dscale_add(double* slot, double v, bool doit) {
     if (doit) atomicAdd(slot, v);
 }
 
+// NTHR > 0: the workgroup's first NTHR threads drain (the others have left: posatt_dhead_finish_tail), in the order a launch
+// with NTHR threads sums in; 0: all of blockDim.x
+template <int NTHR = 0>
 __device__ __forceinline__ void dscale_drain_head(const AttArgs& a, int h, double* s_red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    const int nthr = NTHR ? NTHR : (int)blockDim.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = nthr >> 6;
     double g = 0.0;
-    for (int sl = threadIdx.x; sl < a.nslots; sl += blockDim.x) {      // only the slots this launch used
+    for (int sl = threadIdx.x; sl < a.nslots; sl += nthr) {      // only the slots this launch used
         unsigned long long* w = reinterpret_cast<unsigned long long*>(a.dscale_acc + (long)h * PIT_DSCALE_SLOTS + sl);
         g += __longlong_as_double((long long)atomicExch(w, 0ull));
     }
@@ -127,6 +133,7 @@ struct FinishBatch {
     int flags[FINISH_MAX_LAYERS];            // PIT_HEAD_ACCUMULATE | PIT_HEAD_IS_SCALE
     int wg_base[FINISH_MAX_LAYERS + 1];
 };
+template <int NTHR = 0>
 __device__ __forceinline__ void finish_batch_body(const FinishBatch& fb, double* s_red) {
     int l = 0;
     while (l + 1 < fb.n && (int)blockIdx.x >= fb.wg_base[l + 1]) ++l;
@@ -139,7 +146,7 @@ __device__ __forceinline__ void finish_batch_body(const FinishBatch& fb, double*
     a.accumulate_head = (fb.flags[l] & PIT_HEAD_ACCUMULATE) ? 1 : 0;
     a.head = fb.scale[l] ? fb.scale[l] : fb.head[l];
     a.head_is_scale = (fb.scale[l] || a.dhead_is_scale) ? 1 : 0;
-    dscale_drain_head(a, (int)blockIdx.x - fb.wg_base[l], s_red);
+    dscale_drain_head<NTHR>(a, (int)blockIdx.x - fb.wg_base[l], s_red);
 }
 __global__ __launch_bounds__(256) void posatt_dhead_finish_batch(FinishBatch fb) {
     __shared__ double s_red[10];
@@ -151,6 +158,34 @@ __global__ __launch_bounds__(256) void posatt_dhead_finish_dw(FinishBatch fb, in
     __shared__ double s_red[10];
     if ((int)blockIdx.x < n_fin) { finish_batch_body(fb, s_red); return; }
     dw_pair_body(w, (int)blockIdx.x - n_fin, pit_dyn_smem());
+}
+// Round 10: the finishing launch carrying SEVERAL postponed jobs in the forms pit_block.hip's riders take (gemm_rr_tile tiles,
+// thin_rider, the register-direct body; 8 waves, 64 KiB of LDS): the weight-gradient reductions the last block launches of a
+// fused processor gave up (pit_posatt_dhead_finish_stage) beside the `rider` of the call.  A tile is latency, not throughput, and
+// this launch pays for it once however many run side by side, as long as every workgroup is resident (two per CU at 64 KiB).
+// Workgroups [0, n_fin) drain with their first 256 threads exactly as posatt_dhead_finish_dw's do (the same sums in the same
+// order), job j owns [wg_base[j], wg_base[j + 1]).
+constexpr int FINISH_TAIL_STAGED = 8;                   // staged jobs one launch carries; the call's `rider` has a slot of its own
+constexpr int FINISH_TAIL_JOBS = FINISH_TAIL_STAGED + 1;
+constexpr size_t FINISH_TAIL_SMEM = (size_t)4 * pit_detail::RR_BK * 64 * sizeof(float);
+struct FinishTail {
+    int n;
+    int wg_base[FINISH_TAIL_JOBS + 1];
+    pit_detail::TailPair p[FINISH_TAIL_JOBS];
+};
+static_assert(sizeof(FinishBatch) + 8 + sizeof(FinishTail) <= 4096, "posatt_dhead_finish_tail: kernel arguments beyond 4 KiB");
+static_assert(FINISH_TAIL_STAGED >= 7, "Burgers: 5 blocks + decoder + encoder");
+__global__ __launch_bounds__(512) void posatt_dhead_finish_tail(FinishBatch fb, int n_fin, FinishTail t) {
+    float* smem = pit_dyn_smem();
+    const int id = (int)blockIdx.x;
+    if (id < n_fin) {
+        if (threadIdx.x >= 256) return;                 // (ended waves do not take part in the drain's barriers)
+        finish_batch_body<256>(fb, reinterpret_cast<double*>(smem));
+        return;
+    }
+    int j = 0;
+    while (j + 1 < t.n && id >= t.wg_base[j + 1]) ++j;
+    tail_pair_body(t.p[j], id - t.wg_base[j], smem);
 }
 
 constexpr int KEY_CHUNK = 2048;   // keys staged in LDS per pass (float4 each = 32 KiB)
@@ -3563,39 +3598,171 @@ extern "C" int pit_debug_read_stamps(unsigned long long* host64) {
 }
 #endif
 
+
+namespace {
+// pit_posatt_dhead_finish_stage: the calling thread's staged jobs (copies) and how many of them its notes counted as carried;
+// consumed by the thread's next pit_posatt_dhead_finish.  pit_finish_last_tail: the record of the latest finish call
+thread_local std::vector<pit_mlp_params_job> t_finish_staged;
+thread_local int t_finish_carried = 0;
+std::atomic<int> finish_tail_rec[PIT_FINISH_TAIL_SLOTS];
+
+// a postponed job in the forms posatt_dhead_finish_tail runs: the fp32 math mode without storage flags, what plan_dw_pair takes
+// (accumulate != 0, at most 2^28 MACs) and a TailPair can say
+bool plan_finish_tail(const pit_mlp_params_job& j, int chunks_per_tile, pit_detail::TailPair* tp) {
+    if (j.math_mode != PIT_MATH_FP32) return false;
+    pit_detail::DwPair dw;
+    return pit_detail::plan_dw_pair(j, 8, &dw, 768, 2, chunks_per_tile) && pit_detail::pack_tail(dw, tp);
+}
+
+int run_job_own(const pit_mlp_params_job& j, void* stream, bool quiet) {
+    if (quiet) pit_rider_mute(1);                      // (a staged job: its staging call has noted it)
+    const int rc = pit_mlp_bwd_params(j.x, j.ldx, j.rows, j.n0, j.n1, j.n2, j.h, j.out_gelu, j.d_y, j.ld_dy, j.d_w1, j.d_b1, j.d_w2,
+                                      j.d_b2, j.accumulate, j.scratch, j.math_mode, stream);
+    if (quiet) pit_rider_mute(0);
+    return rc;
+}
+}  // namespace
+
+extern "C" int pit_posatt_dhead_finish_stage(const pit_mlp_params_job* const* jobs, int n) {
+    if (n < 0) return PIT_ERR_SIZE;
+    if (n > 0 && !jobs) return PIT_ERR_NULL;
+    for (int i = 0; i < n; ++i)
+        if (!jobs[i]) return PIT_ERR_NULL;
+    for (int i = 0; i < n; ++i) {
+        pit_detail::TailPair tp;
+        const bool carried = t_finish_carried < FINISH_TAIL_STAGED && plan_finish_tail(*jobs[i], 0, &tp);
+        if (carried) ++t_finish_carried;
+        t_finish_staged.push_back(*jobs[i]);
+        pit_rider_note(carried ? PIT_RIDER_DHEAD_FINISH : PIT_RIDER_OWN);
+    }
+    return 0;
+}
+
+extern "C" int pit_finish_last_tail(int* out, int n) {
+    for (int k = 0; out && k < n && k < PIT_FINISH_TAIL_SLOTS; ++k) out[k] = finish_tail_rec[k].load(std::memory_order_relaxed);
+    return PIT_FINISH_TAIL_SLOTS;
+}
+
 extern "C" int pit_posatt_dhead_finish(int n_layers, double* const* workspaces, float* const* d_heads,
                                        const float* const* heads, const float* const* scales, const int* n_heads,
                                        const int* flags, const pit_mlp_params_job* rider, void* stream) {
-    auto run_rider = [&]() -> int {
-        if (!rider) return 0;
-        return pit_mlp_bwd_params(rider->x, rider->ldx, rider->rows, rider->n0, rider->n1, rider->n2, rider->h, rider->out_gelu,
-                                  rider->d_y, rider->ld_dy, rider->d_w1, rider->d_b1, rider->d_w2, rider->d_b2, rider->accumulate,
-                                  rider->scratch, rider->math_mode, stream);
+    std::vector<pit_mlp_params_job> staged;
+    staged.swap(t_finish_staged);                       // consumed, whatever this call does with them
+    t_finish_carried = 0;
+    int rec[PIT_FINISH_TAIL_SLOTS] = {0, 0, 0, 0, 0, 0};
+    rec[PIT_FINISH_TAIL_STAGED] = (int)staged.size();
+    auto publish = [&]() {
+        for (int k = 0; k < PIT_FINISH_TAIL_SLOTS; ++k) finish_tail_rec[k].store(rec[k], std::memory_order_relaxed);
     };
-    if (n_layers <= 0) return run_rider();
-    if (n_layers > FINISH_MAX_LAYERS) return PIT_ERR_SIZE;
-    if (!workspaces || !d_heads || !heads || !scales || !n_heads || !flags) return PIT_ERR_NULL;
+    // the staged jobs `carried` does not mark, as launches of their own on the stream: no job is ever lost
+    auto run_staged = [&](const std::vector<char>* carried) -> int {
+        int rc = 0;
+        for (size_t i = 0; i < staged.size(); ++i) {
+            if (carried && (*carried)[i]) continue;
+            const int r = run_job_own(staged[i], stream, true);
+            if (r && !rc) rc = r;
+            ++rec[PIT_FINISH_TAIL_OWN];
+        }
+        publish();
+        return rc;
+    };
+    auto run_rider = [&]() -> int { return rider ? run_job_own(*rider, stream, false) : 0; };
+    if (n_layers <= 0) {
+        const int rc = run_rider();
+        const int rs = run_staged(nullptr);
+        return rc ? rc : rs;
+    }
     FinishBatch fb;
     fb.n = n_layers;
-    int total = 0;
-    for (int l = 0; l < n_layers; ++l) {
-        if (!workspaces[l] || !d_heads[l] || !heads[l]) return PIT_ERR_NULL;
-        if (n_heads[l] <= 0) return PIT_ERR_SIZE;
+    int total = 0, bad = 0;
+    if (n_layers > FINISH_MAX_LAYERS) bad = PIT_ERR_SIZE;
+    else if (!workspaces || !d_heads || !heads || !scales || !n_heads || !flags) bad = PIT_ERR_NULL;
+    for (int l = 0; !bad && l < n_layers; ++l) {
+        if (!workspaces[l] || !d_heads[l] || !heads[l]) { bad = PIT_ERR_NULL; break; }
+        if (n_heads[l] <= 0) { bad = PIT_ERR_SIZE; break; }
         fb.ws[l] = workspaces[l]; fb.d_head[l] = d_heads[l]; fb.head[l] = heads[l]; fb.scale[l] = scales[l];
         fb.n_head[l] = n_heads[l]; fb.flags[l] = flags[l];
         fb.wg_base[l] = total;
         total += n_heads[l];
     }
-    fb.wg_base[n_layers] = total;
-    pit_detail::DwPair dw;
-    if (rider && pit_detail::plan_dw_pair(*rider, 4, &dw)) {           // small enough to share the launch
-        hipLaunchKernelGGL(posatt_dhead_finish_dw, dim3((unsigned)(total + dw.n1 + dw.n2)), dim3(256), DW_SMEM_4WAVES,
-                           (hipStream_t)stream, fb, total, dw);
-        PIT_CHECK_LAUNCH();
-        pit_rider_note(PIT_RIDER_DHEAD_FINISH);
-        return 0;
+    if (bad) {
+        run_staged(nullptr);
+        return bad;
     }
-    hipLaunchKernelGGL(posatt_dhead_finish_batch, dim3(total), dim3(256), 0, (hipStream_t)stream, fb);
-    PIT_CHECK_LAUNCH();
-    return run_rider();
+    fb.wg_base[n_layers] = total;
+
+    // staged jobs in the tile forms, FINISH_TAIL_STAGED at the most (the staging call counted the same way)
+    FinishTail ft = FinishTail();
+    const pit_mlp_params_job* src[FINISH_TAIL_JOBS];
+    int cpt[FINISH_TAIL_JOBS];
+    std::vector<char> carried(staged.size(), 0);
+    int nt = 0;
+    for (size_t i = 0; i < staged.size() && nt < FINISH_TAIL_STAGED; ++i)
+        if (plan_finish_tail(staged[i], 0, &ft.p[nt])) { src[nt] = &staged[i]; cpt[nt] = 2; carried[i] = 1; ++nt; }
+    if (nt == 0) {                                      // nothing to carry beside the rider: the launches this call has always made
+        pit_detail::DwPair dw;
+        int rc = 0;
+        if (rider && pit_detail::plan_dw_pair(*rider, 4, &dw)) {           // small enough to share the launch
+            hipLaunchKernelGGL(posatt_dhead_finish_dw, dim3((unsigned)(total + dw.n1 + dw.n2)), dim3(256), DW_SMEM_4WAVES,
+                               (hipStream_t)stream, fb, total, dw);
+            rc = (int)hipGetLastError();
+            if (!rc) pit_rider_note(PIT_RIDER_DHEAD_FINISH);
+        } else {
+            hipLaunchKernelGGL(posatt_dhead_finish_batch, dim3(total), dim3(256), 0, (hipStream_t)stream, fb);
+            rc = (int)hipGetLastError();
+            if (!rc) rc = run_rider();
+        }
+        const int rs = run_staged(nullptr);
+        return rc ? rc : rs;
+    }
+    const int n_staged_in = nt;
+    bool rider_in = false;
+    if (rider && plan_finish_tail(*rider, 0, &ft.p[nt])) { src[nt] = rider; cpt[nt] = 2; rider_in = true; ++nt; }
+    // every workgroup of the launch resident at once - two 64 KiB workgroups per compute unit: beyond that, the job with the most
+    // tiles reduces one more chunk of rows per tile, until the launch fits or that job is one slab
+    static const int n_cus = [] {                       // (one device per process: read once)
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
+        return cus;
+    }();
+    const int budget = 2 * (n_cus > 0 ? n_cus : 256);
+    auto tail_wgs = [&]() { int s = 0; for (int k = 0; k < nt; ++k) s += ft.p[k].n1 + ft.p[k].n2; return s; };
+    for (int trip = 0; trip < 64 && total + tail_wgs() > budget; ++trip) {
+        int big = -1, most = 0;
+        for (int k = 0; k < nt; ++k) {
+            const pit_detail::TailPair& p = ft.p[k];
+            const int tw = (p.rr1 == 1 ? p.n1 : 0) + (p.rr2 == 1 ? p.n2 : 0);
+            if (tw > most && cpt[k] < p.nchunks) { big = k; most = tw; }
+        }
+        if (big < 0) break;
+        pit_detail::TailPair tp;
+        if (!plan_finish_tail(*src[big], cpt[big] + 1, &tp)) break;
+        ++cpt[big];
+        ft.p[big] = tp;
+    }
+    ft.n = nt;
+    int base = total;
+    for (int k = 0; k < nt; ++k) { ft.wg_base[k] = base; base += ft.p[k].n1 + ft.p[k].n2; }
+    for (int k = nt; k <= FINISH_TAIL_JOBS; ++k) ft.wg_base[k] = base;
+    static bool once = ((void)hipFuncSetAttribute((const void*)posatt_dhead_finish_tail, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                  (int)FINISH_TAIL_SMEM), true);
+    (void)once;
+    hipLaunchKernelGGL(posatt_dhead_finish_tail, dim3((unsigned)base), dim3(512), FINISH_TAIL_SMEM, (hipStream_t)stream, fb, total, ft);
+    int rc = (int)hipGetLastError();
+    if (rc) {                                           // nothing was launched: everything on its own
+        std::fill(carried.begin(), carried.end(), 0);
+        const int rs = run_staged(nullptr);
+        (void)rs;
+        return rc;
+    }
+    rec[PIT_FINISH_TAIL_CARRIED] = n_staged_in;
+    for (int k = 0; k < n_staged_in; ++k) {
+        const pit_detail::TailPair& p = ft.p[k];
+        rec[p.rr1 == 2 ? PIT_FINISH_TAIL_THIN : (p.rr1 ? PIT_FINISH_TAIL_TILE : PIT_FINISH_TAIL_RD)] += p.n1;
+        rec[p.rr2 ? PIT_FINISH_TAIL_TILE : PIT_FINISH_TAIL_RD] += p.n2;
+    }
+    if (rider_in) pit_rider_note(PIT_RIDER_DHEAD_FINISH);
+    else rc = run_rider();
+    const int rs = run_staged(&carried);
+    return rc ? rc : rs;
 }

@@ -145,14 +145,20 @@ def _flush_head_finishes(task: int) -> None:
             if job is not None and job[2].device.index == dev and job[2] == torch.cuda.current_stream(job[2].device):
                 rider, job = job, None
                 _PENDING_DW[task] = None
+            # the jobs the last block launches of a fused processor gave up (_PENDING_TAIL), when they sit on this device and stream
+            tail = _tail_take(task, dev)
             with torch.cuda.device(dev):
-                _launch_head_finishes(part, rider)
+                _launch_head_finishes(part, rider, tail)
 
 
-def _launch_head_finishes(entries, rider=None) -> None:
+def _launch_head_finishes(entries, rider=None, tail=()) -> None:
     """ONE pit_posatt_dhead_finish launch on the current device and stream: d(lmda) of every layer in ``entries`` =
     [(work, d_head, head, scale, n_head, flags), ...] from its accumulators ``work`` (flags: PIT_HEAD_ACCUMULATE = add into d_head in
-    place, PIT_HEAD_IS_SCALE = the head is the scale itself), with the postponed weight-gradient job ``rider`` (_PENDING_DW's form) riding along."""
+    place, PIT_HEAD_IS_SCALE = the head is the scale itself), with the postponed weight-gradient job ``rider`` (_PENDING_DW's form)
+    riding along and the jobs ``tail`` (_PENDING_TAIL's form) staged for it (pit_posatt_dhead_finish_stage copies the structs)."""
+    if tail:
+        jobs = (ctypes.c_void_p * len(tail))(*[ctypes.addressof(t[0]) for t in tail])
+        _lib.check(_lib.lib().pit_posatt_dhead_finish_stage(jobs, len(tail)), "pit_posatt_dhead_finish_stage")
     n = len(entries)
     ws, dh, hd, sc = ((ctypes.c_void_p * n)(*[_lib.ptr(e[i]) for e in entries]) for i in range(4))
     nh = (ctypes.c_int * n)(*[e[4] for e in entries])
@@ -361,6 +367,83 @@ def _dw_run_pending(device) -> None:
     job = _dw_take(device)
     if job is not None:
         _dw_run(job)
+
+
+# Round 10: the last launches of a fused processor's backward carry no rider (RIDER_TAIL_BLOCKS below); their jobs wait here for the
+# pass's finishing launch, which has the compute units and pays the latency of a rider tile anyway.  A table of its own: the
+# single slot of _PENDING_DW is flushed by whoever defers next (the encoder) and must be empty when the pass ends.
+_PENDING_TAIL = {}        # graph-task id -> [(MlpParamsJob, keep-alive tensors, stream it was prepared on), ...]
+
+
+def _at_end_of_pass(fn) -> None:
+    """Queue ``fn`` behind the running backward pass (autograd runs the callbacks in the order they were queued)."""
+    torch.autograd.Variable._execution_engine.queue_callback(fn)
+
+
+def _tail_defer(jobs) -> None:
+    """Hand ``jobs`` (_PENDING_DW's form) to the end of the running pass: the finishing launch stages them (_flush_head_finishes),
+    else the end-of-pass callback queued here performs them - whichever runs first takes them out of the table."""
+    task = _graph_task()
+    if task not in _PENDING_TAIL:
+        while len(_PENDING_TAIL) >= _MAX_PENDING_TASKS:       # entries of passes that died long ago (their gradients are void)
+            del _PENDING_TAIL[next(iter(_PENDING_TAIL))]
+        _PENDING_TAIL[task] = []
+        _at_end_of_pass(lambda: _tail_end_of_pass(task))
+    _PENDING_TAIL[task].extend(jobs)
+
+
+def _tail_take(task: int, dev: int) -> list:
+    """The pass's tail jobs prepared on device ``dev``'s current stream, removed from the table (the others stay for the callback)."""
+    jobs = _PENDING_TAIL.get(task)
+    if not jobs:
+        return []
+    take = [j for j in jobs if j[2].device.index == dev and j[2] == torch.cuda.current_stream(j[2].device)]
+    _PENDING_TAIL[task] = [j for j in jobs if not any(j is t for t in take)]
+    return take
+
+
+def _tail_end_of_pass(task: int) -> None:
+    """A pass that ended without a finishing launch on the jobs' device and stream: each on its own, where it was prepared."""
+    for job in _PENDING_TAIL.pop(task, ()):
+        _dw_run(job)
+
+
+# PIT_RIDER_TAIL_BLOCKS = k: the last k pit_block_bwd launches of a fused processor (blocks k-1 .. 0) carry no rider - their own
+# MLP's job and their slice of the decoder MLP's go to the finishing launch.  Read once; tests set the attribute.
+RIDER_TAIL_BLOCKS = int(os.environ.get("PIT_RIDER_TAIL_BLOCKS", "1"))
+
+
+def rider_tail_schedule(n_blocks: int, k: int, complete_by=None, reproducible: bool = False, inplace: bool = True,
+                        heads_deferred: bool = True, has_slices: bool = True, chain_fits: bool = True):
+    """Which launch of a fused processor's backward carries which weight-gradient job - a pure function.
+    ``k`` = RIDER_TAIL_BLOCKS, clamped to [0, n_blocks] and forced to 0 where the jobs cannot wait for the end of the pass: a
+    two-bucket step (``complete_by`` = the block by whose launch the decoder MLP's slices must be enqueued: _Processor's hook),
+    the reproducible mode, gradients returned to autograd instead of accumulated in place, and a pass whose d(lmda) is not
+    deferred (no finishing launch will come).  ``chain_fits`` = the launch's chain and d(scale) workgroups number at most the
+    compute units: the one regime the switch was measured in (Darcy b=8) - beyond it k is 0 as well.  Returns (k, n_slices, plan): the postponed decoder job is cut into ``n_slices``
+    row slices (0 without one), and plan[j] = (own, slice) for the j-th launch (block n_blocks - 1 - j): where the block's own job
+    and slice j go - "launch" (this launch's rider / rider2), "tail" (the finishing launch) or None (no slice j)."""
+    n = int(n_blocks)
+    k = max(0, min(int(k), n))
+    if complete_by is not None or reproducible or not inplace or not heads_deferred or not chain_fits:
+        k = 0
+    n_slices = 0 if not has_slices else (n if complete_by is None else max(1, n - int(complete_by)))
+    plan = []
+    for j in range(n):
+        where = "tail" if j >= n - k else "launch"
+        plan.append((where, where if j < n_slices else None))
+    return k, n_slices, plan
+
+
+_CU_COUNT = {}
+
+
+def _cu_count(device) -> int:
+    idx = torch.device(device).index
+    idx = torch.cuda.current_device() if idx is None else idx
+    if idx not in _CU_COUNT:
+        _CU_COUNT[idx] = int(torch.cuda.get_device_properties(idx).multi_processor_count)
+    return _CU_COUNT[idx]
 
 
 BIG_RIDER_ROWS = 8192
@@ -2473,6 +2556,7 @@ class _Processor(torch.autograd.Function):
         ctx.n, ctx.H, ctx.dims, ctx.plan = n, H, (b, L, D), plan
         ctx.params = params                    # (lmda parameters, (w1, b1, w2, b2) parameters) for the in-place gradient slots
         ctx.hook = _processor_hook()           # the caller's per-thread step state
+        ctx.repro = get_reproducible()         # (read on the calling thread: the backward runs on autograd's)
         ctx.keep = (bufs, wts, heads, E, Q, inv, scale, z1, hh, z2)
         return out
 
@@ -2497,14 +2581,22 @@ class _Processor(torch.autograd.Function):
         # a large job the pass has postponed (the decoder MLP's weight gradients): one row slice per block launch
         extra = _dw_take(dev)
         slices = []
+        sliceable = False
         if extra is not None:
             st = extra[0]
-            if not st.out_gelu and st.accumulate and (st.math_mode & 0xff) == 0:
+            sliceable = bool(not st.out_gelu and st.accumulate and (st.math_mode & 0xff) == 0)
+        # which launch carries what (rider_tail_schedule): the last k launches give their jobs to the pass's finishing launch
+        k_tail, n_slices, plan = rider_tail_schedule(n, RIDER_TAIL_BLOCKS, None if ctx.hook is None else ctx.hook[1], ctx.repro,
+                                                     all(inplace for _, inplace in w_grads), all(h.defer for h in hgs), sliceable,
+                                                     2 * 8 * ((b + 7) // 8) * (L // 16) <= _cu_count(dev))
+        if extra is not None:
+            if sliceable:
                 # a two-bucket step reduces the postponed job's gradients right after block `complete_by`: every
                 # slice must ride in a launch up to that one
-                slices = _dw_slices(extra, n if ctx.hook is None else max(1, n - ctx.hook[1]))
+                slices = _dw_slices(extra, n_slices)
             else:
                 _dw_run(extra)
+        stream = torch.cuda.current_stream(dev)
         # top of the chain: the last block's MLP backward (data path) from d_out
         w1, _, w2, _ = wts[n - 1]
         rc = L_.pit_mlp_bwd_data(rows, W, D, D, w1.data_ptr(), w2.data_ptr(), z1[n - 1].data_ptr(), z2[n - 1].data_ptr(), 1,
@@ -2520,12 +2612,17 @@ class _Processor(torch.autograd.Function):
             else:
                 prev = (None, None, None, None, 0, 0, None, 0, None, dx.data_ptr(), D)
             k = n - 1 - i                              # launch order
-            job2 = ctypes.cast(ctypes.pointer(slices[k]), ctypes.c_void_p) if k < len(slices) else None
+            own_to, slice_to = plan[k]
+            job1 = ctypes.cast(ctypes.pointer(job), ctypes.c_void_p) if own_to == "launch" else None
+            job2 = ctypes.cast(ctypes.pointer(slices[k]), ctypes.c_void_p) if k < len(slices) and slice_to == "launch" else None
             rc = L_.pit_block_bwd(E[i].data_ptr(), inv[i].data_ptr(), Q[i].data_ptr(), L, H, D, b, dxc[i].data_ptr(),
-                                  bufs[i].data_ptr(), hgs[i].work.data_ptr(), *prev,
-                                  ctypes.cast(ctypes.pointer(job), ctypes.c_void_p), job2, ctx.math,
+                                  bufs[i].data_ptr(), hgs[i].work.data_ptr(), *prev, job1, job2, ctx.math,
                                   _lib.stream_ptr())
             _lib.check(rc, "pit_block_bwd")
+            if own_to == "tail":                       # (after the launch: its chain wrote the dZ1 | dZ2 the job reads)
+                _tail_defer([(job, (bufs[i], hh[i], scratch[i]) + tuple(w_grads[i][0]), stream)])
+            if k < len(slices) and slice_to == "tail":
+                _tail_defer([(slices[k], extra[1], stream)])
             if ctx.hook is not None:
                 ctx.hook[0](i)                              # (block i's weight gradients are now enqueued)
         # d(lmda): deferred layers are finished by the pass's one finishing launch; the others here, in one launch
