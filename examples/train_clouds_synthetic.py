@@ -3,11 +3,13 @@
 latent mesh shared by the batch) on synthetic ragged batches (tasks.ragged_clouds), engine.TrainStep with lengths and the fused
 Adam (ddp.FlatAdam(zero_grads=True)).
 
-    python examples/train_clouds_synthetic.py [--epochs 2] [--width 972] [--latent shared|fps:M] [--feed] [--points M]
+    python examples/train_clouds_synthetic.py [--epochs 2] [--width 972] [--latent shared|fps:M|geo:M] [--feed] [--points M]
                                               [--clip NORM] [--ema DECAY] [--save PATH] [--resume PATH]
 
 `--latent fps:M`: tasks.pit_cloud_fps instead - every cloud gets a latent mesh of its own, M of its points chosen by
 farthest-point sampling (ops.farthest_point_sample: one launch inside the captured step, on the clouds the step was fed).
+`--latent geo:M`: metric.pit_cloud_geodesic - M sampled latent points again, and all three attention stages on GEODESIC
+neighbour lists (path lengths on each cloud's 8-nearest-neighbour graph, searched inside the captured step: ops.geo_knn).
 
 The step is captured once for the padded width; every batch then brings its own point counts through
 ``set_batch(..., len_in=...)`` - the lengths live in a static device tensor the kernels read, so no replay waits for the
@@ -75,8 +77,9 @@ def main():
     ap.add_argument("--batch", type=int, default=10)
     ap.add_argument("--width", type=int, default=972)
     ap.add_argument("--hid", type=int, default=64)
-    ap.add_argument("--latent", default="shared", metavar="shared|fps:M",
-                    help="the latent mesh: one 16 x 16 grid shared by the batch, or M points of each cloud by farthest-point sampling")
+    ap.add_argument("--latent", default="shared", metavar="shared|fps:M|geo:M",
+                    help="the latent mesh: one 16 x 16 grid shared by the batch, or M points of each cloud by farthest-point sampling "
+                         "(geo: with geodesic neighbour lists in every attention stage)")
     ap.add_argument("--feed", action="store_true", help="device-resident data feed inside the captured steps")
     ap.add_argument("--points", type=int, default=None, metavar="M",
                     help="train on a random subset of M points of each cloud, drawn inside the captured step (implies --feed)")
@@ -96,8 +99,11 @@ def main():
         model = tasks.pit_cloud_latent(2, 1, 1, args.hid, 2, 4, mesh_ltt, 0.02, 0.02).cuda()
     elif args.latent.startswith("fps:") and args.latent[4:].isdigit() and 1 <= int(args.latent[4:]) <= args.width:
         model = tasks.pit_cloud_fps(2, 1, 1, args.hid, 2, 4, int(args.latent[4:]), 0.02, 0.02).cuda()
+    elif args.latent.startswith("geo:") and args.latent[4:].isdigit() and 1 <= int(args.latent[4:]) <= args.width // 2:
+        from position_induced_transformer_amd import metric
+        model = metric.pit_cloud_geodesic(2, 1, 1, args.hid, 2, 4, int(args.latent[4:]), 0.02, 0.02).cuda()
     else:
-        ap.error(f"--latent {args.latent}: 'shared' or 'fps:M' with 1 <= M <= --width")
+        ap.error(f"--latent {args.latent}: 'shared', 'fps:M' with 1 <= M <= --width or 'geo:M' with 1 <= M <= --width / 2")
     print("parameters:", count_params(model))
     iterations = args.epochs * args.nbatches
     flat = FlatGradients(model.parameters(), flatten_params=True)

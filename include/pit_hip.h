@@ -1361,6 +1361,48 @@ int pit_knn_box_ragged(const float* mesh_out, const float* mesh_in, int batch, i
                        long in_stride, const float* periods, int k, const int* len_out, const int* len_in, int* idx, float* dist,
                        float* next, void* stream);
 
+/* ---- The k nearest keys of every row under the path length of a graph (an addition to ABI 31; csrc/pit_geo.hip) ----------------------
+ * The candidate lists of the any-metric layers where the metric is a geodesic: a truncated single-source shortest-path search per
+ * row, in the list layers' own format (pit_knn_box_ragged's: key -1 / distance 0 in the slots a row does not fill).  A library
+ * built from this header defines PIT_HAS_GEO; PIT_ABI_VERSION is unchanged (nothing that existed changed).
+ *
+ * The graph of sample s on n_vert vertices, padded adjacency: edge t of vertex u leads to adj[s][u][t] and has the length
+ * w[s][u][t] (fp32, finite and >= 0: not checked - nothing is addressed out of bounds whatever adj and w hold); it is valid iff
+ * 0 <= adj[s][u][t] < Vs, Vs = len_v[s] clamped into [1, n_vert] (len_v NULL: n_vert).  Directed; self edges and duplicate edges
+ * are harmless.  adj_bstride: ELEMENTS between two samples' (n_vert, n_edge) arrays, of adj and w alike; 0 = one graph shared by
+ * the batch, otherwise >= n_vert * n_edge.  Adjacency rows of vertices >= Vs are never read.
+ * The path length D from a row's source is the least fixpoint of D(src) = 0, D(v) = min(D(v), fl32(D(u) + w(u, v))): one rounded
+ * fp32 add per edge, which label-setting search reaches exactly (fp32 addition is monotone).
+ * Row i of sample s starts at sources[s * src_bstride + i] (src_bstride 0 = one array for every sample, otherwise >= n_rows;
+ * sources NULL: vertex i, which needs n_rows == n_vert and src_bstride 0); a source outside [0, Vs) is a padded row.  key_of (NULL:
+ * the identity; key_bstride like src_bstride, >= n_vert) maps a vertex to its key index, < 0 = the vertex is no key.  The row's
+ * candidates are the pairs (D(v), v) of the reachable key vertices; its list is the k smallest ascending by (D, v) - the lowest
+ * VERTEX index among equal lengths:
+ *   idx[s][i][t] = key_of[v_t],  dist[s][i][t] = D(v_t) (the length, not its square);  unfilled slots (fewer than k reachable
+ *   keys, a truncated row, a padded row): -1 / 0;
+ *   next[s][i]   = the smaller of candidate k's length (the (k+1)-th) where the search settled one and the least tentative length
+ *                  of the frontier when the row was complete; +inf when neither exists.  Exact when every vertex is a key, a lower
+ *                  bound otherwise.  A padded row and a truncated row: +inf;
+ *   status[s][i] = 0 complete (or padded), 1 truncated.
+ * A row is complete when its frontier is empty, or k candidates are settled and the frontier's least tentative length is strictly
+ * greater than the k-th candidate's (a vertex discovered at a settled length may have the lower index).  `reach` bounds the
+ * discovered vertices (settled or in the frontier) of a row: when relaxing a settled vertex's edges would make them more than
+ * `reach`, the row stops as truncated and lists the key vertices settled so far (that vertex included) - a settled length is
+ * final, so what a truncated row lists is exact.  No row takes more than `reach` steps.
+ * Outputs contiguous: idx (batch, n_rows, k) int32, dist (batch, n_rows, k) fp32, next (batch, n_rows) fp32, status (batch, n_rows)
+ * int32.  One launch, a wavefront per row, the row's state in LDS (8 bytes per discovered vertex and a 16-bit hash slot for two);
+ * no workspace, no global atomics (the same input gives the same bits), no host synchronisation, capturable.
+ * 1 <= k <= PIT_GEO_MAX_K, k <= reach <= PIT_GEO_MAX_REACH, n_vert * n_edge < 2^31, batch * n_rows * k < 2^31.  Refusals, all before
+ * any launch and in this order: PIT_ERR_NULL for a missing adj, w, idx, dist, next or status; PIT_ERR_SIZE for batch, n_vert,
+ * n_edge, n_rows or k < 1, reach < k, n_vert * n_edge >= 2^31, a stride the conventions above refuse, sources NULL with n_rows != n_vert, batch * n_rows * k >= 2^31;
+ * PIT_ERR_UNSUPPORTED for k > PIT_GEO_MAX_K or reach > PIT_GEO_MAX_REACH. */
+#define PIT_HAS_GEO 1
+#define PIT_GEO_MAX_K 1024
+#define PIT_GEO_MAX_REACH 4096
+int pit_geo_knn(const int* adj, const float* w, long adj_bstride, int batch, int n_vert, int n_edge, const int* sources,
+                long src_bstride, int n_rows, const int* key_of, long key_bstride, const int* len_v, int k, int reach, int* idx,
+                float* dist, float* next, int* status, void* stream);
+
 /* ---- The two slab forms of pit_block_fwd (additions to ABI 31; csrc/pit_block.hip) ------------------------------------------------
  * pit_block_fwd runs 16-row slabs, or - n_head = 2, n_pts = 256, the weights through LDS, and 8 * ceil(batch / 8) * n_pts / 8
  * workgroups no more than the device has CUs (batch <= 8 on MI355X) - 8-row slabs with the two heads stacked in the M dimension of

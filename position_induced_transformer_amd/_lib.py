@@ -188,7 +188,8 @@ ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_
                "pit_fps_large_workspace", "pit_fps_large",                         # PIT_HAS_FPS_LARGE
                "pit_knn_box", "pit_knn_rows", "pit_knn_last_form",                 # PIT_HAS_KNN
                "pit_distlist_select_ragged_fwd", "pit_distlist_ragged_fwd", "pit_distlist_ragged_bwd",      # PIT_HAS_DISTLIST_RAGGED
-               "pit_knn_box_ragged"}                                               # PIT_HAS_KNN_RAGGED
+               "pit_knn_box_ragged",                                               # PIT_HAS_KNN_RAGGED
+               "pit_geo_knn"}                                                      # PIT_HAS_GEO
 ABI_VERSION = DEFINES["PIT_ABI_VERSION"]      # of the header this checkout carries; lib() holds the loaded library to it
 FPS_MAX_POINTS = DEFINES["PIT_FPS_MAX_POINTS"]
 FPS_MAX_POINTS_WIDE = DEFINES["PIT_FPS_MAX_POINTS_WIDE"]          # (space_dim 4..8)
@@ -196,6 +197,8 @@ FPS_LARGE_MAX_POINTS = DEFINES["PIT_FPS_LARGE_MAX_POINTS"]        # (every space
 FPS_LARGE_MAX_SAMPLES = DEFINES["PIT_FPS_LARGE_MAX_SAMPLES"]
 KNN_MAX_K = DEFINES["PIT_KNN_MAX_K"]
 KNN_REG_MAX_KEYS = DEFINES["PIT_KNN_REG_MAX_KEYS"]
+GEO_MAX_K = DEFINES["PIT_GEO_MAX_K"]
+GEO_MAX_REACH = DEFINES["PIT_GEO_MAX_REACH"]
 GUARD_MAX_PARTS = DEFINES["PIT_GUARD_MAX_PARTS"]
 GUARD_STATE_DOUBLES = DEFINES["PIT_GUARD_STATE_DOUBLES"]
 FEED_MAX_FIELDS = DEFINES["PIT_FEED_MAX_FIELDS"]

@@ -42,6 +42,11 @@ of sizes.  Sample s comes out as the list layer computes that cloud alone; padde
 receive zero gradients, and the padding may hold anything, NaN included.  Dense matrices (``forward_dist``), ``builder="torch"``,
 metrics that are no box metric, per-sample latent meshes in ``pit_metric`` and the bf16 math mode do not take lengths.
 
+GEODESIC LISTS - the metric is a path length on a graph (a surface's edges, or ``knn_graph`` of the cloud) - are built on the
+device by ``knn_lists_geodesic(adj, w, k, ...)``: one launch of a truncated shortest-path search per row (ops.geo_knn), per-sample
+graphs and lengths included, so the search stays inside a captured step.  ``pit_cloud_geodesic`` runs all three attention stages
+on such lists.  The lists are constants: path lengths carry no gradient to the mesh or the edge weights.
+
 Not part of ``pit.py``, whose star-exports are the reference's.
 """
 from __future__ import annotations
@@ -55,7 +60,7 @@ from . import ops
 from . import pit as _pit
 
 __all__ = ["sqdist_euclid", "sqdist_periodic_box", "posatt_metric", "posatt_cross_metric", "pit_metric", "list_capacity",
-           "NeighborLists", "knn_lists", "knn_lists_box"]
+           "NeighborLists", "knn_lists", "knn_lists_box", "knn_graph", "GeodesicLists", "knn_lists_geodesic", "pit_cloud_geodesic"]
 
 
 def sqdist_euclid(mesh_out: torch.Tensor, mesh_in: torch.Tensor) -> torch.Tensor:
@@ -254,6 +259,97 @@ def knn_lists(sqdist, mesh_out, mesh_in, k=None, chunk: int = 4096, locality: fl
         if cut is None:
             cut = torch.zeros((), dtype=torch.int64, device=idx.device)
     return NeighborLists(idx, _listed_sqdist(sqdist, mesh_out, mesh_in, idx), cut)
+
+
+def knn_graph(mesh, g: int, periods=None, lengths=None):
+    """The directed ``g``-nearest-neighbour graph of a cloud as padded adjacency for ``knn_lists_geodesic`` / ops.geo_knn:
+    ``adj`` (.., n, g + 1) int32 and ``w`` (.., n, g + 1) fp32 from ONE ops.knn_box(mesh, mesh, g + 1, ...), ``w = sqrt(dist)``
+    - edge lengths, not their squares.  The self slot (length 0) is kept: a self edge is harmless to the search.  The graph is
+    NOT symmetrised: u may list v without v listing u.  ``lengths``: a ragged batch of (b, n, s) clouds - padded points get no
+    edges (key -1) and no vertex lists one.  A constant: nothing differentiates through it.  No synchronisation, capturable."""
+    if isinstance(g, bool) or not isinstance(g, int) or g < 1:
+        raise ValueError(f"g must be a positive integer, got {g!r}")
+    with torch.no_grad():
+        got = ops.knn_box(mesh, mesh, g + 1, periods, len_out=lengths, len_in=lengths)
+        return got.idx, torch.sqrt(got.dist)
+
+
+GeodesicLists = namedtuple("GeodesicLists", ["idx", "sqd", "cut_rows", "truncated_rows", "short_rows"])
+
+
+def _cut_rows_geo(got, k: int, n_vert: int, locality: float, sources, key_of, len_v):
+    """``_cut_rows_ragged`` where the rows and keys of a sample are not prefixes but what the search saw: real rows are those
+    whose source is a vertex of the sample, a sample's key count is counted from ``key_of`` below its length.  No
+    synchronisation."""
+    b, n_rows = got.next.shape
+    dev = got.next.device
+    vs = len_v.long().clamp(1, n_vert).view(b, 1)
+    below = torch.arange(n_vert, device=dev).view(1, n_vert) < vs
+    li = vs.view(b) if key_of is None else ((key_of.reshape(-1, n_vert) >= 0) & below).sum(-1).expand(b)
+    src = torch.arange(n_vert, device=dev).view(1, n_vert) if sources is None else sources.reshape(-1, n_rows)
+    real = ((src >= 0) & (src < vs)).expand(b, n_rows) & (li > k).view(b, 1)
+    if float(locality) >= 1.0:
+        return real.sum()
+    rank = torch.floor(torch.mul((li - 1).clamp(min=0).to(torch.float32), float(locality))).long()
+    at = (rank + 1).clamp(max=k - 1).view(b, 1, 1).expand(b, n_rows, 1)
+    return ((got.next <= got.dist.gather(-1, at).squeeze(-1)) & real).sum()
+
+
+def knn_lists_geodesic(adj, w, k=None, locality: float = 1.0, sources=None, key_of=None, n_keys=None, len_v=None,
+                       reach=None) -> GeodesicLists:
+    """Candidate lists under the PATH LENGTH of a graph, from ONE launch of ops.geo_knn (a truncated shortest-path search per
+    row; its arguments are that op's): ``idx`` (int64) lists a row's nearest reachable keys ascending by (length, vertex index),
+    -1 (padding to the list layers) in the slots it does not fill; ``sqd = dist * dist`` (fp32) is the squared path length the
+    layers take.  The lists are CONSTANTS: path lengths carry no gradient to edge weights or mesh coordinates - weights that
+    require grad under grad mode raise NotImplementedError.
+      n_keys     the number of keys J the lists index: needed with ``key_of`` (which must map onto [0, J), no key twice), V
+                 without it.  ``k`` None: default_neighbors(locality, J).
+      cut_rows   knn_lists's count from the search's own (dist, next).  ``next`` is exact when every vertex is a key and a lower
+                 bound otherwise, so with ``key_of`` the count is an upper bound.  Truncated rows are not in it.
+      truncated_rows   0-d device tensor: rows that met the ``reach`` budget.  They list fewer keys than asked - exactly, but
+                 a layer then sees a shorter neighbourhood: raise ``reach`` (at most 4096) until this is 0.
+      short_rows 0-d device tensor: real, complete rows with fewer than ``k`` keys - fewer keys are reachable (another component
+                 of the graph, a short sample).  A MASKED layer (locality < 1) needs k' + 2 valid slots per row, k' its rank
+                 (ListPlan's precondition, the caller's to keep): with short_rows > 0 that holds only if the short rows still
+                 reach that many keys; an unmasked layer attends over what is listed.
+    Every refusal is a ValueError raised before a launch.  No synchronisation, capturable."""
+    if torch.is_tensor(w) and w.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("edge weights that require grad: the geodesic lists are constants - path lengths carry no "
+                                  "gradient (detach the weights)")
+    if not torch.is_tensor(adj) or adj.dim() not in (2, 3) or 0 in adj.shape:
+        raise ValueError("adj must be a non-empty (V, G) or (b, V, G) tensor")
+    n_vert = int(adj.shape[-2])
+    if key_of is None:
+        if n_keys is not None and int(n_keys) != n_vert:
+            raise ValueError(f"n_keys = {n_keys} without key_of: every one of the {n_vert} vertices is a key")
+        n_keys = n_vert
+    elif n_keys is None or isinstance(n_keys, bool) or int(n_keys) < 1 or int(n_keys) > n_vert:
+        raise ValueError(f"key_of needs n_keys, the number of keys it maps onto, in [1, {n_vert}]; got {n_keys!r}")
+    n_keys = int(n_keys)
+    k = _check_neighbors(k, locality, n_keys)
+    if k > ops.GEO_MAX_K:
+        raise ValueError(f"k = {k}: at most {ops.GEO_MAX_K} neighbours are supported by the geodesic builder")
+    batch = ops.check_geo_shapes(adj, w, k, sources, key_of, len_v, reach)[0]
+    with torch.no_grad():
+        if len_v is not None:
+            len_v = ops.as_lengths(len_v, adj.device, batch)
+        got = ops.geo_knn(adj, w, k, sources, key_of, len_v, reach)
+        if len_v is None:
+            cut = _cut_rows(got.dist, got.next, k, n_keys, locality)
+        else:
+            cut = _cut_rows_geo(got, k, n_vert, locality, sources, key_of, len_v)
+        truncated = (got.status == 1).sum()
+        short = ((got.status == 0) & (got.idx[..., k - 1] < 0) & _geo_real_rows(got, sources, len_v, n_vert)).sum()
+        idx = got.idx.long()
+        sqd = got.dist * got.dist
+    return GeodesicLists(idx, sqd, cut, truncated, short)
+
+
+def _geo_real_rows(got, sources, len_v, n_vert: int):
+    """Mask of the rows whose source is a vertex of its sample, in the shape of ``got.next``."""
+    src = torch.arange(n_vert, device=got.next.device) if sources is None else sources
+    hi = n_vert if len_v is None else len_v.long().clamp(1, n_vert).view(-1, 1)
+    return ((src >= 0) & (src < hi)).expand(got.next.shape)
 
 
 class posatt_metric(nn.Module):
@@ -482,3 +578,84 @@ class pit_metric(_pit.pit):
         func = self.encoder(mesh_in, func, mesh_ltt, len_in=len_in)
         func = self.processor(func, mesh_ltt)
         return self.decoder(mesh_ltt, func, mesh_out, len_out=len_out)
+
+
+class pit_cloud_geodesic(_pit.pit):
+    """Per-sample clouds whose three attention stages all run on GEODESIC neighbourhoods: path lengths on a graph over the
+    cloud's points (a surface's edges given by the caller, or the cloud's own ``graph_neighbors``-nearest-neighbour graph), so
+    the two sides of a thin wall or the two arms of a C-shaped plate are far apart although they are close in space.  Glue over
+    ``knn_lists_geodesic`` and the list layers; no kernels of its own.
+      latent     ``n_latent`` points of every cloud by ops.farthest_point_sample (``start``): vertices of the graph
+      down       sources = the latent points, keys = all vertices, locality ``en_loc``
+      processor  every block is ``posatt_metric(..., 1.0).forward_list`` on ONE set of latent-to-latent lists of width
+                 min(n_latent, proc_neighbors): attention over geodesic NEIGHBOURHOODS.  This is a different function from the
+                 dense processor of ``pit`` / ``pit_metric``, which attends over every latent point.
+      up         sources = all vertices, keys = the latent points, locality ``de_loc``
+    ``func_in`` is fed to the encoder as it is (``in_dim`` channels, coordinates included if wanted).  ``reach``: the search
+    budget of all three builds (None: ops.geo_default_reach of each width).  ``last_lists``: the three GeodesicLists (down,
+    processor, up) of the latest forward - read ``truncated_rows`` / ``short_rows`` there.  Preconditions (ListPlan's, the
+    caller's): the cloud holds at least ``n_latent`` distinct points, and every real row of a masked layer reaches its rank + 2
+    keys.  fp32 math mode only; path lengths carry no mesh gradient."""
+
+    def __init__(self, space_dim, in_dim, out_dim, hid_dim, n_head, n_blocks, n_latent, en_loc, de_loc, graph_neighbors: int = 8,
+                 proc_neighbors: int = 64, reach=None, start=0):
+        super().__init__(space_dim, in_dim, out_dim, hid_dim, n_head, n_blocks, None, en_loc, de_loc)
+        for name, v in (("n_latent", n_latent), ("graph_neighbors", graph_neighbors), ("proc_neighbors", proc_neighbors)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"{name} must be a positive integer, got {v!r}")
+        if reach is not None and (isinstance(reach, bool) or not isinstance(reach, int) or not 1 <= reach <= ops.GEO_MAX_REACH):
+            raise ValueError(f"reach must be None or an integer in [1, {ops.GEO_MAX_REACH}], got {reach!r}")
+        self.n_latent, self.graph_neighbors, self.proc_neighbors = n_latent, graph_neighbors, proc_neighbors
+        self.reach, self.start = reach, start
+        self.last_lists = self.last_latent = None
+        self.down = posatt_cross_metric(self.n_head, self.in_dim, self.en_local)
+        self.en_layer = _pit.kaiming_mlp(self.n_head * self.in_dim, self.hid_dim, self.hid_dim)
+        self.conv = nn.ModuleList([posatt_metric(self.n_head, self.hid_dim, 1.0) for _ in range(self.n_blocks)])
+        self.up = posatt_cross_metric(self.n_head, self.hid_dim, self.de_local)
+
+    def forward(self, mesh_in, func_in, mesh_out, len_in=None, adj=None, adj_w=None):
+        """``mesh_in`` (b, n, space_dim): the clouds, padded; ``mesh_out`` must BE ``mesh_in`` (query points are graph vertices);
+        ``len_in``: the point counts of a ragged batch (None = full width); ``adj`` / ``adj_w``: the caller's graph as padded
+        adjacency ((n, G) or (b, n, G), ops.geo_knn's format; edge LENGTHS, not squares), None: the kNN graph of ``mesh_in``.
+        Padded rows of the result are finite and meaningless: mask them, e.g. with ``RelLpNorm(...)(true, pred, lengths)``."""
+        if not torch.is_tensor(mesh_in) or mesh_in.dim() != 3:
+            raise ValueError("pit_cloud_geodesic needs per-sample (batch, n, space_dim) clouds")
+        same = mesh_out is mesh_in or (torch.is_tensor(mesh_out) and mesh_out.shape == mesh_in.shape
+                                       and mesh_out.stride() == mesh_in.stride() and mesh_out.device == mesh_in.device
+                                       and mesh_out.data_ptr() == mesh_in.data_ptr())
+        if not same:
+            raise ValueError("pit_cloud_geodesic: mesh_out must be mesh_in - query points must be vertices of the graph")
+        if (adj is None) != (adj_w is None):
+            raise ValueError("give both adj and adj_w (the graph and its edge lengths) or neither")
+        b, n, _ = mesh_in.shape
+        if self.n_latent > n:
+            raise ValueError(f"n_latent = {self.n_latent} beyond the {n} points of a cloud")
+        if adj is None and self.graph_neighbors + 1 > n:
+            raise ValueError(f"graph_neighbors = {self.graph_neighbors}: a cloud of {n} points has at most {n - 1} neighbours")
+        ops._check_dist_mode()
+        m, kp = self.n_latent, min(self.n_latent, self.proc_neighbors)
+        len_v = None if len_in is None else ops.as_lengths(len_in, mesh_in.device, b)
+        if adj is None:
+            adj, adj_w = knn_graph(mesh_in, self.graph_neighbors, lengths=len_v)
+        with torch.no_grad():
+            latent = ops.farthest_point_sample(mesh_in, m, len_v, self.start)
+            # key_of: a device scatter of arange over the picks (a pick of -1, beyond a short cloud's, lands in a spare column)
+            picks = latent.idx.long()
+            key_of = torch.full((b, n + 1), -1, device=mesh_in.device, dtype=torch.int32)
+            key_of.scatter_(1, torch.where(picks >= 0, picks, torch.full_like(picks, n)),
+                            torch.arange(m, device=mesh_in.device, dtype=torch.int32).expand(b, m))
+            key_of = key_of[:, :n].contiguous()
+        len_l = latent.lengths
+        down = knn_lists_geodesic(adj, adj_w, None, self.en_local, sources=latent.idx, n_keys=n, len_v=len_v, reach=self.reach)
+        proc = knn_lists_geodesic(adj, adj_w, kp, 1.0, sources=latent.idx, key_of=key_of, n_keys=m, len_v=len_v, reach=self.reach)
+        up = knn_lists_geodesic(adj, adj_w, None, self.de_local, key_of=key_of, n_keys=m, len_v=len_v, reach=self.reach)
+        self.last_lists, self.last_latent = (down, proc, up), latent
+        if len_v is None:
+            ltt = self._mlp_gelu(self.en_layer, self.down.forward_list(down.idx, down.sqd, func_in))
+            for a, w in zip(self.conv, self.mlp):
+                ltt = self._mlp_gelu(w, a.forward_list(proc.idx, proc.sqd, ltt))
+            return self.de(self.up.forward_list(up.idx, up.sqd, ltt))
+        ltt = self._mlp_gelu(self.en_layer, self.down.forward_list(down.idx, down.sqd, func_in, len_out=len_l, len_in=len_v))
+        for a, w in zip(self.conv, self.mlp):
+            ltt = self._mlp_gelu(w, a.forward_list(proc.idx, proc.sqd, ltt, lengths=len_l))
+        return self.de(self.up.forward_list(up.idx, up.sqd, ltt, len_out=len_v, len_in=len_l))

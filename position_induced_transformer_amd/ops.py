@@ -4105,6 +4105,222 @@ def knn_box_restated(mesh_out, mesh_in, k: int, periods=None, row_chunk: int = 5
     return out
 
 
+GeoResult = collections.namedtuple("GeoResult", ("idx", "dist", "next", "status"))
+GeoResult.__doc__ = """Result of ``geo_knn``: ``idx`` (.., N, k) int32 - the keys of every row's k nearest reachable key vertices,
+ascending by (path length, vertex index), -1 in the slots a row does not fill; ``dist`` (.., N, k) fp32 - their path lengths (not
+squared), 0 in unfilled slots; ``next`` (.., N) fp32 - a lower bound of the length of the nearest key the list leaves out (exact
+when every vertex is a key), +inf when there is none and on padded and truncated rows; ``status`` (.., N) int32 - 1 where the
+search met its ``reach`` budget (the row lists the keys settled until then, exactly), else 0."""
+GEO_MAX_K = _lib.GEO_MAX_K
+GEO_MAX_REACH = _lib.GEO_MAX_REACH
+
+
+def geo_default_reach(k: int) -> int:
+    """The ``reach`` ``geo_knn`` takes when none is given: the power of two >= 8 k, at most 4096 (and never below k)."""
+    r = 1
+    while r < 8 * int(k):
+        r *= 2
+    return max(int(k), min(GEO_MAX_REACH, r))
+
+
+def check_geo_shapes(adj, w, k, sources=None, key_of=None, len_v=None, reach=None):
+    """Shape, dtype and envelope refusals of ``geo_knn``, raised before the device check and before anything is launched.
+    Returns (batch, n_vert, n_edge, n_rows, k, reach, batched): ``batched`` says whether the results carry a batch axis."""
+    for name, t, dt in (("adj", adj, torch.int32), ("w", w, torch.float32)):
+        if not torch.is_tensor(t) or t.dim() not in (2, 3):
+            raise ValueError(f"{name} must be a (V, G) or (b, V, G) tensor")
+        if t.dtype != dt:
+            raise ValueError(f"{name} must be {dt}, got {t.dtype}")
+        if 0 in t.shape:
+            raise ValueError(f"{name} has an empty axis: {tuple(t.shape)}")
+    if tuple(adj.shape) != tuple(w.shape):
+        raise ValueError(f"adj {tuple(adj.shape)} and w {tuple(w.shape)} must have one shape")
+    n_vert, n_edge = int(adj.shape[-2]), int(adj.shape[-1])
+    if n_vert * n_edge >= 2 ** 31:
+        raise ValueError(f"V * G = {n_vert * n_edge} does not fit 31 bits")
+    batches = {"adj": int(adj.shape[0])} if adj.dim() == 3 else {}
+    for name, t, width in (("sources", sources, None), ("key_of", key_of, n_vert)):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or t.dim() not in (1, 2):
+            raise ValueError(f"{name} must be None or a ({'N' if width is None else 'V'},) or (b, {'N' if width is None else 'V'}) tensor")
+        if t.dtype != torch.int32:
+            raise ValueError(f"{name} must be int32, got {t.dtype}")
+        if 0 in t.shape:
+            raise ValueError(f"{name} has an empty axis: {tuple(t.shape)}")
+        if width is not None and int(t.shape[-1]) != width:
+            raise ValueError(f"{name} has {int(t.shape[-1])} entries for a graph on {width} vertices")
+        if t.dim() == 2:
+            batches[name] = int(t.shape[0])
+    if len(set(batches.values())) > 1:
+        raise ValueError(f"the batched arguments hold different numbers of samples: {batches}")
+    batch = next(iter(batches.values())) if batches else 1
+    if len_v is not None:
+        if torch.is_tensor(len_v) and len_v.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"len_v must be an int32 or int64 tensor, got {len_v.dtype}")
+        count = len_v.numel() if torch.is_tensor(len_v) else len(len_v)
+        if count != batch:
+            raise ValueError(f"len_v must hold one entry per sample: {count} entries for a batch of {batch}")
+    n_rows = n_vert if sources is None else int(sources.shape[-1])
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) < 1:
+        raise ValueError(f"k must be a positive integer, got {k!r}")
+    k = int(k)
+    if k > GEO_MAX_K:
+        raise ValueError(f"k = {k}: at most {GEO_MAX_K} neighbours are supported by the geodesic builder")
+    if reach is None:
+        reach = geo_default_reach(k)
+    if isinstance(reach, bool) or not isinstance(reach, (int, np.integer)):
+        raise ValueError(f"reach must be None or an integer, got {reach!r}")
+    reach = int(reach)
+    if not k <= reach <= GEO_MAX_REACH:
+        raise ValueError(f"reach = {reach}: the discovered vertices of a row are bounded by k = {k} <= reach <= {GEO_MAX_REACH}")
+    if batch * n_rows * k >= 2 ** 31:
+        raise ValueError(f"batch * N * k = {batch * n_rows * k} does not fit 31 bits")
+    return batch, n_vert, n_edge, n_rows, k, reach, bool(batches) or len_v is not None
+
+
+def _geo_shared(t, batch: int, width: int):
+    """An argument of ``geo_knn`` as the kernel reads it: (contiguous tensor to keep alive, sample stride in elements, 0 = shared)."""
+    t = t.detach()
+    lead = t.dim() - (1 if width is None else 2)          # 1: a batch axis
+    if lead == 0 or batch == 1 or t.stride(0) == 0:
+        rows = t if lead == 0 else t[0]
+        return rows.contiguous(), 0
+    t = t.contiguous()
+    return t, t.stride(0)
+
+
+@torch.compiler.disable
+def geo_knn(adj: torch.Tensor, w: torch.Tensor, k: int, sources=None, key_of=None, len_v=None, reach=None) -> GeoResult:
+    """One launch of pit_geo_knn (include/pit_hip.h): for every row its ``k`` nearest key vertices under the PATH LENGTH of a
+    graph - a truncated single-source shortest-path search per row - ascending by (length, vertex index), the lowest vertex index
+    among equals, in the list layers' format.  No workspace, no host synchronisation, capturable; the same input gives the same bits.
+      adj, w     (V, G) or (b, V, G) int32 / fp32, padded adjacency: edge t of vertex u leads to adj[u, t] and has length w[u, t];
+                 valid iff 0 <= adj[u, t] < Vs.  Directed; self edges and duplicates are harmless.  Weights finite and >= 0 (not
+                 checked; nothing is addressed out of bounds whatever they hold).  The length of a path is summed in fp32 along it,
+                 one rounded add per edge; D(v) is the least such sum.
+      sources    (N,) or (b, N) int32: the start vertex of every row; None: every vertex, N = V.  A source outside [0, Vs) is a
+                 padded row (-1 / 0 / +inf / 0).
+      key_of     (V,) or (b, V) int32: a vertex's key index, < 0 = no key; None: the identity
+      len_v      the vertices of every sample (``as_lengths`` forms), read on the device: Vs = len_v[s] clamped into [1, V];
+                 adjacency rows of vertices >= Vs are never read
+      k          1 .. 1024;  reach: k .. 4096, None: the power of two >= 8 k (at most 4096) - the bound on the vertices a row
+                 discovers (settled or in its frontier); a row that would discover more stops with status 1 and lists the keys it
+                 has settled, whose lengths are exact.  Truncation is reported, never silent.
+    Results carry a batch axis when an argument does or ``len_v`` is given.  Nothing differentiates through the search."""
+    batch, n_vert, n_edge, n_rows, k, reach, batched = check_geo_shapes(adj, w, k, sources, key_of, len_v, reach)
+    _need_gpu(w)
+    given = [t for t in (adj, w, sources, key_of) if t is not None]
+    if not all(t.is_cuda for t in given):
+        raise RuntimeError("position_induced_transformer_amd: geo_knn runs on the HIP device only; got a CPU tensor")
+    if len({t.device for t in given}) > 1:
+        raise ValueError(f"the tensors live on different devices: {[str(t.device) for t in given]}")
+    dev = w.device
+    adj_t, adj_s = _geo_shared(adj, batch, n_edge)
+    w_t, w_s = _geo_shared(w, batch, n_edge)
+    if adj_s != w_s:                                      # (one of the two expanded, the other not: one stride serves both)
+        adj_t, w_t = adj.detach().expand(batch, -1, -1).contiguous(), w.detach().expand(batch, -1, -1).contiguous()
+        adj_s = n_vert * n_edge
+    src_t, src_s = (None, 0) if sources is None else _geo_shared(sources, batch, None)
+    key_t, key_s = (None, 0) if key_of is None else _geo_shared(key_of, batch, None)
+    len_t = None if len_v is None else as_lengths(len_v, dev, batch)
+    idx = torch.empty((batch, n_rows, k), device=dev, dtype=torch.int32)
+    dist = torch.empty((batch, n_rows, k), device=dev, dtype=torch.float32)
+    nxt = torch.empty((batch, n_rows), device=dev, dtype=torch.float32)
+    status = torch.empty((batch, n_rows), device=dev, dtype=torch.int32)
+    if _capturing():
+        _pin(adj_t, w_t, src_t, key_t, len_t)
+    rc = _lib.lib().pit_geo_knn(adj_t.data_ptr(), w_t.data_ptr(), adj_s, batch, n_vert, n_edge, _lib.ptr(src_t), src_s, n_rows,
+                                _lib.ptr(key_t), key_s, _lib.ptr(len_t), k, reach, idx.data_ptr(), dist.data_ptr(), nxt.data_ptr(),
+                                status.data_ptr(), _lib.stream_ptr())
+    _lib.check(rc, "pit_geo_knn")
+    if not batched:
+        return GeoResult(idx[0], dist[0], nxt[0], status[0])
+    return GeoResult(idx, dist, nxt, status)
+
+
+def _geo_row_restated(adj, w, vs: int, src: int, key, k: int, reach: int):
+    """One row of ``geo_knn_restated``: (keys, lengths, next, status) as Python lists / floats."""
+    import heapq
+    tent, settled, cands = {src: 0.0}, {}, []
+    heap = [(0.0, src)]                                   # (tentative length, vertex): the order of the header
+    kth, front, truncated = None, float("inf"), False
+    while True:
+        while heap and (heap[0][1] in settled or tent.get(heap[0][1]) != heap[0][0]):
+            heapq.heappop(heap)                           # (an entry a shorter path has replaced)
+        if not heap:
+            break                                         # the frontier is empty
+        d_v, v = heap[0]
+        if len(cands) >= k and d_v > kth:
+            front = d_v                                   # complete: nothing the frontier holds can enter the list
+            break
+        heapq.heappop(heap)
+        settled[v] = d_v
+        del tent[v]
+        if key is None or key[v] >= 0:
+            cands.append((d_v, v))
+            if len(cands) == k:
+                kth = d_v
+        new_len = np.float32(d_v) + w[v]                  # fl32(D(u) + w(u, v)), one rounded add per edge
+        assert new_len.dtype == np.float32
+        row = adj[v]
+        for t in range(row.shape[0]):
+            a = int(row[t])
+            if not 0 <= a < vs or a in settled:
+                continue
+            n = float(new_len[t]) + 0.0                   # (-0.0 counts as +0.0)
+            old = tent.get(a)
+            if old is None:
+                if len(settled) + len(tent) >= reach:     # the discovered set would exceed the budget
+                    truncated = True
+                    break
+                tent[a] = n
+                heapq.heappush(heap, (n, a))
+            elif n < old:
+                tent[a] = n
+                heapq.heappush(heap, (n, a))
+        if truncated:
+            break
+    cands.sort()
+    nxt = float("inf")
+    if not truncated:
+        nxt = min(front, cands[k][0]) if len(cands) > k else front
+    cands = cands[:k]
+    return [v if key is None else int(key[v]) for _, v in cands], [d for d, _ in cands], nxt, 1 if truncated else 0
+
+
+def geo_knn_restated(adj, w, k: int, sources=None, key_of=None, len_v=None, reach=None) -> GeoResult:
+    """``geo_knn`` restated on the host, step by step (the search of include/pit_hip.h): label-setting search in the order
+    (tentative length, vertex index) with numpy fp32 adds, the completion test (k candidates settled and the frontier strictly
+    beyond the k-th), the ``reach`` budget checked at every discovery, the settled key vertices sorted by (length, vertex) and
+    cut at ``k``.  CPU tensors in, CPU tensors out, the shapes and dtypes of ``geo_knn``; for tests."""
+    batch, n_vert, n_edge, n_rows, k, reach, batched = check_geo_shapes(adj, w, k, sources, key_of, len_v, reach)
+    adj_n, w_n = adj.detach().cpu().numpy(), w.detach().cpu().numpy().astype(np.float32, copy=False)
+    src_n = None if sources is None else sources.detach().cpu().numpy()
+    key_n = None if key_of is None else key_of.detach().cpu().numpy()
+    lens = None if len_v is None else [max(1, min(int(x), n_vert)) for x in (len_v.tolist() if torch.is_tensor(len_v) else len_v)]
+    idx = np.full((batch, n_rows, k), -1, np.int32)
+    dist = np.zeros((batch, n_rows, k), np.float32)
+    nxt = np.full((batch, n_rows), np.inf, np.float32)
+    status = np.zeros((batch, n_rows), np.int32)
+    for s in range(batch):
+        a_s, w_s = (adj_n[s] if adj_n.ndim == 3 else adj_n), (w_n[s] if w_n.ndim == 3 else w_n)
+        key = None if key_n is None else (key_n[s] if key_n.ndim == 2 else key_n)
+        vs = n_vert if lens is None else lens[s]
+        for i in range(n_rows):
+            src = i if src_n is None else int(src_n[s, i] if src_n.ndim == 2 else src_n[i])
+            if not 0 <= src < vs:
+                continue
+            keys, lengths, nx, st = _geo_row_restated(a_s, w_s, vs, src, key, k, reach)
+            idx[s, i, :len(keys)] = keys
+            dist[s, i, :len(keys)] = lengths
+            nxt[s, i], status[s, i] = nx, st
+    out = GeoResult(torch.from_numpy(idx), torch.from_numpy(dist), torch.from_numpy(nxt), torch.from_numpy(status))
+    if not batched:
+        return GeoResult(out.idx[0], out.dist[0], out.next[0], out.status[0])
+    return out
+
+
 class _InstanceNorm(torch.autograd.Function):
     """nn.InstanceNorm1d over the point axis on the (batch, points, channels) layout
     (train_vorticity.py:43,56,59), no permutes."""
