@@ -516,7 +516,9 @@ int pit_encoder_bwd(const pit_slab_plan* plan, const float* mesh_in, int space_d
  *                        and, with workspace != NULL, the layer's d(scale) partial sums ADDED to workspace (PIT_HEAD_DEFER
  *                        convention: drain with pit_posatt_dhead_finish) from q = e (m - mbar)/rowsum.
  * e / q: this layer's (n_head, n_pts, n_pts) slices, rowstat its (n_head, n_pts, 4) slice of pit_block_weights' outputs.
- * pit_posatt_pre_supported: 1 when the shape is in the regime these launches cover (else use pit_posatt_fwd / _bwd). */
+ * pit_posatt_pre_supported: 1 when the shape is in the regime these launches cover (else use pit_posatt_fwd / _bwd).
+ * Both entries return PIT_ERR_UNSUPPORTED, before any launch and writing nothing, for a shape outside it: n_pts no multiple of 4,
+ * n_pts > 2048, or a (n_pts, n_head, batch * dim) that the large-regime (tiles) kernels do not take. */
 int pit_posatt_pre_supported(int n_pts, int n_head, int dim, int batch);
 int pit_posatt_pre_fwd(const float* e, const float* rowstat, int n_pts, int n_head, int dim, int batch,
                        const float* values, long ld_values, long values_bstride,
@@ -1570,6 +1572,43 @@ int pit_debug_gemm_counts(int* out, int n, int reset);
 #define PIT_ATT_LAST_GRID_Y       27   /* column blocks of the last list rows / cols launch (grid.y before any remap)      */
 #define PIT_ATT_KINDS             28
 int pit_debug_att_counts(int* out, int n, int reset);
+
+/* Which DENSE (MFMA) position-attention kernel of csrc/pit_posatt.hip ran, and which instance of it: the same kind of record
+ * for launch_rows / launch_cols / launch_rows8 / launch_cols8 / launch_rows_tiles / launch_cols_tiles / launch_bwd_pair, i.e. for
+ * pit_posatt_fwd / pit_posatt_bwd without candidate lists (or where the list path declines) and pit_posatt_pre_fwd / _bwd.
+ * Host-side counters of the CALLING THREAD, one per kernel template, incremented beside the launch call.  The PIT_DENSE_LAST_*
+ * slots are not counters; they hold, in decimal digits, the template arguments of the most recent launch of their family:
+ *   J-split rows / cols / pair (and rows8 / cols8, which are CT 1, IL 0):  CT * 10000 + WAVES * 1000 + IL * 100 + MASKED * 10 + BF
+ *     (WAVES = wavefronts per workgroup, 1..8; BF = the instance contracts in bf16; the pair's rows half is exact fp32 whatever BF)
+ *   tiles rows:  RT * 100000 + TPWG * 1000 + MASKED * 100 + BF * 10 + PRE   (TPWG = column tiles per workgroup = 8 * TPW: 8, 16, 32)
+ *   tiles cols:                TPWG * 1000 + MASKED * 100 + BF * 10 + PRE
+ * and PIT_DENSE_LAST_GRID_X / _Y / _Z the grid of the most recent dense launch of any family (riders' workgroups included).
+ * Copies min(n, PIT_DENSE_KINDS) slots to out (host array) and zeroes them all when reset != 0; returns PIT_DENSE_KINDS.  No
+ * device work, nothing read by a kernel.  A library built from this header defines PIT_HAS_DENSE_COUNTS; PIT_ABI_VERSION is
+ * unchanged.  PIT_ATT_DENSE above still counts what it counted: the launches made through launch_rows, launch_cols and
+ * launch_bwd_pair (not those of pit_posatt_pre_fwd / _bwd). */
+#define PIT_HAS_DENSE_COUNTS 1
+#define PIT_DENSE_ROWS_FWD           0   /* posatt_rows_kernel<CT, 0, M, BF, IL>                                            */
+#define PIT_DENSE_ROWS_DSCALE        1   /* posatt_rows_kernel<CT, 1, M, false, IL>                                         */
+#define PIT_DENSE_COLS               2   /* posatt_cols_kernel<CT, M, BF, IL>                                               */
+#define PIT_DENSE_PAIR               3   /* posatt_bwd_pair_kernel<M, BF>: d(scale) + d(values), CT 1                       */
+#define PIT_DENSE_PAIR_WIDE          4   /* posatt_bwd_pair_wide_kernel<CT, M, BF, IL>: CT 2 / 4, with or without its rider */
+#define PIT_DENSE_PAIR_DW            5   /* posatt_bwd_pair_dw_kernel<M, BF>: the CT 1 pair carrying a weight-gradient rider */
+#define PIT_DENSE_TILES_ROWS_FWD     6   /* posatt_rows_tiles<RT, TPW, 0, M, BF, PRE>                                       */
+#define PIT_DENSE_TILES_ROWS_DSCALE  7   /* posatt_rows_tiles<RT, TPW, 1, M, false, PRE>                                    */
+#define PIT_DENSE_TILES_COLS         8   /* posatt_cols_tiles<TPW, M, BF, PRE>                                              */
+#define PIT_DENSE_ROWS8              9   /* posatt_rows_kernel8<MODE, M, BF>: 4..8 coordinates, either mode                 */
+#define PIT_DENSE_COLS8             10   /* posatt_cols_kernel8<M, BF>                                                      */
+#define PIT_DENSE_LAST_ROWS         11   /* last posatt_rows_kernel / _kernel8 launch (packing above)                       */
+#define PIT_DENSE_LAST_COLS         12   /* last posatt_cols_kernel / _kernel8 launch                                       */
+#define PIT_DENSE_LAST_PAIR         13   /* last pair launch (any of the three kernels)                                     */
+#define PIT_DENSE_LAST_TILES_ROWS   14   /* last posatt_rows_tiles launch                                                   */
+#define PIT_DENSE_LAST_TILES_COLS   15   /* last posatt_cols_tiles launch                                                   */
+#define PIT_DENSE_LAST_GRID_X       16   /* grid of the last dense launch                                                   */
+#define PIT_DENSE_LAST_GRID_Y       17
+#define PIT_DENSE_LAST_GRID_Z       18
+#define PIT_DENSE_KINDS             19
+int pit_debug_dense_counts(int* out, int n, int reset);
 
 #ifdef __cplusplus
 }

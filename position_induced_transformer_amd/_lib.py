@@ -179,6 +179,7 @@ ADDED_LATER = {"pit_distlist_select_fwd", "pit_distlist_fwd", "pit_distlist_bwd_
                "pit_block_bwd_last_riders",                                        # PIT_HAS_RIDER_TAIL
                "pit_posatt_dhead_finish_stage", "pit_finish_last_tail",            # PIT_HAS_FINISH_TAIL
                "pit_debug_att_counts",                                             # PIT_HAS_ATT_COUNTS
+               "pit_debug_dense_counts",                                           # PIT_HAS_DENSE_COUNTS
                "pit_eval_metrics_workspace", "pit_eval_metrics",                   # PIT_HAS_EVAL_METRICS
                "pit_batch_feed",                                                   # PIT_HAS_BATCH_FEED
                "pit_adam_guard_parts", "pit_adam_step_guarded",                    # PIT_HAS_GUARDED_ADAM

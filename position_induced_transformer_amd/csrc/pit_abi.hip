@@ -23,6 +23,7 @@ namespace {
 thread_local int t_rider_counts[PIT_RIDER_KINDS];
 thread_local int t_gemm_counts[PIT_GEMM_KINDS];
 thread_local int t_att_counts[PIT_ATT_KINDS];
+thread_local int t_dense_counts[PIT_DENSE_KINDS];
 thread_local int t_rider_mute = 0;
 }  // namespace
 
@@ -64,6 +65,20 @@ extern "C" int pit_debug_att_counts(int* out, int n, int reset) {
     if (reset)
         for (int k = 0; k < PIT_ATT_KINDS; ++k) t_att_counts[k] = 0;
     return PIT_ATT_KINDS;
+}
+
+void pit_dense_note(int kind) {
+    if (kind >= 0 && kind < PIT_DENSE_LAST_ROWS) ++t_dense_counts[kind];
+}
+void pit_dense_note_last(int slot, int value) {
+    if (slot >= PIT_DENSE_LAST_ROWS && slot < PIT_DENSE_KINDS) t_dense_counts[slot] = value;
+}
+
+extern "C" int pit_debug_dense_counts(int* out, int n, int reset) {
+    for (int k = 0; out && k < n && k < PIT_DENSE_KINDS; ++k) out[k] = t_dense_counts[k];
+    if (reset)
+        for (int k = 0; k < PIT_DENSE_KINDS; ++k) t_dense_counts[k] = 0;
+    return PIT_DENSE_KINDS;
 }
 
 extern "C" const char* pit_error_string(int code) {

@@ -46,6 +46,10 @@ void pit_gemm_note_last(int slot, int value);
 // PIT_ATT_LAST_* slots)
 void pit_att_note(int kind);
 void pit_att_note_last(int slot, int value);
+// include/pit_hip.h, pit_debug_dense_counts: the same for the dense (MFMA) launchers of pit_posatt.hip (PIT_DENSE_* kinds and
+// PIT_DENSE_LAST_* slots)
+void pit_dense_note(int kind);
+void pit_dense_note_last(int slot, int value);
 // bf16 storage (PIT_IO_*): a tensor kept as bf16 in memory is widened exactly (bits << 16), narrowed with RNE
 __device__ __forceinline__ float bf16_to_f(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
 __device__ __forceinline__ unsigned short f_to_bf16(float x) { return __builtin_bit_cast(unsigned short, (__bf16)x); }

@@ -1699,6 +1699,16 @@ void launch_lds96(dim3 grid, dim3 block, size_t smem, hipStream_t s, const Args&
     raise_lds96<K>();
     hipLaunchKernelGGL(K, grid, block, smem, s, args...);
 }
+// pit_debug_dense_counts (include/pit_hip.h): the kernel template, its packed template arguments and the grid of one dense launch
+void note_dense(int kind, int last_slot, int packed, dim3 grid) {
+    pit_dense_note(kind);
+    pit_dense_note_last(last_slot, packed);
+    pit_dense_note_last(PIT_DENSE_LAST_GRID_X, (int)grid.x);
+    pit_dense_note_last(PIT_DENSE_LAST_GRID_Y, (int)grid.y);
+    pit_dense_note_last(PIT_DENSE_LAST_GRID_Z, (int)grid.z);
+}
+int jsplit_pack(int ct, int nwaves, bool il, bool masked, bool bf) { return ct * 10000 + nwaves * 1000 + il * 100 + masked * 10 + bf; }
+int tiles_pack(int rt, int tpwg, bool masked, bool bf, bool pre) { return rt * 100000 + tpwg * 1000 + masked * 100 + bf * 10 + pre; }
 // The ladders below leave combinations that have no kernel instance out with `if constexpr`; no caller reaches one today (the
 // dispatch rules above each ladder say why).  One that did would otherwise launch nothing, silently: it ends the process instead.
 [[noreturn]] void no_instance(const char* kernel) {
@@ -1731,6 +1741,8 @@ void launch_rows_tiles(AttArgs a, TilesRegime r, bool pre, hipStream_t s) {
             else no_instance("posatt_rows_tiles");
         }); }); });
     }); });
+    note_dense(MODE == 0 ? PIT_DENSE_TILES_ROWS_FWD : PIT_DENSE_TILES_ROWS_DSCALE, PIT_DENSE_LAST_TILES_ROWS,
+               tiles_pack(r.rt == 4 || r.rt == 2 ? r.rt : 1, r.tpwg, a.masked != 0, bf, pre), grid);      // (the ladder: any other rt takes RT 1)
 }
 
 // the TPW ladder over posatt_cols_tiles, once: `tpwg` from cols_tiles_regime (!= 0)
@@ -1744,6 +1756,7 @@ void launch_cols_tiles(AttArgs a, int tpwg, bool pre, hipStream_t s) {
             hipLaunchKernelGGL((posatt_cols_tiles<TPWG() / 8, M(), BF(), PRE()>), grid, block, 0, s, a);
         else no_instance("posatt_cols_tiles");
     }); }); }); });
+    note_dense(PIT_DENSE_TILES_COLS, PIT_DENSE_LAST_TILES_COLS, tiles_pack(0, tpwg, a.masked != 0, a.bf16 != 0, pre), grid);
 }
 
 
@@ -1800,6 +1813,7 @@ void launch_rows8(AttArgs a, int mode, hipStream_t s) {
             launch_lds96<posatt_rows_kernel8<MODE(), M(), BF()>>(grid, block, sm, s, a);
         else no_instance("posatt_rows_kernel8");
     }); }); });
+    note_dense(PIT_DENSE_ROWS8, PIT_DENSE_LAST_ROWS, jsplit_pack(1, nwaves, false, a.masked != 0, bf), grid);
 }
 void launch_cols8(AttArgs a, hipStream_t s) {
     const int j_tiles = (a.n_in + 31) / 32;
@@ -1811,11 +1825,15 @@ void launch_cols8(AttArgs a, hipStream_t s) {
     with_bool(a.masked, [&](auto M) { with_bool(a.bf16, [&](auto BF) {
         launch_lds96<posatt_cols_kernel8<M(), BF()>>(grid, block, sm, s, a);
     }); });
+    note_dense(PIT_DENSE_COLS8, PIT_DENSE_LAST_COLS, jsplit_pack(1, nwaves, false, a.masked != 0, a.bf16 != 0), grid);
 }
 
 template <int MODE>
 void launch_rows(const AttArgs& a0, hipStream_t s) {
-    if (a0.sdim > 3) { launch_rows8(a0, MODE, s); pit_att_note(PIT_ATT_DENSE); return; }   // (pit_debug_att_counts: one coarse kind for every dense launcher)
+    // (pit_debug_att_counts: PIT_ATT_DENSE, one coarse kind for the launches made here, in launch_cols and in launch_bwd_pair; WHICH
+    // kernel and instance ran is pit_debug_dense_counts' business - note_dense beside every launch call, launch_rows8 and
+    // launch_rows_tiles note their own)
+    if (a0.sdim > 3) { launch_rows8(a0, MODE, s); pit_att_note(PIT_ATT_DENSE); return; }
     AttArgs a = a0;
     const bool bf = (MODE == 0) && a.bf16 != 0;
     const int n_tiles = (a.n_out + 31) / 32;
@@ -1839,6 +1857,7 @@ void launch_rows(const AttArgs& a0, hipStream_t s) {
             launch_lds96<posatt_rows_kernel<CT(), MODE, M(), BF(), IL()>>(grid, block, sm, s, a);
         else no_instance("posatt_rows_kernel");
     }); }); }); });
+    note_dense(MODE == 0 ? PIT_DENSE_ROWS_FWD : PIT_DENSE_ROWS_DSCALE, PIT_DENSE_LAST_ROWS, jsplit_pack(ct, nwaves, il, a.masked != 0, bf), grid);
     pit_att_note(PIT_ATT_DENSE);
 }
 
@@ -1866,6 +1885,7 @@ void launch_cols(const AttArgs& a0, hipStream_t s) {
             launch_lds96<posatt_cols_kernel<CT(), M(), BF(), IL()>>(grid, block, sm, s, a);
         else no_instance("posatt_cols_kernel");
     }); }); }); });
+    note_dense(PIT_DENSE_COLS, PIT_DENSE_LAST_COLS, jsplit_pack(ct, nwaves, il, a.masked != 0, bf), grid);
     pit_att_note(PIT_ATT_DENSE);
 }
 
@@ -1924,6 +1944,7 @@ bool launch_bwd_pair(const AttArgs& a0, hipStream_t s, const pit_mlp_params_job*
         }); });
         *rider_done = true;
         pit_rider_note(PIT_RIDER_PAIR_DW);
+        note_dense(PIT_DENSE_PAIR_DW, PIT_DENSE_LAST_PAIR, jsplit_pack(1, nwaves, false, a0.masked != 0, a0.bf16 != 0), gridw);
         pit_att_note(PIT_ATT_DENSE);
         return true;
     }
@@ -1956,6 +1977,8 @@ bool launch_bwd_pair(const AttArgs& a0, hipStream_t s, const pit_mlp_params_job*
                                                                              a0.mesh_batch * ar.colgroups, a0.n_head, (int)(rows_wgs + cols_wgs), wdw);
         else no_instance("posatt_bwd_pair_wide_kernel");
     }); }); }); });
+    note_dense(ct == 1 ? PIT_DENSE_PAIR : PIT_DENSE_PAIR_WIDE, PIT_DENSE_LAST_PAIR, jsplit_pack(ct, nwaves, il, a0.masked != 0, a0.bf16 != 0),
+               ct == 1 ? grid : wgrid);
     pit_att_note(PIT_ATT_DENSE);
     return true;
 }
@@ -3303,6 +3326,7 @@ extern "C" int pit_posatt_pre_fwd(const float* e, const float* rowstat, int n_pt
     PIT_ENTER_MATH(math_mode);
     if (!e || !rowstat || !values || !out) return PIT_ERR_NULL;
     if (math_mode & ~0xff) return PIT_ERR_UNSUPPORTED;
+    if (n_pts % 4 != 0 || n_pts > 2048) return PIT_ERR_UNSUPPORTED;     // (outside pit_posatt_pre_supported's regime: refused here as well)
     AttArgs a;
     if (int rc = fill_pre(a, n_pts, n_head, dim, batch, values, ld_values, values_bstride)) return rc;
     const unsigned long long vb = ((unsigned long long)(batch - 1) * values_bstride + (unsigned long long)(n_pts - 1) * ld_values + dim) * 4ull;
@@ -3324,6 +3348,7 @@ extern "C" int pit_posatt_pre_bwd(const float* e, const float* q, const float* r
     if (!e || !rowstat || !d_out || !d_values) return PIT_ERR_NULL;
     if (workspace && (!q || !values)) return PIT_ERR_NULL;
     if (math_mode & ~0xff) return PIT_ERR_UNSUPPORTED;
+    if (n_pts % 4 != 0 || n_pts > 2048) return PIT_ERR_UNSUPPORTED;     // (outside pit_posatt_pre_supported's regime: refused here as well)
     const unsigned long long db = ((unsigned long long)(batch - 1) * dout_bstride + (unsigned long long)(n_pts - 1) * ld_dout +
                                    out_col0 + (unsigned long long)n_head * dim) * 4ull;
     if (db > PIT_MAX_BUFFER_BYTES) return PIT_ERR_UNSUPPORTED;

@@ -4477,4 +4477,14 @@ def att_launch_counts(reset: bool = False) -> list:
     return list(buf)
 
 
+def dense_launch_counts(reset: bool = False) -> list:
+    """The calling thread's launch record of the dense (MFMA) position-attention launchers (pit_debug_dense_counts): one slot
+    per PIT_DENSE_* kind of include/pit_hip.h, in order (the library says how many).  Host-side integers; no device work."""
+    fn = _lib.lib().pit_debug_dense_counts
+    n = fn(None, 0, 0)
+    buf = (ctypes.c_int * n)()
+    fn(buf, n, 1 if reset else 0)
+    return list(buf)
+
+
 _ = ctypes  # keep the import explicit: pointers cross the ABI as plain integers
